@@ -1,6 +1,7 @@
 """Headline benchmark: RGB+T frame-pairs / second on 640x512 FLIR-shaped frames.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4] [--batch B] [--feed hbm|host]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4] [--batch B] [--feed hbm|host] [--full]
+                    [--dump-outputs DIR]
 
 Default workload (BASELINE.json configs[2]): two Faster R-CNN R101-FPN detectors (thermal + RGB, K = 3, fp16 MFMA
 convs / fp32 post-ops) + ProbEn fusion (probEn score, v-avg box), batch 32 frame pairs per GPU, synthetic uint8
@@ -17,9 +18,15 @@ data-path collective ("weak" scaling: per-GPU batch fixed).
 Multi-GPU: `python bench.py --gpus N` launches N ranks itself (torch.distributed.run, one process per GPU, backend
 nccl = RCCL) when it is not already running under a launcher; `n_gpus` in the line is the world size RCCL reports.
 
-Prints ONE JSON line on rank 0 with the throughput, the roofline of the dominant kernel (HIP events around every
-distinct launch replayed back-to-back), the ProbEn kernel's B = 4096 micro-figure and the CPU baseline (the oracle's
-restatement of the reference's MODEL.DEVICE=cpu path timed on the host cores, all cores and 1 thread, bounded sample).
+Prints ONE JSON line on rank 0 with the throughput (`value`, `ms_per_step`, `value_windows`).  A plain run does nothing
+else: set up, warm up, time the K steps, print.  `--full` adds the legs beside the headline figure: the board power and
+shader clock of the timed region, the roofline of the dominant kernel (HIP events around every distinct launch replayed
+back-to-back), the ProbEn kernel's B = 4096 micro-figure and the CPU baseline (the oracle's restatement of the
+reference's MODEL.DEVICE=cpu path timed on the host cores, all cores and 1 thread, bounded sample); `--no-power`,
+`--no-roofline`, `--no-micro` and `--no-cpu-baseline` drop single legs of it.
+
+`--dump-outputs DIR` writes what the last timed step returned (every detector's detections and the fused rows, rank 0's
+shard) as DIR/<name>.npy, float32 / float64: the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -79,8 +86,15 @@ def parse(argv=None):
                     help="N > 0 (default 3, two-detector configs): throughput mode of the pipeline - detector 2 trails detector 1 by its "
                          "res<N> stage and batches follow each other without a device-wide wait (all K timed steps still complete "
                          "inside the timed region); 0: every step waits for its own fusion before the next one starts")
-    ap.add_argument("--layers", type=str, default="", help="write a per-conv-launch table (shape, ms, TFLOP/s) to this file")
-    return ap.parse_args(argv)
+    ap.add_argument("--layers", type=str, default="", help="write a per-conv-launch table (shape, ms, TFLOP/s) to this file (--full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: board power, roofline, ProbEn micro-figure, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    args = ap.parse_args(argv)
+    if args.layers and not (args.full and not args.no_roofline):
+        ap.error("--layers is written by the roofline leg: add --full")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -474,6 +488,50 @@ class BoardPower:
                 "source": "rocm-smi --showpower --showclocks polled by a helper process during the timed region (socket package power)"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dets, fused, out_dir, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: the (dets, fused) one pipeline step returned, as a caller receives them, one .npy per array:
+    det<i>_{boxes,scores,classes,class_logits,prob_score,vars} [B, D, ...] and det<i>_counts [B] per detector,
+    fused_{boxes,scores,classes} [B, S, ...] (image b's rows [offsets[b], offsets[b] + counts[b]) of the flat arrays) and
+    fused_counts [B].  Rows past an image's count are zeroed (the library leaves them unwritten); float64 arrays stay
+    float64, the others are written as float32 (integers as float64: exact).  Above `max_bytes` a fixed, seeded sample of
+    the images is kept and its indices are written as images.npy.  Returns {name: shape}."""
+    import numpy as np
+    arrays = {}
+    for i, d in enumerate(dets):
+        cnt = d["counts"].cpu().numpy().astype(np.int64)
+        B, D = d["scores"].shape
+        valid = np.arange(D)[None, :] < cnt[:, None]
+        for k in ("boxes", "scores", "classes", "class_logits", "prob_score", "vars"):
+            v = d[k].cpu().numpy()
+            arrays[f"det{i}_{k}"] = np.where(valid.reshape(B, D, *([1] * (v.ndim - 2))), v, 0)
+        arrays[f"det{i}_counts"] = cnt
+    if fused is not None:
+        cnt = fused["counts"].cpu().numpy().astype(np.int64)
+        off = fused["offsets"].cpu().numpy().astype(np.int64)
+        S = int(fused["stride"])
+        for k in ("boxes", "scores", "classes"):
+            flat = fused[k].cpu().numpy()
+            v = np.zeros((len(cnt), S) + flat.shape[1:], flat.dtype)
+            for b, (o, c) in enumerate(zip(off, cnt)):
+                v[b, :c] = flat[o:o + c]
+            arrays[f"fused_{k}"] = v
+        arrays["fused_counts"] = cnt
+    arrays = {k: v.astype(np.float64 if v.dtype in (np.float64, np.int64, np.int32) else np.float32) for k, v in arrays.items()}
+    B = len(next(iter(arrays.values())))
+    total = sum(v.nbytes for v in arrays.values())
+    if total > max_bytes:
+        keep = np.sort(np.random.default_rng(0).choice(B, max(1, int(B * max_bytes // total)), replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays["images"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def cpu_baseline(sds, cfg, depth, pairs, threads):
     """The oracle = this repo's restatement of the reference's CPU path (torch fp32 NCHW unfused conv/BN/ReLU,
     all-anchor decode, per-level sort, per-level ROIAlign, NumPy-f64 ProbEn), timed on the host cores: all `threads`
@@ -575,7 +633,7 @@ def main(argv=None):
 
     for _ in range(args.warmup):
         out = step()
-    power = BoardPower(local) if rank == 0 and not args.no_power else None
+    power = BoardPower(local) if rank == 0 and args.full and not args.no_power else None
     if power is not None:
         power.start()
     # The timed region is cut into up to 5 equal sub-windows by EVENTS (recorded on every stream the step launches on; no
@@ -618,6 +676,8 @@ def main(argv=None):
     for d in dets:           # outside the timed region: a box head that ran out of candidate slots would have dropped detections
         check_candidate_overflow(d)
     n_det = float(sum(d["counts"].float().mean() for d in dets)) / len(dets)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(dets, fused, args.dump_outputs)
     if rank == 0:
         units = world * B * args.steps
         value = units / dt
@@ -654,12 +714,12 @@ def main(argv=None):
             line["config"]["collective"] = "one all_gather_into_tensor of the fused rows per step (RCCL)" + ("" if world > 1 else
                                            "; PROBEN_FORCE_DIST: a ONE-rank RCCL group, the collective runs but moves nothing between devices")
             line["config"]["collective_calls_per_step"] = n_coll / args.steps     # counted at torch.distributed's entry points inside the timed loop
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             # rank-local leg: no collective inside (the other ranks are already waiting at the final barrier)
             line["roofline"] = roofline_leg(make_step(models, frames_dev, cfg, world, with_comm=False, concurrent=False), args.layers)
-        if not args.no_micro:
+        if args.full and not args.no_micro:
             line["proben_micro"] = proben_micro(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sds, cfg, depth, args.cpu_pairs, args.cpu_threads)
         print(json.dumps(line), flush=True)
     if world > 1 or comm_active():

@@ -2,7 +2,7 @@
 # round 6: the other BASELINE workloads + host feeding + a sustained run, one box (profiles/r06_bench_configs.jsonl, r06_sustained.txt)
 O=gpurun_out/r06_configs
 mkdir -p $O
-F="--no-cpu-baseline --no-roofline --no-micro"
+F="--full --no-cpu-baseline --no-roofline --no-micro"
 : > $O/bench_configs.jsonl
 for c in 1 3 4; do timeout 900 python bench.py --config $c --steps 100 --warmup 5 $F 2>/dev/null | tail -1 >> $O/bench_configs.jsonl; done
 timeout 900 python bench.py --config 2 --feed host --steps 100 --warmup 5 $F 2>/dev/null | tail -1 >> $O/bench_configs.jsonl
