@@ -205,6 +205,17 @@ int pe_preprocess_pack_pil_u8(const void* src, int32_t num_images, int32_t src_h
                               int32_t ch0, int32_t nch, int32_t flip_rgb, int32_t dst_h, int32_t dst_w, int32_t pad_h,
                               int32_t pad_w, const float* mean_host, const float* std_host, const int32_t* xtab,
                               int32_t xk, const int32_t* ytab, int32_t yk, void* dst, void* stream);
+/* pe_fusion_input_pack: the FLIR early / middle fusion input (demo/FLIR/demo_FLIR_save_predictions.py:98-121) built on the
+ * device from the uint8 frames, one launch per output group.  thermal [N,th_h,th_w,3] and rgb [N,rgb_h,rgb_w,3] are DEVICE
+ * uint8 BGR batches (data.read_image).  The RGB frame is resized to the thermal size with OpenCV's 8-bit INTER_LINEAR rule
+ * (proben_amd.data.cv2_linear_resize_u8; the identity when the sizes agree), stacked as B,G,R,T0,T1,T2, and channels
+ * [ch0, ch0+nch) of that stack go through the float INTER_LINEAR resize of pe_preprocess_pack (src_kind 1) to dst_h x dst_w,
+ * normalise and zero-pad to pad_h x pad_w (multiples of pad_multiple, less than one multiple above the resized size).
+ * Bit for bit the output of the host build + float32 upload + pe_preprocess_pack_batch.  rgb may be null when ch0 >= 3;
+ * mean/std are HOST arrays of length nch. */
+int pe_fusion_input_pack(const void* thermal, const void* rgb, int32_t num_images, int32_t th_h, int32_t th_w, int32_t rgb_h,
+                         int32_t rgb_w, int32_t ch0, int32_t nch, int32_t dst_h, int32_t dst_w, int32_t pad_h, int32_t pad_w,
+                         int32_t pad_multiple, const float* mean_host, const float* std_host, void* dst, void* stream);
 int pe_maxpool3x3s2_nhwc(const void* in, void* out, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 int pe_subsample2_nhwc(const void* in, void* out, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 /* Fused BasicStem.forward (modeling/backbone/resnet.py:375-384): conv 7x7 / 2 / pad 3 with the frozen BN folded

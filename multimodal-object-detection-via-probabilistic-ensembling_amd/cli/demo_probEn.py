@@ -3,6 +3,13 @@ them on the GPU, evaluate with FLIREvaluator.
 
     python -m proben_amd.cli.demo_probEn --dataset_path DATA/FLIR/val --prediction_path out/ \
         --score_fusion probEn --box_fusion v-avg [--detectors thermal_only,early_fusion,middle_fusion]
+
+--one-pass runs the detectors too, in the same process: frame pairs stream from disk (stream.FlirPairLoader, --workers decode
+processes) through FramePairPipeline and ProbEn to FLIREvaluator, with no prediction files in between (--write-predictions
+still writes them, so the two-stage route can be replayed):
+
+    python -m proben_amd.cli.demo_probEn --one-pass --dataset_path DATA/FLIR/val --detectors thermal_only,early_fusion \
+        --model_paths thermal.pth,early.pth [--workers 4] [--batch 32] [--write-predictions --prediction_path out/]
 """
 import json
 import os
@@ -24,19 +31,15 @@ def main(cmd=None):
     rank, world, dev = launch.init_distributed(args.device, expect_world=args.world_size)
     names = [n for n in args.detectors.split(",") if n]
     assert 2 <= len(names) <= 3, "--detectors takes 2 or 3 names"
+    if args.one_pass:
+        return one_pass(args, names, world, dev)
     files = [os.path.join(args.prediction_path, f"val_{n}_predictions.json") for n in names]
     if comm.is_main_process():
         for i, f in enumerate(files):
             print(f"detection file {i + 1}:", f)
         os.makedirs(args.outfolder, exist_ok=True)
     val_json = os.path.join(args.dataset_path, "FLIR_thermal_RGBT_pairs_val.json")
-    register_coco_instances(args.dataset_name, {}, val_json, os.path.join(args.dataset_path, "thermal_8_bit"))
-    DatasetCatalog.get(args.dataset_name)
-    cfg = get_cfg()
-    cfg.OUTPUT_DIR = args.outfolder
-    cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST = 0.5
-    cfg.MODEL.ROI_HEADS.NUM_CLASSES = 3
-    cfg.DATASETS.TEST = (args.dataset_name,)
+    cfg = _register(args)
     dets = [read_j1(f) for f in files]
     # the files are sharded with ONE index range: they must list the same images in the same order (the reference pairs by det_2's
     # position too, demo_probEn.py:205-233, and silently mis-pairs otherwise)
@@ -54,6 +57,120 @@ def main(cmd=None):
     res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
                                          det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev))
     if main_rank:
+        print(json.dumps(res, indent=1))
+    if comm.is_distributed():
+        launch.shutdown()
+    return res
+
+
+def _register(args):
+    val_json = os.path.join(args.dataset_path, "FLIR_thermal_RGBT_pairs_val.json")
+    register_coco_instances(args.dataset_name, {}, val_json, os.path.join(args.dataset_path, "thermal_8_bit"))
+    DatasetCatalog.get(args.dataset_name)
+    cfg = get_cfg()
+    cfg.OUTPUT_DIR = args.outfolder
+    cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST = 0.5
+    cfg.MODEL.ROI_HEADS.NUM_CLASSES = 3
+    cfg.DATASETS.TEST = (args.dataset_name,)
+    return cfg
+
+
+def one_pass(args, names, world, dev):
+    """loader -> FramePairPipeline (one DefaultPredictor model per --detectors entry, cfg as save_predictions.build_cfg) ->
+    ProbEn -> evaluation rows on the device (late_fusion.fused_rows_device) -> one all-gather -> FLIREvaluator on rank 0."""
+    import argparse
+    import time
+    import torch
+    from ..data import PairFrames, resize_shortest_edge_shape
+    from ..late_fusion import fused_rows_device, predictions_to_j1, write_j1
+    from ..pipeline import FramePairPipeline, HostFeeder
+    from ..predictor import DefaultPredictor
+    from ..stream import FlirPairLoader, check_workers
+    from .save_predictions import build_cfg
+    if "rgb_only" in names:
+        raise ValueError("--one-pass does not run rgb_only: that detector sees the RGB frame at its own size while the frame-pair "
+                         "pipeline shares one output size over its detectors.  Use the two-stage route: save_predictions per "
+                         "detector, then demo_probEn without --one-pass.")
+    paths = args.model_paths.split(",") if args.model_paths else [args.model_path] * len(names)
+    if len(paths) != len(names):
+        raise ValueError(f"--model_paths lists {len(paths)} weights for {len(names)} --detectors")
+    workers = check_workers(args.workers)
+    main_rank = comm.is_main_process()
+    if main_rank:
+        os.makedirs(args.outfolder, exist_ok=True)
+    cfg = _register(args)
+    preds = []
+    for m, p in zip(names, paths):
+        c = build_cfg(argparse.Namespace(fusion_method=m, model_path=p))
+        c.MODEL.DEVICE = dev.type
+        preds.append(DefaultPredictor(c))
+    need_rgb = any(p.input_format in ("BGRT", "BGRTTT") for p in preds)
+    loader = FlirPairLoader(args.dataset_path, args.batch, need_rgb=need_rgb, workers=workers)
+    pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion)
+    j1 = [([], [], []) for _ in names]       # per detector: names, ids, instances
+    rows = []
+    feeder, feed_key, host = None, None, None
+    pending = None
+    timed = {"pairs": 0, "t0": None, "wait0": 0.0}
+
+    def finish(p):
+        dets, fused, batch = p
+        rows.append(fused_rows_device(fused, batch.ids))        # the batch's one host synchronisation
+        if args.write_predictions:
+            for d, det, (nm, ids, insts) in zip(preds, dets, j1):
+                nm += batch.names
+                ids += batch.ids
+                insts += [o["instances"] for o in d.model.to_instances(det)]
+
+    for batch in loader:          # the loader assembles batch i+1 while the GPU runs batch i
+        key = (tuple(batch.thermal.shape), None if batch.rgb is None else tuple(batch.rgb.shape))
+        if pending is not None:
+            finish(pending)          # waits for batch i only: batch i+1 is not enqueued yet
+            pending = None
+        if key != feed_key:
+            # a new batch shape (a size change, the last partial batch): a fresh feeder, once nothing reads the old one's buffers
+            torch.cuda.current_stream().synchronize()
+            feeder = HostFeeder(lambda: host, dev)
+            feed_key = key
+        host = [batch.thermal] + ([batch.rgb] if batch.rgb is not None else [])
+        up = feeder.next()
+        h, w = batch.hw
+        n = len(batch)
+        frames = PairFrames(up[0], up[1] if len(up) > 1 else None)
+        dets, fused = pipe([frames] * len(preds), [(h, w)] * n, resize_shortest_edge_shape(h, w, preds[0].min_size, preds[0].max_size))
+        feeder.mark_consumed()
+        pending = (dets, fused, batch)
+        if timed["t0"] is None:      # the first batch warms up (allocations, tables): the timed part starts after it
+            finish(pending)
+            pending = None
+            timed["t0"], timed["wait0"] = time.perf_counter(), loader.wait_s
+        else:
+            timed["pairs"] += n
+    if pending is not None:
+        finish(pending)
+    wall = time.perf_counter() - timed["t0"] if timed["t0"] is not None else 0.0
+    stats = {"pairs": len(loader), "timed_pairs": timed["pairs"], "pairs_per_s": timed["pairs"] / wall if wall > 0 else float("nan"),
+             "decode_wait_fraction": (loader.wait_s - timed["wait0"]) / wall if wall > 0 else float("nan"), "workers": workers,
+             "batch": args.batch, "world_size": world}
+    mine = torch.cat(rows) if rows else torch.zeros((0, 7), dtype=torch.float64)
+    all_rows = comm.gather_rows(mine)             # one padded all-gather on the device, rank order == dataset order
+    if args.write_predictions:
+        pdir = args.prediction_path or args.outfolder
+        for m, (nm, ids, insts) in zip(names, j1):
+            pred = predictions_to_j1(nm, ids, insts)
+            gathered = comm.gather(pred, dst=0)
+            if main_rank:
+                os.makedirs(pdir, exist_ok=True)
+                write_j1(os.path.join(pdir, f"val_{m}_predictions.json"), {k: sum((g[k] for g in gathered), []) for k in pred})
+    res = {}
+    if main_rank:
+        print(f"one-pass: {stats['timed_pairs']} pairs timed, {stats['pairs_per_s']:.1f} pairs/s, GPU side waited on decode "
+              f"{100 * stats['decode_wait_fraction']:.1f}% of the wall time ({workers} workers, batch {args.batch}, {world} rank(s))")
+        ev = FLIREvaluator(args.dataset_name, cfg, False, output_dir=args.outfolder, save_eval=True,
+                           out_eval_path=os.path.join(args.outfolder, "FLIR_probEn_eval.json"))
+        ev.process_rows(all_rows.numpy())
+        res = ev.evaluate()
+        res["one_pass"] = stats
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
         launch.shutdown()

@@ -195,6 +195,20 @@ def cv2_linear_resize_f(img, new_h, new_w):
     return rows[y0] * by0[:, None, None].astype(dt) + rows[y1] * by1[:, None, None].astype(dt)
 
 
+class PairFrames:
+    """One batch of aligned FLIR frame pairs as the detectors take them: thermal [N,Ht,Wt,3] and RGB [N,Hr,Wr,3] uint8 BGR
+    device tensors (data.read_image order; the RGB size may differ from the thermal one, rgb may be None when no detector
+    needs it).  GeneralizedRCNN routes it by INPUT.FORMAT: BGR (thermal_only) reads the thermal batch, BGRT / BGRTTT build
+    the fusion input on the device (pe_fusion_input_pack) exactly as the host build of
+    demo_FLIR_save_predictions.py:98-121 + float32 upload would.  One instance can be handed to every detector."""
+
+    def __init__(self, thermal, rgb=None):
+        self.thermal, self.rgb = thermal, rgb
+
+    def __len__(self):
+        return self.thermal.shape[0]
+
+
 class InferenceSampler:
     """Contiguous per-rank index blocks of ceil(N / W)."""
 

@@ -479,3 +479,24 @@ def preprocess_pack_batch(src, dst, *, src_kind, ch0, nch, flip_rgb, dst_hw, mea
     st = _lib.lib().pe_preprocess_pack_batch(_lib.ptr(src), n, src_kind, h, w, c, ch0, nch, int(flip_rgb), dst_hw[0], dst_hw[1],
                                              dst.shape[1], dst.shape[2], m, s, _lib.ptr(dst), _lib.stream())
     _lib.check(st, "pe_preprocess_pack_batch")
+
+
+def fusion_input_pack(thermal, rgb, dst, *, ch0, nch, dst_hw, mean, std, pad_multiple=32):
+    """thermal / rgb: [N,H,W,3] uint8 BGR device batches (rgb may be None when ch0 >= 3; its size may differ from the thermal
+    one); dst: [N,pad_h,pad_w,4] fp16.  Stacked channels [ch0, ch0+nch) of B,G,R,T0,T1,T2 - the RGB frame first resized to the
+    thermal size with OpenCV's 8-bit rule - resized to dst_hw with the float rule, normalised and padded: the FLIR early / middle
+    fusion input of demo_FLIR_save_predictions.py:98-121 without the host-side build (pe_fusion_input_pack)."""
+    _lib.require_cuda(thermal, rgb, dst)
+    assert thermal.dtype == torch.uint8 and thermal.dim() == 4 and thermal.shape[3] == 3 and thermal.is_contiguous()
+    n, th_h, th_w, _ = thermal.shape
+    rgb_h = rgb_w = 0
+    if rgb is not None:
+        assert rgb.dtype == torch.uint8 and rgb.dim() == 4 and rgb.shape[3] == 3 and rgb.shape[0] == n and rgb.is_contiguous()
+        rgb_h, rgb_w = rgb.shape[1], rgb.shape[2]
+    assert dst.dtype == torch.float16 and dst.shape[0] == n and dst.shape[3] == 4 and dst.is_contiguous()
+    m = (ctypes.c_float * 4)(*(list(mean) + [0.0] * (4 - len(mean))))
+    s = (ctypes.c_float * 4)(*(list(std) + [1.0] * (4 - len(std))))
+    st = _lib.lib().pe_fusion_input_pack(_lib.ptr(thermal), _lib.ptr(rgb), n, th_h, th_w, rgb_h, rgb_w,
+                                         ch0, nch, dst_hw[0], dst_hw[1], dst.shape[1], dst.shape[2], pad_multiple, m, s,
+                                         _lib.ptr(dst), _lib.stream())
+    _lib.check(st, "pe_fusion_input_pack")

@@ -1,5 +1,5 @@
 """The ProbEn CLI flag set (detectron2/utils/opt.py:3-19; the reference uses configargparse, plain argparse
-here) plus the MI355X additions --device / --batch / --world-size."""
+here) plus the MI355X additions --device / --batch / --world-size and demo_probEn's --one-pass mode."""
 import argparse
 
 
@@ -20,4 +20,12 @@ def config_parser(cmd=None):
                    help="ranks (one per GPU) the dataset is sharded over; > 1 re-launches the driver under torch.distributed.run (launch.py)")
     p.add_argument("--detectors", type=str, default="thermal_only,early_fusion,middle_fusion",
                    help="comma separated prediction files to fuse, in order (val_<name>_predictions.json)")
+    # one-pass mode of demo_probEn (stream.py -> FramePairPipeline -> ProbEn -> FLIREvaluator, no prediction files in between)
+    p.add_argument("--one-pass", action="store_true",
+                   help="demo_probEn: run the --detectors on the frame pairs themselves (decoded by --workers processes) and fuse on the GPU")
+    p.add_argument("--model_paths", type=str, default=None,
+                   help="--one-pass: comma separated weights, one per --detectors entry (.pth or synthetic://<seed>)")
+    p.add_argument("--workers", type=int, default=4, help="--one-pass: JPEG decode processes (0 = in-process, at most 15)")
+    p.add_argument("--write-predictions", action="store_true",
+                   help="--one-pass: also write every detector's val_<method>_predictions.json to --prediction_path (or --outfolder)")
     return p.parse_args(cmd) if cmd is not None else p.parse_args()

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from . import layers as L
+from .data import PairFrames
 from .structures import Boxes, Instances
 from .weights import STAGE_BLOCKS, PackedDetector
 
@@ -178,6 +179,8 @@ class GeneralizedRCNN:
         Returns NHWC4 fp16 batch(es) and [(h, w)] of the resized, unpadded images."""
         cfg = self.cfg
         C = cfg.in_channels
+        if isinstance(images, PairFrames):
+            return self._preprocess_pair(images, resize_to)
         if isinstance(images, torch.Tensor):  # one [N,H,W,C] (or [N,C,H,W] f32) batch of equally sized frames
             return self._preprocess_batch(images, resize_to)
         sizes, kinds = [], []
@@ -233,6 +236,34 @@ class GeneralizedRCNN:
                 continue
             L.preprocess_pack_batch(images.contiguous(), x, src_kind=kind, ch0=ch0, nch=nch, flip_rgb=False, dst_hw=size,
                                     mean=mean[ch0:ch0 + nch], std=std[sd0:sd0 + nch])
+            batches.append(x)
+        return batches, [size] * N
+
+    def _preprocess_pair(self, pair, resize_to):
+        """data.PairFrames: thermal_only (BGR) takes the thermal batch on the Pillow-exact route; early / middle fusion
+        (BGRT / BGRTTT) build their stacked input from the two uint8 batches in one launch per output group."""
+        cfg = self.cfg
+        if cfg.input_format == "BGR":
+            return self._preprocess_batch(pair.thermal, resize_to)
+        if cfg.input_format not in ("BGRT", "BGRTTT"):
+            raise ValueError(f"PairFrames feeds the thermal_only / early_fusion / middle_fusion detectors; INPUT.FORMAT "
+                             f"{cfg.input_format} sees the RGB frame at its own size - give it the RGB batch itself")
+        if pair.rgb is None:
+            raise ValueError(f"INPUT.FORMAT {cfg.input_format} needs the RGB batch of the frame pairs")
+        C = cfg.in_channels
+        N, h, w = pair.thermal.shape[:3]
+        size = tuple(resize_to) if resize_to is not None else (h, w)
+        d = cfg.size_divisibility
+        Hp, Wp = (size[0] + d - 1) // d * d, (size[1] + d - 1) // d * d
+        mean = list(cfg.pixel_mean)
+        std = list(cfg.pixel_std) + [cfg.pixel_std[-1]] * (C - len(cfg.pixel_std))
+        assert len(mean) == C, f"PIXEL_MEAN needs {C} entries for INPUT.FORMAT {cfg.input_format}"
+        batches = []
+        for ch0, nch in ([(0, 4)] if C == 4 else [(0, 3), (3, 3)]):
+            x = torch.empty((N, Hp, Wp, 4), dtype=torch.float16, device=self.device)
+            sd0 = 0 if ch0 == 3 else ch0    # BGRTTT: thermal half uses PIXEL_STD[:3] (meta_arch/rcnn.py:63-66)
+            L.fusion_input_pack(pair.thermal.contiguous(), pair.rgb.contiguous() if ch0 < 3 else None, x, ch0=ch0, nch=nch,
+                                dst_hw=size, mean=mean[ch0:ch0 + nch], std=std[sd0:sd0 + nch], pad_multiple=d)
             batches.append(x)
         return batches, [size] * N
 
@@ -343,7 +374,7 @@ class GeneralizedRCNN:
         out_sizes: list of (height, width) per image for the final rescale (default: resized size).
         Returns a dict of padded device tensors: boxes [N,D,4], scores, classes, class_logits,
         prob_score, vars, counts [N]."""
-        N = images.shape[0] if isinstance(images, torch.Tensor) else len(images)
+        N = images.shape[0] if isinstance(images, torch.Tensor) else len(images)   # list of frames or data.PairFrames
         batches, sizes = self._preprocess(images, resize_to)
         dev = self.device
         out_sizes = out_sizes if out_sizes is not None else sizes
