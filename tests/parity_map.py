@@ -166,6 +166,20 @@ def load_fused_fixture(golden_dir, max_sets=None):
     return sds, sets
 
 
+def labelled_gts(n, seed):
+    """The ground truth of labelled_frames(n, seed=seed) (the frames are drawn and dropped: the same random stream)."""
+    from proben_amd.synthetic import labelled_frames
+    return labelled_frames(n, seed=seed)[1]
+
+
+def fixture_ground_truth(n, seeds, workers=8):
+    """labelled_gts of several sets in spawned worker processes (7 s of normal draws per 256-frame set; the workers never touch the GPU)."""
+    import multiprocessing as mp
+    from concurrent.futures import ProcessPoolExecutor
+    with ProcessPoolExecutor(max_workers=max(1, min(workers, len(seeds))), mp_context=mp.get_context("spawn")) as ex:
+        return list(ex.map(labelled_gts, [n] * len(seeds), seeds))
+
+
 def _info(rows, f):
     r = rows[rows[:, 0] == f]
     return {"img_name": str(f), "bbox": r[:, 1:5].astype(np.float64), "score": r[:, 5].astype(np.float64), "class": r[:, 6].astype(np.int64),
@@ -209,13 +223,38 @@ def hip_detections(models, frames_t, frames_r, batch=16):
 
 
 def detector_rows(batches, which):
+    """One detector's rows in the fixture's 11 columns: frame, box x4, score, class, prob x3, var (slice [:, :7] for the COCO rows)."""
     rows = []
     for b0, dets in batches:
         d = dets[which]
         for i, c in enumerate(d["counts"].cpu().tolist()):
             b_, s_, c_ = d["boxes"][i, :c].cpu().numpy(), d["scores"][i, :c].cpu().numpy(), d["classes"][i, :c].cpu().numpy()
-            rows += [[b0 + i, *b_[j], s_[j], c_[j]] for j in range(c)]
-    return np.asarray(rows, dtype=np.float32).reshape(-1, 7)
+            p_, v_ = d["prob_score"][i, :c].cpu().numpy(), d["vars"][i, :c].cpu().numpy()
+            rows += [[b0 + i, *b_[j], s_[j], c_[j], *p_[j], v_[j]] for j in range(c)]
+    return np.asarray(rows, dtype=np.float32).reshape(-1, 11)
+
+
+def fixture_batches(rows_t, rows_r, n_frames, batch=16, device="cuda"):
+    """The inverse of detector_rows: two detectors' 11-column rows -> per-batch device dicts in GeneralizedRCNN.forward_batch's layout
+    (boxes [B,D,4], scores [B,D], classes [B,D] int32, prob_score [B,D,K], vars [B,D], counts [B]; float32), rows of a frame in file
+    order, D = the batch's longest list.  What fusion.fuse_detections reads, without running a detector."""
+    out = []
+    for b0 in range(0, n_frames, batch):
+        B = min(batch, n_frames - b0)
+        per = [[rows[rows[:, 0] == f] for f in range(b0, b0 + B)] for rows in (rows_t, rows_r)]
+        D = max(1, max(len(r) for p in per for r in p))
+        K = rows_t.shape[1] - 8
+        dets = []
+        for p in per:
+            box, sc, cl = np.zeros((B, D, 4), np.float32), np.zeros((B, D), np.float32), np.zeros((B, D), np.int32)
+            pr, va, cnt = np.zeros((B, D, K), np.float32), np.ones((B, D), np.float32), np.zeros(B, np.int32)
+            for i, r in enumerate(p):
+                c = len(r)
+                box[i, :c], sc[i, :c], cl[i, :c], pr[i, :c], va[i, :c], cnt[i] = r[:, 1:5], r[:, 5], r[:, 6], r[:, 7:7 + K], r[:, 7 + K], c
+            t = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
+            dets.append({"boxes": t(box), "scores": t(sc), "classes": t(cl), "prob_score": t(pr), "vars": t(va), "counts": t(cnt)})
+        out.append((b0, dets))
+    return out
 
 
 def hip_fused_rows(batches, method):
@@ -232,6 +271,59 @@ def hip_fused_rows(batches, method):
             assert c >= 0, "a fused image ran out of rows"
             rows += [[b0 + i, *bx[o + j], sc[o + j], cl[o + j]] for j in range(c)]
     return np.asarray(rows, dtype=np.float32).reshape(-1, 7)
+
+
+def fused_rows_mismatch(ora, hip, rtol=1e-6):
+    """Row-level identity of two routes' fused rows (frame, box x4, score, class; both in cluster order per frame): None when every frame
+    has the same number of rows, the same classes, NaN scores in the same places, finite scores within `rtol` (device log / exp against
+    glibc's) and the same float32 boxes; otherwise a description of the first difference."""
+    if len(ora) != len(hip) or not np.array_equal(ora[:, 0], hip[:, 0]):
+        fo, fh = np.bincount(ora[:, 0].astype(np.int64)), np.bincount(hip[:, 0].astype(np.int64))
+        n = max(len(fo), len(fh))
+        fo, fh = np.pad(fo, (0, n - len(fo))), np.pad(fh, (0, n - len(fh)))
+        bad = np.nonzero(fo != fh)[0]
+        return f"row counts differ: {len(ora)} / {len(hip)} rows; frames {bad[:8].tolist()} have {fo[bad[:8]].tolist()} / {fh[bad[:8]].tolist()}"
+    checks = (("class", ora[:, 6] != hip[:, 6]),
+              ("NaN score", np.isnan(ora[:, 5]) != np.isnan(hip[:, 5])),
+              ("score", np.isfinite(ora[:, 5]) & ~(np.abs(hip[:, 5].astype(np.float64) - ora[:, 5]) <= rtol * np.abs(ora[:, 5].astype(np.float64)))),
+              ("box", ~((ora[:, 1:5] == hip[:, 1:5]) | (np.isnan(ora[:, 1:5]) & np.isnan(hip[:, 1:5]))).all(1)))
+    for what, bad in checks:
+        if bad.any():
+            i = int(np.nonzero(bad)[0][0])
+            return f"{int(bad.sum())} rows differ in {what}; first: frame {int(ora[i, 0])}, row {i}: {ora[i].tolist()} / {hip[i].tolist()}"
+    return None
+
+
+def background_shares(ora_det, hip_det, n_frames, iou_min=0.9):
+    """The ProbEn background term 1 - sum(p) (float64, left to right, demo_probEn.py:36) of the detector rows both routes have (same frame
+    and class, IoU >= iou_min): per route the share that is negative (a NaN score after fusion), exactly zero (log 0 = -inf) and below
+    1e-6.  Diagnostic only: which route's detector rows sit nearer the saturation edge."""
+    io, ih = _matched_pairs(ora_det, hip_det, n_frames, iou_min)
+    out = {"pairs": int(len(io))}
+    for tag, rows, idx in (("oracle", ora_det, io), ("hip", hip_det, ih)):
+        p = rows[idx, 7:10].astype(np.float64)
+        bg = 1.0 - p[:, 0] - p[:, 1] - p[:, 2]
+        n = max(len(bg), 1)
+        out[tag] = {"negative": float((bg < 0).sum() / n), "zero": float((bg == 0).sum() / n), "below_1e-6": float((bg < 1e-6).sum() / n)}
+    return out
+
+
+def _matched_pairs(a, b, n_frames, iou_min=0.9):
+    """Greedy per-frame pairs of a's and b's rows (same class, IoU >= iou_min; match_signed's rule) -> (indices into a, indices into b)."""
+    ia_all, ib_all = [], []
+    for f in range(n_frames):
+        ia, ib = np.nonzero(a[:, 0] == f)[0], np.nonzero(b[:, 0] == f)[0]
+        used = np.zeros(len(ib), bool)
+        for i in ia:
+            cand = np.nonzero((~used) & (b[ib, 6] == a[i, 6]))[0]
+            if len(cand):
+                iou = _iou_to(a[i], b[ib[cand]])
+                j = int(iou.argmax())
+                if iou[j] >= iou_min:
+                    used[cand[j]] = True
+                    ia_all.append(i)
+                    ib_all.append(ib[cand[j]])
+    return np.asarray(ia_all, dtype=np.int64), np.asarray(ib_all, dtype=np.int64)
 
 
 def _iou_to(r, q):
@@ -301,25 +393,34 @@ def measure_fused(golden_dir, methods=FUSED_METHODS, flips=True, max_sets=None):
     for name, ft, fr, gts, ot, orr in sets:
         n = len(ft)
         batches = hip_detections(models, ft, fr)
-        ht, hr = detector_rows(batches, 0), detector_rows(batches, 1)
+        ht, hr = detector_rows(batches, 0), detector_rows(batches, 1)       # 11 columns, like the fixture's oracle rows
+        ht7, hr7 = ht[:, :7], hr[:, :7]
         if flips:      # detector-level rows only one side has (same class, IoU >= 0.9), both detectors together
-            o_in_only = np.concatenate([ot[_unmatched(ot[:, :7], ht, n), :7], orr[_unmatched(orr[:, :7], hr, n), :7]])
-            h_in_only = np.concatenate([ht[_unmatched(ht, ot[:, :7], n)], hr[_unmatched(hr, orr[:, :7], n)]])
+            o_in_only = np.concatenate([ot[_unmatched(ot[:, :7], ht7, n), :7], orr[_unmatched(orr[:, :7], hr7, n), :7]])
+            h_in_only = np.concatenate([ht7[_unmatched(ht7, ot[:, :7], n)], hr7[_unmatched(hr7, orr[:, :7], n)]])
         for method in methods:
             acc = per_method[method]
             ora = oracle_fused_rows(ot, orr, n, method)
             hip = hip_fused_rows(batches, method)
-            so, sh = coco_stats(gts, ora), coco_stats(gts, hip)
+            # the swap leg: the oracle's fusion on the PRODUCT's detector rows - splits the fused delta into a kernel part (swap vs hip,
+            # expected identical) and an input part (ora vs swap: the detector rows)
+            swap = oracle_fused_rows(ht, hr, n, method)
+            so, sh, ss = coco_stats(gts, ora), coco_stats(gts, hip), coco_stats(gts, swap)
             acc["deltas"].append((sh - so)[:6] * 100)
             ds, db, un_o, un_h = match_signed(ora, hip, n)
+            mismatch = fused_rows_mismatch(swap, hip)
             srec = {"frames": n, "ground_truth_objects": int(sum(len(g[0]) for g in gts)), "oracle_fused_rows": int(len(ora)), "hip_fused_rows": int(len(hip)),
                     "nan_scores": [int(np.isnan(ora[:, 5]).sum()), int(np.isnan(hip[:, 5]).sum())],
                     "oracle": {k: float(so[i] * 100) for i, k in enumerate(NAMES)}, "hip": {k: float(sh[i] * 100) for i, k in enumerate(NAMES)},
                     "delta": {k: float(acc["deltas"][-1][i]) for i, k in enumerate(NAMES)}, "matched_pairs": int(len(ds)), "oracle_only": un_o, "hip_only": un_h,
                     "matched_score_diff_sigma": float(np.nanstd(ds)) if len(ds) else None,
-                    "matched_box_abs_max_coord_median_px": float(np.median(np.abs(db).max(1))) if len(db) else None}
+                    "matched_box_abs_max_coord_median_px": float(np.median(np.abs(db).max(1))) if len(db) else None,
+                    "swap_exact": mismatch is None, "swap_mismatch": mismatch,
+                    "swap_delta": {k: float((sh[i] - ss[i]) * 100) for i, k in enumerate(NAMES)},
+                    "input_delta": {k: float((ss[i] - so[i]) * 100) for i, k in enumerate(NAMES)}}
             if method == methods[0]:      # the detectors alone on the same frames (method-independent)
-                for tag, o_, h_ in (("thermal", ot[:, :7], ht), ("rgb", orr[:, :7], hr)):
+                srec["background_terms"] = {"thermal": background_shares(ot, ht, n), "rgb": background_shares(orr, hr, n)}
+                for tag, o_, h_ in (("thermal", ot[:, :7], ht7), ("rgb", orr[:, :7], hr7)):
                     a, b = coco_stats(gts, o_), coco_stats(gts, h_)
                     srec["detector_" + tag] = {"oracle": {k: float(a[i] * 100) for i, k in enumerate(NAMES[:3])},
                                                "delta": {k: float((b[i] - a[i]) * 100) for i, k in enumerate(NAMES[:3])}}
@@ -349,6 +450,9 @@ def measure_fused(golden_dir, methods=FUSED_METHODS, flips=True, max_sets=None):
                 "delta_standard_error": {k: float(d[:, i].std(ddof=1) / len(d) ** 0.5) if len(d) > 1 else None for i, k in enumerate(NAMES)}}
         po, ph = coco_stats(acc["pool_gt"], np.concatenate(acc["pool_o"])), coco_stats(acc["pool_gt"], np.concatenate(acc["pool_h"]))
         mrec["pooled"] = {"frames": off, "oracle": {k: float(po[i] * 100) for i, k in enumerate(NAMES)}, "delta": {k: float((ph[i] - po[i]) * 100) for i, k in enumerate(NAMES)}}
+        for leg in ("swap_delta", "input_delta"):
+            mrec[leg + "_mean"] = {k: float(np.mean([s[leg][k] for s in acc["sets"].values()])) for k in NAMES}
+        mrec["swap_exact_sets"] = int(sum(s["swap_exact"] for s in acc["sets"].values()))
         if flips:
             mrec["flip_class_totals"] = acc["totals"]
         rec["methods"]["/".join(method)] = mrec

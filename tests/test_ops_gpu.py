@@ -1018,3 +1018,104 @@ def test_boxhead_matches_oracle_quirks():
         np.testing.assert_array_equal(o["logits"][n, :c].cpu().numpy(), want["class_logits"].numpy())
         np.testing.assert_allclose(o["probs"][n, :c].cpu().numpy(), want["prob_score"].numpy(), rtol=2e-6, atol=1e-7)
         np.testing.assert_allclose(o["vars"][n, :c].cpu().numpy(), want["vars"].numpy().reshape(-1), rtol=2e-6)
+
+
+def _softmax_rows(rng, n, K):
+    """Box-head logit rows [n, K+1] on a 2^-12 grid (|logit| < 64, so the kernel's float32 `logit - max` is exact): a foreground top class,
+    foreground margins 0-25 (a tenth of the rows tied exactly at the top, a tenth with all other logits tied), background and the other
+    classes below the top by the margin plus up to 3."""
+    q = lambda a: np.round(np.asarray(a) * 4096.0) / 4096.0  # noqa: E731
+    top = q(rng.uniform(-5.0, 10.0, n))
+    margin = q(rng.uniform(0.0, 25.0, n))
+    lg = top[:, None] - margin[:, None] - q(rng.uniform(0.0, 3.0, (n, K + 1)))
+    t = rng.integers(0, K, n)
+    lg[np.arange(n), t] = top
+    tie = rng.random(n) < 0.1
+    t2 = (t + 1 + rng.integers(0, K - 1, n)) % K if K > 1 else t
+    lg[tie, t2[tie]] = top[tie]
+    flat = rng.random(n) < 0.1
+    lg[flat] = np.where(np.arange(K + 1)[None] == t[flat, None], top[flat, None], (top - margin)[flat, None])
+    return lg.astype(np.float32)
+
+
+def _ulp32(v):
+    """float32 spacing at the float64 value v (> 0): 2^(floor(log2 v) - 23), the subnormal spacing below 2^-126."""
+    e = np.floor(np.log2(v))
+    return np.exp2(np.maximum(e, -126.0) - 23.0)
+
+
+@pytest.mark.parametrize("K", [3, 80])
+def test_boxhead_softmax_against_float64_at_saturation(K):
+    """The box head's softmax (csrc/boxhead.hip: x = l - max, expf, float32 left-to-right sum over the K+1 columns, divide) against the
+    float64 softmax of the SAME float32 logits, on ~10^5 rows per K through model._roi_heads(head=...): proposals on a grid that does not
+    overlap (NMS keeps every candidate), zero deltas, score threshold 0.05.  ProbEn's background term 1 - sum(p) is set near saturation
+    by these last bits (the float32 spacing below 1.0 is 6e-8), so they are pinned, not `atol=1e-7`.
+
+    (1) Maximum error, derived per element.  With u = 2^-24 and first-order terms: x_k = l_k - max is exact on these logits (dx_k = 0;
+    kept in the bound as the exact float32 rounding of the subtraction, computed here); e_k = expf(x_k) has a relative error <= 2u
+    (1 ulp); the sum S of the e_j carries their weighted relative error sum_j (e_j / S) (|dx_j| + 2u) plus its own roundings,
+    <= sum_i |partial_i| u / S over the K+1 additions; the divide adds u.  So |p_k - p_k*| / p_k* <= r_k = |dx_k| + 2u + sum_j (e_j / S)
+    (|dx_j| + 2u) + sum_i |partial_i| u / S + u, i.e. r_k p_k* / ulp(p_k*) ulps of float32 (<= 2^24 r_k; a few ulps), + 1e-3 ulp for the
+    second-order terms.  __expf (exp2 of a rounded x log2 e: ~|x| ulps), a lower-accuracy divide or a reordered sum break it.
+
+    (2) Mean signed error of the top probability over the saturated rows (p > 0.999), in ulps: rounding to nearest is not unbiased
+    here - an e_j below half an ulp of 1 vanishes from the sum, so p = 1 / S leans upward - so the mean is compared to the same sequence
+    evaluated with correctly rounded float32 operations (float64 exp rounded to float32) within 0.1 ulp: a fast reciprocal, __expf or
+    another summation order shifts it."""
+    import proben_amd  # noqa: F401
+    from proben_amd.rcnn import DetectorConfig, GeneralizedRCNN
+    from proben_amd.synthetic import synthetic_state_dict
+    P, N, H, W = 100, 1000, 600, 600
+    model = GeneralizedRCNN(DetectorConfig(num_classes=K, score_thresh=0.05, post_nms_topk=P, detections_per_image=P),
+                            synthetic_state_dict(50, K, 3, seed=4))
+    rng = np.random.default_rng(1016 + K)
+    logits = _softmax_rows(rng, N * P, K)
+    head = np.zeros((N * P, model.w.head_stride), np.float32)
+    head[:, :K + 1] = logits
+    g = np.arange(P)
+    cell = np.stack([(g % 10) * 60 + 5, (g // 10) * 60 + 5, (g % 10) * 60 + 50, (g // 10) * 60 + 50], 1).astype(np.float32)
+    props = torch.from_numpy(np.tile(cell[None], (N, 1, 1))).cuda()
+    pcnt = torch.full((N,), P, dtype=torch.int32, device="cuda")
+    hw = torch.tensor([[H, W]] * N, dtype=torch.int32, device="cuda")
+    det = model._roi_heads(None, props, pcnt, hw, hw.clone(), N, head=torch.from_numpy(head).cuda())
+    cnt = det["counts"].cpu().numpy()
+    rows = det["rows"].cpu().numpy()
+    sel = np.concatenate([n * P + rows[n, :cnt[n]] for n in range(N)])
+    got = np.concatenate([det["prob_score"][n, :cnt[n]].cpu().numpy() for n in range(N)]).astype(np.float64)
+    np.testing.assert_array_equal(np.concatenate([det["class_logits"][n, :cnt[n]].cpu().numpy() for n in range(N)]), logits[sel])
+    assert len(sel) >= 0.9 * N * P, len(sel)
+    lg = logits[sel]
+    # float64 softmax of the same float32 logits
+    l64 = lg.astype(np.float64)
+    e64 = np.exp(l64 - l64.max(1, keepdims=True))
+    p64 = e64 / e64.sum(1, keepdims=True)
+    # the bound's ingredients, from the kernel's own sequence
+    x32 = (lg - lg.max(1, keepdims=True)).astype(np.float32)
+    dx = np.abs(x32.astype(np.float64) - (l64 - l64.max(1, keepdims=True)))
+    u = 2.0 ** -24
+    e32 = np.exp(x32.astype(np.float64)).astype(np.float32)
+    part = np.zeros(len(lg), np.float32)
+    round_sum = np.zeros(len(lg))
+    for k in range(K + 1):
+        part = (part + e32[:, k]).astype(np.float32)
+        round_sum += np.abs(part.astype(np.float64)) * u
+    S = part.astype(np.float64)
+    wsum = ((e32.astype(np.float64) / S[:, None]) * (dx + 2 * u)).sum(1)
+    r = dx + 2 * u + (wsum + round_sum / S + u)[:, None]
+    p64k, r = p64[:, :K], r[:, :K]
+    ulp = _ulp32(p64k)
+    err = (got - p64k) / ulp
+    bound = r * p64k / ulp + 1e-3
+    worst = np.unravel_index(np.argmax(np.abs(err) - bound), err.shape)
+    print(f"K={K}: {len(sel)} rows, max |error| {np.abs(err).max():.3f} ulp (bound at that element {bound[worst]:.3f})")
+    assert (np.abs(err) <= bound).all(), (worst, err[worst], bound[worst], lg[worst[0]].tolist())
+    # (2) bias over the saturated rows, against the correctly rounded float32 sequence
+    emu = (e32 / part[:, None]).astype(np.float32).astype(np.float64)[:, :K]
+    top = p64k.argmax(1)
+    sat = p64k[np.arange(len(top)), top] > 0.999
+    assert sat.sum() > 0.3 * len(sat)
+    i = np.nonzero(sat)[0]
+    mean_dev = float(err[i, top[i]].mean())
+    mean_emu = float(((emu - p64k) / ulp)[i, top[i]].mean())
+    print(f"K={K}: {len(i)} saturated rows, mean signed error of the top probability {mean_dev:+.4f} ulp (correctly rounded sequence {mean_emu:+.4f})")
+    assert abs(mean_dev - mean_emu) <= 0.1, (mean_dev, mean_emu)

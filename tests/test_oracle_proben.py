@@ -81,3 +81,41 @@ def test_oracle_driver_reproduces_the_references_records(golden_dir):
             np.testing.assert_allclose(g["boxes"], np.asarray(w["boxes"], np.float32).reshape(-1, 4), rtol=1e-6, atol=1e-5)
     # the firing patterns of the fixture cover every branch of the driver's case split
     assert {tuple(f) for f in z["fire"]} == {(a, b, c) for a in (0, 1) for b in (0, 1) for c in (0, 1)}
+
+
+# ---- saturation edges (tests/golden/gen_proben_saturated.py: softmax rows whose float64 sum(p) is below / exactly / above 1, scores of
+# exactly 1.0f, IoU exactly 0.5 under the "+1" rule and one float32 ulp off, degenerate boxes, class-band overlap, extreme variances,
+# three detectors, the K = 1 form with scores 0 and 1) ----
+@pytest.fixture(scope="module")
+def saturated(golden_dir):
+    return np.load(os.path.join(golden_dir, "proben_saturated.npz"))
+
+
+@pytest.mark.parametrize("sm,bm", [(s, b) for s in SCORE for b in BOX if not (s == "max" and b == "argmax")])
+def test_oracle_matches_reference_fusion_at_saturation(saturated, sm, bm):
+    """Scores bit for bit (NaN included), classes exact, boxes to 1e-12: the oracle's float64 arithmetic IS the reference's here.
+    (max / argmax is the nms_1 route, which needs torchvision: not in the fixture.)"""
+    z = saturated
+    nan_seen = 0
+    for ci in range(int(z["num_cases"])):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            b, s, c = O.fusion([sm, bm], *load_case(z, ci))
+        rb, rs, rc = z[f"c{ci}_{sm}_{bm}_boxes"], z[f"c{ci}_{sm}_{bm}_scores"], z[f"c{ci}_{sm}_{bm}_classes"]
+        assert b.shape == rb.shape, (ci, sm, bm)
+        np.testing.assert_array_equal(c, rc, err_msg=f"case {ci}")
+        np.testing.assert_array_equal(s.view(np.int32)[~np.isnan(s)], rs.view(np.int32)[~np.isnan(rs)], err_msg=f"case {ci}")
+        np.testing.assert_array_equal(np.isnan(s), np.isnan(rs), err_msg=f"case {ci}")
+        np.testing.assert_allclose(b, rb, rtol=1e-12, atol=1e-12, equal_nan=True, err_msg=f"case {ci}")
+        nan_seen += int(np.isnan(rs).sum())
+    if sm == "probEn":
+        assert nan_seen >= 5     # the fixture does reach the negative background term
+
+
+def test_binary_bayesian_fusion_at_zero_and_one(saturated):
+    vals, off = saturated["binary_in"], 0
+    for m, want in zip(saturated["binary_len"], saturated["binary_out"]):
+        v = vals[off:off + m]
+        off += m
+        with np.errstate(divide="ignore", invalid="ignore"):
+            got, _ = O.fuse_score("probEn_binary", np.zeros((m, 1)), v, 0)
+        assert (np.isnan(got) and np.isnan(want)) or got == want, (v, got, want)

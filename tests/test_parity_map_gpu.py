@@ -151,3 +151,22 @@ def test_fused_map_is_consistent_with_the_north_star_tolerance(golden_dir):
             c = committed["methods"][method]["sets"][name]
             for n in ("AP", "AP50", "AP75"):
                 assert abs(s["delta"][n] - c["delta"][n]) <= 1e-6, (method, name, n, s["delta"][n], c["delta"][n])
+
+
+def test_fused_swap_leg_the_kernel_part_of_the_fused_delta_is_zero(golden_dir):
+    """The swap leg of the live record: the ORACLE's fusion on the PRODUCT's own detector rows (prob_score / vars from the result dicts)
+    against the product's fusion of the same rows (pe_proben_pack_detections -> pe_proben_fuse_batch) - per set and method the same
+    fused rows (count, classes, NaN places, scores to 1e-6, float32 boxes) and the same AP / AP50 / AP75 to 1e-9.  With that exact,
+    the whole fused delta above is the detector rows' (the input part), none of it ProbEn's kernel."""
+    rec = fused_record(golden_dir)
+    for method, m in rec["methods"].items():
+        print(method, "sets", m["n_sets"], "swap-exact sets", m["swap_exact_sets"], "fused delta", m["delta_mean"], "input part",
+              m["input_delta_mean"], "kernel part", m["swap_delta_mean"])
+        first = next(iter(m["sets"].values()))
+        if "background_terms" in first:
+            print(method, "background terms of matched detector rows (first set)", first["background_terms"])
+        for name, s in m["sets"].items():
+            assert s["swap_exact"], (method, name, s["swap_mismatch"])
+            for n in ("AP", "AP50", "AP75"):
+                assert abs(s["swap_delta"][n]) <= 1e-7, (method, name, n, s["swap_delta"])     # points of 100: 1e-9 of the AP
+                assert abs(s["input_delta"][n] + s["swap_delta"][n] - s["delta"][n]) <= 1e-9, (method, name, n)

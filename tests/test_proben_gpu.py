@@ -158,3 +158,73 @@ def test_full_size_properties():
     assert torch.equal(outk["counts"], counts)  # clustering is independent of the fusion formulas
     for i in (0, 1, 777, 4095):
         assert torch.equal(outk["keep"][oh[i]:oh[i] + ch[i]], out["keep"][oh[i]:oh[i] + ch[i]])
+
+
+# ---- saturation edges: tests/golden/proben_saturated.npz (gen_proben_saturated.py, the reference's own fusion) ----
+@pytest.fixture(scope="module")
+def saturated(golden_dir):
+    return np.load(os.path.join(golden_dir, "proben_saturated.npz"))
+
+
+def _assert_like_reference(b, s, c, rb, rs, rc, what):
+    assert b.shape == rb.shape, what
+    np.testing.assert_array_equal(c, rc, err_msg=what)
+    np.testing.assert_array_equal(np.isnan(s), np.isnan(rs), err_msg=what)
+    np.testing.assert_allclose(s, rs, rtol=1e-6, atol=0, equal_nan=True, err_msg=what)
+    np.testing.assert_allclose(b, rb, rtol=1e-9, atol=1e-9, equal_nan=True, err_msg=what)
+
+
+@pytest.mark.parametrize("sm,bm", COMBOS)
+def test_hip_matches_reference_at_saturation(saturated, sm, bm):
+    """fusion.fusion (one image per launch) and fuse_batch (all cases in one launch) against the reference's outputs on softmax rows whose
+    float64 sum(p) is below / exactly / above 1 (log 0 = -inf, NaN background), scores of exactly 1.0f, IoU exactly 0.5 and one float32 ulp
+    off, 0/0 IoUs of degenerate boxes, class-band overlap, variances of 1e-6 / 1e6 and three detectors.  Tolerances of
+    test_hip_matches_reference_goldens, NaN scores in the same places.  The batched launch runs both clustering forms: the bit-matrix walk
+    (bound = the longest image) and the sequential walk (max_rows=1100)."""
+    from proben_amd import fusion as F
+    z = saturated
+    n = int(z["num_cases"])
+    for ci in range(n):
+        b, s, c = F.fusion([sm, bm], *load_case(z, ci))
+        _assert_like_reference(np.asarray(b, dtype=np.float64).reshape(-1, 4), s.numpy(), c.numpy(), z[f"c{ci}_{sm}_{bm}_boxes"],
+                               z[f"c{ci}_{sm}_{bm}_scores"], z[f"c{ci}_{sm}_{bm}_classes"], f"fusion case {ci}")
+    bb, ss, pp, vv, cc, offs = F.pack_infos([load_case(z, ci) for ci in range(n)])
+    offs_h = offs.cpu().numpy()
+    for bound in (None, 1100):
+        out = F.fuse_batch(bb, ss, pp, vv, cc, offs, sm, bm, max_rows=bound)
+        cnt = out["counts"].cpu().numpy()
+        ob, os_, oc = out["boxes"].cpu().numpy(), out["scores"].cpu().numpy(), out["classes"].cpu().numpy()
+        for ci in range(n):
+            sl = slice(offs_h[ci], offs_h[ci] + cnt[ci])
+            _assert_like_reference(ob[sl], os_[sl], oc[sl], z[f"c{ci}_{sm}_{bm}_boxes"], z[f"c{ci}_{sm}_{bm}_scores"],
+                                   z[f"c{ci}_{sm}_{bm}_classes"], f"fuse_batch max_rows={bound} case {ci}")
+
+
+def test_binary_mode_at_zero_and_one(saturated):
+    """K = 1 (PROBEN_BINARY) on clusters whose member scores include exactly 0 and 1 (log 0 = -inf on either side, 0 / 0 = NaN):
+    each vector of the fixture is one image of identical boxes, its rows given in cluster order reversed - the pivot (highest score,
+    ties: highest index) last in the sum, matches in sorted order before it, as demo_probEn.py:24-30 receives them."""
+    from oracle import proben as O
+    from proben_amd import fusion as F
+    import itertools
+    vals, lens, want = saturated["binary_in"], saturated["binary_len"], saturated["binary_out"]
+    vecs = np.split(vals, np.cumsum(lens)[:-1])
+    for v, w in zip(vecs, want):
+        rows = len(v)
+        # an input order whose clustering takes v[-1] as the pivot and v[:-1] as its matches in that order
+        for perm in itertools.permutations(range(rows)):
+            sc = v[list(perm)]
+            od = O.order_desc(sc)
+            cl = [perm[i] for i in od[1:]] + [perm[od[0]]]
+            if cl == list(range(rows)):
+                break
+        else:
+            pytest.fail(f"no input order gives the cluster order of {v}")
+        info = {"img_name": "x", "bbox": np.tile([[10.0, 10.0, 50.0, 60.0]], (rows, 1)), "score": sc, "class": np.zeros(rows, int),
+                "prob": sc[:, None], "vars": np.ones((rows, 1))}
+        b, s, p, vv, c, offs = F.pack_infos([[info, dict(info, bbox=np.zeros((0, 4)), score=np.zeros(0), prob=np.zeros((0, 1)),
+                                                         vars=np.zeros((0, 1)), **{"class": np.zeros(0, int)})]])
+        out = F.fuse_batch(b, s, p, vv, c, offs, "probEn_binary", "avg")
+        assert int(out["counts"][0]) == 1
+        got = float(out["scores"][0])
+        assert (np.isnan(got) and np.isnan(w)) or got == pytest.approx(np.float32(w), rel=1e-6, abs=0), (v, got, w)
