@@ -93,6 +93,43 @@ int pe_proben_pack_detections(const float* const* det_boxes_host, const float* c
                               void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Temperature calibration of the detectors' class posteriors (csrc/calibrate.hip): one scalar T per detector,
+ *   p = softmax(logits / T)  over the K + 1 columns of the box head's class_logits (background last),
+ * computed per row in float64: z_k = (double)logit_k / T, m = max_k z_k, p_k = exp(z_k - m) / sum_j exp(z_j - m).
+ * Nothing is clamped: a NaN / +inf logit gives a NaN row, as the float64 NumPy expression does.
+ * Every entry point checks its arguments before any device work: T must be finite and > 0.
+ *
+ * pe_proben_pack_logits: pe_proben_pack_detections with det_logits_host[d] (f32 [B,D,K+1]) in place of the probabilities and
+ *   temperatures_host[d] (host doubles, one per detector).  out_probs receives the K foreground p_k, out_scores the row's own
+ *   p_class (so avg / max score fusion and the clustering order see the calibrated score; a class outside [0,K] gives NaN).
+ *   Boxes, variances, classes, offsets, counts and the single-source flag are those of pe_proben_pack_detections, bit for bit.
+ *   The background column is not stored: pe_proben_fuse_batch forms it as 1 - sum(p).
+ * pe_calibrated_softmax: the same arithmetic over a flat f32 [num_rows, num_columns] tensor; out_probs f64 [num_rows, num_columns]
+ *   holds all K + 1 columns.  A row gets the same bits here and in pe_proben_pack_logits.
+ * pe_temperature_nll: for each of num_temperatures <= 64 candidates T_t (host doubles), over logits f32 [num_rows, num_columns] and
+ *   labels i32 [num_rows] in [0, K] (K = background):
+ *     out[2t]     = sum_i -log softmax(logits_i / T_t)[label_i]
+ *     out[2t + 1] = its derivative with respect to log T_t = sum_i (z_label - sum_k p_k z_k)
+ *   One read of the logits serves all candidates.  Deterministic: per-workgroup partial sums in a fixed order into
+ *   workspace (f64, PE_TEMPERATURE_NLL_MAX_BLOCKS * num_temperatures * 2 values), then one fixed-order pass; no floating-point
+ *   atomics, so the same input gives the same bits.  out_flags i32 [2]: [0] = rows whose label is outside [0, K] (they add nothing
+ *   to the sums: the caller must treat a non-zero count as an argument error), [1] = 1 + the largest such row index.
+ * ------------------------------------------------------------------------------------------- */
+#define PE_TEMPERATURE_NLL_MAX_BLOCKS 1024
+int pe_proben_pack_logits(const float* const* det_boxes_host, const int32_t* const* det_classes_host,
+                          const float* const* det_logits_host, const float* const* det_vars_host,
+                          const int32_t* const* det_counts_host, const double* temperatures_host,
+                          int32_t num_detectors, int32_t num_images, int32_t det_stride, int32_t num_classes,
+                          int32_t max_class, int32_t row_stride, double* out_boxes, double* out_scores,
+                          double* out_probs, double* out_vars, int32_t* out_classes, int32_t* out_offsets,
+                          int32_t* out_counts, int32_t* out_single_source, void* stream);
+int pe_calibrated_softmax(const float* logits, int64_t num_rows, int32_t num_columns, double temperature,
+                          double* out_probs, void* stream);
+int pe_temperature_nll(const float* logits, const int32_t* labels, int64_t num_rows, int32_t num_columns,
+                       const double* temperatures_host, int32_t num_temperatures, double* workspace,
+                       double* out, int32_t* out_flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused convolution / GEMM: NHWC fp16 activations, [Cout][KH][KW][Cin] fp16 weights, fp32 accumulate
  * on MFMA, epilogue = + bias[Cout] (fp32) + residual + ReLU, fp16 (or fp32) NHWC output.
  * Replaces, per layer, detectron2.layers.Conv2d.forward (layers/wrappers.py:62-98) + FrozenBatchNorm2d

@@ -1,0 +1,228 @@
+"""Temperature calibration of the detectors' class posteriors ahead of ProbEn.
+
+ProbEn multiplies the detectors' posteriors, which is right for calibrated posteriors only.  One scalar T per detector,
+    p = softmax(class_logits / T)            (K + 1 columns, background last; float64 on the device, csrc/calibrate.hip)
+keeps every detection's argmax and ranking.  This module holds
+  calibrated_probs   the row arithmetic of pe_proben_pack_logits over a flat [M, K+1] tensor
+  match_labels       detections -> labels in [0, K] from the ground truth
+  fit_temperature    T that minimises the negative log-likelihood of the labels (pe_temperature_nll, 64 candidates per launch)
+  save / load        the calibration file  {"detectors": {name: T}, "nll": {...}, "rows": {...}}
+  resolve / calibrate_j1 / require_logits   what the drivers (fusion.fusion, late_fusion, cli/demo_probEn) share.
+"""
+import ctypes
+import json
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+NLL_CANDIDATES = 64          # pe_temperature_nll's limit: one launch evaluates this many temperatures
+NLL_MAX_BLOCKS = 1024        # PE_TEMPERATURE_NLL_MAX_BLOCKS (include/proben_hip.h): sizes the partial-sum workspace
+
+
+def check_temperature(t, what="temperature"):
+    t = float(t)
+    if not (math.isfinite(t) and t > 0):
+        raise ValueError(f"{what} {t!r} is not finite and > 0")
+    return t
+
+
+def calibrated_probs(logits, T):
+    """logits: CUDA tensor [M, K+1] (background last), T: one positive float.  Returns (p f64 [M, K], background f64 [M]):
+    softmax(logits / T) in float64, the bits pe_proben_pack_logits writes for the same row."""
+    _lib.require_cuda(logits)
+    if logits.dim() != 2 or logits.shape[1] < 2:
+        raise ValueError(f"calibrated_probs: logits must be [M, K+1] with K >= 1, got {tuple(logits.shape)}")
+    logits = logits.contiguous().float()
+    M, k1 = logits.shape
+    out = torch.empty((M, k1), dtype=torch.float64, device=logits.device)
+    st = _lib.lib().pe_calibrated_softmax(_lib.ptr(logits), M, k1, float(T), _lib.ptr(out), _lib.stream())
+    _lib.check(st, "pe_calibrated_softmax")
+    return out[:, :k1 - 1], out[:, k1 - 1]
+
+
+def match_labels(boxes, classes, gt_boxes, gt_classes, iou_thresh=0.5, gt_crowd=None, num_classes=3):
+    """Label of every detection for the fit: the class of the ground-truth box it overlaps most, at IoU >= iou_thresh, whatever
+    class the detection itself predicted (`classes` only sizes the result: a confident wrong class is what the NLL must see);
+    every other detection is background (label `num_classes`).  Ties go to the lower ground-truth index.  Crowd boxes
+    (gt_crowd != 0) take no part, as FLIREvaluator never lets one count as a match for a true positive; annotations with
+    `ignore` set are already dropped by data.load_coco_json.  boxes [n,4], gt_boxes [g,4] XYXY; returns int32 [n] (CPU)."""
+    from .finetune import pairwise_iou
+    boxes = torch.as_tensor(np.asarray(boxes, dtype=np.float64)).reshape(-1, 4)
+    n = boxes.shape[0]
+    assert len(classes) == n, f"match_labels: {len(classes)} classes for {n} boxes"
+    labels = torch.full((n,), int(num_classes), dtype=torch.int32)
+    gt_boxes = torch.as_tensor(np.asarray(gt_boxes, dtype=np.float64)).reshape(-1, 4)
+    gt_classes = torch.as_tensor(np.asarray(gt_classes, dtype=np.int64)).reshape(-1)
+    if gt_crowd is not None:
+        keep = torch.as_tensor(np.asarray(gt_crowd)).reshape(-1) == 0
+        gt_boxes, gt_classes = gt_boxes[keep], gt_classes[keep]
+    if n == 0 or gt_boxes.shape[0] == 0:
+        return labels
+    iou = pairwise_iou(boxes, gt_boxes)                  # float64 [n, g]
+    best = iou.max(dim=1).values
+    first = (iou == best[:, None]).int().argmax(dim=1)   # the lowest index among equal maxima
+    hit = best >= iou_thresh
+    labels[hit] = gt_classes[first[hit]].to(torch.int32)
+    return labels
+
+
+def temperature_nll(logits, labels, temperatures):
+    """(nll, d nll / d log T) per candidate, float64 numpy [n_t] each; logits CUDA f32 [M, K+1], labels CUDA i32 [M] in [0, K],
+    at most 64 candidates.  One pe_temperature_nll launch; synchronises (the result and the bad-label flag come back together)."""
+    _lib.require_cuda(logits, labels)
+    logits = logits.contiguous().float()
+    labels = labels.contiguous().to(torch.int32)
+    M, k1 = logits.shape
+    assert labels.shape == (M,), f"temperature_nll: {tuple(labels.shape)} labels for {M} rows"
+    ts = [float(t) for t in temperatures]
+    n_t = len(ts)
+    dev = logits.device
+    # [out 2 n_t | flags (2 x i32 in one f64 slot)] in one buffer: one download
+    res = torch.empty((2 * n_t + 1,), dtype=torch.float64, device=dev)
+    work = torch.empty((NLL_MAX_BLOCKS * max(n_t, 1) * 2,), dtype=torch.float64, device=dev)
+    flags = res[2 * n_t:].view(torch.int32)
+    st = _lib.lib().pe_temperature_nll(_lib.ptr(logits), _lib.ptr(labels), M, k1, (ctypes.c_double * max(n_t, 1))(*ts), n_t,
+                                      _lib.ptr(work), _lib.ptr(res), ctypes.c_void_p(flags.data_ptr()), _lib.stream())
+    _lib.check(st, "pe_temperature_nll")
+    host = res.cpu()
+    bad, last = host[2 * n_t:].view(torch.int32).tolist()
+    if bad:
+        raise ValueError(f"temperature_nll: {bad} of {M} rows have a label outside [0, {k1 - 1}] (row {last - 1} is one, "
+                         f"label {int(labels[last - 1])})")
+    out = host[:2 * n_t].numpy().reshape(n_t, 2)
+    return out[:, 0].copy(), out[:, 1].copy()
+
+
+def fit_temperature(logits, labels, lo=0.05, hi=20.0, tol=1e-6):
+    """T in [lo, hi] that minimises sum_i -log softmax(logits_i / T)[label_i], by repeated 64-point bracketing over log T: every round
+    evaluates 64 log-spaced candidates in one launch and keeps the interval in which d nll / d log T changes sign, until it is
+    narrower than `tol` in log T.  The NLL is convex in 1 / T, so it has one minimum along log T and its derivative one sign change:
+    the bracket holds the minimum.  (The derivative, not the NLL values, picks the interval: near the minimum the NLL differs
+    between neighbours by less than float64 resolves, the derivative does not.)
+    Returns a dict: T (the end of the final bracket with the smaller NLL), nll (at T), nll_at_1, dnll (d nll / d log T at T),
+    bracket (T_lo, T_hi), bracket_dnll (the derivative at the two ends), rounds, rows, at_bound: "lo" / "hi" when the NLL still
+    falls towards that end of [lo, hi] - the search range, not the data, decided T, which is then that end - else None."""
+    lo, hi = check_temperature(lo, "lo"), check_temperature(hi, "hi")
+    if not lo < hi:
+        raise ValueError(f"fit_temperature: lo {lo} >= hi {hi}")
+    a, b = math.log(lo), math.log(hi)
+    rounds, at = 0, None
+    while True:
+        xs = np.linspace(a, b, NLL_CANDIDATES)
+        nll, dn = temperature_nll(logits, labels, np.exp(xs))
+        rounds += 1
+        if not (np.all(np.isfinite(nll)) and np.all(np.isfinite(dn))):
+            raise ValueError("fit_temperature: the NLL is not finite (non-finite logits?)")
+        up = np.nonzero(dn >= 0)[0]
+        j = int(up[0]) if len(up) else NLL_CANDIDATES
+        if rounds == 1 and j in (0, NLL_CANDIDATES):       # rising from lo on, or still falling at hi
+            at = "lo" if j == 0 else "hi"
+            i = 0 if j == 0 else NLL_CANDIDATES - 1
+            x, f, d, br, bd = xs[i], nll[i], dn[i], (xs[i], xs[i]), (dn[i], dn[i])
+            break
+        j = min(max(j, 1), NLL_CANDIDATES - 1)
+        a, b = xs[j - 1], xs[j]
+        if b - a < tol or rounds >= 32:
+            i = j - 1 if nll[j - 1] <= nll[j] else j
+            x, f, d, br, bd = xs[i], nll[i], dn[i], (a, b), (dn[j - 1], dn[j])
+            break
+    n1, _ = temperature_nll(logits, labels, [1.0])
+    return {"T": float(math.exp(x)), "nll": float(f), "nll_at_1": float(n1[0]), "dnll": float(d),
+            "bracket": (float(math.exp(br[0])), float(math.exp(br[1]))), "bracket_dnll": (float(bd[0]), float(bd[1])),
+            "rounds": rounds, "rows": int(logits.shape[0]), "at_bound": at}
+
+
+def save(path, detectors, nll=None, rows=None, **extra):
+    """Write the calibration file.  detectors {name: T}; nll {name: {"before": .., "after": ..}}; rows {name: fitted rows};
+    extra keys (cli/fit_temperature adds "holdout" and "fitted_image_ids") are kept as given."""
+    rec = {"detectors": {k: check_temperature(v, f"temperature of {k}") for k, v in detectors.items()},
+           "nll": nll or {}, "rows": rows or {}}
+    rec.update(extra)
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1)
+    return rec
+
+
+def load(path):
+    with open(path) as f:
+        rec = json.load(f)
+    if not isinstance(rec.get("detectors"), dict):
+        raise ValueError(f"{path}: not a calibration file (no \"detectors\" table)")
+    for k, v in rec["detectors"].items():
+        check_temperature(v, f"{path}: temperature of {k}")
+    return rec
+
+
+def parse_temperatures(text, names):
+    """--temperatures value -> [T per name].  'a,b[,c]' is matched by position, 'name=a,name=b' by name; not both."""
+    items = [x.strip() for x in text.split(",") if x.strip()]
+    named = ["=" in x for x in items]
+    if any(named) != all(named):
+        raise ValueError(f"--temperatures {text!r} mixes positional and name=value entries")
+    if not all(named):
+        if len(items) != len(names):
+            raise ValueError(f"--temperatures lists {len(items)} values for {len(names)} --detectors ({','.join(names)})")
+        return [check_temperature(x, f"temperature of {n}") for x, n in zip(items, names)]
+    table = {}
+    for x in items:
+        k, v = x.split("=", 1)
+        if k in table:
+            raise ValueError(f"--temperatures names {k} twice")
+        table[k] = v
+    return resolve(table, names, "--temperatures")
+
+
+def resolve(table, names, source):
+    """{name: T} -> [T per name]; every name must be there."""
+    missing = [n for n in names if n not in table]
+    if missing:
+        raise ValueError(f"{source} has no temperature for {','.join(missing)} (it lists {','.join(sorted(table)) or 'nothing'})")
+    return [check_temperature(table[n], f"temperature of {n}") for n in names]
+
+
+def require_logits(det, name):
+    """A prediction dict (late_fusion J1 schema) must carry K+1 logits for every detection; `name` = the file it came from."""
+    rows = det.get("class_logits")
+    if rows is None:
+        raise ValueError(f"{name}: no class_logits: temperature calibration needs the detectors' logits "
+                         "(write the predictions with cfg.MODEL.ROI_BOX_HEAD.OUTPUT_LOGITS)")
+    for i, (lg, bx) in enumerate(zip(rows, det["boxes"])):
+        if len(lg) != len(bx) or any(len(r) < 2 for r in lg):
+            raise ValueError(f"{name}: no class_logits for the detections of image {i} ({det['image'][i]}): temperature calibration "
+                             "needs the detectors' logits (write the predictions with cfg.MODEL.ROI_BOX_HEAD.OUTPUT_LOGITS)")
+
+
+def calibrate_rows(logits, classes, T, device="cuda"):
+    """Python lists of one detector's rows -> (probs f64 ndarray [n, K], scores f64 ndarray [n] = the row's own p_class)."""
+    lg = torch.tensor(logits, dtype=torch.float32).reshape(len(logits), -1)
+    if lg.shape[0] == 0:
+        return np.zeros((0, max(lg.shape[1] - 1, 0))), np.zeros((0,))
+    p, bg = calibrated_probs(lg.to(device), T)
+    full = torch.cat([p, bg[:, None]], dim=1).cpu()
+    cls = torch.tensor(classes, dtype=torch.int64)
+    ok = (cls >= 0) & (cls < full.shape[1])
+    score = torch.full((len(cls),), float("nan"), dtype=torch.float64)
+    score[ok] = full[ok].gather(1, cls[ok, None])[:, 0]
+    return full[:, :-1].numpy(), score.numpy()
+
+
+def calibrate_j1(det, T, name="prediction file", device="cuda"):
+    """A copy of a J1 prediction dict whose probs / scores are the calibrated ones, from its class_logits (one launch over all the
+    file's rows).  Scores stay float64 here; they are rounded where the uncalibrated route rounds them."""
+    require_logits(det, name)
+    flat = [r for rows in det["class_logits"] for r in rows]
+    cls = [c for rows in det["classes"] for c in rows]
+    out = dict(det)
+    if not flat:
+        return out
+    p, s = calibrate_rows(flat, cls, T, device)
+    probs, scores, k = [], [], 0
+    for rows in det["class_logits"]:
+        probs.append(p[k:k + len(rows)].tolist())
+        scores.append(s[k:k + len(rows)].tolist())
+        k += len(rows)
+    out["probs"], out["scores"] = probs, scores
+    return out

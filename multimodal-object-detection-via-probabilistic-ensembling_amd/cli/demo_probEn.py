@@ -10,6 +10,10 @@ still writes them, so the two-stage route can be replayed):
 
     python -m proben_amd.cli.demo_probEn --one-pass --dataset_path DATA/FLIR/val --detectors thermal_only,early_fusion \
         --model_paths thermal.pth,early.pth [--workers 4] [--batch 32] [--write-predictions --prediction_path out/]
+
+Either route takes per-detector softmax temperatures (calibration.py): --temperatures 1.4,0.9 (by position) or
+--temperatures thermal_only=1.4,early_fusion=0.9 (by name), or --calibration FILE written by cli/fit_temperature.  ProbEn then fuses
+softmax(class_logits / T) instead of the detectors' own prob_score; the result names the temperatures used.
 """
 import json
 import os
@@ -31,8 +35,9 @@ def main(cmd=None):
     rank, world, dev = launch.init_distributed(args.device, expect_world=args.world_size)
     names = [n for n in args.detectors.split(",") if n]
     assert 2 <= len(names) <= 3, "--detectors takes 2 or 3 names"
+    temps = _temperatures(args, names)
     if args.one_pass:
-        return one_pass(args, names, world, dev)
+        return one_pass(args, names, world, dev, temps)
     files = [os.path.join(args.prediction_path, f"val_{n}_predictions.json") for n in names]
     if comm.is_main_process():
         for i, f in enumerate(files):
@@ -54,13 +59,39 @@ def main(cmd=None):
     main_rank = comm.is_main_process()
     ev = FLIREvaluator(args.dataset_name, cfg, world > 1 or comm.is_distributed(), output_dir=args.outfolder if main_rank else None, save_eval=main_rank,
                        out_eval_path=os.path.join(args.outfolder, "FLIR_probEn_eval.json"))
-    res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
-                                         det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev))
+    if temps is None:
+        res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
+                                             det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev))
+    else:
+        _warn_fitted(temps, [i for d in dets for i in d["image_id"]])
+        res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
+                                             det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev),
+                                             temperatures=temps["values"], names=files)
+        res["temperatures"] = dict(zip(names, temps["values"]))
     if main_rank:
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
         launch.shutdown()
     return res
+
+
+def _temperatures(args, names):
+    """--temperatures / --calibration -> {"values": [T per --detectors entry], "fitted": image ids the file was fitted on} or None."""
+    from .. import calibration
+    if args.temperatures is not None:
+        return {"values": calibration.parse_temperatures(args.temperatures, names), "fitted": set()}
+    if args.calibration is not None:
+        rec = calibration.load(args.calibration)
+        return {"values": calibration.resolve(rec["detectors"], names, args.calibration), "fitted": set(rec.get("fitted_image_ids", []))}
+    return None
+
+
+def _warn_fitted(temps, image_ids):
+    """The calibration file records the images its temperatures were fitted on: say so when the evaluation includes them."""
+    seen = temps["fitted"] & set(image_ids)
+    if seen and comm.is_main_process():
+        print(f"warning: {len(seen)} of the evaluated images were used to fit the temperatures (the calibration file's holdout split): "
+              "the result is optimistic on them")
 
 
 def _register(args):
@@ -75,7 +106,7 @@ def _register(args):
     return cfg
 
 
-def one_pass(args, names, world, dev):
+def one_pass(args, names, world, dev, temps=None):
     """loader -> FramePairPipeline (one DefaultPredictor model per --detectors entry, cfg as save_predictions.build_cfg) ->
     ProbEn -> evaluation rows on the device (late_fusion.fused_rows_device) -> one all-gather -> FLIREvaluator on rank 0."""
     import argparse
@@ -106,7 +137,11 @@ def one_pass(args, names, world, dev):
         preds.append(DefaultPredictor(c))
     need_rgb = any(p.input_format in ("BGRT", "BGRTTT") for p in preds)
     loader = FlirPairLoader(args.dataset_path, args.batch, need_rgb=need_rgb, workers=workers)
-    pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion)
+    if temps is None:
+        pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion)
+    else:
+        _warn_fitted(temps, [loader.items[i]["id"] for i in loader.mine])
+        pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion, temperatures=temps["values"])
     j1 = [([], [], []) for _ in names]       # per detector: names, ids, instances
     rows = []
     feeder, feed_key, host = None, None, None
@@ -171,6 +206,8 @@ def one_pass(args, names, world, dev):
         ev.process_rows(all_rows.numpy())
         res = ev.evaluate()
         res["one_pass"] = stats
+        if temps is not None:
+            res["temperatures"] = dict(zip(names, temps["values"]))
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
         launch.shutdown()

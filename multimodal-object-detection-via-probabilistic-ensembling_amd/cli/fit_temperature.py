@@ -1,0 +1,93 @@
+"""Fit one softmax temperature per detector from its validation predictions (calibration.py).
+
+    python -m proben_amd.cli.fit_temperature --dataset_path DATA/FLIR/val \\
+        --predictions out/val_thermal_only_predictions.json out/val_early_fusion_predictions.json \\
+        [--holdout 0.5] --out calibration.json
+
+Every detection of a prediction file is labelled from the ground truth (calibration.match_labels: the class of the box it overlaps
+most at IoU >= 0.5, else background), and T minimises the negative log-likelihood of those labels under softmax(class_logits / T)
+(calibration.fit_temperature).  --holdout f: the first fraction f of the images, in dataset order, is fitted; the rest is left for
+evaluation.  The fitted image ids go into the file, and demo_probEn warns when it evaluates on them.  The detector's name is the
+<name> of val_<name>_predictions.json.  Prints, per detector, T and the NLL before (T = 1) and after.
+"""
+import argparse
+import json
+import os
+import re
+import sys
+
+import torch
+
+from .. import calibration
+from ..data import load_coco_json
+from ..late_fusion import read_j1
+
+
+def detector_name(path):
+    m = re.fullmatch(r"val_(.+)_predictions\.json", os.path.basename(path))
+    return m.group(1) if m else os.path.splitext(os.path.basename(path))[0]
+
+
+def parse(argv):
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--predictions", nargs="+", required=True, help="val_<method>_predictions.json files, one per detector")
+    p.add_argument("--dataset_path", required=True, help="FLIR val folder (FLIR_thermal_RGBT_pairs_val.json)")
+    p.add_argument("--holdout", type=float, default=0.5, help="fraction of the images (the first ones, dataset order) that is fitted")
+    p.add_argument("--out", default="calibration.json")
+    p.add_argument("--iou", type=float, default=0.5, help="IoU from which a detection takes a ground-truth box's class")
+    p.add_argument("--device", default="cuda")
+    args = p.parse_args(argv)
+    if not 0.0 < args.holdout <= 1.0:
+        p.error(f"--holdout {args.holdout} is not in (0, 1]")
+    return args
+
+
+def labelled_rows(pred, records, fitted_ids, iou, name):
+    """(logits [M, K+1] list, labels [M] list) of the file's detections on the fitted images."""
+    calibration.require_logits(pred, name)
+    logits, labels = [], []
+    for i, iid in enumerate(pred["image_id"]):
+        if iid not in fitted_ids or not pred["boxes"][i]:
+            continue
+        anns = records[iid]["annotations"]
+        # COCO XYWH -> XYXY
+        gt = [[a["bbox"][0], a["bbox"][1], a["bbox"][0] + a["bbox"][2], a["bbox"][1] + a["bbox"][3]] for a in anns]
+        k = len(pred["class_logits"][i][0]) - 1
+        lab = calibration.match_labels(pred["boxes"][i], pred["classes"][i], gt, [a["category_id"] for a in anns], iou,
+                                       gt_crowd=[a["iscrowd"] for a in anns], num_classes=k)
+        # a ground-truth class the detector has no column for (FLIR's dog, category 17 -> index 3 of a 3-class head) is background to it
+        lab[(lab < 0) | (lab > k)] = k
+        logits += pred["class_logits"][i]
+        labels += lab.tolist()
+    return logits, labels
+
+
+def main(cmd=None):
+    args = parse(list(cmd) if cmd is not None else sys.argv[1:])
+    records = load_coco_json(os.path.join(args.dataset_path, "FLIR_thermal_RGBT_pairs_val.json"),
+                             os.path.join(args.dataset_path, "thermal_8_bit"))
+    order = [r["image_id"] for r in records]
+    n_fit = max(1, int(len(order) * args.holdout))
+    fitted = order[:n_fit]
+    by_id = {r["image_id"]: r for r in records}
+    temps, nll, rows, bound = {}, {}, {}, {}
+    for path in args.predictions:
+        name = detector_name(path)
+        if name in temps:
+            raise ValueError(f"{path}: a second prediction file for detector {name}")
+        logits, labels = labelled_rows(read_j1(path), by_id, set(fitted), args.iou, path)
+        if not logits:
+            raise ValueError(f"{path}: no detections on the {n_fit} fitted images: nothing to fit")
+        fit = calibration.fit_temperature(torch.tensor(logits, dtype=torch.float32, device=args.device),
+                                          torch.tensor(labels, dtype=torch.int32, device=args.device))
+        temps[name], rows[name], bound[name] = fit["T"], fit["rows"], fit["at_bound"]
+        nll[name] = {"before": fit["nll_at_1"], "after": fit["nll"]}
+        note = f"  (minimum on the {fit['at_bound']} end of the search range: not a fitted value)" if fit["at_bound"] else ""
+        print(f"{name}: T = {fit['T']:.6f}  NLL {fit['nll_at_1']:.6f} -> {fit['nll']:.6f} over {fit['rows']} rows{note}")
+    calibration.save(args.out, temps, nll, rows, holdout=args.holdout, fitted_image_ids=fitted, at_bound=bound)
+    print("calibration file:", args.out)
+    return args.out
+
+
+if __name__ == "__main__":
+    main()

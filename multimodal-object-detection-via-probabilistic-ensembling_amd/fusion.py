@@ -94,13 +94,28 @@ def pack_infos(per_image_infos, device="cuda"):
             torch.tensor(offs, dtype=torch.int32, device=device))
 
 
-def fusion(method, info_1, info_2, info_3=""):
+def fusion(method, info_1, info_2, info_3="", temperatures=None):
     """Drop-in for the reference's ``fusion`` (demo_probEn.py:189-196).
 
     Returns (out_boxes, out_scores, out_class): boxes as a list of float64 ndarrays [4]
     (or a float32 Tensor [n,4] on the ('max','argmax') route), scores / classes as float32
-    CPU tensors - the reference's return types."""
+    CPU tensors - the reference's return types.
+    temperatures (one T per info): the rows' prob / score are rebuilt from their class_logits as softmax(logits / T)
+    (calibration.calibrate_rows); an info without logits is refused."""
     infos = [info_1, info_2] + ([info_3] if info_3 else [])
+    if temperatures is not None:
+        from . import calibration
+        if len(temperatures) != len(infos):
+            raise ValueError(f"fusion: {len(temperatures)} temperatures for {len(infos)} detectors")
+        cal = []
+        for k, (d, T) in enumerate(zip(infos, temperatures)):
+            lg = d.get("class_logits")
+            if lg is None or len(lg) != len(d["bbox"]) or any(len(r) < 2 for r in lg):
+                raise ValueError(f"fusion: info_{k + 1} ({d.get('img_name', '?')}) carries no class_logits: temperature calibration "
+                                 "needs the detector's logits")
+            p, s = calibration.calibrate_rows(lg, d["class"], calibration.check_temperature(T, f"temperature of info_{k + 1}"))
+            cal.append(dict(d, prob=p, score=s))
+        infos = cal
     if method[0] == "max" and method[1] == "argmax":
         from .layers import batched_nms
         boxes = torch.tensor(sum([list(d["bbox"]) for d in infos], []), dtype=torch.float32).reshape(-1, 4)
@@ -117,19 +132,14 @@ def fusion(method, info_1, info_2, info_3=""):
     return [boxes[i] for i in range(m)], out["scores"][:m].cpu(), out["classes"][:m].cpu()
 
 
-def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=0.5):
-    """Device-to-device stage fusion: `dets` = the result dicts of 2 or 3 detectors run on the SAME batch
-    (rcnn.GeneralizedRCNN.forward_batch).  Packs their detections into ProbEn rows (classes <= max_class,
-    like the JSON writer demo_FLIR_save_predictions.py:148-155), applies the reference's per-image case
-    split (0 detectors -> nothing, 1 -> passthrough, >= 2 -> fusion; demo_probEn.py:237-267) and fuses.
-    No host synchronisation.  Returns a dict: boxes f64 [B*S,4], scores f32, classes f32, counts i32 [B],
-    offsets i32 [B], stride S = len(dets) * D."""
+def pack_rows(dets, max_class=2, temperatures=None):
+    """The detectors' padded outputs -> ProbEn input rows on the device (pe_proben_pack_detections; with temperatures
+    pe_proben_pack_logits: probabilities and scores from class_logits as softmax(logits / T_d) in float64).
+    Returns (boxes f64 [B*S,4], scores f64, probs f64 [B*S,K], vars f64, classes i32, offsets i32 [B], counts i32 [B],
+    single-source flags i32 [B]), S = len(dets) * D."""
     import ctypes
     nd = len(dets)
     B, D = dets[0]["scores"].shape
-    # the box heads' candidate-cap bookkeeping travels with the result (no kernel here): check_candidate_overflow() looks
-    # at it at the consumer's first host synchronisation
-    overflow_src = [(d["cand_total"], d["cand_max"]) for d in dets if "cand_total" in d]
     K = dets[0]["prob_score"].shape[2]
     dev = dets[0]["scores"].device
     S = nd * D
@@ -144,11 +154,42 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     ooff = torch.empty((B,), dtype=torch.int32, device=dev)
     ocnt = torch.empty((B,), dtype=torch.int32, device=dev)
     osingle = torch.empty((B,), dtype=torch.int32, device=dev)
-    st = _lib.lib().pe_proben_pack_detections(arr("boxes"), arr("scores"), arr("classes"), arr("prob_score"), arr("vars"),
-                                             arr("counts"), nd, B, D, K, max_class, S, _lib.ptr(ob), _lib.ptr(os_),
-                                             _lib.ptr(op), _lib.ptr(ov), _lib.ptr(oc), _lib.ptr(ooff), _lib.ptr(ocnt),
-                                             _lib.ptr(osingle), _lib.stream())
-    _lib.check(st, "pe_proben_pack_detections")
+    if temperatures is None:
+        st = _lib.lib().pe_proben_pack_detections(arr("boxes"), arr("scores"), arr("classes"), arr("prob_score"), arr("vars"),
+                                                 arr("counts"), nd, B, D, K, max_class, S, _lib.ptr(ob), _lib.ptr(os_),
+                                                 _lib.ptr(op), _lib.ptr(ov), _lib.ptr(oc), _lib.ptr(ooff), _lib.ptr(ocnt),
+                                                 _lib.ptr(osingle), _lib.stream())
+        _lib.check(st, "pe_proben_pack_detections")
+    else:
+        if len(temperatures) != nd:
+            raise ValueError(f"fuse_detections: {len(temperatures)} temperatures for {nd} detectors")
+        for d in dets:
+            if d["class_logits"].shape != (B, D, K + 1) or d["class_logits"].dtype != torch.float32:
+                raise ValueError(f"fuse_detections: class_logits {tuple(d['class_logits'].shape)} is not float32 [{B}, {D}, {K + 1}]")
+        st = _lib.lib().pe_proben_pack_logits(arr("boxes"), arr("classes"), arr("class_logits"), arr("vars"), arr("counts"),
+                                             (ctypes.c_double * nd)(*[float(t) for t in temperatures]), nd, B, D, K, max_class, S,
+                                             _lib.ptr(ob), _lib.ptr(os_), _lib.ptr(op), _lib.ptr(ov), _lib.ptr(oc), _lib.ptr(ooff),
+                                             _lib.ptr(ocnt), _lib.ptr(osingle), _lib.stream())
+        _lib.check(st, "pe_proben_pack_logits")
+    return ob, os_, op, ov, oc, ooff, ocnt, osingle
+
+
+def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=0.5, temperatures=None):
+    """Device-to-device stage fusion: `dets` = the result dicts of 2 or 3 detectors run on the SAME batch
+    (rcnn.GeneralizedRCNN.forward_batch).  Packs their detections into ProbEn rows (classes <= max_class,
+    like the JSON writer demo_FLIR_save_predictions.py:148-155), applies the reference's per-image case
+    split (0 detectors -> nothing, 1 -> passthrough, >= 2 -> fusion; demo_probEn.py:237-267) and fuses.
+    temperatures (one T per detector): the rows' probabilities and scores come from the detectors' class_logits as
+    softmax(logits / T) in float64 (pe_proben_pack_logits) instead of the float32 prob_score / scores.
+    No host synchronisation.  Returns a dict: boxes f64 [B*S,4], scores f32, classes f32, counts i32 [B],
+    offsets i32 [B], stride S = len(dets) * D."""
+    # the box heads' candidate-cap bookkeeping travels with the result (no kernel here): check_candidate_overflow() looks
+    # at it at the consumer's first host synchronisation
+    overflow_src = [(d["cand_total"], d["cand_max"]) for d in dets if "cand_total" in d]
+    B, D = dets[0]["scores"].shape
+    S = len(dets) * D
+    dev = dets[0]["scores"].device
+    ob, os_, op, ov, oc, ooff, ocnt, osingle = pack_rows(dets, max_class, temperatures)
     if score_fusion == "max" and box_fusion == "argmax":
         from .layers import nms_batched_raw
         b32 = ob.float().view(B, S, 4)

@@ -63,11 +63,22 @@ def _info(det, i):
             "class_logits": det["class_logits"][i], "prob": det["probs"][i], "vars": det["vars"][i]}
 
 
-def late_fusion(dets, method, device="cuda"):
+def late_fusion(dets, method, device="cuda", temperatures=None, names=None):
     """dets: 2 or 3 J1 dicts over the same images (order = detector order).  Returns per-image
     (boxes float64 [m,4] | None, scores f32, classes f32); None = skipped image (no detector fired).
     Case split of demo_probEn.py:237-267: 0 detectors -> skip, 1 -> passthrough, >= 2 -> fusion of the
-    non-empty lists in order.  All images needing fusion go through ONE batched launch."""
+    non-empty lists in order.  All images needing fusion go through ONE batched launch.
+    temperatures (one T per detector): every file's probs / scores are rebuilt from its class_logits as softmax(logits / T) before
+    the case split (calibration.calibrate_j1), so passed-through rows carry the calibrated score like the device route's;
+    `names` (the files) word the refusal of a file without logits."""
+    if temperatures is not None:
+        from . import calibration
+        if len(temperatures) != len(dets):
+            raise ValueError(f"late_fusion: {len(temperatures)} temperatures for {len(dets)} detectors")
+        names = names or [f"prediction file {k + 1}" for k in range(len(dets))]
+        for d, n in zip(dets, names):          # every file is checked before the first launch
+            calibration.require_logits(d, n)
+        dets = [calibration.calibrate_j1(d, t, n, device) for d, t, n in zip(dets, temperatures, names)]
     n_img = len(dets[1]["image"]) if len(dets) > 1 else len(dets[0]["image"])      # the reference loops over det_2's images (:205)
     results = [None] * n_img
     batch, where = [], []
@@ -101,7 +112,7 @@ def late_fusion(dets, method, device="cuda"):
 
 
 def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="", image_hw=None, device="cuda",
-                                   img_folder="../../../Datasets/FLIR/val/thermal_8_bit/"):
+                                   img_folder="../../../Datasets/FLIR/val/thermal_8_bit/", temperatures=None, names=None):
     """Same call as the reference (demo_probEn.py:198).  `image_hw`: {image_id: (H, W)} from the dataset
     json (the reference re-reads every thermal JPEG just for its shape); default 512 x 640 (FLIR).
     `img_folder`: the prefix the reference hard-codes into the `file_name` it hands to the evaluator (:200,271).
@@ -111,7 +122,7 @@ def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="
     print("Method: ", method)
     start = time.time()
     dets = [det_1, det_2] + ([det_3] if det_3 else [])
-    fused = late_fusion(dets, method, device)
+    fused = late_fusion(dets, method, device) if temperatures is None else late_fusion(dets, method, device, temperatures, names)
     for i, r in enumerate(fused):
         if r is None:
             continue

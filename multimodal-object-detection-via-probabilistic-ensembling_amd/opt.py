@@ -28,4 +28,10 @@ def config_parser(cmd=None):
     p.add_argument("--workers", type=int, default=4, help="--one-pass: JPEG decode processes (0 = in-process, at most 15)")
     p.add_argument("--write-predictions", action="store_true",
                    help="--one-pass: also write every detector's val_<method>_predictions.json to --prediction_path (or --outfolder)")
+    # temperature calibration of the detectors' posteriors ahead of ProbEn (calibration.py)
+    cal = p.add_mutually_exclusive_group()
+    cal.add_argument("--temperatures", type=str, default=None,
+                     help="demo_probEn: one softmax temperature per --detectors entry, 'a,b[,c]' by position or 'name=a,name=b' by name")
+    cal.add_argument("--calibration", type=str, default=None,
+                     help="demo_probEn: calibration file written by cli/fit_temperature (temperatures looked up by detector name)")
     return p.parse_args(cmd) if cmd is not None else p.parse_args()

@@ -22,11 +22,15 @@ class FramePairPipeline:
     synchronisation); inputs must not be modified before that either."""
 
     def __init__(self, models, score_fusion="probEn", box_fusion="v-avg", max_class=2, concurrent=True,
-                 staggered=False, stagger_stage=4, fuse=True):
+                 staggered=False, stagger_stage=4, fuse=True, temperatures=None):
         self.models = list(models)
         self.fuse = fuse and len(self.models) > 1   # a single detector has nothing to fuse (configs[1])
         self.method = (score_fusion, box_fusion)
         self.max_class = max_class
+        # one T per detector: ProbEn's rows are softmax(class_logits / T) (pe_proben_pack_logits); None = the detectors' own prob_score
+        self.temperatures = None if temperatures is None else [float(t) for t in temperatures]
+        if self.temperatures is not None and len(self.temperatures) != len(self.models):
+            raise ValueError(f"FramePairPipeline: {len(self.temperatures)} temperatures for {len(self.models)} detectors")
         self.concurrent = concurrent and len(self.models) > 1
         self.staggered = staggered and self.concurrent and len(self.models) == 2
         self.stagger_stage = stagger_stage
@@ -81,7 +85,7 @@ class FramePairPipeline:
             for v in det_a.values():    # detector 0's results were allocated on sa and are read on sb
                 if isinstance(v, torch.Tensor):
                     v.record_stream(sb)
-            fused = F.fuse_detections([det_a, det_b], self.method[0], self.method[1], max_class=self.max_class)
+            fused = self._fuse([det_a, det_b])
         return [det_a, det_b], fused
 
     @torch.no_grad()
@@ -110,8 +114,13 @@ class FramePairPipeline:
                 for v in d.values():
                     if isinstance(v, torch.Tensor):
                         v.record_stream(main)
-        fused = F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class) if self.fuse else None
+        fused = self._fuse(dets) if self.fuse else None
         return dets, fused
+
+    def _fuse(self, dets):
+        if self.temperatures is None:
+            return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class)
+        return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class, temperatures=self.temperatures)
 
 
 class HostFeeder:
