@@ -34,6 +34,7 @@ extern "C" {
 #define PE_SCORE_AVG 1
 #define PE_SCORE_MAX 2
 #define PE_SCORE_PROBEN_BINARY 3 /* demo_probEn.py:24-30, the K = 1 (KAIST) form */
+#define PE_SCORE_PROBEN_LOGP 4   /* pe_proben_fuse_batch_logp only: ProbEn over log-posteriors with an explicit background column */
 #define PE_BOX_VAVG 0
 #define PE_BOX_SAVG 1
 #define PE_BOX_AVG 2
@@ -128,6 +129,51 @@ int pe_calibrated_softmax(const float* logits, int64_t num_rows, int32_t num_col
 int pe_temperature_nll(const float* logits, const int32_t* labels, int64_t num_rows, int32_t num_columns,
                        const double* temperatures_host, int32_t num_temperatures, double* workspace,
                        double* out, int32_t* out_flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Log-posterior ProbEn (PE_SCORE_PROBEN_LOGP): the Bayes rule of bayesian_fusion_multiclass (demo/FLIR/demo_probEn.py:32-42) evaluated
+ * on log-posteriors over all K + 1 columns, background included.  It departs from the reference in three places, on purpose:
+ *   - :35-36 forms the background as 1 - sum(p) over float32 probabilities: 0 or a few 1e-8 of either sign on a saturated row, so its
+ *     log is -inf or NaN and the whole cluster's score is NaN.  Here the background is the box head's own column,
+ *     log p_k = z_k - m - log(sum_j exp(z_j - m)), z = (double)logit / T, m = max_k z_k: finite for every finite logit;
+ *   - :38-40 takes exp(sum of logs) before normalising, which underflows to 0 / 0 on large clusters of confident rows.  Here the
+ *     cluster's columns a_j are normalised as exp(a_j - max a) / sum_j exp(a_j - max a): the largest term is exp(0) = 1;
+ *   - the reference drops the class prior of p(y | x_1..x_m) ~ prod_i p(y | x_i) / p(y)^(m-1) (uniform prior).  Here log_prior, when
+ *     given, is subtracted (m - 1) times per column.
+ * Where probEn is well conditioned the two agree to rounding (float64), so after the float32 exit to within 1 ulp.  Opt-in: the other
+ * score modes and entry points are untouched.
+ *
+ * pe_proben_pack_log_posteriors: pe_proben_pack_logits plus out_log_probs f64 [rows, K + 1] (row stride K + 1, background column
+ *   stored).  Every other output - out_scores (the row's calibrated p_class) and out_probs included - is pe_proben_pack_logits' bit for
+ *   bit (one device function), so the clustering order and the s-avg / argmax box rules see what the temperature route sees.  max and
+ *   sum of a row are the lane group's xor butterflies for K + 1 <= 64 (every lane gets the same bits), a serial column-order loop above.
+ * pe_log_softmax: the same arithmetic over a flat f32 [num_rows, num_columns] tensor; a row gets the same bits here and in the pack.
+ * pe_proben_fuse_batch_logp: pe_proben_fuse_batch with log_probs f64 [Ntot, K + 1] in place of probs and no score_mode; same kernel
+ *   (a template instantiation), clustering (both forms), box modes, LDS budget (L = K + 1), K <= 62, out_counts = -1 and passthrough
+ *   rules.  For a cluster of m > 1 rows in cluster order (matches first, pivot last):
+ *     a_j = (sum_t log_probs[t][j]) - (m - 1) * log_prior[j]      (sequential sum; the prior term only when log_prior != NULL)
+ *     s_j = exp(a_j - max_j a_j) / sum_j exp(a_j - max_j a_j)     (column order)
+ *   fused score = max_j s_j over the K + 1 entries INCLUDING background, class = its first index, NaN wins (the rule of PE_SCORE_PROBEN).
+ *   A cluster of one keeps its row's score and class.  log_prior: optional DEVICE f64 [K + 1] (NULL = uniform), log of a normalised
+ *   prior; being a device pointer it cannot be checked here - entries must be finite (no NaN, no +-inf): the caller's contract
+ *   (fusion.log_class_prior validates it).  -inf / NaN log_probs propagate as in NumPy (a NaN column gives a NaN score).
+ * ------------------------------------------------------------------------------------------- */
+int pe_proben_pack_log_posteriors(const float* const* det_boxes_host, const int32_t* const* det_classes_host,
+                                  const float* const* det_logits_host, const float* const* det_vars_host,
+                                  const int32_t* const* det_counts_host, const double* temperatures_host,
+                                  int32_t num_detectors, int32_t num_images, int32_t det_stride, int32_t num_classes,
+                                  int32_t max_class, int32_t row_stride, double* out_boxes, double* out_scores,
+                                  double* out_probs, double* out_log_probs, double* out_vars, int32_t* out_classes,
+                                  int32_t* out_offsets, int32_t* out_counts, int32_t* out_single_source, void* stream);
+int pe_log_softmax(const float* logits, int64_t num_rows, int32_t num_columns, double temperature, double* out_log_probs,
+                   void* stream);
+int pe_proben_fuse_batch_logp(const double* boxes, const double* scores, const double* log_probs, /* [Ntot,K+1] */
+                              const double* variances, const int32_t* classes, const int32_t* offsets,
+                              const int32_t* row_counts, const int32_t* passthrough, int32_t num_images, int32_t num_classes,
+                              int32_t max_rows_per_image, int32_t box_mode, double iou_thresh, double frame_w, double frame_h,
+                              const double* log_prior, /* optional [K+1] */
+                              double* out_boxes, float* out_scores, float* out_classes, int32_t* out_keep, int32_t* out_counts,
+                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused convolution / GEMM: NHWC fp16 activations, [Cout][KH][KW][Cin] fp16 weights, fp32 accumulate

@@ -16,6 +16,9 @@ SIGNATURES = {
     "pe_version": [],
     "pe_proben_pack_detections": [c_void_p] * 6 + [c_int] * 6 + [c_void_p] * 9,
     "pe_proben_pack_logits": [c_void_p] * 6 + [c_int] * 6 + [c_void_p] * 9,
+    "pe_proben_pack_log_posteriors": [c_void_p] * 6 + [c_int] * 6 + [c_void_p] * 10,
+    "pe_log_softmax": [c_void_p, ctypes.c_int64, c_int, c_double, c_void_p, c_void_p],
+    "pe_proben_fuse_batch_logp": [c_void_p] * 8 + [c_int] * 4 + [c_double] * 3 + [c_void_p] * 6 + [c_void_p],
     "pe_calibrated_softmax": [c_void_p, ctypes.c_int64, c_int, c_double, c_void_p, c_void_p],
     "pe_temperature_nll": [c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "pe_proben_fuse_batch": [c_void_p] * 8 + [c_int] * 5 + [c_double] * 3 + [c_void_p] * 5 + [c_void_p],

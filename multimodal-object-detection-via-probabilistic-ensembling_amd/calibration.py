@@ -6,7 +6,9 @@ keeps every detection's argmax and ranking.  This module holds
   calibrated_probs   the row arithmetic of pe_proben_pack_logits over a flat [M, K+1] tensor
   match_labels       detections -> labels in [0, K] from the ground truth
   fit_temperature    T that minimises the negative log-likelihood of the labels (pe_temperature_nll, 64 candidates per launch)
-  save / load        the calibration file  {"detectors": {name: T}, "nll": {...}, "rows": {...}}
+  save / load        the calibration file  {"detectors": {name: T}, "nll": {...}, "rows": {...}[, "class_prior": [K + 1]]}
+  log_posteriors     log_softmax(logits / T) over all K + 1 columns (pe_log_softmax): the rows of score_fusion "probEn-log"
+  check_class_prior / parse_class_prior      the class prior of that mode (K + 1 probabilities, background last)
   resolve / calibrate_j1 / require_logits   what the drivers (fusion.fusion, late_fusion, cli/demo_probEn) share.
 """
 import ctypes
@@ -41,6 +43,46 @@ def calibrated_probs(logits, T):
     st = _lib.lib().pe_calibrated_softmax(_lib.ptr(logits), M, k1, float(T), _lib.ptr(out), _lib.stream())
     _lib.check(st, "pe_calibrated_softmax")
     return out[:, :k1 - 1], out[:, k1 - 1]
+
+
+def log_posteriors(logits, T):
+    """logits: CUDA tensor [M, K+1] (background last).  Returns log_softmax(logits / T) f64 [M, K+1], the bits
+    pe_proben_pack_log_posteriors writes for the same row."""
+    _lib.require_cuda(logits)
+    if logits.dim() != 2 or logits.shape[1] < 2:
+        raise ValueError(f"log_posteriors: logits must be [M, K+1] with K >= 1, got {tuple(logits.shape)}")
+    logits = logits.contiguous().float()
+    M, k1 = logits.shape
+    out = torch.empty((M, k1), dtype=torch.float64, device=logits.device)
+    st = _lib.lib().pe_log_softmax(_lib.ptr(logits), M, k1, float(T), _lib.ptr(out), _lib.stream())
+    _lib.check(st, "pe_log_softmax")
+    return out
+
+
+def check_class_prior(prior, num_columns=None, what="class_prior"):
+    """K + 1 probabilities (background last) -> float64 ndarray normalised to sum 1.  Every entry must be finite and > 0 (its log
+    is subtracted from the cluster's columns); anything else, or a length other than num_columns, raises ValueError."""
+    try:
+        p = np.asarray(prior, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} {prior!r} is not a list of numbers") from None
+    if p.ndim != 1 or p.size < 2:
+        raise ValueError(f"{what} must list K + 1 >= 2 probabilities (background last), got shape {p.shape}")
+    if num_columns is not None and p.size != num_columns:
+        raise ValueError(f"{what} lists {p.size} entries for K + 1 = {num_columns} columns (background last)")
+    if not (np.all(np.isfinite(p)) and np.all(p > 0)):
+        raise ValueError(f"{what} {p.tolist()} has an entry that is not finite and > 0")
+    return p / p.sum()
+
+
+def parse_class_prior(text):
+    """--class_prior value 'a,b,...' (K + 1 numbers, background last) -> normalised float64 ndarray."""
+    items = [x.strip() for x in str(text).split(",")]
+    try:
+        vals = [float(x) for x in items]
+    except ValueError:
+        raise ValueError(f"--class_prior {text!r} is not a comma separated list of numbers") from None
+    return check_class_prior(vals, what="--class_prior")
 
 
 def match_labels(boxes, classes, gt_boxes, gt_classes, iou_thresh=0.5, gt_crowd=None, num_classes=3):
@@ -135,11 +177,14 @@ def fit_temperature(logits, labels, lo=0.05, hi=20.0, tol=1e-6):
             "rounds": rounds, "rows": int(logits.shape[0]), "at_bound": at}
 
 
-def save(path, detectors, nll=None, rows=None, **extra):
+def save(path, detectors, nll=None, rows=None, class_prior=None, **extra):
     """Write the calibration file.  detectors {name: T}; nll {name: {"before": .., "after": ..}}; rows {name: fitted rows};
-    extra keys (cli/fit_temperature adds "holdout" and "fitted_image_ids") are kept as given."""
+    class_prior (optional, K + 1 probabilities, background last: the prior of score_fusion "probEn-log") is written normalised -
+    without it the file has no such key; extra keys (cli/fit_temperature adds "holdout" and "fitted_image_ids") are kept as given."""
     rec = {"detectors": {k: check_temperature(v, f"temperature of {k}") for k, v in detectors.items()},
            "nll": nll or {}, "rows": rows or {}}
+    if class_prior is not None:
+        rec["class_prior"] = check_class_prior(class_prior).tolist()
     rec.update(extra)
     with open(path, "w") as f:
         json.dump(rec, f, indent=1)
@@ -153,6 +198,8 @@ def load(path):
         raise ValueError(f"{path}: not a calibration file (no \"detectors\" table)")
     for k, v in rec["detectors"].items():
         check_temperature(v, f"{path}: temperature of {k}")
+    if "class_prior" in rec:
+        rec["class_prior"] = check_class_prior(rec["class_prior"], what=f"{path}: class_prior").tolist()
     return rec
 
 
@@ -209,14 +256,25 @@ def calibrate_rows(logits, classes, T, device="cuda"):
     return full[:, :-1].numpy(), score.numpy()
 
 
-def calibrate_j1(det, T, name="prediction file", device="cuda"):
+def log_posterior_rows(logits, T, device="cuda"):
+    """Python lists of one detector's rows -> log-posteriors f64 ndarray [n, K+1]."""
+    lg = torch.tensor(logits, dtype=torch.float32).reshape(len(logits), -1)
+    if lg.shape[0] == 0:
+        return np.zeros((0, lg.shape[1]))
+    return log_posteriors(lg.to(device), T).cpu().numpy()
+
+
+def calibrate_j1(det, T, name="prediction file", device="cuda", log_probs=False):
     """A copy of a J1 prediction dict whose probs / scores are the calibrated ones, from its class_logits (one launch over all the
-    file's rows).  Scores stay float64 here; they are rounded where the uncalibrated route rounds them."""
+    file's rows).  Scores stay float64 here; they are rounded where the uncalibrated route rounds them.
+    log_probs: also "log_probs" [n][K+1] per image, the rows' log-posteriors (score_fusion "probEn-log")."""
     require_logits(det, name)
     flat = [r for rows in det["class_logits"] for r in rows]
     cls = [c for rows in det["classes"] for c in rows]
     out = dict(det)
     if not flat:
+        if log_probs:
+            out["log_probs"] = [[] for _ in det["class_logits"]]
         return out
     p, s = calibrate_rows(flat, cls, T, device)
     probs, scores, k = [], [], 0
@@ -225,4 +283,10 @@ def calibrate_j1(det, T, name="prediction file", device="cuda"):
         scores.append(s[k:k + len(rows)].tolist())
         k += len(rows)
     out["probs"], out["scores"] = probs, scores
+    if log_probs:
+        lp = log_posterior_rows(flat, T, device)
+        out["log_probs"], k = [], 0
+        for rows in det["class_logits"]:
+            out["log_probs"].append(lp[k:k + len(rows)].tolist())
+            k += len(rows)
     return out

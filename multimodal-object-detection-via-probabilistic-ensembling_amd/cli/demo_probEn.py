@@ -14,6 +14,11 @@ still writes them, so the two-stage route can be replayed):
 Either route takes per-detector softmax temperatures (calibration.py): --temperatures 1.4,0.9 (by position) or
 --temperatures thermal_only=1.4,early_fusion=0.9 (by name), or --calibration FILE written by cli/fit_temperature.  ProbEn then fuses
 softmax(class_logits / T) instead of the detectors' own prob_score; the result names the temperatures used.
+
+--score_fusion probEn-log (either route) fuses log_softmax(class_logits / T) over all K + 1 columns, background included, and
+normalises in the log domain: ProbEn's rule, defined where probEn's `1 - sum(p)` background gives NaN.  T = 1 without
+--temperatures / --calibration.  --class_prior 0.2,0.5,0.2,0.1 (K + 1 numbers, background last) divides the prior out
+(p(y)^(m-1) for a cluster of m rows); without the flag a --calibration file written by `fit_temperature --with-prior` supplies it.
 """
 import json
 import os
@@ -36,8 +41,12 @@ def main(cmd=None):
     names = [n for n in args.detectors.split(",") if n]
     assert 2 <= len(names) <= 3, "--detectors takes 2 or 3 names"
     temps = _temperatures(args, names)
+    logp = args.score_fusion == "probEn-log"
+    prior = _class_prior(args) if logp else None
+    if logp and temps is None:
+        temps = {"values": [1.0] * len(names), "fitted": set()}
     if args.one_pass:
-        return one_pass(args, names, world, dev, temps)
+        return one_pass(args, names, world, dev, temps, prior)
     files = [os.path.join(args.prediction_path, f"val_{n}_predictions.json") for n in names]
     if comm.is_main_process():
         for i, f in enumerate(files):
@@ -66,8 +75,10 @@ def main(cmd=None):
         _warn_fitted(temps, [i for d in dets for i in d["image_id"]])
         res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
                                              det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev),
-                                             temperatures=temps["values"], names=files)
+                                             temperatures=temps["values"], names=files, class_prior=prior)
         res["temperatures"] = dict(zip(names, temps["values"]))
+        if prior is not None:
+            res["class_prior"] = prior
     if main_rank:
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
@@ -83,6 +94,16 @@ def _temperatures(args, names):
     if args.calibration is not None:
         rec = calibration.load(args.calibration)
         return {"values": calibration.resolve(rec["detectors"], names, args.calibration), "fitted": set(rec.get("fitted_image_ids", []))}
+    return None
+
+
+def _class_prior(args):
+    """--class_prior, else the calibration file's "class_prior" (fit_temperature --with-prior), else None (uniform); a list."""
+    from .. import calibration
+    if args.class_prior is not None:
+        return calibration.parse_class_prior(args.class_prior).tolist()
+    if args.calibration is not None:
+        return calibration.load(args.calibration).get("class_prior")
     return None
 
 
@@ -106,7 +127,7 @@ def _register(args):
     return cfg
 
 
-def one_pass(args, names, world, dev, temps=None):
+def one_pass(args, names, world, dev, temps=None, prior=None):
     """loader -> FramePairPipeline (one DefaultPredictor model per --detectors entry, cfg as save_predictions.build_cfg) ->
     ProbEn -> evaluation rows on the device (late_fusion.fused_rows_device) -> one all-gather -> FLIREvaluator on rank 0."""
     import argparse
@@ -141,7 +162,8 @@ def one_pass(args, names, world, dev, temps=None):
         pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion)
     else:
         _warn_fitted(temps, [loader.items[i]["id"] for i in loader.mine])
-        pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion, temperatures=temps["values"])
+        pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion, temperatures=temps["values"],
+                                 class_prior=prior)
     j1 = [([], [], []) for _ in names]       # per detector: names, ids, instances
     rows = []
     feeder, feed_key, host = None, None, None
@@ -208,6 +230,8 @@ def one_pass(args, names, world, dev, temps=None):
         res["one_pass"] = stats
         if temps is not None:
             res["temperatures"] = dict(zip(names, temps["values"]))
+        if prior is not None:
+            res["class_prior"] = prior
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
         launch.shutdown()

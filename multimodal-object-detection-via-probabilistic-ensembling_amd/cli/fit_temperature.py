@@ -9,6 +9,9 @@ most at IoU >= 0.5, else background), and T minimises the negative log-likelihoo
 (calibration.fit_temperature).  --holdout f: the first fraction f of the images, in dataset order, is fitted; the rest is left for
 evaluation.  The fitted image ids go into the file, and demo_probEn warns when it evaluates on them.  The detector's name is the
 <name> of val_<name>_predictions.json.  Prints, per detector, T and the NLL before (T = 1) and after.
+--with-prior also writes "class_prior": the frequencies of the labels 0..K (background last) over the fitted rows of all the files
+together, with one added to every count so that a class no fitted row carries keeps a prior > 0 ("class_prior_counts" holds the raw
+counts).  `demo_probEn --score_fusion probEn-log --calibration FILE` uses it.  Without the flag the file is what it always was.
 """
 import argparse
 import json
@@ -36,6 +39,8 @@ def parse(argv):
     p.add_argument("--out", default="calibration.json")
     p.add_argument("--iou", type=float, default=0.5, help="IoU from which a detection takes a ground-truth box's class")
     p.add_argument("--device", default="cuda")
+    p.add_argument("--with-prior", action="store_true",
+                   help="also write the label frequencies of the fitted rows (background last, add-one smoothed) as class_prior")
     args = p.parse_args(argv)
     if not 0.0 < args.holdout <= 1.0:
         p.error(f"--holdout {args.holdout} is not in (0, 1]")
@@ -71,6 +76,7 @@ def main(cmd=None):
     fitted = order[:n_fit]
     by_id = {r["image_id"]: r for r in records}
     temps, nll, rows, bound = {}, {}, {}, {}
+    counts = None
     for path in args.predictions:
         name = detector_name(path)
         if name in temps:
@@ -78,13 +84,23 @@ def main(cmd=None):
         logits, labels = labelled_rows(read_j1(path), by_id, set(fitted), args.iou, path)
         if not logits:
             raise ValueError(f"{path}: no detections on the {n_fit} fitted images: nothing to fit")
+        if args.with_prior:
+            k1 = len(logits[0])
+            if counts is not None and len(counts) != k1:
+                raise ValueError(f"{path}: {k1} class columns, the files before it have {len(counts)}: one prior cannot serve both")
+            counts = [a + b for a, b in zip(counts or [0] * k1, [labels.count(j) for j in range(k1)])]
         fit = calibration.fit_temperature(torch.tensor(logits, dtype=torch.float32, device=args.device),
                                           torch.tensor(labels, dtype=torch.int32, device=args.device))
         temps[name], rows[name], bound[name] = fit["T"], fit["rows"], fit["at_bound"]
         nll[name] = {"before": fit["nll_at_1"], "after": fit["nll"]}
         note = f"  (minimum on the {fit['at_bound']} end of the search range: not a fitted value)" if fit["at_bound"] else ""
         print(f"{name}: T = {fit['T']:.6f}  NLL {fit['nll_at_1']:.6f} -> {fit['nll']:.6f} over {fit['rows']} rows{note}")
-    calibration.save(args.out, temps, nll, rows, holdout=args.holdout, fitted_image_ids=fitted, at_bound=bound)
+    if args.with_prior:
+        calibration.save(args.out, temps, nll, rows, class_prior=[c + 1 for c in counts], holdout=args.holdout, fitted_image_ids=fitted,
+                         at_bound=bound, class_prior_counts=counts)
+        print("class prior (background last):", ", ".join(f"{c + 1}/{sum(counts) + len(counts)}" for c in counts))
+    else:
+        calibration.save(args.out, temps, nll, rows, holdout=args.holdout, fitted_image_ids=fitted, at_bound=bound)
     print("calibration file:", args.out)
     return args.out
 

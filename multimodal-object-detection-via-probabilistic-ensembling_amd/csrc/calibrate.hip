@@ -1,6 +1,8 @@
 // Temperature calibration of the detectors' class posteriors (gfx950).
 //   pe_proben_pack_logits   : pe_proben_pack_detections with p = softmax(logits / T_d) in float64 in place of the float32 prob_score
 //   pe_calibrated_softmax   : the same row arithmetic over a flat [M, K+1] tensor (all K+1 columns stored)
+//   pe_proben_pack_log_posteriors / pe_log_softmax : the two above with log p_k = z_k - m - log(sum_j e_j) stored for all K+1 columns
+//                             (the input of the log-posterior fusion, pe_proben_fuse_batch_logp in csrc/proben.hip)
 //   pe_temperature_nll      : sum_i -log softmax(logits_i / T)[label_i] and d/d(log T), for up to 64 candidate T in one launch
 //
 // Row arithmetic (one definition, softmax_group / softmax_serial, shared by the first two entry points so a row gets the same bits
@@ -9,6 +11,8 @@
 // ends with the same bits (a + b == b + a at every level), the logits of the group's rows are read coalesced and 64 / G rows are
 // in flight per wavefront.  Above 64 columns a lane walks its row serially.  Nothing is clamped: a NaN or +inf logit (or a row of
 // -inf) gives NaN probabilities like the float64 NumPy expression.  Built with -ffp-contract=off like the other ProbEn code.
+// The log-posterior (LOGP instantiations) reuses z, m and the sum s of the same call: log p_k = (z_k - m) - log(s), finite for every
+// finite logit (s is in [1, K+1]), where log(p_k) is -inf once p_k underflows and log(1 - sum p) is NaN on a saturated row.
 #include "common.h"
 
 namespace {
@@ -22,8 +26,9 @@ __host__ __device__ __forceinline__ int group_width(int k1) {   // smallest powe
 }
 
 // One column of one row per lane; `row` = the row's K+1 logits (ignored when !live), col = lane % G.  Every lane of the wavefront
-// calls this (the shuffles are wave-wide).  Returns p_col (0 on the padding lanes col >= k1).
-__device__ __forceinline__ double softmax_group(const float* row, bool live, int col, int k1, int G, double T) {
+// calls this (the shuffles are wave-wide).  Returns p_col (0 on the padding lanes col >= k1); LOGP: *lp = log p_col.
+template <bool LOGP = false>
+__device__ __forceinline__ double softmax_group(const float* row, bool live, int col, int k1, int G, double T, double* lp = nullptr) {
     const bool real = live && col < k1;
     const double z = real ? (double)row[col] / T : kNegInf;
     double m = z;
@@ -34,11 +39,14 @@ __device__ __forceinline__ double softmax_group(const float* row, bool live, int
     const double e = real ? exp(z - m) : 0.0;
     double s = e;
     for (int o = G >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (LOGP) *lp = (z - m) - log(s);
     return e / s;
 }
 
 // K+1 > 64: the lane owns the row.  Sum in column order; out[k] for k < n_store, returns p_want (want < 0: nothing).
-__device__ __forceinline__ double softmax_serial(const float* row, int k1, double T, double* out, int n_store, int want) {
+// out_lp (optional): log p_k for all k1 columns.
+__device__ __forceinline__ double softmax_serial(const float* row, int k1, double T, double* out, int n_store, int want,
+                                                 double* out_lp = nullptr) {
     double m = kNegInf;
     for (int k = 0; k < k1; ++k) {
         const double z = (double)row[k] / T;
@@ -51,6 +59,10 @@ __device__ __forceinline__ double softmax_serial(const float* row, int k1, doubl
         const double p = exp((double)row[k] / T - m) / s;
         if (k < n_store) out[k] = p;
         if (k == want) pw = p;
+    }
+    if (out_lp) {
+        const double ls = log(s);
+        for (int k = 0; k < k1; ++k) out_lp[k] = ((double)row[k] / T - m) - ls;
     }
     return pw;
 }
@@ -71,10 +83,12 @@ struct PackLogitsArgs {
     int32_t* ooff;
     int32_t* ocnt;
     int32_t* osingle;
+    double* olp;     // LOGP: [rows, K+1] log-posteriors
 };
 
 // one wavefront per image: the ordered compaction of proben_pack_kernel (csrc/proben.hip), then the chunk's 64 rows go through the
-// softmax 64 / G at a time
+// softmax 64 / G at a time.  LOGP (pe_proben_pack_log_posteriors) stores the row's K+1 log-posteriors next to everything else.
+template <bool LOGP>
 __global__ __launch_bounds__(64) void proben_pack_logits_kernel(PackLogitsArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int k1 = a.K + 1;
@@ -110,16 +124,18 @@ __global__ __launch_bounds__(64) void proben_pack_logits_kernel(PackLogitsArgs a
                     const int rdst = __shfl(dst_local, r);
                     const int rcls = __shfl(cls, r);
                     const float* row = a.logits[d] + ((size_t)b * a.D + base + r) * k1;
-                    const double p = softmax_group(row, live, col, k1, G, T);
+                    double lp = 0.0;
+                    const double p = softmax_group<LOGP>(row, live, col, k1, G, T, &lp);
                     if (live) {
                         const size_t o = (size_t)b * a.stride + rdst;
                         if (col < a.K) a.op[o * a.K + col] = p;
                         if (col == rcls) a.os[o] = p;
+                        if (LOGP && col < k1) a.olp[o * k1 + col] = lp;
                     }
                 }
             } else if (ok) {
                 // a class outside [0, K] cannot index the row: its score is NaN rather than a neighbour's value
-                const double pw = softmax_serial(a.logits[d] + src * k1, k1, T, a.op + dst * a.K, a.K, cls);
+                const double pw = softmax_serial(a.logits[d] + src * k1, k1, T, a.op + dst * a.K, a.K, cls, LOGP ? a.olp + dst * k1 : nullptr);
                 a.os[dst] = (cls >= 0 && cls < k1) ? pw : __builtin_nan("");
             }
             if (G && ok && (cls < 0 || cls >= k1)) a.os[dst] = __builtin_nan("");
@@ -134,7 +150,8 @@ __global__ __launch_bounds__(64) void proben_pack_logits_kernel(PackLogitsArgs a
     }
 }
 
-// flat [M, k1] -> [M, k1]; 256 threads, grid-stride over row groups
+// flat [M, k1] -> [M, k1]; 256 threads, grid-stride over row groups.  LOGP (pe_log_softmax): out = log p.
+template <bool LOGP>
 __global__ __launch_bounds__(256) void calibrated_softmax_kernel(const float* logits, long long M, int k1, double T, double* out) {
     const int lane = threadIdx.x & 63;
     const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6), waves = (long long)gridDim.x * 4;
@@ -143,9 +160,12 @@ __global__ __launch_bounds__(256) void calibrated_softmax_kernel(const float* lo
         for (long long r0 = wave * rpp; r0 < M; r0 += waves * rpp) {      // wave-uniform
             const long long r = r0 + lane / G;
             const bool live = r < M;
-            const double p = softmax_group(logits + r * k1, live, col, k1, G, T);
-            if (live && col < k1) out[r * k1 + col] = p;
+            double lp = 0.0;
+            const double p = softmax_group<LOGP>(logits + r * k1, live, col, k1, G, T, &lp);
+            if (live && col < k1) out[r * k1 + col] = LOGP ? lp : p;
         }
+    } else if (LOGP) {
+        for (long long r = wave * 64 + lane; r < M; r += waves * 64) softmax_serial(logits + r * k1, k1, T, nullptr, 0, -1, out + r * k1);
     } else {
         for (long long r = wave * 64 + lane; r < M; r += waves * 64) softmax_serial(logits + r * k1, k1, T, out + r * k1, k1, -1);
     }
@@ -239,6 +259,61 @@ __global__ __launch_bounds__(64 * kFinishSegments) void temperature_nll_finish_k
 
 bool good_temperature(double t) { return t == t && t > 0.0 && t < __builtin_huge_val(); }
 
+// pe_proben_pack_logits / pe_proben_pack_log_posteriors: one body, `what` words the messages, logp selects the kernel
+int pack_logits_impl(const char* what, const float* const* det_boxes_host, const int32_t* const* det_classes_host,
+                     const float* const* det_logits_host, const float* const* det_vars_host, const int32_t* const* det_counts_host,
+                     const double* temperatures_host, int32_t num_detectors, int32_t num_images, int32_t det_stride,
+                     int32_t num_classes, int32_t max_class, int32_t row_stride, double* out_boxes, double* out_scores,
+                     double* out_probs, double* out_vars, int32_t* out_classes, int32_t* out_offsets, int32_t* out_counts,
+                     int32_t* out_single_source, double* out_log_probs, bool logp, void* stream) {
+    PE_CHECK_ARG(num_detectors >= 1 && num_detectors <= 4, "%s: num_detectors %d", what, num_detectors);
+    PE_CHECK_ARG(num_images >= 0 && det_stride >= 0, "%s: num_images %d, det_stride %d", what, num_images, det_stride);
+    PE_CHECK_ARG(num_classes >= 1, "%s: num_classes %d", what, num_classes);
+    PE_CHECK_ARG(row_stride >= num_detectors * det_stride, "%s: row_stride %d < %d", what, row_stride, num_detectors * det_stride);
+    PE_CHECK_ARG(det_boxes_host && det_classes_host && det_logits_host && det_vars_host && det_counts_host && temperatures_host,
+                 "%s: null pointer (detector tables / temperatures)", what);
+    PE_CHECK_ARG(out_boxes && out_scores && out_probs && out_vars && out_classes && out_offsets && out_counts, "%s: null output", what);
+    PE_CHECK_ARG(!logp || out_log_probs, "%s: null output (out_log_probs)", what);
+    PackLogitsArgs a{};
+    for (int d = 0; d < num_detectors; ++d) {
+        PE_CHECK_ARG(good_temperature(temperatures_host[d]), "%s: temperature %g of detector %d is not finite and > 0", what,
+                     temperatures_host[d], d);
+        a.boxes[d] = det_boxes_host[d]; a.classes[d] = det_classes_host[d]; a.logits[d] = det_logits_host[d];
+        a.vars[d] = det_vars_host[d]; a.counts[d] = det_counts_host[d]; a.T[d] = temperatures_host[d];
+        PE_CHECK_ARG(a.boxes[d] && a.classes[d] && a.logits[d] && a.vars[d] && a.counts[d], "%s: null pointer of detector %d", what, d);
+    }
+    if (num_images == 0) return PE_OK;
+    a.nd = num_detectors; a.B = num_images; a.D = det_stride; a.K = num_classes; a.max_class = max_class;
+    a.stride = row_stride; a.ob = out_boxes; a.os = out_scores; a.op = out_probs; a.ov = out_vars; a.oc = out_classes;
+    a.ooff = out_offsets; a.ocnt = out_counts; a.osingle = out_single_source; a.olp = out_log_probs;
+    if (logp)
+        hipLaunchKernelGGL(proben_pack_logits_kernel<true>, dim3(num_images), dim3(64), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(proben_pack_logits_kernel<false>, dim3(num_images), dim3(64), 0, (hipStream_t)stream, a);
+    PE_CHECK_LAUNCH(what);
+    return PE_OK;
+}
+
+int flat_softmax_impl(const char* what, const float* logits, int64_t num_rows, int32_t num_columns, double temperature, double* out,
+                      bool logp, void* stream) {
+    PE_CHECK_ARG(good_temperature(temperature), "%s: temperature %g is not finite and > 0", what, temperature);
+    PE_CHECK_ARG(num_rows >= 0, "%s: num_rows %lld", what, (long long)num_rows);
+    PE_CHECK_ARG(num_columns >= 2, "%s: num_columns %d (K + 1) < 2", what, num_columns);
+    if (num_rows == 0) return PE_OK;
+    PE_CHECK_ARG(logits && out, "%s: null pointer", what);
+    const int rows_per_wave = num_columns <= 64 ? 64 / group_width(num_columns) : 64;
+    const long long waves = (num_rows + rows_per_wave - 1) / rows_per_wave;
+    const int blocks = (int)std::min<long long>((waves + 3) / 4, 4096);
+    if (logp)
+        hipLaunchKernelGGL(calibrated_softmax_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, (long long)num_rows,
+                           (int)num_columns, temperature, out);
+    else
+        hipLaunchKernelGGL(calibrated_softmax_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, (long long)num_rows,
+                           (int)num_columns, temperature, out);
+    PE_CHECK_LAUNCH(what);
+    return PE_OK;
+}
+
 }  // namespace
 
 extern "C" int pe_proben_pack_logits(const float* const* det_boxes_host, const int32_t* const* det_classes_host,
@@ -248,47 +323,33 @@ extern "C" int pe_proben_pack_logits(const float* const* det_boxes_host, const i
                                      int32_t max_class, int32_t row_stride, double* out_boxes, double* out_scores,
                                      double* out_probs, double* out_vars, int32_t* out_classes, int32_t* out_offsets,
                                      int32_t* out_counts, int32_t* out_single_source, void* stream) {
-    PE_CHECK_ARG(num_detectors >= 1 && num_detectors <= 4, "pe_proben_pack_logits: num_detectors %d", num_detectors);
-    PE_CHECK_ARG(num_images >= 0 && det_stride >= 0, "pe_proben_pack_logits: num_images %d, det_stride %d", num_images, det_stride);
-    PE_CHECK_ARG(num_classes >= 1, "pe_proben_pack_logits: num_classes %d", num_classes);
-    PE_CHECK_ARG(row_stride >= num_detectors * det_stride, "pe_proben_pack_logits: row_stride %d < %d", row_stride,
-                 num_detectors * det_stride);
-    PE_CHECK_ARG(det_boxes_host && det_classes_host && det_logits_host && det_vars_host && det_counts_host && temperatures_host,
-                 "pe_proben_pack_logits: null pointer (detector tables / temperatures)");
-    PE_CHECK_ARG(out_boxes && out_scores && out_probs && out_vars && out_classes && out_offsets && out_counts,
-                 "pe_proben_pack_logits: null output");
-    PackLogitsArgs a{};
-    for (int d = 0; d < num_detectors; ++d) {
-        PE_CHECK_ARG(good_temperature(temperatures_host[d]), "pe_proben_pack_logits: temperature %g of detector %d is not finite and > 0",
-                     temperatures_host[d], d);
-        a.boxes[d] = det_boxes_host[d]; a.classes[d] = det_classes_host[d]; a.logits[d] = det_logits_host[d];
-        a.vars[d] = det_vars_host[d]; a.counts[d] = det_counts_host[d]; a.T[d] = temperatures_host[d];
-        PE_CHECK_ARG(a.boxes[d] && a.classes[d] && a.logits[d] && a.vars[d] && a.counts[d],
-                     "pe_proben_pack_logits: null pointer of detector %d", d);
-    }
-    if (num_images == 0) return PE_OK;
-    a.nd = num_detectors; a.B = num_images; a.D = det_stride; a.K = num_classes; a.max_class = max_class;
-    a.stride = row_stride; a.ob = out_boxes; a.os = out_scores; a.op = out_probs; a.ov = out_vars; a.oc = out_classes;
-    a.ooff = out_offsets; a.ocnt = out_counts; a.osingle = out_single_source;
-    hipLaunchKernelGGL(proben_pack_logits_kernel, dim3(num_images), dim3(64), 0, (hipStream_t)stream, a);
-    PE_CHECK_LAUNCH("pe_proben_pack_logits");
-    return PE_OK;
+    return pack_logits_impl("pe_proben_pack_logits", det_boxes_host, det_classes_host, det_logits_host, det_vars_host, det_counts_host,
+                            temperatures_host, num_detectors, num_images, det_stride, num_classes, max_class, row_stride, out_boxes,
+                            out_scores, out_probs, out_vars, out_classes, out_offsets, out_counts, out_single_source, nullptr, false,
+                            stream);
+}
+
+extern "C" int pe_proben_pack_log_posteriors(const float* const* det_boxes_host, const int32_t* const* det_classes_host,
+                                             const float* const* det_logits_host, const float* const* det_vars_host,
+                                             const int32_t* const* det_counts_host, const double* temperatures_host,
+                                             int32_t num_detectors, int32_t num_images, int32_t det_stride, int32_t num_classes,
+                                             int32_t max_class, int32_t row_stride, double* out_boxes, double* out_scores,
+                                             double* out_probs, double* out_log_probs, double* out_vars, int32_t* out_classes,
+                                             int32_t* out_offsets, int32_t* out_counts, int32_t* out_single_source, void* stream) {
+    return pack_logits_impl("pe_proben_pack_log_posteriors", det_boxes_host, det_classes_host, det_logits_host, det_vars_host,
+                            det_counts_host, temperatures_host, num_detectors, num_images, det_stride, num_classes, max_class,
+                            row_stride, out_boxes, out_scores, out_probs, out_vars, out_classes, out_offsets, out_counts,
+                            out_single_source, out_log_probs, true, stream);
 }
 
 extern "C" int pe_calibrated_softmax(const float* logits, int64_t num_rows, int32_t num_columns, double temperature,
                                      double* out_probs, void* stream) {
-    PE_CHECK_ARG(good_temperature(temperature), "pe_calibrated_softmax: temperature %g is not finite and > 0", temperature);
-    PE_CHECK_ARG(num_rows >= 0, "pe_calibrated_softmax: num_rows %lld", (long long)num_rows);
-    PE_CHECK_ARG(num_columns >= 2, "pe_calibrated_softmax: num_columns %d (K + 1) < 2", num_columns);
-    if (num_rows == 0) return PE_OK;
-    PE_CHECK_ARG(logits && out_probs, "pe_calibrated_softmax: null pointer");
-    const int rows_per_wave = num_columns <= 64 ? 64 / group_width(num_columns) : 64;
-    const long long waves = (num_rows + rows_per_wave - 1) / rows_per_wave;
-    const int blocks = (int)std::min<long long>((waves + 3) / 4, 4096);
-    hipLaunchKernelGGL(calibrated_softmax_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, (long long)num_rows,
-                       (int)num_columns, temperature, out_probs);
-    PE_CHECK_LAUNCH("pe_calibrated_softmax");
-    return PE_OK;
+    return flat_softmax_impl("pe_calibrated_softmax", logits, num_rows, num_columns, temperature, out_probs, false, stream);
+}
+
+extern "C" int pe_log_softmax(const float* logits, int64_t num_rows, int32_t num_columns, double temperature, double* out_log_probs,
+                              void* stream) {
+    return flat_softmax_impl("pe_log_softmax", logits, num_rows, num_columns, temperature, out_log_probs, true, stream);
 }
 
 extern "C" int pe_temperature_nll(const float* logits, const int32_t* labels, int64_t num_rows, int32_t num_columns,

@@ -31,6 +31,7 @@ struct ProbenArgs {
     float* out_classes;
     int32_t* out_keep;
     int32_t* out_counts;
+    const double* log_prior;   // LOGP only: optional [K+1] log class prior (NULL = uniform)
 };
 
 // Sort rule shared with oracle/proben.py: NaN first, score descending, ties by ORIGINAL index
@@ -52,6 +53,9 @@ __device__ __forceinline__ bool precedes(double sa, int ia, double sb, int ib) {
 // matrix lines are fetched per LDS round trip.  The sequential form (below, when the matrices do not fit the LDS) computes the
 // IoUs inside the walk: ~1 500 cycles per row against ~100; with the rank sort on one wave that was 0.26 ms per step at the END
 // of the step, where nothing overlaps it (profiles/r05_proben_phases.txt).
+// LOGP (pe_proben_fuse_batch_logp, PE_SCORE_PROBEN_LOGP): a.probs holds the rows' K+1 LOG-posteriors, background column included.  Phase 2
+// copies them into glog instead of taking logs of p and of 1 - sum(p), phase 4 normalises the cluster's summed columns with a
+// max-subtracted log-sum-exp.  A template parameter, not a run-time branch: the four other score modes compile to what they were.
 constexpr int kFuseThreads = 1024;
 
 __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int l) {
@@ -59,7 +63,7 @@ __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, i
     return ((unsigned long long)hi << 32) | lo;
 }
 
-template <bool BITS>
+template <bool BITS, bool LOGP>
 __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int ncl_s;
@@ -86,7 +90,7 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
     const int K = a.K;
     const int W = (R + 63) >> 6;   // 64-row words per matrix line
     // columns of log-probabilities kept per row (0 when the score mode does not need them)
-    const int L = (a.score_mode == PE_SCORE_PROBEN) ? K + 1 : (a.score_mode == PE_SCORE_PROBEN_BINARY ? 2 : 0);
+    const int L = (LOGP || a.score_mode == PE_SCORE_PROBEN) ? K + 1 : (a.score_mode == PE_SCORE_PROBEN_BINARY ? 2 : 0);
     // ---- LDS carve (all arrays indexed by SORTED position unless noted) ----
     unsigned long long* mbits = reinterpret_cast<unsigned long long*>(smem);      // BITS: match [R][W], then the clusters' member bits
     unsigned long long* kbits = mbits + (BITS ? (size_t)R * W : 0);               // BITS: kill [R][W]
@@ -132,7 +136,10 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
         gob[p] = b[0]; gob[R + p] = b[1]; gob[2 * (size_t)R + p] = b[2]; gob[3 * (size_t)R + p] = b[3];
         gcls[p] = a.classes[beg + r];
         if (a.box_mode == PE_BOX_VAVG) ginv[p] = 1.0 / a.vars[beg + r];
-        if (a.score_mode == PE_SCORE_PROBEN) {
+        if (LOGP) {
+            const double* lp = a.probs + (size_t)(beg + r) * (K + 1);
+            for (int j = 0; j <= K; ++j) glog[(size_t)j * R + p] = lp[j];
+        } else if (a.score_mode == PE_SCORE_PROBEN) {
             const double* pr = a.probs + (size_t)(beg + r) * K;
             double sum = 0.0;
             for (int j = 0; j < K; ++j) {
@@ -259,7 +266,34 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
             for (int c4 = 0; c4 < 4; ++c4) out_coord[c4] = coord(c4, pos);
         } else {
             // ---------- score fusion ----------
-            if (L > 0) {
+            if (LOGP) {
+                // a_j = sum over the members (cluster order) of log p_j, less (m - 1) log prior_j; s = softmax(a) with the maximum
+                // subtracted first, so the largest term is exp(0) and nothing under- or overflows before the division.  np.max /
+                // np.argmax over the K+1 entries INCLUDING background, NaN wins, first index - the rule of PE_SCORE_PROBEN below.
+                auto column = [&](int j) {
+                    double acc = 0.0;
+                    const double* col = glog + (size_t)j * R;
+                    for (int t = 0; t < m; ++t) acc += col[at(t)];
+                    if (a.log_prior) acc -= (double)(m - 1) * a.log_prior[j];
+                    return acc;
+                };
+                double top = column(0);
+                for (int j = 1; j < L; ++j) {
+                    const double v = column(j);
+                    top = (v > top || v != v) ? v : top;          // NaN wins, like np.max
+                }
+                double tot = 0.0;
+                for (int j = 0; j < L; ++j) tot += exp(column(j) - top);
+                double best = exp(column(0) - top) / tot;
+                int bi = 0;
+                bool bnan = best != best;
+                for (int j = 1; j < L; ++j) {
+                    const double v = exp(column(j) - top) / tot;
+                    if (!bnan && (v != v || v > best)) { best = v; bi = j; bnan = v != v; }
+                }
+                out_score = best;
+                out_class = (double)bi;
+            } else if (L > 0) {
                 auto column = [&](int j) {       // exp of the cluster's summed log-probability of column j
                     double acc = 0.0;
                     const double* col = glog + (size_t)j * R;
@@ -424,6 +458,51 @@ extern "C" int pe_proben_pack_detections(const float* const* det_boxes_host, con
     return PE_OK;
 }
 
+namespace {
+
+// pe_proben_fuse_batch / pe_proben_fuse_batch_logp behind their own argument checks: LDS sizing, clustering form, launch
+int launch_fuse(const char* what, ProbenArgs a, int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, void* stream) {
+    const bool logp = a.score_mode == PE_SCORE_PROBEN_LOGP;
+    const int R = (max_rows_per_image + 1) & ~1;  // keep the int/short/byte carves 8-byte aligned
+    const int L = (logp || a.score_mode == PE_SCORE_PROBEN) ? num_classes + 1 : (a.score_mode == PE_SCORE_PROBEN_BINARY ? 2 : 0);
+    const size_t lds_seq = (size_t)R * (8 * (6 + L + 5) + 4 + 4 + 4 * 2 + 1) + 16;
+    const size_t lds_bits = lds_seq + (size_t)R * ((R + 63) / 64) * 16;        // + the two bit matrices
+    constexpr size_t kStatic = 512;                                            // the kernels' static __shared__ scratch (ncl_s, reductions)
+    const bool bits = lds_bits + kStatic <= 160 * 1024;
+    const size_t lds = bits ? lds_bits : lds_seq;
+    if (lds + kStatic > 160 * 1024) {
+        // a whole image's rows live in LDS (boxes, 1 / variance, class ids, log-odds, cluster tables: 8 (11 + L) + 17 bytes per row);
+        // capacity at K = 3: 1 195 rows per image (probEn), 1 400 (other score modes) - a detector contributes at most 100
+        pe::set_error("%s: %zu bytes of LDS needed (> 160 KiB): max_rows_per_image %d is above the per-image capacity of %zu rows "
+                      "for this score mode / class count", what, lds + kStatic, max_rows_per_image,
+                      (size_t)(160 * 1024 - kStatic - 16) / (size_t)(8 * (6 + L + 5) + 4 + 4 + 4 * 2 + 1));
+        return PE_ERR_UNSUPPORTED;
+    }
+    a.max_rows = R;
+    const void* fn = logp ? (bits ? reinterpret_cast<const void*>(proben_fuse_kernel<true, true>) : reinterpret_cast<const void*>(proben_fuse_kernel<false, true>))
+                          : (bits ? reinterpret_cast<const void*>(proben_fuse_kernel<true, false>) : reinterpret_cast<const void*>(proben_fuse_kernel<false, false>));
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            pe::set_error("%s: cannot raise dynamic LDS to %zu: %s", what, lds, hipGetErrorString(e));
+            return PE_ERR_HIP;
+        }
+    }
+    const dim3 grid(num_images), block(kFuseThreads);
+    if (logp && bits)
+        hipLaunchKernelGGL((proben_fuse_kernel<true, true>), grid, block, lds, (hipStream_t)stream, a);
+    else if (logp)
+        hipLaunchKernelGGL((proben_fuse_kernel<false, true>), grid, block, lds, (hipStream_t)stream, a);
+    else if (bits)
+        hipLaunchKernelGGL((proben_fuse_kernel<true, false>), grid, block, lds, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL((proben_fuse_kernel<false, false>), grid, block, lds, (hipStream_t)stream, a);
+    PE_CHECK_LAUNCH(what);
+    return PE_OK;
+}
+
+}  // namespace
+
 extern "C" int pe_proben_fuse_batch(const double* boxes, const double* scores, const double* probs,
                                     const double* variances, const int32_t* classes, const int32_t* offsets,
                                     const int32_t* row_counts, const int32_t* passthrough, int32_t num_images, int32_t num_classes, int32_t max_rows_per_image,
@@ -446,36 +525,30 @@ extern "C" int pe_proben_fuse_batch(const double* boxes, const double* scores, c
                  "pe_proben_fuse_batch: probs required for this score_mode");
     PE_CHECK_ARG(max_rows_per_image >= 1 && max_rows_per_image <= 2048,
                  "pe_proben_fuse_batch: max_rows_per_image %d not in [1,2048]", max_rows_per_image);
-    const int R = (max_rows_per_image + 1) & ~1;  // keep the int/short/byte carves 8-byte aligned
-    const int L = score_mode == PE_SCORE_PROBEN ? num_classes + 1 : (score_mode == PE_SCORE_PROBEN_BINARY ? 2 : 0);
-    const size_t lds_seq = (size_t)R * (8 * (6 + L + 5) + 4 + 4 + 4 * 2 + 1) + 16;
-    const size_t lds_bits = lds_seq + (size_t)R * ((R + 63) / 64) * 16;        // + the two bit matrices
-    constexpr size_t kStatic = 512;                                            // the kernels' static __shared__ scratch (ncl_s, reductions)
-    const bool bits = lds_bits + kStatic <= 160 * 1024;
-    const size_t lds = bits ? lds_bits : lds_seq;
-    if (lds + kStatic > 160 * 1024) {
-        // a whole image's rows live in LDS (boxes, 1 / variance, class ids, log-odds, cluster tables: 8 (11 + L) + 17 bytes per row);
-        // capacity at K = 3: 1 195 rows per image (probEn), 1 400 (other score modes) - a detector contributes at most 100
-        pe::set_error("pe_proben_fuse_batch: %zu bytes of LDS needed (> 160 KiB): max_rows_per_image %d is above the per-image capacity of %zu rows "
-                      "for this score mode / class count", lds + kStatic, max_rows_per_image,
-                      (size_t)(160 * 1024 - kStatic - 16) / (size_t)(8 * (6 + L + 5) + 4 + 4 + 4 * 2 + 1));
-        return PE_ERR_UNSUPPORTED;
-    }
-    ProbenArgs a{boxes, scores, probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, R,
+    ProbenArgs a{boxes, scores, probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
                  score_mode, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts};
-    const void* fn = bits ? reinterpret_cast<const void*>(proben_fuse_kernel<true>) : reinterpret_cast<const void*>(proben_fuse_kernel<false>);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            pe::set_error("pe_proben_fuse_batch: cannot raise dynamic LDS to %zu: %s", lds, hipGetErrorString(e));
-            return PE_ERR_HIP;
-        }
-    }
-    if (bits)
-        hipLaunchKernelGGL(proben_fuse_kernel<true>, dim3(num_images), dim3(kFuseThreads), lds, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(proben_fuse_kernel<false>, dim3(num_images), dim3(kFuseThreads), lds, (hipStream_t)stream, a);
-    PE_CHECK_LAUNCH("pe_proben_fuse_batch");
-    return PE_OK;
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, nullptr};
+    return launch_fuse("pe_proben_fuse_batch", a, num_images, num_classes, max_rows_per_image, stream);
+}
+
+extern "C" int pe_proben_fuse_batch_logp(const double* boxes, const double* scores, const double* log_probs,
+                                         const double* variances, const int32_t* classes, const int32_t* offsets,
+                                         const int32_t* row_counts, const int32_t* passthrough, int32_t num_images,
+                                         int32_t num_classes, int32_t max_rows_per_image, int32_t box_mode, double iou_thresh,
+                                         double frame_w, double frame_h, const double* log_prior, double* out_boxes,
+                                         float* out_scores, float* out_classes, int32_t* out_keep, int32_t* out_counts, void* stream) {
+    PE_CHECK_ARG(num_images >= 0, "pe_proben_fuse_batch_logp: num_images < 0");
+    if (num_images == 0) return PE_OK;
+    PE_CHECK_ARG(boxes && scores && log_probs && variances && classes && offsets,
+                 "pe_proben_fuse_batch_logp: null input pointer");
+    PE_CHECK_ARG(out_boxes && out_scores && out_classes && out_keep && out_counts,
+                 "pe_proben_fuse_batch_logp: null output pointer");
+    PE_CHECK_ARG(box_mode >= 0 && box_mode <= 3, "pe_proben_fuse_batch_logp: bad box_mode %d", box_mode);
+    PE_CHECK_ARG(num_classes >= 1 && num_classes <= 62, "pe_proben_fuse_batch_logp: num_classes %d not in [1,62]", num_classes);
+    PE_CHECK_ARG(max_rows_per_image >= 1 && max_rows_per_image <= 2048,
+                 "pe_proben_fuse_batch_logp: max_rows_per_image %d not in [1,2048]", max_rows_per_image);
+    ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
+                 PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior};
+    return launch_fuse("pe_proben_fuse_batch_logp", a, num_images, num_classes, max_rows_per_image, stream);
 }

@@ -5,20 +5,51 @@ Mirrors the reference's call surface (demo/FLIR/demo_probEn.py):
 and adds the batched form the MI355X path actually uses:
   fuse_batch(...)                             one launch, one 1024-thread workgroup per image.
 The arithmetic lives in csrc/proben.hip behind pe_proben_fuse_batch.
+
+score_fusion "probEn-log" (not in the reference) is ProbEn on the detectors' log-posteriors, log_softmax(class_logits / T) over all
+K + 1 columns with the background column kept, normalised by a max-subtracted log-sum-exp (pe_proben_fuse_batch_logp): the same Bayes
+rule, defined on saturated rows and large clusters where "probEn" gives NaN, with an optional class prior (`class_prior`).
 """
 import numpy as np
 import torch
 
 from . import _lib
 
-SCORE_MODES = {"probEn": 0, "avg": 1, "max": 2, "probEn_binary": 3}
+SCORE_MODES = {"probEn": 0, "avg": 1, "max": 2, "probEn_binary": 3, "probEn-log": 4}
+LOGP = "probEn-log"
 BOX_MODES = {"v-avg": 0, "s-avg": 1, "avg": 2, "argmax": 3}
 FRAME_W, FRAME_H = 640.0, 512.0  # class-band shift hard-coded by the reference (demo_probEn.py:100-103)
 
 
+def log_class_prior(class_prior, num_columns, device):
+    """class_prior (K + 1 probabilities, background last; calibration.check_class_prior validates and normalises) -> the DEVICE
+    f64 [K + 1] log-prior pe_proben_fuse_batch_logp takes.  None -> None (uniform).  A CUDA tensor is taken as the result of an
+    earlier call (FramePairPipeline uploads once, not per batch)."""
+    if class_prior is None:
+        return None
+    if isinstance(class_prior, torch.Tensor) and class_prior.is_cuda:
+        if class_prior.dtype != torch.float64 or tuple(class_prior.shape) != (num_columns,):
+            raise ValueError(f"log-prior tensor {tuple(class_prior.shape)} {class_prior.dtype} is not float64 [{num_columns}]")
+        return class_prior.contiguous()
+    from .calibration import check_class_prior
+    return torch.from_numpy(np.log(check_class_prior(class_prior, num_columns))).to(device)
+
+
+def _check_mode(score_fusion, class_prior, who):
+    if score_fusion not in SCORE_MODES:
+        raise ValueError(f"{who}: unknown score_fusion {score_fusion!r} (one of {', '.join(SCORE_MODES)})")
+    if class_prior is not None and score_fusion != LOGP:
+        raise ValueError(f"{who}: class_prior belongs to score_fusion '{LOGP}' (got {score_fusion!r}): the other score fusions "
+                         "have no prior term")
+
+
 def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="probEn", box_fusion="v-avg",
-               max_rows=None, iou_thresh=0.5, frame=(FRAME_W, FRAME_H), row_counts=None, passthrough=None):
+               max_rows=None, iou_thresh=0.5, frame=(FRAME_W, FRAME_H), row_counts=None, passthrough=None, log_probs=None,
+               class_prior=None):
     """Fuse B images in one launch.
+
+    score_fusion "probEn-log": log_probs f64 [Ntot,K+1] (calibration.log_posteriors / pack_rows(log_posteriors=True)) replaces
+    probs (ignored, may be None); class_prior: K + 1 probabilities, background last, or None = uniform.
 
     boxes f64 [Ntot,4], scores f64 [Ntot], probs f64 [Ntot,K], variances f64 [Ntot],
     classes i32 [Ntot], offsets i32 [B+1] - all CUDA tensors, rows of each image already
@@ -26,12 +57,21 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
       boxes f64 [Ntot,4], scores f32 [Ntot], classes f32 [Ntot], keep i32 [Ntot], counts i32 [B];
     image b's fused rows are [offsets[b], offsets[b]+counts[b]).
     """
+    _check_mode(score_fusion, class_prior, "fuse_batch")
+    logp = score_fusion == LOGP
+    if logp:
+        if log_probs is None or log_probs.dim() != 2 or log_probs.shape[1] < 2 or log_probs.shape[0] != boxes.shape[0]:
+            raise ValueError(f"fuse_batch: score_fusion '{LOGP}' needs log_probs [Ntot, K+1] for the {boxes.shape[0]} rows, got "
+                             f"{None if log_probs is None else tuple(log_probs.shape)}")
+        probs = log_probs
     _lib.require_cuda(boxes, scores, probs, variances, classes, offsets)
     if score_fusion == "max" and box_fusion == "argmax":
         raise ValueError("('max','argmax') is the class-aware NMS route: use fusion()/nms_fuse_batch")
     B = offsets.numel() - (0 if row_counts is not None else 1)
     ntot = boxes.shape[0]
     K = probs.shape[1] if probs is not None and probs.dim() == 2 else 1
+    K -= 1 if logp else 0
+    log_prior = log_class_prior(class_prior, K + 1, boxes.device) if logp else None
     boxes = boxes.contiguous().double()
     scores = scores.contiguous().double()
     probs = probs.contiguous().double() if probs is not None else None
@@ -50,6 +90,15 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
         "keep": torch.empty((ntot,), dtype=torch.int32, device=dev),
         "counts": torch.zeros((max(B, 1),), dtype=torch.int32, device=dev)[:B],
     }
+    if logp:
+        st = _lib.lib().pe_proben_fuse_batch_logp(
+            _lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(probs), _lib.ptr(variances), _lib.ptr(classes),
+            _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows, BOX_MODES[box_fusion],
+            float(iou_thresh), float(frame[0]), float(frame[1]), _lib.ptr(log_prior),
+            _lib.ptr(out["boxes"]), _lib.ptr(out["scores"]), _lib.ptr(out["classes"]), _lib.ptr(out["keep"]),
+            _lib.ptr(out["counts"]), _lib.stream())
+        _lib.check(st, "pe_proben_fuse_batch_logp")
+        return out
     st = _lib.lib().pe_proben_fuse_batch(
         _lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(probs), _lib.ptr(variances), _lib.ptr(classes),
         _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows, SCORE_MODES[score_fusion], BOX_MODES[box_fusion],
@@ -60,10 +109,12 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
     return out
 
 
-def pack_infos(per_image_infos, device="cuda"):
+def pack_infos(per_image_infos, device="cuda", with_log_probs=False):
     """per_image_infos: list (images) of lists (detectors) of reference-style dicts
-    {bbox, score, class, prob, vars}.  Returns the flat device tensors + offsets."""
+    {bbox, score, class, prob, vars}.  Returns the flat device tensors + offsets (with_log_probs: + the rows' "log_prob"
+    [n][K+1] as a seventh tensor)."""
     bb, ss, cc, pp, vv, offs = [], [], [], [], [], [0]
+    ll = []
     K = None
     for infos in per_image_infos:
         for d in infos:
@@ -83,26 +134,35 @@ def pack_infos(per_image_infos, device="cuda"):
             cc.append(np.asarray(d["class"], dtype=np.int32).reshape(-1))
             pp.append(np.asarray(d["prob"], dtype=np.float64).reshape(-1, K))
             vv.append(np.asarray(d["vars"], dtype=np.float64).reshape(-1))
+            if with_log_probs:
+                ll.append(np.asarray(d["log_prob"], dtype=np.float64).reshape(-1, K + 1))
             n += len(ss[-1])
         offs.append(offs[-1] + n)
 
     def cat(xs, shape, dt):
         return torch.from_numpy(np.concatenate(xs) if xs else np.zeros(shape, dtype=dt)).to(device)
 
-    return (cat(bb, (0, 4), np.float64), cat(ss, (0,), np.float64), cat(pp, (0, K), np.float64),
-            cat(vv, (0,), np.float64), cat(cc, (0,), np.int32),
-            torch.tensor(offs, dtype=torch.int32, device=device))
+    out = (cat(bb, (0, 4), np.float64), cat(ss, (0,), np.float64), cat(pp, (0, K), np.float64),
+           cat(vv, (0,), np.float64), cat(cc, (0,), np.int32),
+           torch.tensor(offs, dtype=torch.int32, device=device))
+    return out + (cat(ll, (0, K + 1), np.float64),) if with_log_probs else out
 
 
-def fusion(method, info_1, info_2, info_3="", temperatures=None):
+def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=None):
     """Drop-in for the reference's ``fusion`` (demo_probEn.py:189-196).
 
     Returns (out_boxes, out_scores, out_class): boxes as a list of float64 ndarrays [4]
     (or a float32 Tensor [n,4] on the ('max','argmax') route), scores / classes as float32
     CPU tensors - the reference's return types.
     temperatures (one T per info): the rows' prob / score are rebuilt from their class_logits as softmax(logits / T)
-    (calibration.calibrate_rows); an info without logits is refused."""
+    (calibration.calibrate_rows); an info without logits is refused.
+    method[0] "probEn-log": the rows' log-posteriors come from their class_logits too (temperatures None = 1 for every info) and
+    are fused by pe_proben_fuse_batch_logp, with class_prior (K + 1 probabilities, background last) when given."""
     infos = [info_1, info_2] + ([info_3] if info_3 else [])
+    _check_mode(method[0], class_prior, "fusion")
+    logp = method[0] == LOGP
+    if logp and temperatures is None:
+        temperatures = [1.0] * len(infos)
     if temperatures is not None:
         from . import calibration
         if len(temperatures) != len(infos):
@@ -115,6 +175,8 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None):
                                  "needs the detector's logits")
             p, s = calibration.calibrate_rows(lg, d["class"], calibration.check_temperature(T, f"temperature of info_{k + 1}"))
             cal.append(dict(d, prob=p, score=s))
+            if logp:
+                cal[-1]["log_prob"] = calibration.log_posterior_rows(lg, calibration.check_temperature(T, f"temperature of info_{k + 1}"))
         infos = cal
     if method[0] == "max" and method[1] == "argmax":
         from .layers import batched_nms
@@ -123,8 +185,12 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None):
         classes = torch.tensor(sum([list(d["class"]) for d in infos], []), dtype=torch.float32)
         keep = batched_nms(boxes.cuda(), scores.cuda(), classes.cuda(), 0.5).cpu()
         return boxes[keep], scores[keep], classes[keep]
-    b, s, p, v, c, offs = pack_infos([infos])
-    out = fuse_batch(b, s, p, v, c, offs, method[0], method[1])
+    if logp:
+        b, s, p, v, c, offs, lp = pack_infos([infos], with_log_probs=True)
+        out = fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior)
+    else:
+        b, s, p, v, c, offs = pack_infos([infos])
+        out = fuse_batch(b, s, p, v, c, offs, method[0], method[1])
     m = int(out["counts"][0].item())
     if m < 0:
         raise RuntimeError("fusion: too many rows for one image")
@@ -132,11 +198,12 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None):
     return [boxes[i] for i in range(m)], out["scores"][:m].cpu(), out["classes"][:m].cpu()
 
 
-def pack_rows(dets, max_class=2, temperatures=None):
+def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False):
     """The detectors' padded outputs -> ProbEn input rows on the device (pe_proben_pack_detections; with temperatures
     pe_proben_pack_logits: probabilities and scores from class_logits as softmax(logits / T_d) in float64).
     Returns (boxes f64 [B*S,4], scores f64, probs f64 [B*S,K], vars f64, classes i32, offsets i32 [B], counts i32 [B],
-    single-source flags i32 [B]), S = len(dets) * D."""
+    single-source flags i32 [B]), S = len(dets) * D.  log_posteriors (needs temperatures): pe_proben_pack_log_posteriors, the
+    same eight plus the rows' log-posteriors f64 [B*S,K+1] as a ninth."""
     import ctypes
     nd = len(dets)
     B, D = dets[0]["scores"].shape
@@ -154,6 +221,8 @@ def pack_rows(dets, max_class=2, temperatures=None):
     ooff = torch.empty((B,), dtype=torch.int32, device=dev)
     ocnt = torch.empty((B,), dtype=torch.int32, device=dev)
     osingle = torch.empty((B,), dtype=torch.int32, device=dev)
+    if log_posteriors and temperatures is None:
+        raise ValueError("pack_rows: log_posteriors needs temperatures (1.0 per detector for the uncalibrated logits)")
     if temperatures is None:
         st = _lib.lib().pe_proben_pack_detections(arr("boxes"), arr("scores"), arr("classes"), arr("prob_score"), arr("vars"),
                                                  arr("counts"), nd, B, D, K, max_class, S, _lib.ptr(ob), _lib.ptr(os_),
@@ -166,29 +235,50 @@ def pack_rows(dets, max_class=2, temperatures=None):
         for d in dets:
             if d["class_logits"].shape != (B, D, K + 1) or d["class_logits"].dtype != torch.float32:
                 raise ValueError(f"fuse_detections: class_logits {tuple(d['class_logits'].shape)} is not float32 [{B}, {D}, {K + 1}]")
+        temps = (ctypes.c_double * nd)(*[float(t) for t in temperatures])
+        if log_posteriors:
+            olp = torch.empty((B * S, K + 1), dtype=torch.float64, device=dev)
+            st = _lib.lib().pe_proben_pack_log_posteriors(arr("boxes"), arr("classes"), arr("class_logits"), arr("vars"), arr("counts"),
+                                                         temps, nd, B, D, K, max_class, S, _lib.ptr(ob), _lib.ptr(os_), _lib.ptr(op),
+                                                         _lib.ptr(olp), _lib.ptr(ov), _lib.ptr(oc), _lib.ptr(ooff), _lib.ptr(ocnt),
+                                                         _lib.ptr(osingle), _lib.stream())
+            _lib.check(st, "pe_proben_pack_log_posteriors")
+            return ob, os_, op, ov, oc, ooff, ocnt, osingle, olp
         st = _lib.lib().pe_proben_pack_logits(arr("boxes"), arr("classes"), arr("class_logits"), arr("vars"), arr("counts"),
-                                             (ctypes.c_double * nd)(*[float(t) for t in temperatures]), nd, B, D, K, max_class, S,
+                                             temps, nd, B, D, K, max_class, S,
                                              _lib.ptr(ob), _lib.ptr(os_), _lib.ptr(op), _lib.ptr(ov), _lib.ptr(oc), _lib.ptr(ooff),
                                              _lib.ptr(ocnt), _lib.ptr(osingle), _lib.stream())
         _lib.check(st, "pe_proben_pack_logits")
     return ob, os_, op, ov, oc, ooff, ocnt, osingle
 
 
-def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=0.5, temperatures=None):
+def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=0.5, temperatures=None,
+                    class_prior=None):
     """Device-to-device stage fusion: `dets` = the result dicts of 2 or 3 detectors run on the SAME batch
     (rcnn.GeneralizedRCNN.forward_batch).  Packs their detections into ProbEn rows (classes <= max_class,
     like the JSON writer demo_FLIR_save_predictions.py:148-155), applies the reference's per-image case
     split (0 detectors -> nothing, 1 -> passthrough, >= 2 -> fusion; demo_probEn.py:237-267) and fuses.
     temperatures (one T per detector): the rows' probabilities and scores come from the detectors' class_logits as
     softmax(logits / T) in float64 (pe_proben_pack_logits) instead of the float32 prob_score / scores.
+    score_fusion "probEn-log": pe_proben_pack_log_posteriors + pe_proben_fuse_batch_logp (temperatures None = 1 per detector;
+    class_prior: K + 1 probabilities, background last, or the device tensor of log_class_prior).
     No host synchronisation.  Returns a dict: boxes f64 [B*S,4], scores f32, classes f32, counts i32 [B],
     offsets i32 [B], stride S = len(dets) * D."""
     # the box heads' candidate-cap bookkeeping travels with the result (no kernel here): check_candidate_overflow() looks
     # at it at the consumer's first host synchronisation
+    _check_mode(score_fusion, class_prior, "fuse_detections")
     overflow_src = [(d["cand_total"], d["cand_max"]) for d in dets if "cand_total" in d]
     B, D = dets[0]["scores"].shape
     S = len(dets) * D
     dev = dets[0]["scores"].device
+    if score_fusion == LOGP:
+        ob, os_, op, ov, oc, ooff, ocnt, osingle, olp = pack_rows(dets, max_class, temperatures if temperatures is not None else [1.0] * len(dets),
+                                                                     log_posteriors=True)
+        out = fuse_batch(ob, os_, op, ov, oc, ooff, score_fusion, box_fusion, max_rows=S, iou_thresh=iou_thresh,
+                         row_counts=ocnt, passthrough=osingle, log_probs=olp, class_prior=class_prior)
+        out["offsets"], out["stride"], out["in_counts"] = ooff, S, ocnt
+        out["cand_overflow_src"] = overflow_src
+        return out
     ob, os_, op, ov, oc, ooff, ocnt, osingle = pack_rows(dets, max_class, temperatures)
     if score_fusion == "max" and box_fusion == "argmax":
         from .layers import nms_batched_raw

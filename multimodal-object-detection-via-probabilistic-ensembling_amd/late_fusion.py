@@ -59,18 +59,27 @@ def shard_j1(det, index_range):
 
 
 def _info(det, i):
-    return {"img_name": det["image"][i], "bbox": det["boxes"][i], "score": det["scores"][i], "class": det["classes"][i],
-            "class_logits": det["class_logits"][i], "prob": det["probs"][i], "vars": det["vars"][i]}
+    d = {"img_name": det["image"][i], "bbox": det["boxes"][i], "score": det["scores"][i], "class": det["classes"][i],
+         "class_logits": det["class_logits"][i], "prob": det["probs"][i], "vars": det["vars"][i]}
+    if "log_probs" in det:        # calibration.calibrate_j1(log_probs=True): score_fusion "probEn-log"
+        d["log_prob"] = det["log_probs"][i]
+    return d
 
 
-def late_fusion(dets, method, device="cuda", temperatures=None, names=None):
+def late_fusion(dets, method, device="cuda", temperatures=None, names=None, class_prior=None):
     """dets: 2 or 3 J1 dicts over the same images (order = detector order).  Returns per-image
     (boxes float64 [m,4] | None, scores f32, classes f32); None = skipped image (no detector fired).
     Case split of demo_probEn.py:237-267: 0 detectors -> skip, 1 -> passthrough, >= 2 -> fusion of the
     non-empty lists in order.  All images needing fusion go through ONE batched launch.
     temperatures (one T per detector): every file's probs / scores are rebuilt from its class_logits as softmax(logits / T) before
     the case split (calibration.calibrate_j1), so passed-through rows carry the calibrated score like the device route's;
-    `names` (the files) word the refusal of a file without logits."""
+    `names` (the files) word the refusal of a file without logits.
+    method[0] "probEn-log": the files' log-posteriors log_softmax(class_logits / T) (temperatures None = 1 per file) go through
+    pe_proben_fuse_batch_logp, with class_prior (K + 1 probabilities, background last) when given."""
+    F._check_mode(method[0], class_prior, "late_fusion")
+    logp = method[0] == F.LOGP
+    if logp and temperatures is None:
+        temperatures = [1.0] * len(dets)
     if temperatures is not None:
         from . import calibration
         if len(temperatures) != len(dets):
@@ -78,7 +87,7 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None):
         names = names or [f"prediction file {k + 1}" for k in range(len(dets))]
         for d, n in zip(dets, names):          # every file is checked before the first launch
             calibration.require_logits(d, n)
-        dets = [calibration.calibrate_j1(d, t, n, device) for d, t, n in zip(dets, temperatures, names)]
+        dets = [calibration.calibrate_j1(d, t, n, device, log_probs=logp) for d, t, n in zip(dets, temperatures, names)]
     n_img = len(dets[1]["image"]) if len(dets) > 1 else len(dets[0]["image"])      # the reference loops over det_2's images (:205)
     results = [None] * n_img
     batch, where = [], []
@@ -100,8 +109,12 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None):
                 b, s, c = F.fusion(method, *live)
                 results[i] = (b.double().numpy(), s, c)
         else:
-            b, s, p, v, c, offs = F.pack_infos(batch, device)
-            out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1])
+            if logp:
+                b, s, p, v, c, offs, lp = F.pack_infos(batch, device, with_log_probs=True)
+                out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior)
+            else:
+                b, s, p, v, c, offs = F.pack_infos(batch, device)
+                out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1])
             cnt = out["counts"].cpu().numpy()
             ob, os_, oc = out["boxes"].cpu().numpy(), out["scores"].cpu(), out["classes"].cpu()
             oh = offs.cpu().numpy()
@@ -112,7 +125,8 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None):
 
 
 def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="", image_hw=None, device="cuda",
-                                   img_folder="../../../Datasets/FLIR/val/thermal_8_bit/", temperatures=None, names=None):
+                                   img_folder="../../../Datasets/FLIR/val/thermal_8_bit/", temperatures=None, names=None,
+                                   class_prior=None):
     """Same call as the reference (demo_probEn.py:198).  `image_hw`: {image_id: (H, W)} from the dataset
     json (the reference re-reads every thermal JPEG just for its shape); default 512 x 640 (FLIR).
     `img_folder`: the prefix the reference hard-codes into the `file_name` it hands to the evaluator (:200,271).
@@ -122,7 +136,10 @@ def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="
     print("Method: ", method)
     start = time.time()
     dets = [det_1, det_2] + ([det_3] if det_3 else [])
-    fused = late_fusion(dets, method, device) if temperatures is None else late_fusion(dets, method, device, temperatures, names)
+    if method[0] == F.LOGP or class_prior is not None:
+        fused = late_fusion(dets, method, device, temperatures, names, class_prior)
+    else:
+        fused = late_fusion(dets, method, device) if temperatures is None else late_fusion(dets, method, device, temperatures, names)
     for i, r in enumerate(fused):
         if r is None:
             continue

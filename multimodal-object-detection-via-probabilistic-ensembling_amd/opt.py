@@ -12,7 +12,9 @@ def config_parser(cmd=None):
     p.add_argument("--fusion_method", type=str, default="middle_fusion",
                    choices=["rgb_only", "thermal_only", "early_fusion", "middle_fusion"], help="Which fusion method to use?")
     p.add_argument("--model_path", type=str, default=None, help="path to trained model")
-    p.add_argument("--score_fusion", type=str, default="probEn", choices=["avg", "max", "probEn"], help="Which fusion method to use?")
+    p.add_argument("--score_fusion", type=str, default="probEn", choices=["avg", "max", "probEn", "probEn-log"],
+                   help="Which fusion method to use?  probEn-log (not in the reference): ProbEn on log_softmax(class_logits / T) with the "
+                        "background column kept - needs prediction files with class_logits")
     p.add_argument("--box_fusion", type=str, default="v-avg", choices=["avg", "s-avg", "v-avg", "argmax"], help="Which fusion method to use?")
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--batch", type=int, default=16)
@@ -34,4 +36,16 @@ def config_parser(cmd=None):
                      help="demo_probEn: one softmax temperature per --detectors entry, 'a,b[,c]' by position or 'name=a,name=b' by name")
     cal.add_argument("--calibration", type=str, default=None,
                      help="demo_probEn: calibration file written by cli/fit_temperature (temperatures looked up by detector name)")
-    return p.parse_args(cmd) if cmd is not None else p.parse_args()
+    p.add_argument("--class_prior", type=str, default=None,
+                   help="demo_probEn --score_fusion probEn-log: class prior 'p_0,...,p_K' (K + 1 numbers > 0, background last; normalised); "
+                        "default: the calibration file's class_prior if it has one, else uniform")
+    args = p.parse_args(cmd) if cmd is not None else p.parse_args()
+    if args.class_prior is not None:
+        if args.score_fusion != "probEn-log":
+            p.error(f"--class_prior belongs to --score_fusion probEn-log (got {args.score_fusion})")
+        from .calibration import parse_class_prior
+        try:
+            parse_class_prior(args.class_prior)
+        except ValueError as e:
+            p.error(str(e))
+    return args

@@ -22,7 +22,7 @@ class FramePairPipeline:
     synchronisation); inputs must not be modified before that either."""
 
     def __init__(self, models, score_fusion="probEn", box_fusion="v-avg", max_class=2, concurrent=True,
-                 staggered=False, stagger_stage=4, fuse=True, temperatures=None):
+                 staggered=False, stagger_stage=4, fuse=True, temperatures=None, class_prior=None):
         self.models = list(models)
         self.fuse = fuse and len(self.models) > 1   # a single detector has nothing to fuse (configs[1])
         self.method = (score_fusion, box_fusion)
@@ -31,6 +31,17 @@ class FramePairPipeline:
         self.temperatures = None if temperatures is None else [float(t) for t in temperatures]
         if self.temperatures is not None and len(self.temperatures) != len(self.models):
             raise ValueError(f"FramePairPipeline: {len(self.temperatures)} temperatures for {len(self.models)} detectors")
+        # score_fusion "probEn-log": ProbEn on log_softmax(class_logits / T) with the background column kept (pe_proben_pack_log_posteriors,
+        # pe_proben_fuse_batch_logp); T = 1 without temperatures; class_prior = K + 1 probabilities (background last) or None = uniform
+        F._check_mode(score_fusion, class_prior, "FramePairPipeline")
+        self.logp = score_fusion == F.LOGP
+        if self.logp and self.temperatures is None:
+            self.temperatures = [1.0] * len(self.models)
+        if class_prior is not None:
+            from .calibration import check_class_prior
+            class_prior = check_class_prior(class_prior)
+        self.class_prior = class_prior
+        self._log_prior = None      # its log on the device, uploaded at the first batch
         self.concurrent = concurrent and len(self.models) > 1
         self.staggered = staggered and self.concurrent and len(self.models) == 2
         self.stagger_stage = stagger_stage
@@ -118,6 +129,11 @@ class FramePairPipeline:
         return dets, fused
 
     def _fuse(self, dets):
+        if self.logp:
+            if self.class_prior is not None and self._log_prior is None:
+                self._log_prior = F.log_class_prior(self.class_prior, len(self.class_prior), dets[0]["scores"].device)
+            return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class, temperatures=self.temperatures,
+                                     class_prior=self._log_prior)
         if self.temperatures is None:
             return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class)
         return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class, temperatures=self.temperatures)
