@@ -176,6 +176,52 @@ int pe_proben_fuse_batch_logp(const double* boxes, const double* scores, const d
                               void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Variance calibration of the detectors' box heads (csrc/variance.hip): one scale s_d per detector, variance' = s_d * variance, where
+ * the variance is the box head's one scalar per detection, exp(var_pred), trained by a Gaussian NLL in box-delta units
+ * (training.py::bbox_gaussian_loss).  Not in the reference, which fuses the heads' variances as they come (demo/FLIR/demo_probEn.py
+ * :155-160 weights each member box by 1 / variance); v-avg only sees the ratios between detectors, so this is a per-detector correction.
+ *
+ * pe_match_ground_truth: replaces calibration.match_labels (an image at a time on the CPU, labels only) for flat device tensors.
+ *   det_boxes f64 [M,4] XYXY with det_offsets i32 [B+1], gt_boxes f64 [G,4] with gt_offsets i32 [B+1], gt_classes i32 [G], gt_crowd
+ *   optional i32 [G] (!= 0: the box takes no part).  Per detection: out_labels = the class of the ground-truth box of its image with
+ *   the largest IoU if that IoU >= iou_thresh, else num_classes; out_match = that box's flat index in [0, G), else -1; out_iou = the
+ *   largest IoU over the boxes that took part (0 without one).  IoU as finetune.pairwise_iou, float64, unfused: the same bits.  The
+ *   lowest index wins among equal maxima.  A class outside [0, num_classes] is passed on as it is (the caller folds it).  Images
+ *   without detections or ground truth are legal; the ground truth of an image is walked in LDS-sized chunks, any number of boxes.
+ * pe_variance_stats: over num_rows matched rows (det_boxes f64 [M,4], match i32 [M] into gt_boxes f64 [num_gt,4], variances f64 [M]),
+ *   r = Box2BoxTransform.get_deltas(detection, matched ground truth) (modeling.py; weights bbox_reg_weights_host, 4 host floats, NULL
+ *   = 10, 10, 5, 5) in float64 and q_i = sum_c r_ic^2 / var_i:
+ *     out[0] = n rows used, out[1] = sum_i q_i, out[2] = sum_i log var_i,
+ *     out[3] / out[4] = (row, coordinate) pairs with r^2 <= scale * var / r^2 <= 4 * scale * var   (counts, exact in f64).
+ *   A row is excluded (adds nothing) when match < 0 (or >= num_gt: never read), a width or height of either box is not > 0, or the
+ *   variance is not finite and > 0; out_flags i32 [2]: [0] = excluded rows, [1] = 1 + the largest excluded row index, as
+ *   pe_temperature_nll reports bad labels.  Deterministic like pe_temperature_nll: per-workgroup partials in a fixed order into
+ *   workspace (f64, PE_VARIANCE_STATS_MAX_BLOCKS * 5 values), then one fixed-order pass; no floating-point atomics.
+ *   The fit is closed: s_hat = out[1] / (4 n), NLL(s) = 0.5 (4 n log s + 4 out[2] + out[1] / s).
+ * pe_proben_pack_calibrated: pe_proben_pack_detections (det_scores_host + det_probs_host given, det_logits_host, temperatures_host
+ *   and out_log_probs NULL), pe_proben_pack_logits (det_logits_host + temperatures_host given, scores / probs NULL) or
+ *   pe_proben_pack_log_posteriors (the latter with out_log_probs) behind one signature, plus var_scales_host (optional host doubles,
+ *   one per detector, finite and > 0): out_vars = (double)var_f32 * s_d, one float64 multiply.  Every other output is written by the
+ *   entry point it stands for, so it is that entry point's bits; with var_scales_host NULL (no second launch) or all 1.0 so is out_vars.
+ * ------------------------------------------------------------------------------------------- */
+#define PE_VARIANCE_STATS_MAX_BLOCKS 1024
+int pe_match_ground_truth(const double* det_boxes, const int32_t* det_offsets, const double* gt_boxes, const int32_t* gt_offsets,
+                          const int32_t* gt_classes, const int32_t* gt_crowd /* optional */, int32_t num_images, double iou_thresh,
+                          int32_t num_classes, int32_t* out_labels, int32_t* out_match, double* out_iou, void* stream);
+int pe_variance_stats(const double* det_boxes, const int32_t* match, const double* gt_boxes, const double* variances,
+                      int64_t num_rows, int64_t num_gt, const float* bbox_reg_weights_host /* optional [4] */, double scale,
+                      double* workspace, double* out /* [5] */, int32_t* out_flags /* [2] */, void* stream);
+int pe_proben_pack_calibrated(const float* const* det_boxes_host, const float* const* det_scores_host,
+                              const int32_t* const* det_classes_host, const float* const* det_probs_host,
+                              const float* const* det_logits_host, const float* const* det_vars_host,
+                              const int32_t* const* det_counts_host, const double* temperatures_host,
+                              const double* var_scales_host /* optional */, int32_t num_detectors, int32_t num_images,
+                              int32_t det_stride, int32_t num_classes, int32_t max_class, int32_t row_stride, double* out_boxes,
+                              double* out_scores, double* out_probs, double* out_log_probs /* optional */, double* out_vars,
+                              int32_t* out_classes, int32_t* out_offsets, int32_t* out_counts, int32_t* out_single_source,
+                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused convolution / GEMM: NHWC fp16 activations, [Cout][KH][KW][Cin] fp16 weights, fp32 accumulate
  * on MFMA, epilogue = + bias[Cout] (fp32) + residual + ReLU, fp16 (or fp32) NHWC output.
  * Replaces, per layer, detectron2.layers.Conv2d.forward (layers/wrappers.py:62-98) + FrozenBatchNorm2d

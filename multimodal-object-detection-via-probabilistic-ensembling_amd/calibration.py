@@ -10,6 +10,12 @@ keeps every detection's argmax and ranking.  This module holds
   log_posteriors     log_softmax(logits / T) over all K + 1 columns (pe_log_softmax): the rows of score_fusion "probEn-log"
   check_class_prior / parse_class_prior      the class prior of that mode (K + 1 probabilities, background last)
   resolve / calibrate_j1 / require_logits   what the drivers (fusion.fusion, late_fusion, cli/demo_probEn) share.
+
+Variance calibration (csrc/variance.hip): one scale s per detector, variance' = s * variance, for the 1 / variance weights of v-avg.
+  match_rows_device    detections -> (label, matched ground-truth index, IoU) on the device, batched (pe_match_ground_truth)
+  variance_stats / fit_variance_scale      the Gaussian NLL's statistics of the matched rows (pe_variance_stats) and the closed-form fit
+  check_variance_scale / parse_variance_scales / resolve_variance_scales / scale_j1_vars
+  save_variance / load_variance            the "variance_*" keys of the calibration file (save / load above do not know them)
 """
 import ctypes
 import json
@@ -22,6 +28,8 @@ from . import _lib
 
 NLL_CANDIDATES = 64          # pe_temperature_nll's limit: one launch evaluates this many temperatures
 NLL_MAX_BLOCKS = 1024        # PE_TEMPERATURE_NLL_MAX_BLOCKS (include/proben_hip.h): sizes the partial-sum workspace
+VARIANCE_MAX_BLOCKS = 1024   # PE_VARIANCE_STATS_MAX_BLOCKS: 5 partial values per workgroup
+BBOX_REG_WEIGHTS = (10.0, 10.0, 5.0, 5.0)      # cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS: the units the variance head is trained in
 
 
 def check_temperature(t, what="temperature"):
@@ -289,4 +297,172 @@ def calibrate_j1(det, T, name="prediction file", device="cuda", log_probs=False)
         for rows in det["class_logits"]:
             out["log_probs"].append(lp[k:k + len(rows)].tolist())
             k += len(rows)
+    return out
+
+
+# ---- variance calibration ------------------------------------------------------------------------------------------------------
+
+def check_variance_scale(s, what="variance scale"):
+    s = float(s)
+    if not (math.isfinite(s) and s > 0):
+        raise ValueError(f"{what} {s!r} is not finite and > 0")
+    return s
+
+
+def check_variance_scales(scales, num_detectors, who):
+    """variance_scales argument of the fusion entry points -> [s per detector] or None."""
+    if scales is None:
+        return None
+    scales = list(scales)
+    if len(scales) != num_detectors:
+        raise ValueError(f"{who}: {len(scales)} variance scales for {num_detectors} detectors")
+    return [check_variance_scale(s, f"variance scale of detector {k + 1}") for k, s in enumerate(scales)]
+
+
+def match_rows_device(det_boxes, det_offsets, gt_boxes, gt_offsets, gt_classes, gt_crowd=None, iou_thresh=0.5, num_classes=3):
+    """match_labels over flat device tensors, all images in one launch (pe_match_ground_truth).  det_boxes [M,4] XYXY with det_offsets
+    [B+1], gt_boxes [G,4] with gt_offsets [B+1], gt_classes [G], gt_crowd [G] or None.  Returns (labels i32 [M], match i32 [M]: flat
+    index into gt_boxes or -1, iou f64 [M]) on the device.  Labels outside [0, num_classes] are the caller's to fold."""
+    _lib.require_cuda(det_boxes, det_offsets, gt_boxes, gt_offsets, gt_classes, gt_crowd)
+    dev = det_boxes.device
+    det_boxes = det_boxes.reshape(-1, 4).contiguous().double()
+    gt_boxes = gt_boxes.reshape(-1, 4).contiguous().double()
+    det_offsets = det_offsets.contiguous().to(torch.int32)
+    gt_offsets = gt_offsets.contiguous().to(torch.int32)
+    gt_classes = gt_classes.reshape(-1).contiguous().to(torch.int32)
+    M, G, B = det_boxes.shape[0], gt_boxes.shape[0], det_offsets.numel() - 1
+    if B < 0 or gt_offsets.numel() != B + 1 or gt_classes.numel() != G or (gt_crowd is not None and gt_crowd.numel() != G):
+        raise ValueError(f"match_rows_device: {det_offsets.numel()} / {gt_offsets.numel()} offsets, {gt_classes.numel()} classes"
+                         f"{'' if gt_crowd is None else f', {gt_crowd.numel()} crowd flags'} for {G} ground-truth boxes")
+    ends = torch.stack([det_offsets[0], det_offsets[-1], gt_offsets[0], gt_offsets[-1]]).tolist()
+    if ends != [0, M, 0, G]:
+        raise ValueError(f"match_rows_device: offsets span {ends[:2]} / {ends[2:]} for {M} detections / {G} ground-truth boxes")
+    labels = torch.full((M,), int(num_classes), dtype=torch.int32, device=dev)
+    match = torch.full((M,), -1, dtype=torch.int32, device=dev)
+    iou = torch.zeros((M,), dtype=torch.float64, device=dev)
+    if M == 0 or G == 0 or B == 0:
+        return labels, match, iou
+    crowd = None if gt_crowd is None else gt_crowd.reshape(-1).contiguous().to(torch.int32)
+    st = _lib.lib().pe_match_ground_truth(_lib.ptr(det_boxes), _lib.ptr(det_offsets), _lib.ptr(gt_boxes), _lib.ptr(gt_offsets),
+                                         _lib.ptr(gt_classes), _lib.ptr(crowd), B, float(iou_thresh), int(num_classes),
+                                         _lib.ptr(labels), _lib.ptr(match), _lib.ptr(iou), _lib.stream())
+    _lib.check(st, "pe_match_ground_truth")
+    return labels, match, iou
+
+
+def variance_stats(det_boxes, match, gt_boxes, variances, scale=1.0, bbox_reg_weights=BBOX_REG_WEIGHTS):
+    """One pe_variance_stats launch over the matched rows (device tensors: det_boxes [M,4], match i32 [M] into gt_boxes [G,4],
+    variances [M]).  Returns {"n", "sum_q", "sum_log_var", "cover1", "cover2", "excluded", "last_excluded"}; synchronises."""
+    _lib.require_cuda(det_boxes, match, gt_boxes, variances)
+    scale = check_variance_scale(scale, "scale")
+    det_boxes = det_boxes.reshape(-1, 4).contiguous().double()
+    gt_boxes = gt_boxes.reshape(-1, 4).contiguous().double()
+    match = match.reshape(-1).contiguous().to(torch.int32)
+    variances = variances.reshape(-1).contiguous().double()
+    M, G = det_boxes.shape[0], gt_boxes.shape[0]
+    if match.numel() != M or variances.numel() != M:
+        raise ValueError(f"variance_stats: {match.numel()} matches and {variances.numel()} variances for {M} rows")
+    w = [float(x) for x in bbox_reg_weights]
+    if len(w) != 4:
+        raise ValueError(f"variance_stats: bbox_reg_weights {bbox_reg_weights!r} is not 4 numbers")
+    dev = det_boxes.device
+    res = torch.empty((6,), dtype=torch.float64, device=dev)           # [out 5 | flags (2 x i32 in one f64 slot)]: one download
+    work = torch.empty((VARIANCE_MAX_BLOCKS * 5,), dtype=torch.float64, device=dev)
+    flags = res[5:].view(torch.int32)
+    st = _lib.lib().pe_variance_stats(_lib.ptr(det_boxes) if M else None, _lib.ptr(match) if M else None, _lib.ptr(gt_boxes) if G else None,
+                                     _lib.ptr(variances) if M else None, M, G, (ctypes.c_float * 4)(*w), scale, _lib.ptr(work),
+                                     _lib.ptr(res), ctypes.c_void_p(flags.data_ptr()), _lib.stream())
+    _lib.check(st, "pe_variance_stats")
+    host = res.cpu()
+    bad, last = host[5:].view(torch.int32).tolist()
+    n, sq, sl, c1, c2 = host[:5].tolist()
+    return {"n": int(n), "sum_q": sq, "sum_log_var": sl, "cover1": int(c1), "cover2": int(c2), "excluded": bad, "last_excluded": last - 1}
+
+
+def variance_nll(stats, s):
+    """0.5 * (4 n log s + 4 sum log var + sum q / s): the Gaussian NLL of the rows at scale s, up to the constant 2 n log(2 pi)."""
+    return 0.5 * (4 * stats["n"] * math.log(s) + 4 * stats["sum_log_var"] + stats["sum_q"] / s)
+
+
+def fit_variance_scale(det_boxes, match, gt_boxes, variances, bbox_reg_weights=BBOX_REG_WEIGHTS):
+    """s that minimises the Gaussian NLL of the matched rows' box-delta residuals under variance s * var_i: closed form
+    s_hat = sum_i q_i / (4 n).  Two launches: at s = 1 (the sums and the coverage before), at s_hat (the coverage after).
+    Returns {"scale", "nll_before", "nll_after", "rows", "excluded", "coverage_before", "coverage_after"}; coverage = the fractions
+    of (row, coordinate) pairs within 1 and 2 standard deviations (0.6827 / 0.9545 for a calibrated Gaussian)."""
+    a = variance_stats(det_boxes, match, gt_boxes, variances, 1.0, bbox_reg_weights)
+    n = a["n"]
+    if n == 0:
+        raise ValueError(f"fit_variance_scale: no usable row ({a['excluded']} excluded: unmatched, a degenerate box or a variance that "
+                         "is not finite and > 0)")
+    s_hat = a["sum_q"] / (4 * n)
+    if not (math.isfinite(s_hat) and s_hat > 0):
+        raise ValueError(f"fit_variance_scale: the fitted scale {s_hat!r} is not finite and > 0 (every residual 0, or non-finite boxes)")
+    b = variance_stats(det_boxes, match, gt_boxes, variances, s_hat, bbox_reg_weights)
+    return {"scale": s_hat, "nll_before": variance_nll(a, 1.0), "nll_after": variance_nll(a, s_hat), "rows": n,
+            "excluded": a["excluded"], "coverage_before": [a["cover1"] / (4 * n), a["cover2"] / (4 * n)],
+            "coverage_after": [b["cover1"] / (4 * n), b["cover2"] / (4 * n)]}
+
+
+def parse_variance_scales(text, names):
+    """--variance_scales value -> [s per name].  'a,b[,c]' is matched by position, 'name=a,name=b' by name; not both."""
+    items = [x.strip() for x in text.split(",") if x.strip()]
+    named = ["=" in x for x in items]
+    if any(named) != all(named):
+        raise ValueError(f"--variance_scales {text!r} mixes positional and name=value entries")
+    if not all(named):
+        if len(items) != len(names):
+            raise ValueError(f"--variance_scales lists {len(items)} values for {len(names)} --detectors ({','.join(names)})")
+        return [check_variance_scale(x, f"variance scale of {n}") for x, n in zip(items, names)]
+    table = {}
+    for x in items:
+        k, v = x.split("=", 1)
+        if k in table:
+            raise ValueError(f"--variance_scales names {k} twice")
+        table[k] = v
+    return resolve_variance_scales(table, names, "--variance_scales")
+
+
+def resolve_variance_scales(table, names, source):
+    """{name: s} -> [s per name]; every name must be there."""
+    missing = [n for n in names if n not in table]
+    if missing:
+        raise ValueError(f"{source} has no variance scale for {','.join(missing)} (it lists {','.join(sorted(table)) or 'nothing'})")
+    return [check_variance_scale(table[n], f"variance scale of {n}") for n in names]
+
+
+def save_variance(path, scales, nll=None, rows=None, excluded=None, coverage=None):
+    """Add the variance keys to the calibration file at `path` (written by save): "variance_scales" {name: s}, "variance_nll"
+    {name: {"before", "after"}}, "variance_rows", "variance_excluded", "variance_coverage" {name: {"before": [c1, c2], "after": ..}}.
+    Everything else in the file stays as it is."""
+    with open(path) as f:
+        rec = json.load(f)
+    if not isinstance(rec.get("detectors"), dict):
+        raise ValueError(f"{path}: not a calibration file (no \"detectors\" table)")
+    rec["variance_scales"] = {k: check_variance_scale(v, f"variance scale of {k}") for k, v in scales.items()}
+    rec["variance_nll"], rec["variance_rows"] = nll or {}, rows or {}
+    rec["variance_excluded"], rec["variance_coverage"] = excluded or {}, coverage or {}
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1)
+    return rec
+
+
+def load_variance(path):
+    """The calibration file's {name: s}, validated, or None when it carries no "variance_scales" (a file written without
+    --with-variance: nothing is scaled)."""
+    with open(path) as f:
+        rec = json.load(f)
+    table = rec.get("variance_scales")
+    if table is None:
+        return None
+    if not isinstance(table, dict):
+        raise ValueError(f"{path}: \"variance_scales\" is not a table of detector names")
+    return {k: check_variance_scale(v, f"{path}: variance scale of {k}") for k, v in table.items()}
+
+
+def scale_j1_vars(det, s):
+    """A copy of a J1 prediction dict whose vars are s times the file's: float64 (the JSON's numbers are float64 already, and a
+    float32 value read back from JSON is that float32 exactly) times s, one multiply - what pe_proben_pack_calibrated does."""
+    s = check_variance_scale(s)
+    out = dict(det)
+    out["vars"] = [(np.asarray(v, dtype=np.float64) * s).tolist() for v in det["vars"]]
     return out

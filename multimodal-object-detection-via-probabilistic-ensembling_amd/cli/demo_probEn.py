@@ -19,6 +19,10 @@ softmax(class_logits / T) instead of the detectors' own prob_score; the result n
 normalises in the log domain: ProbEn's rule, defined where probEn's `1 - sum(p)` background gives NaN.  T = 1 without
 --temperatures / --calibration.  --class_prior 0.2,0.5,0.2,0.1 (K + 1 numbers, background last) divides the prior out
 (p(y)^(m-1) for a cluster of m rows); without the flag a --calibration file written by `fit_temperature --with-prior` supplies it.
+
+--variance_scales 0.5,2 (by position) or thermal_only=0.5,early_fusion=2 (by name) multiplies every detector's box variances by its
+scale ahead of the fusion (either route): the 1 / variance weights of --box_fusion v-avg.  Without the flag a --calibration file
+written by `fit_temperature --with-variance` supplies them, and the run says so; a file without them changes nothing.
 """
 import json
 import os
@@ -45,8 +49,9 @@ def main(cmd=None):
     prior = _class_prior(args) if logp else None
     if logp and temps is None:
         temps = {"values": [1.0] * len(names), "fitted": set()}
+    vscales = _variance_scales(args, names)
     if args.one_pass:
-        return one_pass(args, names, world, dev, temps, prior)
+        return one_pass(args, names, world, dev, temps, prior, vscales)
     files = [os.path.join(args.prediction_path, f"val_{n}_predictions.json") for n in names]
     if comm.is_main_process():
         for i, f in enumerate(files):
@@ -68,17 +73,14 @@ def main(cmd=None):
     main_rank = comm.is_main_process()
     ev = FLIREvaluator(args.dataset_name, cfg, world > 1 or comm.is_distributed(), output_dir=args.outfolder if main_rank else None, save_eval=main_rank,
                        out_eval_path=os.path.join(args.outfolder, "FLIR_probEn_eval.json"))
-    if temps is None:
-        res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
-                                             det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev))
-    else:
+    if temps is not None:
         _warn_fitted(temps, [i for d in dets for i in d["image_id"]])
-        res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
-                                             det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev),
-                                             temperatures=temps["values"], names=files, class_prior=prior)
-        res["temperatures"] = dict(zip(names, temps["values"]))
-        if prior is not None:
-            res["class_prior"] = prior
+    # every option is None unless it was asked for, and None is the callee's default
+    res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
+                                         det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev),
+                                         temperatures=None if temps is None else temps["values"], names=files, class_prior=prior,
+                                         variance_scales=vscales)
+    _name_options(res, names, temps, prior, vscales)
     if main_rank:
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
@@ -97,6 +99,21 @@ def _temperatures(args, names):
     return None
 
 
+def _variance_scales(args, names):
+    """--variance_scales, else the calibration file's "variance_scales" (fit_temperature --with-variance), else None; a list."""
+    from .. import calibration
+    if getattr(args, "variance_scales", None) is not None:
+        return calibration.parse_variance_scales(args.variance_scales, names)
+    if args.calibration is not None:
+        table = calibration.load_variance(args.calibration)
+        if table is not None:
+            vals = calibration.resolve_variance_scales(table, names, args.calibration)
+            if comm.is_main_process():
+                print(f"variance scales of {args.calibration}:", ", ".join(f"{n}={v:.6g}" for n, v in zip(names, vals)))
+            return vals
+    return None
+
+
 def _class_prior(args):
     """--class_prior, else the calibration file's "class_prior" (fit_temperature --with-prior), else None (uniform); a list."""
     from .. import calibration
@@ -105,6 +122,16 @@ def _class_prior(args):
     if args.calibration is not None:
         return calibration.load(args.calibration).get("class_prior")
     return None
+
+
+def _name_options(res, names, temps, prior, vscales):
+    """The printed result names the calibration it was made with; a run without any carries none of the keys."""
+    if temps is not None:
+        res["temperatures"] = dict(zip(names, temps["values"]))
+    if prior is not None:
+        res["class_prior"] = prior
+    if vscales is not None:
+        res["variance_scales"] = dict(zip(names, vscales))
 
 
 def _warn_fitted(temps, image_ids):
@@ -127,7 +154,7 @@ def _register(args):
     return cfg
 
 
-def one_pass(args, names, world, dev, temps=None, prior=None):
+def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None):
     """loader -> FramePairPipeline (one DefaultPredictor model per --detectors entry, cfg as save_predictions.build_cfg) ->
     ProbEn -> evaluation rows on the device (late_fusion.fused_rows_device) -> one all-gather -> FLIREvaluator on rank 0."""
     import argparse
@@ -158,12 +185,10 @@ def one_pass(args, names, world, dev, temps=None, prior=None):
         preds.append(DefaultPredictor(c))
     need_rgb = any(p.input_format in ("BGRT", "BGRTTT") for p in preds)
     loader = FlirPairLoader(args.dataset_path, args.batch, need_rgb=need_rgb, workers=workers)
-    if temps is None:
-        pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion)
-    else:
+    if temps is not None:
         _warn_fitted(temps, [loader.items[i]["id"] for i in loader.mine])
-        pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion, temperatures=temps["values"],
-                                 class_prior=prior)
+    pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion,
+                             temperatures=None if temps is None else temps["values"], class_prior=prior, variance_scales=vscales)
     j1 = [([], [], []) for _ in names]       # per detector: names, ids, instances
     rows = []
     feeder, feed_key, host = None, None, None
@@ -228,10 +253,7 @@ def one_pass(args, names, world, dev, temps=None, prior=None):
         ev.process_rows(all_rows.numpy())
         res = ev.evaluate()
         res["one_pass"] = stats
-        if temps is not None:
-            res["temperatures"] = dict(zip(names, temps["values"]))
-        if prior is not None:
-            res["class_prior"] = prior
+        _name_options(res, names, temps, prior, vscales)
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
         launch.shutdown()

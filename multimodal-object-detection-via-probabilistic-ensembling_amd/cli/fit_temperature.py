@@ -12,6 +12,15 @@ evaluation.  The fitted image ids go into the file, and demo_probEn warns when i
 --with-prior also writes "class_prior": the frequencies of the labels 0..K (background last) over the fitted rows of all the files
 together, with one added to every count so that a class no fitted row carries keeps a prior > 0 ("class_prior_counts" holds the raw
 counts).  `demo_probEn --score_fusion probEn-log --calibration FILE` uses it.  Without the flag the file is what it always was.
+--with-variance also fits one box-variance scale per detector on the same fitted images: every detection is matched to the ground
+truth on the device (calibration.match_rows_device, --iou), the matched rows' residuals are the box deltas from the detection to its
+ground-truth box (--bbox_reg_weights, the units of the variance head), and s = sum_i q_i / (4 n) minimises their Gaussian NLL under
+variance s * var_i (calibration.fit_variance_scale).  The file gains "variance_scales" {name: s}, "variance_nll", "variance_rows",
+"variance_excluded" and "variance_coverage"; `demo_probEn --calibration FILE` then fuses with the scaled variances.  Only matched
+detections are rows of the fit, so "variance_rows" + "variance_excluded" is the number of matched detections: the excluded count (and the
+printed one) is over matched rows - a degenerate box, a variance that is not finite and > 0 - and never includes unmatched detections.  Matching at
+IoU >= --iou cuts off the residuals' tails: s is biased low for a detector whose misses are large.  The fit
+takes the vars the file carries: fit and fuse under the same PROBEN.FIX_VARS setting.
 """
 import argparse
 import json
@@ -41,10 +50,49 @@ def parse(argv):
     p.add_argument("--device", default="cuda")
     p.add_argument("--with-prior", action="store_true",
                    help="also write the label frequencies of the fitted rows (background last, add-one smoothed) as class_prior")
+    p.add_argument("--with-variance", action="store_true",
+                   help="also fit one box-variance scale per detector on the fitted images and write the variance_* keys")
+    p.add_argument("--bbox_reg_weights", type=str, default="10,10,5,5",
+                   help="--with-variance: the box head's BBOX_REG_WEIGHTS 'wx,wy,ww,wh' (the units of the predicted variance)")
     args = p.parse_args(argv)
     if not 0.0 < args.holdout <= 1.0:
         p.error(f"--holdout {args.holdout} is not in (0, 1]")
+    try:
+        args.bbox_reg_weights = [float(x) for x in args.bbox_reg_weights.split(",")]
+    except ValueError:
+        p.error(f"--bbox_reg_weights {args.bbox_reg_weights!r} is not 'wx,wy,ww,wh'")
+    if len(args.bbox_reg_weights) != 4 or not all(0 < w < float("inf") for w in args.bbox_reg_weights):
+        p.error(f"--bbox_reg_weights {args.bbox_reg_weights} is not four numbers that are finite and > 0")
     return args
+
+
+def variance_fit(pred, records, fitted_ids, iou, name, weights, device):
+    """calibration.fit_variance_scale over the file's detections on the fitted images, matched on the device."""
+    det, var, gt, cls, crowd, doff, goff = [], [], [], [], [], [0], [0]
+    k = None
+    for i, iid in enumerate(pred["image_id"]):
+        if iid not in fitted_ids:
+            continue
+        anns = records[iid]["annotations"]
+        if len(pred["vars"][i]) != len(pred["boxes"][i]):
+            raise ValueError(f"{name}: {len(pred['vars'][i])} vars for the {len(pred['boxes'][i])} detections of image {i} "
+                             f"({pred['image'][i]}): the variance fit needs the box head's vars")
+        if k is None and pred["class_logits"][i] and len(pred["class_logits"][i][0]) >= 2:
+            k = len(pred["class_logits"][i][0]) - 1
+        det += pred["boxes"][i]
+        var += [v[0] if isinstance(v, (list, tuple)) else v for v in pred["vars"][i]]
+        gt += [[a["bbox"][0], a["bbox"][1], a["bbox"][0] + a["bbox"][2], a["bbox"][1] + a["bbox"][3]] for a in anns]      # COCO XYWH -> XYXY
+        cls += [a["category_id"] for a in anns]
+        crowd += [a["iscrowd"] for a in anns]
+        doff.append(len(det))
+        goff.append(len(gt))
+    t = lambda x, dt, shape: torch.tensor(x, dtype=dt).reshape(shape).to(device)
+    db, gb = t(det, torch.float64, (-1, 4)), t(gt, torch.float64, (-1, 4))
+    _, match, _ = calibration.match_rows_device(db, t(doff, torch.int32, (-1,)), gb, t(goff, torch.int32, (-1,)), t(cls, torch.int32, (-1,)),
+                                                t(crowd, torch.int32, (-1,)), iou, k if k is not None else 1)     # k sizes the labels only,
+    # which this fit does not read (k is None when no fitted image has a detection: nothing is matched then either)
+    hit = match >= 0               # the unmatched detections are no residuals: only the matched rows are rows of the fit
+    return calibration.fit_variance_scale(db[hit], match[hit], gb, t(var, torch.float64, (-1,))[hit], weights)
 
 
 def labelled_rows(pred, records, fitted_ids, iou, name):
@@ -76,12 +124,14 @@ def main(cmd=None):
     fitted = order[:n_fit]
     by_id = {r["image_id"]: r for r in records}
     temps, nll, rows, bound = {}, {}, {}, {}
+    vfit = {}
     counts = None
     for path in args.predictions:
         name = detector_name(path)
         if name in temps:
             raise ValueError(f"{path}: a second prediction file for detector {name}")
-        logits, labels = labelled_rows(read_j1(path), by_id, set(fitted), args.iou, path)
+        pred = read_j1(path)
+        logits, labels = labelled_rows(pred, by_id, set(fitted), args.iou, path)
         if not logits:
             raise ValueError(f"{path}: no detections on the {n_fit} fitted images: nothing to fit")
         if args.with_prior:
@@ -95,12 +145,25 @@ def main(cmd=None):
         nll[name] = {"before": fit["nll_at_1"], "after": fit["nll"]}
         note = f"  (minimum on the {fit['at_bound']} end of the search range: not a fitted value)" if fit["at_bound"] else ""
         print(f"{name}: T = {fit['T']:.6f}  NLL {fit['nll_at_1']:.6f} -> {fit['nll']:.6f} over {fit['rows']} rows{note}")
+        if args.with_variance:
+            try:
+                v = vfit[name] = variance_fit(pred, by_id, set(fitted), args.iou, path, args.bbox_reg_weights, args.device)
+            except ValueError as e:
+                raise ValueError(f"{path}: {e}") from None
+            print(f"{name}: variance scale = {v['scale']:.6f}  NLL {v['nll_before']:.6f} -> {v['nll_after']:.6f} over {v['rows']} matched rows "
+                  f"({v['excluded']} excluded), within 1 / 2 sigma {v['coverage_before'][0]:.4f} / {v['coverage_before'][1]:.4f} -> "
+                  f"{v['coverage_after'][0]:.4f} / {v['coverage_after'][1]:.4f} (a Gaussian: 0.6827 / 0.9545)")
     if args.with_prior:
         calibration.save(args.out, temps, nll, rows, class_prior=[c + 1 for c in counts], holdout=args.holdout, fitted_image_ids=fitted,
                          at_bound=bound, class_prior_counts=counts)
         print("class prior (background last):", ", ".join(f"{c + 1}/{sum(counts) + len(counts)}" for c in counts))
     else:
         calibration.save(args.out, temps, nll, rows, holdout=args.holdout, fitted_image_ids=fitted, at_bound=bound)
+    if args.with_variance:
+        calibration.save_variance(args.out, {n: v["scale"] for n, v in vfit.items()},
+                                  {n: {"before": v["nll_before"], "after": v["nll_after"]} for n, v in vfit.items()},
+                                  {n: v["rows"] for n, v in vfit.items()}, {n: v["excluded"] for n, v in vfit.items()},
+                                  {n: {"before": v["coverage_before"], "after": v["coverage_after"]} for n, v in vfit.items()})
     print("calibration file:", args.out)
     return args.out
 

@@ -88,6 +88,7 @@ struct PackLogitsArgs {
 
 // one wavefront per image: the ordered compaction of proben_pack_kernel (csrc/proben.hip), then the chunk's 64 rows go through the
 // softmax 64 / G at a time.  LOGP (pe_proben_pack_log_posteriors) stores the row's K+1 log-posteriors next to everything else.
+// (proben_scale_vars_kernel, csrc/variance.hip, repeats this compaction to rewrite out_vars: keep the row order of the two in step)
 template <bool LOGP>
 __global__ __launch_bounds__(64) void proben_pack_logits_kernel(PackLogitsArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;

@@ -392,6 +392,8 @@ struct PackArgs {
 };
 
 // one wavefront per image: ordered compaction of every detector's live rows (class <= max_class)
+// (proben_scale_vars_kernel, csrc/variance.hip, walks the same compaction - min(counts, D), class <= max_class, the `written` prefix -
+// to rewrite out_vars: a change to the row order here belongs there too; tests/test_variance_gpu.py pins the pair)
 __global__ __launch_bounds__(64) void proben_pack_kernel(PackArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     int written = 0, sources = 0;

@@ -1,0 +1,291 @@
+// Variance calibration of the detectors' box heads (gfx950): one positive scale s_d per detector, variance' = s_d * variance.
+//   pe_match_ground_truth      : detections -> (label, matched ground-truth index, best IoU), batched over images
+//   pe_variance_stats          : the sufficient statistics of the Gaussian NLL of the matched rows' box-delta residuals
+//   pe_proben_pack_calibrated  : the three pack entry points behind one signature, then out_vars = (double)var_f32 * s_d
+//
+// Matching is calibration.match_labels / finetune.pairwise_iou in float64, in that expression order (built with -ffp-contract=off,
+// so no multiply-add is fused): area = (x2 - x1) * (y2 - y1), w = max(min(ax2, bx2) - max(ax1, bx1), 0), inter = w * h,
+// union = (area_a + area_b) - inter, IoU = inter > 0 ? inter / union : 0.  Every operation is one IEEE float64 operation on both
+// sides, so the IoU is the same bits.  Boxes are expected finite (a NaN coordinate never wins here; torch's max would return it).
+//
+// The statistics are reduced without floating-point atomics: a thread adds its rows in row order (row r belongs to thread r mod
+// (blocks * 256)), the workgroup adds its 256 threads in a stride-halving tree, the second kernel adds the (at most 1 024) workgroup
+// partials in the same tree.  The grid is a function of the row count alone: same input, same bits.
+#include "common.h"
+
+namespace {
+
+constexpr int kMatchThreads = 256;
+constexpr int kMatchChunk = 512;          // ground-truth boxes staged in LDS at a time: 512 * (5 * 8 + 4) = 22 KiB
+
+// A workgroup per image, a thread per detection (tiles of 256 when an image has more), the image's ground truth staged in LDS in
+// chunks of kMatchChunk: every lane reads the same LDS address (broadcast).  All loop bounds are workgroup-uniform.
+__global__ __launch_bounds__(kMatchThreads) void match_ground_truth_kernel(const double* det, const int32_t* det_off, const double* gt,
+                                                                           const int32_t* gt_off, const int32_t* gt_cls,
+                                                                           const int32_t* gt_crowd, double thresh, int num_classes,
+                                                                           int32_t* out_label, int32_t* out_match, double* out_iou) {
+    __shared__ double gx1[kMatchChunk], gy1[kMatchChunk], gx2[kMatchChunk], gy2[kMatchChunk], garea[kMatchChunk];
+    __shared__ int32_t glive[kMatchChunk];
+    const int b = blockIdx.x;
+    const int d0 = det_off[b], d1 = det_off[b + 1], g0 = gt_off[b], g1 = gt_off[b + 1];
+    for (int tile = d0; tile < d1; tile += kMatchThreads) {
+        const int i = tile + (int)threadIdx.x;
+        const bool live = i < d1;
+        double ax1 = 0, ay1 = 0, ax2 = 0, ay2 = 0, area_a = 0;
+        if (live) {
+            ax1 = det[(size_t)i * 4]; ay1 = det[(size_t)i * 4 + 1]; ax2 = det[(size_t)i * 4 + 2]; ay2 = det[(size_t)i * 4 + 3];
+            area_a = (ax2 - ax1) * (ay2 - ay1);
+        }
+        double best = -1.0;             // an IoU is >= 0: the first ground-truth box that takes part always replaces this
+        int best_g = -1;
+        for (int c0 = g0; c0 < g1; c0 += kMatchChunk) {
+            const int n = min(kMatchChunk, g1 - c0);
+            __syncthreads();            // the previous chunk (or tile) has been read by every thread
+            for (int k = threadIdx.x; k < n; k += kMatchThreads) {
+                const size_t g = (size_t)(c0 + k);
+                const double x1 = gt[g * 4], y1 = gt[g * 4 + 1], x2 = gt[g * 4 + 2], y2 = gt[g * 4 + 3];
+                gx1[k] = x1; gy1[k] = y1; gx2[k] = x2; gy2[k] = y2;
+                garea[k] = (x2 - x1) * (y2 - y1);
+                glive[k] = gt_crowd ? (gt_crowd[g] == 0) : 1;
+            }
+            __syncthreads();
+            if (live) {
+                for (int k = 0; k < n; ++k) {
+                    if (!glive[k]) continue;
+                    const double w = fmax(fmin(ax2, gx2[k]) - fmax(ax1, gx1[k]), 0.0);
+                    const double h = fmax(fmin(ay2, gy2[k]) - fmax(ay1, gy1[k]), 0.0);
+                    const double inter = w * h;
+                    const double uni = area_a + garea[k] - inter;
+                    const double iou = inter > 0.0 ? inter / uni : 0.0;
+                    if (iou > best) { best = iou; best_g = c0 + k; }      // strict: the lowest index keeps an equal maximum
+                }
+            }
+        }
+        if (live) {
+            const bool hit = best_g >= 0 && best >= thresh;
+            out_label[i] = hit ? gt_cls[best_g] : num_classes;
+            out_match[i] = hit ? best_g : -1;
+            out_iou[i] = best_g >= 0 ? best : 0.0;
+        }
+    }
+}
+
+constexpr int kStatThreads = 256;
+constexpr int kStatValues = 5;            // n, sum q, sum log var, coverage at 1 sigma, coverage at 2 sigma
+
+struct StatArgs {
+    const double* det;
+    const int32_t* match;
+    const double* gt;
+    const double* var;
+    long long M, G;
+    double w[4];
+    double s;
+    double* partial;      // [blocks, 5]
+    int32_t* flags;       // [0] excluded rows, [1] 1 + the largest excluded row index (saturating)
+};
+
+// x[0..255] of the five values -> x[0], stride-halving tree: level by level, the same pairs whatever the data
+__device__ __forceinline__ void block_tree(double (*x)[kStatValues], int n) {
+    for (int s = n >> 1; s > 0; s >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < s)
+            for (int v = 0; v < kStatValues; ++v) x[threadIdx.x][v] += x[threadIdx.x + s][v];
+    }
+}
+
+__global__ __launch_bounds__(kStatThreads) void variance_stats_kernel(StatArgs a) {
+    __shared__ double x[kStatThreads][kStatValues];
+    double n = 0.0, sq = 0.0, sl = 0.0, c1 = 0.0, c2 = 0.0;
+    const long long step = (long long)gridDim.x * kStatThreads;
+    for (long long r = (long long)blockIdx.x * kStatThreads + threadIdx.x; r < a.M; r += step) {
+        const int m = a.match[r];
+        const double v = a.var[r];
+        bool ok = m >= 0 && m < a.G && v > 0.0 && v < __builtin_huge_val();       // NaN fails v > 0; an index beyond the table is never read
+        double sw = 0, sh = 0, tw = 0, th = 0;
+        const double* s = a.det + r * 4;
+        const double* t = a.gt + (size_t)(ok ? m : 0) * 4;
+        if (ok) {
+            sw = s[2] - s[0]; sh = s[3] - s[1];
+            tw = t[2] - t[0]; th = t[3] - t[1];
+            ok = sw > 0.0 && sh > 0.0 && tw > 0.0 && th > 0.0;
+        }
+        if (!ok) {
+            atomicAdd(&a.flags[0], 1);
+            atomicMax(&a.flags[1], (int)min(r + 1, (long long)0x7fffffff));
+            continue;
+        }
+        // Box2BoxTransform.get_deltas(detection, ground truth): w[:2] * (tc - sc) / swh, w[2:] * log(twh / swh)
+        const double scx = s[0] + 0.5 * sw, scy = s[1] + 0.5 * sh;
+        const double tcx = t[0] + 0.5 * tw, tcy = t[1] + 0.5 * th;
+        double res[4];
+        res[0] = a.w[0] * (tcx - scx) / sw;
+        res[1] = a.w[1] * (tcy - scy) / sh;
+        res[2] = a.w[2] * log(tw / sw);
+        res[3] = a.w[3] * log(th / sh);
+        const double sv = a.s * v, sv4 = 4.0 * sv;
+        double q = 0.0;
+        for (int c = 0; c < 4; ++c) {
+            const double r2 = res[c] * res[c];
+            q += r2 / v;
+            c1 += r2 <= sv ? 1.0 : 0.0;
+            c2 += r2 <= sv4 ? 1.0 : 0.0;
+        }
+        n += 1.0;
+        sq += q;
+        sl += log(v);
+    }
+    x[threadIdx.x][0] = n; x[threadIdx.x][1] = sq; x[threadIdx.x][2] = sl; x[threadIdx.x][3] = c1; x[threadIdx.x][4] = c2;
+    block_tree(x, kStatThreads);
+    if (threadIdx.x == 0)
+        for (int v = 0; v < kStatValues; ++v) a.partial[(size_t)blockIdx.x * kStatValues + v] = x[0][v];
+}
+
+// second pass, one workgroup: thread k holds workgroup k's partial (0 beyond the grid: adding it is exact), 1 024 -> 1 in the same tree
+__global__ __launch_bounds__(PE_VARIANCE_STATS_MAX_BLOCKS) void variance_stats_finish_kernel(const double* partial, int blocks,
+                                                                                             double* out) {
+    __shared__ double x[PE_VARIANCE_STATS_MAX_BLOCKS][kStatValues];
+    for (int v = 0; v < kStatValues; ++v)
+        x[threadIdx.x][v] = (int)threadIdx.x < blocks ? partial[(size_t)threadIdx.x * kStatValues + v] : 0.0;
+    block_tree(x, PE_VARIANCE_STATS_MAX_BLOCKS);
+    if (threadIdx.x == 0)
+        for (int v = 0; v < kStatValues; ++v) out[v] = x[0][v];
+}
+
+struct ScaleArgs {
+    const int32_t* classes[4];
+    const float* vars[4];
+    const int32_t* counts[4];
+    double s[4];
+    int nd, D, max_class, stride;
+    double* ov;
+};
+
+// one wavefront per image: the ordered compaction of proben_pack_kernel (csrc/proben.hip) once more, writing the variances only
+// (the same walk as proben_pack_kernel and proben_pack_logits_kernel, csrc/calibrate.hip: the three must agree on the row order)
+__global__ __launch_bounds__(64) void proben_scale_vars_kernel(ScaleArgs a) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int written = 0;
+    for (int d = 0; d < a.nd; ++d) {
+        const int c = min(a.counts[d][b], a.D);
+        const double s = a.s[d];
+        for (int base = 0; base < c; base += 64) {
+            const int j = base + lane;
+            const size_t src = (size_t)b * a.D + j;
+            const bool ok = j < c && a.classes[d][src] <= a.max_class;
+            const unsigned long long m = __ballot(ok);
+            if (ok) a.ov[(size_t)b * a.stride + written + __popcll(m & pe::lanemask_lt())] = (double)a.vars[d][src] * s;
+            written += __popcll(m);
+        }
+    }
+}
+
+bool good_scale(double s) { return s == s && s > 0.0 && s < __builtin_huge_val(); }
+
+}  // namespace
+
+extern "C" int pe_match_ground_truth(const double* det_boxes, const int32_t* det_offsets, const double* gt_boxes,
+                                     const int32_t* gt_offsets, const int32_t* gt_classes, const int32_t* gt_crowd,
+                                     int32_t num_images, double iou_thresh, int32_t num_classes, int32_t* out_labels,
+                                     int32_t* out_match, double* out_iou, void* stream) {
+    PE_CHECK_ARG(num_images >= 0, "pe_match_ground_truth: num_images %d", num_images);
+    PE_CHECK_ARG(num_classes >= 1, "pe_match_ground_truth: num_classes %d", num_classes);
+    PE_CHECK_ARG(iou_thresh == iou_thresh, "pe_match_ground_truth: iou_thresh %g", iou_thresh);
+    if (num_images == 0) return PE_OK;
+    PE_CHECK_ARG(det_offsets && gt_offsets, "pe_match_ground_truth: null pointer (det_offsets / gt_offsets)");
+    // images without detections or without ground truth are legal, so the row pointers may belong to empty tensors: they are only
+    // dereferenced inside [offsets[b], offsets[b + 1]); the outputs are per detection
+    PE_CHECK_ARG(det_boxes && gt_boxes && gt_classes, "pe_match_ground_truth: null pointer (det_boxes / gt_boxes / gt_classes)");
+    PE_CHECK_ARG(out_labels && out_match && out_iou, "pe_match_ground_truth: null output");
+    hipLaunchKernelGGL(match_ground_truth_kernel, dim3(num_images), dim3(kMatchThreads), 0, (hipStream_t)stream, det_boxes, det_offsets,
+                       gt_boxes, gt_offsets, gt_classes, gt_crowd, iou_thresh, (int)num_classes, out_labels, out_match, out_iou);
+    PE_CHECK_LAUNCH("pe_match_ground_truth");
+    return PE_OK;
+}
+
+extern "C" int pe_variance_stats(const double* det_boxes, const int32_t* match, const double* gt_boxes, const double* variances,
+                                 int64_t num_rows, int64_t num_gt, const float* bbox_reg_weights_host, double scale, double* workspace, double* out,
+                                 int32_t* out_flags, void* stream) {
+    PE_CHECK_ARG(good_scale(scale), "pe_variance_stats: scale %g is not finite and > 0", scale);
+    PE_CHECK_ARG(num_rows >= 0 && num_gt >= 0, "pe_variance_stats: num_rows %lld, num_gt %lld", (long long)num_rows, (long long)num_gt);
+    PE_CHECK_ARG(workspace && out && out_flags, "pe_variance_stats: null pointer (workspace / out / out_flags)");
+    PE_CHECK_ARG(num_rows == 0 || (det_boxes && match && variances && (gt_boxes || num_gt == 0)),
+                 "pe_variance_stats: null pointer (det_boxes / match / gt_boxes / variances)");
+    static const float kDefaultWeights[4] = {10.f, 10.f, 5.f, 5.f};
+    const float* w = bbox_reg_weights_host ? bbox_reg_weights_host : kDefaultWeights;
+    StatArgs a{};
+    for (int c = 0; c < 4; ++c) {
+        PE_CHECK_ARG(w[c] == w[c] && w[c] > 0.f && w[c] < __builtin_huge_valf(), "pe_variance_stats: bbox_reg_weights[%d] %g is not finite and > 0",
+                     c, (double)w[c]);
+        a.w[c] = (double)w[c];
+    }
+    a.det = det_boxes; a.match = match; a.gt = gt_boxes; a.var = variances; a.M = num_rows; a.G = num_gt; a.s = scale;
+    a.partial = workspace; a.flags = out_flags;
+    // the grid is a function of num_rows alone: same input, same partition, same bits
+    const int blocks = (int)std::max<long long>(1, std::min<long long>((num_rows + kStatThreads - 1) / kStatThreads,
+                                                                        PE_VARIANCE_STATS_MAX_BLOCKS));
+    if (hipMemsetAsync(out_flags, 0, 2 * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) {
+        pe::set_error("pe_variance_stats: hipMemsetAsync of the flags failed");
+        return PE_ERR_HIP;
+    }
+    hipLaunchKernelGGL(variance_stats_kernel, dim3(blocks), dim3(kStatThreads), 0, (hipStream_t)stream, a);
+    PE_CHECK_LAUNCH("pe_variance_stats");
+    hipLaunchKernelGGL(variance_stats_finish_kernel, dim3(1), dim3(PE_VARIANCE_STATS_MAX_BLOCKS), 0, (hipStream_t)stream, workspace, blocks,
+                       out);
+    PE_CHECK_LAUNCH("pe_variance_stats (finish)");
+    return PE_OK;
+}
+
+extern "C" int pe_proben_pack_calibrated(const float* const* det_boxes_host, const float* const* det_scores_host,
+                                         const int32_t* const* det_classes_host, const float* const* det_probs_host,
+                                         const float* const* det_logits_host, const float* const* det_vars_host,
+                                         const int32_t* const* det_counts_host, const double* temperatures_host,
+                                         const double* var_scales_host, int32_t num_detectors, int32_t num_images,
+                                         int32_t det_stride, int32_t num_classes, int32_t max_class, int32_t row_stride,
+                                         double* out_boxes, double* out_scores, double* out_probs, double* out_log_probs,
+                                         double* out_vars, int32_t* out_classes, int32_t* out_offsets, int32_t* out_counts,
+                                         int32_t* out_single_source, void* stream) {
+    const char* what = "pe_proben_pack_calibrated";
+    PE_CHECK_ARG(num_detectors >= 1 && num_detectors <= 4, "%s: num_detectors %d", what, num_detectors);
+    PE_CHECK_ARG(num_images >= 0 && det_stride >= 0, "%s: num_images %d, det_stride %d", what, num_images, det_stride);
+    PE_CHECK_ARG(det_boxes_host && det_classes_host && det_vars_host && det_counts_host, "%s: null pointer (detector tables)", what);
+    const bool from_logits = det_logits_host != nullptr;
+    if (from_logits) {
+        PE_CHECK_ARG(temperatures_host, "%s: null pointer (temperatures: the logits route needs one per detector)", what);
+        PE_CHECK_ARG(!det_scores_host && !det_probs_host, "%s: both probabilities and logits given: one route at a time", what);
+    } else {
+        PE_CHECK_ARG(det_scores_host && det_probs_host, "%s: null pointer (neither probabilities nor logits)", what);
+        PE_CHECK_ARG(!temperatures_host && !out_log_probs, "%s: temperatures / out_log_probs belong to the logits route", what);
+    }
+    ScaleArgs a{};
+    for (int d = 0; d < num_detectors; ++d) {
+        if (var_scales_host)
+            PE_CHECK_ARG(good_scale(var_scales_host[d]), "%s: variance scale %g of detector %d is not finite and > 0", what,
+                         var_scales_host[d], d);
+        a.classes[d] = det_classes_host[d]; a.vars[d] = det_vars_host[d]; a.counts[d] = det_counts_host[d];
+        a.s[d] = var_scales_host ? var_scales_host[d] : 1.0;
+        PE_CHECK_ARG(a.classes[d] && a.vars[d] && a.counts[d] && det_boxes_host[d], "%s: null pointer of detector %d", what, d);
+        if (!from_logits)
+            PE_CHECK_ARG(det_scores_host[d] && det_probs_host[d], "%s: null pointer of detector %d", what, d);
+    }
+    // every output but out_vars is the existing entry point's, because it is the existing entry point that writes it
+    int st;
+    if (!from_logits)
+        st = pe_proben_pack_detections(det_boxes_host, det_scores_host, det_classes_host, det_probs_host, det_vars_host, det_counts_host,
+                                       num_detectors, num_images, det_stride, num_classes, max_class, row_stride, out_boxes, out_scores,
+                                       out_probs, out_vars, out_classes, out_offsets, out_counts, out_single_source, stream);
+    else if (out_log_probs)
+        st = pe_proben_pack_log_posteriors(det_boxes_host, det_classes_host, det_logits_host, det_vars_host, det_counts_host,
+                                           temperatures_host, num_detectors, num_images, det_stride, num_classes, max_class, row_stride,
+                                           out_boxes, out_scores, out_probs, out_log_probs, out_vars, out_classes, out_offsets,
+                                           out_counts, out_single_source, stream);
+    else
+        st = pe_proben_pack_logits(det_boxes_host, det_classes_host, det_logits_host, det_vars_host, det_counts_host, temperatures_host,
+                                   num_detectors, num_images, det_stride, num_classes, max_class, row_stride, out_boxes, out_scores,
+                                   out_probs, out_vars, out_classes, out_offsets, out_counts, out_single_source, stream);
+    if (st != PE_OK || !var_scales_host || num_images == 0) return st;
+    a.nd = num_detectors; a.D = det_stride; a.max_class = max_class; a.stride = row_stride; a.ov = out_vars;
+    hipLaunchKernelGGL(proben_scale_vars_kernel, dim3(num_images), dim3(64), 0, (hipStream_t)stream, a);
+    PE_CHECK_LAUNCH(what);
+    return PE_OK;
+}

@@ -148,7 +148,7 @@ def pack_infos(per_image_infos, device="cuda", with_log_probs=False):
     return out + (cat(ll, (0, K + 1), np.float64),) if with_log_probs else out
 
 
-def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=None):
+def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=None, variance_scales=None):
     """Drop-in for the reference's ``fusion`` (demo_probEn.py:189-196).
 
     Returns (out_boxes, out_scores, out_class): boxes as a list of float64 ndarrays [4]
@@ -157,9 +157,15 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=Non
     temperatures (one T per info): the rows' prob / score are rebuilt from their class_logits as softmax(logits / T)
     (calibration.calibrate_rows); an info without logits is refused.
     method[0] "probEn-log": the rows' log-posteriors come from their class_logits too (temperatures None = 1 for every info) and
-    are fused by pe_proben_fuse_batch_logp, with class_prior (K + 1 probabilities, background last) when given."""
+    are fused by pe_proben_fuse_batch_logp, with class_prior (K + 1 probabilities, background last) when given.
+    variance_scales (one s per info): the rows' vars are multiplied by s in float64 (one multiply, as pe_proben_pack_calibrated does
+    on the device route); only box rule "v-avg" reads them."""
     infos = [info_1, info_2] + ([info_3] if info_3 else [])
     _check_mode(method[0], class_prior, "fusion")
+    if variance_scales is not None:
+        from .calibration import check_variance_scales
+        variance_scales = check_variance_scales(variance_scales, len(infos), "fusion")
+        infos = [dict(d, vars=(np.asarray(d["vars"], dtype=np.float64) * s).tolist()) for d, s in zip(infos, variance_scales)]
     logp = method[0] == LOGP
     if logp and temperatures is None:
         temperatures = [1.0] * len(infos)
@@ -198,14 +204,19 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=Non
     return [boxes[i] for i in range(m)], out["scores"][:m].cpu(), out["classes"][:m].cpu()
 
 
-def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False):
+def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, variance_scales=None):
     """The detectors' padded outputs -> ProbEn input rows on the device (pe_proben_pack_detections; with temperatures
     pe_proben_pack_logits: probabilities and scores from class_logits as softmax(logits / T_d) in float64).
     Returns (boxes f64 [B*S,4], scores f64, probs f64 [B*S,K], vars f64, classes i32, offsets i32 [B], counts i32 [B],
     single-source flags i32 [B]), S = len(dets) * D.  log_posteriors (needs temperatures): pe_proben_pack_log_posteriors, the
-    same eight plus the rows' log-posteriors f64 [B*S,K+1] as a ninth."""
+    same eight plus the rows' log-posteriors f64 [B*S,K+1] as a ninth.
+    variance_scales (one s per detector): pe_proben_pack_calibrated, whichever of the three routes the other arguments select, with
+    vars = (double)var * s_d; None calls the three entry points above as before."""
     import ctypes
     nd = len(dets)
+    if variance_scales is not None:
+        from .calibration import check_variance_scales
+        variance_scales = check_variance_scales(variance_scales, nd, "pack_rows")
     B, D = dets[0]["scores"].shape
     K = dets[0]["prob_score"].shape[2]
     dev = dets[0]["scores"].device
@@ -223,6 +234,23 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False):
     osingle = torch.empty((B,), dtype=torch.int32, device=dev)
     if log_posteriors and temperatures is None:
         raise ValueError("pack_rows: log_posteriors needs temperatures (1.0 per detector for the uncalibrated logits)")
+    if temperatures is not None:       # (worded for fuse_detections, the caller these messages have always named)
+        if len(temperatures) != nd:
+            raise ValueError(f"fuse_detections: {len(temperatures)} temperatures for {nd} detectors")
+        for d in dets:
+            if d["class_logits"].shape != (B, D, K + 1) or d["class_logits"].dtype != torch.float32:
+                raise ValueError(f"fuse_detections: class_logits {tuple(d['class_logits'].shape)} is not float32 [{B}, {D}, {K + 1}]")
+    if variance_scales is not None:
+        logits = temperatures is not None
+        olp = torch.empty((B * S, K + 1), dtype=torch.float64, device=dev) if log_posteriors else None
+        st = _lib.lib().pe_proben_pack_calibrated(
+            arr("boxes"), None if logits else arr("scores"), arr("classes"), None if logits else arr("prob_score"),
+            arr("class_logits") if logits else None, arr("vars"), arr("counts"),
+            (ctypes.c_double * nd)(*[float(t) for t in temperatures]) if logits else None, (ctypes.c_double * nd)(*variance_scales),
+            nd, B, D, K, max_class, S, _lib.ptr(ob), _lib.ptr(os_), _lib.ptr(op), _lib.ptr(olp), _lib.ptr(ov), _lib.ptr(oc),
+            _lib.ptr(ooff), _lib.ptr(ocnt), _lib.ptr(osingle), _lib.stream())
+        _lib.check(st, "pe_proben_pack_calibrated")
+        return (ob, os_, op, ov, oc, ooff, ocnt, osingle) + ((olp,) if log_posteriors else ())
     if temperatures is None:
         st = _lib.lib().pe_proben_pack_detections(arr("boxes"), arr("scores"), arr("classes"), arr("prob_score"), arr("vars"),
                                                  arr("counts"), nd, B, D, K, max_class, S, _lib.ptr(ob), _lib.ptr(os_),
@@ -230,11 +258,6 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False):
                                                  _lib.ptr(osingle), _lib.stream())
         _lib.check(st, "pe_proben_pack_detections")
     else:
-        if len(temperatures) != nd:
-            raise ValueError(f"fuse_detections: {len(temperatures)} temperatures for {nd} detectors")
-        for d in dets:
-            if d["class_logits"].shape != (B, D, K + 1) or d["class_logits"].dtype != torch.float32:
-                raise ValueError(f"fuse_detections: class_logits {tuple(d['class_logits'].shape)} is not float32 [{B}, {D}, {K + 1}]")
         temps = (ctypes.c_double * nd)(*[float(t) for t in temperatures])
         if log_posteriors:
             olp = torch.empty((B * S, K + 1), dtype=torch.float64, device=dev)
@@ -253,7 +276,7 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False):
 
 
 def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=0.5, temperatures=None,
-                    class_prior=None):
+                    class_prior=None, variance_scales=None):
     """Device-to-device stage fusion: `dets` = the result dicts of 2 or 3 detectors run on the SAME batch
     (rcnn.GeneralizedRCNN.forward_batch).  Packs their detections into ProbEn rows (classes <= max_class,
     like the JSON writer demo_FLIR_save_predictions.py:148-155), applies the reference's per-image case
@@ -262,6 +285,8 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     softmax(logits / T) in float64 (pe_proben_pack_logits) instead of the float32 prob_score / scores.
     score_fusion "probEn-log": pe_proben_pack_log_posteriors + pe_proben_fuse_batch_logp (temperatures None = 1 per detector;
     class_prior: K + 1 probabilities, background last, or the device tensor of log_class_prior).
+    variance_scales (one s per detector): the rows' variances are (double)var * s_d (pe_proben_pack_calibrated); they weight the
+    member boxes of box_fusion "v-avg" and nothing else, so every other box rule and the NMS route give the bits they gave.
     No host synchronisation.  Returns a dict: boxes f64 [B*S,4], scores f32, classes f32, counts i32 [B],
     offsets i32 [B], stride S = len(dets) * D."""
     # the box heads' candidate-cap bookkeeping travels with the result (no kernel here): check_candidate_overflow() looks
@@ -273,13 +298,13 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     dev = dets[0]["scores"].device
     if score_fusion == LOGP:
         ob, os_, op, ov, oc, ooff, ocnt, osingle, olp = pack_rows(dets, max_class, temperatures if temperatures is not None else [1.0] * len(dets),
-                                                                     log_posteriors=True)
+                                                                     log_posteriors=True, variance_scales=variance_scales)
         out = fuse_batch(ob, os_, op, ov, oc, ooff, score_fusion, box_fusion, max_rows=S, iou_thresh=iou_thresh,
                          row_counts=ocnt, passthrough=osingle, log_probs=olp, class_prior=class_prior)
         out["offsets"], out["stride"], out["in_counts"] = ooff, S, ocnt
         out["cand_overflow_src"] = overflow_src
         return out
-    ob, os_, op, ov, oc, ooff, ocnt, osingle = pack_rows(dets, max_class, temperatures)
+    ob, os_, op, ov, oc, ooff, ocnt, osingle = pack_rows(dets, max_class, temperatures, variance_scales=variance_scales)
     if score_fusion == "max" and box_fusion == "argmax":
         from .layers import nms_batched_raw
         b32 = ob.float().view(B, S, 4)

@@ -66,7 +66,7 @@ def _info(det, i):
     return d
 
 
-def late_fusion(dets, method, device="cuda", temperatures=None, names=None, class_prior=None):
+def late_fusion(dets, method, device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None):
     """dets: 2 or 3 J1 dicts over the same images (order = detector order).  Returns per-image
     (boxes float64 [m,4] | None, scores f32, classes f32); None = skipped image (no detector fired).
     Case split of demo_probEn.py:237-267: 0 detectors -> skip, 1 -> passthrough, >= 2 -> fusion of the
@@ -75,8 +75,14 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
     the case split (calibration.calibrate_j1), so passed-through rows carry the calibrated score like the device route's;
     `names` (the files) word the refusal of a file without logits.
     method[0] "probEn-log": the files' log-posteriors log_softmax(class_logits / T) (temperatures None = 1 per file) go through
-    pe_proben_fuse_batch_logp, with class_prior (K + 1 probabilities, background last) when given."""
+    pe_proben_fuse_batch_logp, with class_prior (K + 1 probabilities, background last) when given.
+    variance_scales (one s per detector): every file's vars are multiplied by s in float64 (calibration.scale_j1_vars), the single
+    multiply of the device route's pe_proben_pack_calibrated, so both routes fuse identical variances."""
     F._check_mode(method[0], class_prior, "late_fusion")
+    if variance_scales is not None:
+        from . import calibration
+        variance_scales = calibration.check_variance_scales(variance_scales, len(dets), "late_fusion")
+        dets = [calibration.scale_j1_vars(d, s) for d, s in zip(dets, variance_scales)]
     logp = method[0] == F.LOGP
     if logp and temperatures is None:
         temperatures = [1.0] * len(dets)
@@ -126,7 +132,7 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
 
 def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="", image_hw=None, device="cuda",
                                    img_folder="../../../Datasets/FLIR/val/thermal_8_bit/", temperatures=None, names=None,
-                                   class_prior=None):
+                                   class_prior=None, variance_scales=None):
     """Same call as the reference (demo_probEn.py:198).  `image_hw`: {image_id: (H, W)} from the dataset
     json (the reference re-reads every thermal JPEG just for its shape); default 512 x 640 (FLIR).
     `img_folder`: the prefix the reference hard-codes into the `file_name` it hands to the evaluator (:200,271).
@@ -136,10 +142,7 @@ def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="
     print("Method: ", method)
     start = time.time()
     dets = [det_1, det_2] + ([det_3] if det_3 else [])
-    if method[0] == F.LOGP or class_prior is not None:
-        fused = late_fusion(dets, method, device, temperatures, names, class_prior)
-    else:
-        fused = late_fusion(dets, method, device) if temperatures is None else late_fusion(dets, method, device, temperatures, names)
+    fused = late_fusion(dets, method, device, temperatures, names, class_prior, variance_scales)
     for i, r in enumerate(fused):
         if r is None:
             continue

@@ -36,6 +36,10 @@ def config_parser(cmd=None):
                      help="demo_probEn: one softmax temperature per --detectors entry, 'a,b[,c]' by position or 'name=a,name=b' by name")
     cal.add_argument("--calibration", type=str, default=None,
                      help="demo_probEn: calibration file written by cli/fit_temperature (temperatures looked up by detector name)")
+    p.add_argument("--variance_scales", type=str, default=None,
+                   help="demo_probEn: one box-variance scale per --detectors entry, 'a,b[,c]' by position or 'name=a,name=b' by name "
+                        "(variance' = s * variance, the weights of --box_fusion v-avg); default: the calibration file's variance_scales "
+                        "if it has them (fit_temperature --with-variance), else none")
     p.add_argument("--class_prior", type=str, default=None,
                    help="demo_probEn --score_fusion probEn-log: class prior 'p_0,...,p_K' (K + 1 numbers > 0, background last; normalised); "
                         "default: the calibration file's class_prior if it has one, else uniform")

@@ -22,7 +22,7 @@ class FramePairPipeline:
     synchronisation); inputs must not be modified before that either."""
 
     def __init__(self, models, score_fusion="probEn", box_fusion="v-avg", max_class=2, concurrent=True,
-                 staggered=False, stagger_stage=4, fuse=True, temperatures=None, class_prior=None):
+                 staggered=False, stagger_stage=4, fuse=True, temperatures=None, class_prior=None, variance_scales=None):
         self.models = list(models)
         self.fuse = fuse and len(self.models) > 1   # a single detector has nothing to fuse (configs[1])
         self.method = (score_fusion, box_fusion)
@@ -42,6 +42,9 @@ class FramePairPipeline:
             class_prior = check_class_prior(class_prior)
         self.class_prior = class_prior
         self._log_prior = None      # its log on the device, uploaded at the first batch
+        # one s per detector: the rows' variances are (double)var * s (pe_proben_pack_calibrated); None = the box heads' own
+        from .calibration import check_variance_scales
+        self.variance_scales = check_variance_scales(variance_scales, len(self.models), "FramePairPipeline")
         self.concurrent = concurrent and len(self.models) > 1
         self.staggered = staggered and self.concurrent and len(self.models) == 2
         self.stagger_stage = stagger_stage
@@ -129,14 +132,11 @@ class FramePairPipeline:
         return dets, fused
 
     def _fuse(self, dets):
-        if self.logp:
-            if self.class_prior is not None and self._log_prior is None:
-                self._log_prior = F.log_class_prior(self.class_prior, len(self.class_prior), dets[0]["scores"].device)
-            return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class, temperatures=self.temperatures,
-                                     class_prior=self._log_prior)
-        if self.temperatures is None:
-            return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class)
-        return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class, temperatures=self.temperatures)
+        # every option is None unless it was asked for (a class prior exists with "probEn-log" only), and None is fuse_detections' default
+        if self.class_prior is not None and self._log_prior is None:
+            self._log_prior = F.log_class_prior(self.class_prior, len(self.class_prior), dets[0]["scores"].device)
+        return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class, temperatures=self.temperatures,
+                                 class_prior=self._log_prior, variance_scales=self.variance_scales)
 
 
 class HostFeeder:
