@@ -201,8 +201,9 @@ int pe_proben_fuse_batch_logp(const double* boxes, const double* scores, const d
  * pe_proben_pack_calibrated: pe_proben_pack_detections (det_scores_host + det_probs_host given, det_logits_host, temperatures_host
  *   and out_log_probs NULL), pe_proben_pack_logits (det_logits_host + temperatures_host given, scores / probs NULL) or
  *   pe_proben_pack_log_posteriors (the latter with out_log_probs) behind one signature, plus var_scales_host (optional host doubles,
- *   one per detector, finite and > 0): out_vars = (double)var_f32 * s_d, one float64 multiply.  Every other output is written by the
- *   entry point it stands for, so it is that entry point's bits; with var_scales_host NULL (no second launch) or all 1.0 so is out_vars.
+ *   one per detector, finite and > 0): out_vars = (double)var_f32 * s_d, one float64 multiply where the variance is written (one
+ *   launch, the route's own kernel).  Every other output is the bits of the entry point it stands for; with var_scales_host NULL (the
+ *   plain conversion, no multiply) or all 1.0 so is out_vars.
  * ------------------------------------------------------------------------------------------- */
 #define PE_VARIANCE_STATS_MAX_BLOCKS 1024
 int pe_match_ground_truth(const double* det_boxes, const int32_t* det_offsets, const double* gt_boxes, const int32_t* gt_offsets,

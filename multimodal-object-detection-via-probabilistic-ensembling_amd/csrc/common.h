@@ -52,6 +52,9 @@ __device__ __forceinline__ unsigned long long lanemask_lt() {
 // proposals and no detections, tests/test_model_e2e.py:91-120 - depends on NaN surviving).  gfx950: one v_maximum3_f32.
 __device__ __forceinline__ float relu_nan(float x) { return __builtin_elementwise_maximum(x, 0.f); }
 
+// the rule for a temperature or a variance scale
+inline bool finite_positive(double x) { return x == x && x > 0.0 && x < __builtin_huge_val(); }
+
 static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 }  // namespace pe

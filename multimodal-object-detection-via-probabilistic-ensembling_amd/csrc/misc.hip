@@ -13,7 +13,7 @@ namespace {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
-struct PackArgs {
+struct PreprocessArgs {
     const void* src;  // HWC uint8 / HWC float32 / CHW float32
     int src_kind;     // 0: HWC u8, 1: HWC f32, 2: CHW f32
     int src_h, src_w, src_c;
@@ -26,13 +26,13 @@ struct PackArgs {
     size_t src_image_bytes;  // batched form: image z starts at src + z * src_image_bytes
 };
 
-__device__ __forceinline__ float src_at(const PackArgs& a, int y, int x, int c) {
+__device__ __forceinline__ float src_at(const PreprocessArgs& a, int y, int x, int c) {
     if (a.src_kind == 0) return (float)reinterpret_cast<const unsigned char*>(a.src)[((size_t)y * a.src_w + x) * a.src_c + c];
     if (a.src_kind == 1) return reinterpret_cast<const float*>(a.src)[((size_t)y * a.src_w + x) * a.src_c + c];
     return reinterpret_cast<const float*>(a.src)[((size_t)c * a.src_h + y) * a.src_w + x];
 }
 
-__global__ void preprocess_pack_kernel(PackArgs a) {
+__global__ void preprocess_pack_kernel(PreprocessArgs a) {
     a.src = reinterpret_cast<const unsigned char*>(a.src) + (size_t)blockIdx.z * a.src_image_bytes;
     a.dst += (size_t)blockIdx.z * a.pad_h * a.pad_w * 4;
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -260,7 +260,7 @@ static int preprocess_launch(const void* src, int32_t num_images, int32_t src_ki
     PE_CHECK_ARG(nch >= 1 && nch <= 4 && ch0 >= 0 && ch0 + nch <= src_c, "pe_preprocess_pack: channel window [%d,%d) of %d",
                  ch0, ch0 + nch, src_c);
     PE_CHECK_ARG(dst_h <= pad_h && dst_w <= pad_w && dst_h > 0 && dst_w > 0, "pe_preprocess_pack: bad sizes");
-    PackArgs a{};
+    PreprocessArgs a{};
     a.src = src; a.src_kind = src_kind; a.src_h = src_h; a.src_w = src_w; a.src_c = src_c; a.ch0 = ch0; a.nch = nch;
     a.flip_rgb = flip_rgb; a.dst_h = dst_h; a.dst_w = dst_w; a.pad_h = pad_h; a.pad_w = pad_w; a.dst = (_Float16*)dst;
     a.src_image_bytes = (size_t)src_h * src_w * src_c * (src_kind == 0 ? 1 : 4);

@@ -373,98 +373,22 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
     if (tid == 0) a.out_counts[img] = ncl;
 }
 
-struct PackArgs {
-    const float* boxes[4];
-    const float* scores[4];
-    const int32_t* classes[4];
-    const float* probs[4];
-    const float* vars[4];
-    const int32_t* counts[4];
-    int nd, B, D, K, max_class, stride;
-    double* ob;
-    double* os;
-    double* op;
-    double* ov;
-    int32_t* oc;
-    int32_t* ooff;
-    int32_t* ocnt;
-    int32_t* osingle;
-};
-
-// one wavefront per image: ordered compaction of every detector's live rows (class <= max_class)
-// (proben_scale_vars_kernel, csrc/variance.hip, walks the same compaction - min(counts, D), class <= max_class, the `written` prefix -
-// to rewrite out_vars: a change to the row order here belongs there too; tests/test_variance_gpu.py pins the pair)
-__global__ __launch_bounds__(64) void proben_pack_kernel(PackArgs a) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    int written = 0, sources = 0;
-    for (int d = 0; d < a.nd; ++d) {
-        const int before = written;
-        const int c = min(a.counts[d][b], a.D);
-        for (int base = 0; base < c; base += 64) {
-            const int j = base + lane;
-            bool ok = false;
-            int cls = 0;
-            if (j < c) {
-                cls = a.classes[d][(size_t)b * a.D + j];
-                ok = cls <= a.max_class;
-            }
-            const unsigned long long m = __ballot(ok);
-            if (ok) {
-                const size_t src = (size_t)b * a.D + j;
-                const size_t dst = (size_t)b * a.stride + written + __popcll(m & pe::lanemask_lt());
-                for (int e = 0; e < 4; ++e) a.ob[dst * 4 + e] = (double)a.boxes[d][src * 4 + e];
-                a.os[dst] = (double)a.scores[d][src];
-                for (int k = 0; k < a.K; ++k) a.op[dst * a.K + k] = (double)a.probs[d][src * a.K + k];
-                a.ov[dst] = (double)a.vars[d][src];
-                a.oc[dst] = cls;
-            }
-            written += __popcll(m);
-        }
-        sources += written > before ? 1 : 0;
-    }
-    if (lane == 0) {
-        a.ooff[b] = b * a.stride;
-        a.ocnt[b] = written;
-        if (a.osingle) a.osingle[b] = sources == 1 ? 1 : 0;
-    }
-}
-
-}  // namespace
-
-extern "C" int pe_proben_pack_detections(const float* const* det_boxes_host, const float* const* det_scores_host,
-                                         const int32_t* const* det_classes_host, const float* const* det_probs_host,
-                                         const float* const* det_vars_host, const int32_t* const* det_counts_host,
-                                         int32_t num_detectors, int32_t num_images, int32_t det_stride,
-                                         int32_t num_classes, int32_t max_class, int32_t row_stride,
-                                         double* out_boxes, double* out_scores, double* out_probs, double* out_vars,
-                                         int32_t* out_classes, int32_t* out_offsets, int32_t* out_counts,
-                                         int32_t* out_single_source, void* stream) {
-    PE_CHECK_ARG(num_detectors >= 1 && num_detectors <= 4, "pe_proben_pack_detections: num_detectors %d", num_detectors);
-    PE_CHECK_ARG(row_stride >= num_detectors * det_stride, "pe_proben_pack_detections: row_stride %d < %d", row_stride,
-                 num_detectors * det_stride);
-    PE_CHECK_ARG(out_boxes && out_scores && out_probs && out_vars && out_classes && out_offsets && out_counts,
-                 "pe_proben_pack_detections: null output");
+// pe_proben_fuse_batch / pe_proben_fuse_batch_logp: the argument checks, LDS sizing, clustering form, launch.  logp: a.probs holds the
+// K+1 log-posteriors (required), a.score_mode is PE_SCORE_PROBEN_LOGP and is not the caller's to choose.
+int fuse_impl(const char* what, bool logp, ProbenArgs a, int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, void* stream) {
+    PE_CHECK_ARG(num_images >= 0, "%s: num_images < 0", what);
     if (num_images == 0) return PE_OK;
-    PackArgs a{};
-    for (int d = 0; d < num_detectors; ++d) {
-        a.boxes[d] = det_boxes_host[d]; a.scores[d] = det_scores_host[d]; a.classes[d] = det_classes_host[d];
-        a.probs[d] = det_probs_host[d]; a.vars[d] = det_vars_host[d]; a.counts[d] = det_counts_host[d];
-        PE_CHECK_ARG(a.boxes[d] && a.scores[d] && a.classes[d] && a.probs[d] && a.vars[d] && a.counts[d],
-                     "pe_proben_pack_detections: null detector pointer");
-    }
-    a.nd = num_detectors; a.B = num_images; a.D = det_stride; a.K = num_classes; a.max_class = max_class;
-    a.stride = row_stride; a.ob = out_boxes; a.os = out_scores; a.op = out_probs; a.ov = out_vars; a.oc = out_classes;
-    a.ooff = out_offsets; a.ocnt = out_counts; a.osingle = out_single_source;
-    hipLaunchKernelGGL(proben_pack_kernel, dim3(num_images), dim3(64), 0, (hipStream_t)stream, a);
-    PE_CHECK_LAUNCH("pe_proben_pack_detections");
-    return PE_OK;
-}
-
-namespace {
-
-// pe_proben_fuse_batch / pe_proben_fuse_batch_logp behind their own argument checks: LDS sizing, clustering form, launch
-int launch_fuse(const char* what, ProbenArgs a, int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, void* stream) {
-    const bool logp = a.score_mode == PE_SCORE_PROBEN_LOGP;
+    PE_CHECK_ARG(a.boxes && a.scores && (a.probs || !logp) && a.vars && a.classes && a.offsets, "%s: null input pointer", what);
+    PE_CHECK_ARG(a.out_boxes && a.out_scores && a.out_classes && a.out_keep && a.out_counts, "%s: null output pointer", what);
+    PE_CHECK_ARG(logp || (a.score_mode >= 0 && a.score_mode <= 3), "%s: bad score_mode %d", what, a.score_mode);
+    PE_CHECK_ARG(a.box_mode >= 0 && a.box_mode <= 3, "%s: bad box_mode %d", what, a.box_mode);
+    // K <= 62: a wavefront keeps a cluster's per-class log-odds in lanes (K + background in 64 lanes).  Enough for every fusion the
+    // reference can run: prediction files of different class counts cannot be fused there either (prepare_data concatenates the
+    // `probs` arrays, demo_probEn.py:79-90), and the 80-class rgb_only file is evaluated on its own.
+    PE_CHECK_ARG(num_classes >= 1 && num_classes <= 62, "%s: num_classes %d not in [1,62]", what, num_classes);
+    PE_CHECK_ARG(a.probs || (a.score_mode != PE_SCORE_PROBEN && a.score_mode != PE_SCORE_MAX), "%s: probs required for this score_mode", what);
+    PE_CHECK_ARG(max_rows_per_image >= 1 && max_rows_per_image <= 2048, "%s: max_rows_per_image %d not in [1,2048]", what,
+                 max_rows_per_image);
     const int R = (max_rows_per_image + 1) & ~1;  // keep the int/short/byte carves 8-byte aligned
     const int L = (logp || a.score_mode == PE_SCORE_PROBEN) ? num_classes + 1 : (a.score_mode == PE_SCORE_PROBEN_BINARY ? 2 : 0);
     const size_t lds_seq = (size_t)R * (8 * (6 + L + 5) + 4 + 4 + 4 * 2 + 1) + 16;
@@ -481,24 +405,16 @@ int launch_fuse(const char* what, ProbenArgs a, int32_t num_images, int32_t num_
         return PE_ERR_UNSUPPORTED;
     }
     a.max_rows = R;
-    const void* fn = logp ? (bits ? reinterpret_cast<const void*>(proben_fuse_kernel<true, true>) : reinterpret_cast<const void*>(proben_fuse_kernel<false, true>))
-                          : (bits ? reinterpret_cast<const void*>(proben_fuse_kernel<true, false>) : reinterpret_cast<const void*>(proben_fuse_kernel<false, false>));
+    void (*kernel)(ProbenArgs) = logp ? (bits ? proben_fuse_kernel<true, true> : proben_fuse_kernel<false, true>)
+                                      : (bits ? proben_fuse_kernel<true, false> : proben_fuse_kernel<false, false>);
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
             pe::set_error("%s: cannot raise dynamic LDS to %zu: %s", what, lds, hipGetErrorString(e));
             return PE_ERR_HIP;
         }
     }
-    const dim3 grid(num_images), block(kFuseThreads);
-    if (logp && bits)
-        hipLaunchKernelGGL((proben_fuse_kernel<true, true>), grid, block, lds, (hipStream_t)stream, a);
-    else if (logp)
-        hipLaunchKernelGGL((proben_fuse_kernel<false, true>), grid, block, lds, (hipStream_t)stream, a);
-    else if (bits)
-        hipLaunchKernelGGL((proben_fuse_kernel<true, false>), grid, block, lds, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((proben_fuse_kernel<false, false>), grid, block, lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(kernel, dim3(num_images), dim3(kFuseThreads), lds, (hipStream_t)stream, a);
     PE_CHECK_LAUNCH(what);
     return PE_OK;
 }
@@ -511,26 +427,10 @@ extern "C" int pe_proben_fuse_batch(const double* boxes, const double* scores, c
                                     int32_t score_mode, int32_t box_mode, double iou_thresh, double frame_w,
                                     double frame_h, double* out_boxes, float* out_scores, float* out_classes,
                                     int32_t* out_keep, int32_t* out_counts, void* stream) {
-    PE_CHECK_ARG(num_images >= 0, "pe_proben_fuse_batch: num_images < 0");
-    if (num_images == 0) return PE_OK;
-    PE_CHECK_ARG(boxes && scores && variances && classes && offsets, "pe_proben_fuse_batch: null input pointer");
-    PE_CHECK_ARG(out_boxes && out_scores && out_classes && out_keep && out_counts,
-                 "pe_proben_fuse_batch: null output pointer");
-    PE_CHECK_ARG(score_mode >= 0 && score_mode <= 3, "pe_proben_fuse_batch: bad score_mode %d", score_mode);
-    PE_CHECK_ARG(box_mode >= 0 && box_mode <= 3, "pe_proben_fuse_batch: bad box_mode %d", box_mode);
-    // K <= 62: a wavefront keeps a cluster's per-class log-odds in lanes (K + background in 64 lanes).  Enough for every fusion the
-    // reference can run: prediction files of different class counts cannot be fused there either (prepare_data concatenates the
-    // `probs` arrays, demo_probEn.py:79-90), and the 80-class rgb_only file is evaluated on its own.
-    PE_CHECK_ARG(num_classes >= 1 && num_classes <= 62, "pe_proben_fuse_batch: num_classes %d not in [1,62]",
-                 num_classes);
-    PE_CHECK_ARG(probs || (score_mode != PE_SCORE_PROBEN && score_mode != PE_SCORE_MAX),
-                 "pe_proben_fuse_batch: probs required for this score_mode");
-    PE_CHECK_ARG(max_rows_per_image >= 1 && max_rows_per_image <= 2048,
-                 "pe_proben_fuse_batch: max_rows_per_image %d not in [1,2048]", max_rows_per_image);
     ProbenArgs a{boxes, scores, probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
                  score_mode, box_mode, iou_thresh, frame_w, frame_h,
                  out_boxes, out_scores, out_classes, out_keep, out_counts, nullptr};
-    return launch_fuse("pe_proben_fuse_batch", a, num_images, num_classes, max_rows_per_image, stream);
+    return fuse_impl("pe_proben_fuse_batch", false, a, num_images, num_classes, max_rows_per_image, stream);
 }
 
 extern "C" int pe_proben_fuse_batch_logp(const double* boxes, const double* scores, const double* log_probs,
@@ -539,18 +439,8 @@ extern "C" int pe_proben_fuse_batch_logp(const double* boxes, const double* scor
                                          int32_t num_classes, int32_t max_rows_per_image, int32_t box_mode, double iou_thresh,
                                          double frame_w, double frame_h, const double* log_prior, double* out_boxes,
                                          float* out_scores, float* out_classes, int32_t* out_keep, int32_t* out_counts, void* stream) {
-    PE_CHECK_ARG(num_images >= 0, "pe_proben_fuse_batch_logp: num_images < 0");
-    if (num_images == 0) return PE_OK;
-    PE_CHECK_ARG(boxes && scores && log_probs && variances && classes && offsets,
-                 "pe_proben_fuse_batch_logp: null input pointer");
-    PE_CHECK_ARG(out_boxes && out_scores && out_classes && out_keep && out_counts,
-                 "pe_proben_fuse_batch_logp: null output pointer");
-    PE_CHECK_ARG(box_mode >= 0 && box_mode <= 3, "pe_proben_fuse_batch_logp: bad box_mode %d", box_mode);
-    PE_CHECK_ARG(num_classes >= 1 && num_classes <= 62, "pe_proben_fuse_batch_logp: num_classes %d not in [1,62]", num_classes);
-    PE_CHECK_ARG(max_rows_per_image >= 1 && max_rows_per_image <= 2048,
-                 "pe_proben_fuse_batch_logp: max_rows_per_image %d not in [1,2048]", max_rows_per_image);
     ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
                  PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
                  out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior};
-    return launch_fuse("pe_proben_fuse_batch_logp", a, num_images, num_classes, max_rows_per_image, stream);
+    return fuse_impl("pe_proben_fuse_batch_logp", true, a, num_images, num_classes, max_rows_per_image, stream);
 }

@@ -1,7 +1,7 @@
 // Variance calibration of the detectors' box heads (gfx950): one positive scale s_d per detector, variance' = s_d * variance.
 //   pe_match_ground_truth      : detections -> (label, matched ground-truth index, best IoU), batched over images
 //   pe_variance_stats          : the sufficient statistics of the Gaussian NLL of the matched rows' box-delta residuals
-//   pe_proben_pack_calibrated  : the three pack entry points behind one signature, then out_vars = (double)var_f32 * s_d
+// (the scale is applied where the rows are packed: pe_proben_pack_calibrated, csrc/pack.hip)
 //
 // Matching is calibration.match_labels / finetune.pairwise_iou in float64, in that expression order (built with -ffp-contract=off,
 // so no multiply-add is fused): area = (x2 - x1) * (y2 - y1), w = max(min(ax2, bx2) - max(ax1, bx1), 0), inter = w * h,
@@ -152,36 +152,6 @@ __global__ __launch_bounds__(PE_VARIANCE_STATS_MAX_BLOCKS) void variance_stats_f
         for (int v = 0; v < kStatValues; ++v) out[v] = x[0][v];
 }
 
-struct ScaleArgs {
-    const int32_t* classes[4];
-    const float* vars[4];
-    const int32_t* counts[4];
-    double s[4];
-    int nd, D, max_class, stride;
-    double* ov;
-};
-
-// one wavefront per image: the ordered compaction of proben_pack_kernel (csrc/proben.hip) once more, writing the variances only
-// (the same walk as proben_pack_kernel and proben_pack_logits_kernel, csrc/calibrate.hip: the three must agree on the row order)
-__global__ __launch_bounds__(64) void proben_scale_vars_kernel(ScaleArgs a) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    int written = 0;
-    for (int d = 0; d < a.nd; ++d) {
-        const int c = min(a.counts[d][b], a.D);
-        const double s = a.s[d];
-        for (int base = 0; base < c; base += 64) {
-            const int j = base + lane;
-            const size_t src = (size_t)b * a.D + j;
-            const bool ok = j < c && a.classes[d][src] <= a.max_class;
-            const unsigned long long m = __ballot(ok);
-            if (ok) a.ov[(size_t)b * a.stride + written + __popcll(m & pe::lanemask_lt())] = (double)a.vars[d][src] * s;
-            written += __popcll(m);
-        }
-    }
-}
-
-bool good_scale(double s) { return s == s && s > 0.0 && s < __builtin_huge_val(); }
-
 }  // namespace
 
 extern "C" int pe_match_ground_truth(const double* det_boxes, const int32_t* det_offsets, const double* gt_boxes,
@@ -206,7 +176,7 @@ extern "C" int pe_match_ground_truth(const double* det_boxes, const int32_t* det
 extern "C" int pe_variance_stats(const double* det_boxes, const int32_t* match, const double* gt_boxes, const double* variances,
                                  int64_t num_rows, int64_t num_gt, const float* bbox_reg_weights_host, double scale, double* workspace, double* out,
                                  int32_t* out_flags, void* stream) {
-    PE_CHECK_ARG(good_scale(scale), "pe_variance_stats: scale %g is not finite and > 0", scale);
+    PE_CHECK_ARG(pe::finite_positive(scale), "pe_variance_stats: scale %g is not finite and > 0", scale);
     PE_CHECK_ARG(num_rows >= 0 && num_gt >= 0, "pe_variance_stats: num_rows %lld, num_gt %lld", (long long)num_rows, (long long)num_gt);
     PE_CHECK_ARG(workspace && out && out_flags, "pe_variance_stats: null pointer (workspace / out / out_flags)");
     PE_CHECK_ARG(num_rows == 0 || (det_boxes && match && variances && (gt_boxes || num_gt == 0)),
@@ -233,59 +203,5 @@ extern "C" int pe_variance_stats(const double* det_boxes, const int32_t* match, 
     hipLaunchKernelGGL(variance_stats_finish_kernel, dim3(1), dim3(PE_VARIANCE_STATS_MAX_BLOCKS), 0, (hipStream_t)stream, workspace, blocks,
                        out);
     PE_CHECK_LAUNCH("pe_variance_stats (finish)");
-    return PE_OK;
-}
-
-extern "C" int pe_proben_pack_calibrated(const float* const* det_boxes_host, const float* const* det_scores_host,
-                                         const int32_t* const* det_classes_host, const float* const* det_probs_host,
-                                         const float* const* det_logits_host, const float* const* det_vars_host,
-                                         const int32_t* const* det_counts_host, const double* temperatures_host,
-                                         const double* var_scales_host, int32_t num_detectors, int32_t num_images,
-                                         int32_t det_stride, int32_t num_classes, int32_t max_class, int32_t row_stride,
-                                         double* out_boxes, double* out_scores, double* out_probs, double* out_log_probs,
-                                         double* out_vars, int32_t* out_classes, int32_t* out_offsets, int32_t* out_counts,
-                                         int32_t* out_single_source, void* stream) {
-    const char* what = "pe_proben_pack_calibrated";
-    PE_CHECK_ARG(num_detectors >= 1 && num_detectors <= 4, "%s: num_detectors %d", what, num_detectors);
-    PE_CHECK_ARG(num_images >= 0 && det_stride >= 0, "%s: num_images %d, det_stride %d", what, num_images, det_stride);
-    PE_CHECK_ARG(det_boxes_host && det_classes_host && det_vars_host && det_counts_host, "%s: null pointer (detector tables)", what);
-    const bool from_logits = det_logits_host != nullptr;
-    if (from_logits) {
-        PE_CHECK_ARG(temperatures_host, "%s: null pointer (temperatures: the logits route needs one per detector)", what);
-        PE_CHECK_ARG(!det_scores_host && !det_probs_host, "%s: both probabilities and logits given: one route at a time", what);
-    } else {
-        PE_CHECK_ARG(det_scores_host && det_probs_host, "%s: null pointer (neither probabilities nor logits)", what);
-        PE_CHECK_ARG(!temperatures_host && !out_log_probs, "%s: temperatures / out_log_probs belong to the logits route", what);
-    }
-    ScaleArgs a{};
-    for (int d = 0; d < num_detectors; ++d) {
-        if (var_scales_host)
-            PE_CHECK_ARG(good_scale(var_scales_host[d]), "%s: variance scale %g of detector %d is not finite and > 0", what,
-                         var_scales_host[d], d);
-        a.classes[d] = det_classes_host[d]; a.vars[d] = det_vars_host[d]; a.counts[d] = det_counts_host[d];
-        a.s[d] = var_scales_host ? var_scales_host[d] : 1.0;
-        PE_CHECK_ARG(a.classes[d] && a.vars[d] && a.counts[d] && det_boxes_host[d], "%s: null pointer of detector %d", what, d);
-        if (!from_logits)
-            PE_CHECK_ARG(det_scores_host[d] && det_probs_host[d], "%s: null pointer of detector %d", what, d);
-    }
-    // every output but out_vars is the existing entry point's, because it is the existing entry point that writes it
-    int st;
-    if (!from_logits)
-        st = pe_proben_pack_detections(det_boxes_host, det_scores_host, det_classes_host, det_probs_host, det_vars_host, det_counts_host,
-                                       num_detectors, num_images, det_stride, num_classes, max_class, row_stride, out_boxes, out_scores,
-                                       out_probs, out_vars, out_classes, out_offsets, out_counts, out_single_source, stream);
-    else if (out_log_probs)
-        st = pe_proben_pack_log_posteriors(det_boxes_host, det_classes_host, det_logits_host, det_vars_host, det_counts_host,
-                                           temperatures_host, num_detectors, num_images, det_stride, num_classes, max_class, row_stride,
-                                           out_boxes, out_scores, out_probs, out_log_probs, out_vars, out_classes, out_offsets,
-                                           out_counts, out_single_source, stream);
-    else
-        st = pe_proben_pack_logits(det_boxes_host, det_classes_host, det_logits_host, det_vars_host, det_counts_host, temperatures_host,
-                                   num_detectors, num_images, det_stride, num_classes, max_class, row_stride, out_boxes, out_scores,
-                                   out_probs, out_vars, out_classes, out_offsets, out_counts, out_single_source, stream);
-    if (st != PE_OK || !var_scales_host || num_images == 0) return st;
-    a.nd = num_detectors; a.D = det_stride; a.max_class = max_class; a.stride = row_stride; a.ov = out_vars;
-    hipLaunchKernelGGL(proben_scale_vars_kernel, dim3(num_images), dim3(64), 0, (hipStream_t)stream, a);
-    PE_CHECK_LAUNCH(what);
     return PE_OK;
 }

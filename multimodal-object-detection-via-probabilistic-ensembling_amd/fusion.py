@@ -90,22 +90,14 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
         "keep": torch.empty((ntot,), dtype=torch.int32, device=dev),
         "counts": torch.zeros((max(B, 1),), dtype=torch.int32, device=dev)[:B],
     }
-    if logp:
-        st = _lib.lib().pe_proben_fuse_batch_logp(
-            _lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(probs), _lib.ptr(variances), _lib.ptr(classes),
-            _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows, BOX_MODES[box_fusion],
-            float(iou_thresh), float(frame[0]), float(frame[1]), _lib.ptr(log_prior),
-            _lib.ptr(out["boxes"]), _lib.ptr(out["scores"]), _lib.ptr(out["classes"]), _lib.ptr(out["keep"]),
-            _lib.ptr(out["counts"]), _lib.stream())
-        _lib.check(st, "pe_proben_fuse_batch_logp")
-        return out
-    st = _lib.lib().pe_proben_fuse_batch(
-        _lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(probs), _lib.ptr(variances), _lib.ptr(classes),
-        _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows, SCORE_MODES[score_fusion], BOX_MODES[box_fusion],
-        float(iou_thresh), float(frame[0]), float(frame[1]),
-        _lib.ptr(out["boxes"]), _lib.ptr(out["scores"]), _lib.ptr(out["classes"]), _lib.ptr(out["keep"]),
-        _lib.ptr(out["counts"]), _lib.stream())
-    _lib.check(st, "pe_proben_fuse_batch")
+    name = "pe_proben_fuse_batch_logp" if logp else "pe_proben_fuse_batch"
+    head = (_lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(probs), _lib.ptr(variances), _lib.ptr(classes), _lib.ptr(offsets),
+            _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows)
+    geometry = (BOX_MODES[box_fusion], float(iou_thresh), float(frame[0]), float(frame[1]))
+    mode = geometry + (_lib.ptr(log_prior),) if logp else (SCORE_MODES[score_fusion],) + geometry
+    st = getattr(_lib.lib(), name)(*head, *mode, _lib.ptr(out["boxes"]), _lib.ptr(out["scores"]), _lib.ptr(out["classes"]),
+                                   _lib.ptr(out["keep"]), _lib.ptr(out["counts"]), _lib.stream())
+    _lib.check(st, name)
     return out
 
 
@@ -240,39 +232,26 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, varian
         for d in dets:
             if d["class_logits"].shape != (B, D, K + 1) or d["class_logits"].dtype != torch.float32:
                 raise ValueError(f"fuse_detections: class_logits {tuple(d['class_logits'].shape)} is not float32 [{B}, {D}, {K + 1}]")
+    logits = temperatures is not None
+    olp = torch.empty((B * S, K + 1), dtype=torch.float64, device=dev) if log_posteriors else None
+    temps = (ctypes.c_double * nd)(*[float(t) for t in temperatures]) if logits else None
+    scores, probs, lg = (None, None, arr("class_logits")) if logits else (arr("scores"), arr("prob_score"), None)
+    dims = (nd, B, D, K, max_class, S)
+    head, tail = [_lib.ptr(t) for t in (ob, os_, op)], [_lib.ptr(t) for t in (ov, oc, ooff, ocnt, osingle)]
     if variance_scales is not None:
-        logits = temperatures is not None
-        olp = torch.empty((B * S, K + 1), dtype=torch.float64, device=dev) if log_posteriors else None
-        st = _lib.lib().pe_proben_pack_calibrated(
-            arr("boxes"), None if logits else arr("scores"), arr("classes"), None if logits else arr("prob_score"),
-            arr("class_logits") if logits else None, arr("vars"), arr("counts"),
-            (ctypes.c_double * nd)(*[float(t) for t in temperatures]) if logits else None, (ctypes.c_double * nd)(*variance_scales),
-            nd, B, D, K, max_class, S, _lib.ptr(ob), _lib.ptr(os_), _lib.ptr(op), _lib.ptr(olp), _lib.ptr(ov), _lib.ptr(oc),
-            _lib.ptr(ooff), _lib.ptr(ocnt), _lib.ptr(osingle), _lib.stream())
-        _lib.check(st, "pe_proben_pack_calibrated")
-        return (ob, os_, op, ov, oc, ooff, ocnt, osingle) + ((olp,) if log_posteriors else ())
-    if temperatures is None:
-        st = _lib.lib().pe_proben_pack_detections(arr("boxes"), arr("scores"), arr("classes"), arr("prob_score"), arr("vars"),
-                                                 arr("counts"), nd, B, D, K, max_class, S, _lib.ptr(ob), _lib.ptr(os_),
-                                                 _lib.ptr(op), _lib.ptr(ov), _lib.ptr(oc), _lib.ptr(ooff), _lib.ptr(ocnt),
-                                                 _lib.ptr(osingle), _lib.stream())
-        _lib.check(st, "pe_proben_pack_detections")
+        name = "pe_proben_pack_calibrated"
+        args = (arr("boxes"), scores, arr("classes"), probs, lg, arr("vars"), arr("counts"), temps,
+                (ctypes.c_double * nd)(*variance_scales), *dims, *head, _lib.ptr(olp), *tail)
+    elif not logits:
+        name = "pe_proben_pack_detections"
+        args = (arr("boxes"), scores, arr("classes"), probs, arr("vars"), arr("counts"), *dims, *head, *tail)
     else:
-        temps = (ctypes.c_double * nd)(*[float(t) for t in temperatures])
-        if log_posteriors:
-            olp = torch.empty((B * S, K + 1), dtype=torch.float64, device=dev)
-            st = _lib.lib().pe_proben_pack_log_posteriors(arr("boxes"), arr("classes"), arr("class_logits"), arr("vars"), arr("counts"),
-                                                         temps, nd, B, D, K, max_class, S, _lib.ptr(ob), _lib.ptr(os_), _lib.ptr(op),
-                                                         _lib.ptr(olp), _lib.ptr(ov), _lib.ptr(oc), _lib.ptr(ooff), _lib.ptr(ocnt),
-                                                         _lib.ptr(osingle), _lib.stream())
-            _lib.check(st, "pe_proben_pack_log_posteriors")
-            return ob, os_, op, ov, oc, ooff, ocnt, osingle, olp
-        st = _lib.lib().pe_proben_pack_logits(arr("boxes"), arr("classes"), arr("class_logits"), arr("vars"), arr("counts"),
-                                             temps, nd, B, D, K, max_class, S,
-                                             _lib.ptr(ob), _lib.ptr(os_), _lib.ptr(op), _lib.ptr(ov), _lib.ptr(oc), _lib.ptr(ooff),
-                                             _lib.ptr(ocnt), _lib.ptr(osingle), _lib.stream())
-        _lib.check(st, "pe_proben_pack_logits")
-    return ob, os_, op, ov, oc, ooff, ocnt, osingle
+        name = "pe_proben_pack_log_posteriors" if log_posteriors else "pe_proben_pack_logits"
+        args = (arr("boxes"), arr("classes"), lg, arr("vars"), arr("counts"), temps, *dims, *head,
+                *([_lib.ptr(olp)] if log_posteriors else []), *tail)
+    st = getattr(_lib.lib(), name)(*args, _lib.stream())
+    _lib.check(st, name)
+    return (ob, os_, op, ov, oc, ooff, ocnt, osingle) + ((olp,) if log_posteriors else ())
 
 
 def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=0.5, temperatures=None,
@@ -296,15 +275,11 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     B, D = dets[0]["scores"].shape
     S = len(dets) * D
     dev = dets[0]["scores"].device
-    if score_fusion == LOGP:
-        ob, os_, op, ov, oc, ooff, ocnt, osingle, olp = pack_rows(dets, max_class, temperatures if temperatures is not None else [1.0] * len(dets),
-                                                                     log_posteriors=True, variance_scales=variance_scales)
-        out = fuse_batch(ob, os_, op, ov, oc, ooff, score_fusion, box_fusion, max_rows=S, iou_thresh=iou_thresh,
-                         row_counts=ocnt, passthrough=osingle, log_probs=olp, class_prior=class_prior)
-        out["offsets"], out["stride"], out["in_counts"] = ooff, S, ocnt
-        out["cand_overflow_src"] = overflow_src
-        return out
-    ob, os_, op, ov, oc, ooff, ocnt, osingle = pack_rows(dets, max_class, temperatures, variance_scales=variance_scales)
+    logp = score_fusion == LOGP
+    if logp and temperatures is None:
+        temperatures = [1.0] * len(dets)
+    ob, os_, op, ov, oc, ooff, ocnt, osingle, *olp = pack_rows(dets, max_class, temperatures, log_posteriors=logp,
+                                                               variance_scales=variance_scales)
     if score_fusion == "max" and box_fusion == "argmax":
         from .layers import nms_batched_raw
         b32 = ob.float().view(B, S, 4)
@@ -319,7 +294,7 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
         return {"boxes": ob[g], "scores": os_.float()[g], "classes": oc.float()[g], "counts": kcnt, "keep": keep,
                 "offsets": ooff, "stride": S, "in_counts": ocnt, "nms_route": True, "cand_overflow_src": overflow_src}
     out = fuse_batch(ob, os_, op, ov, oc, ooff, score_fusion, box_fusion, max_rows=S, iou_thresh=iou_thresh,
-                     row_counts=ocnt, passthrough=osingle)
+                     row_counts=ocnt, passthrough=osingle, log_probs=olp[0] if logp else None, class_prior=class_prior)
     out["offsets"], out["stride"], out["in_counts"] = ooff, S, ocnt
     out["cand_overflow_src"] = overflow_src
     return out

@@ -38,9 +38,9 @@ for d in range(2):
 T = (1.5, 0.8)
 prior = F.log_class_prior([0.2, 0.5, 0.2, 0.1], K + 1, "cuda")
 for it in range(50):
-    F.fuse_detections(dets)                                                   # proben_pack_kernel + proben_fuse_kernel (probEn)
-    F.fuse_detections(dets, temperatures=T)                                   # proben_pack_logits_kernel<false> + proben_fuse_kernel
-    F.fuse_detections(dets, "probEn-log", temperatures=T)                     # <true> pack + logp fuse, uniform prior
+    F.fuse_detections(dets)                                                   # proben_pack_kernel<PROBS> + proben_fuse_kernel (probEn)
+    F.fuse_detections(dets, temperatures=T)                                   # proben_pack_kernel<LOGITS> + proben_fuse_kernel
+    F.fuse_detections(dets, "probEn-log", temperatures=T)                     # proben_pack_kernel<LOGITS_LOGP> + logp fuse, uniform prior
     F.fuse_detections(dets, "probEn-log", temperatures=T, class_prior=prior)  # ... with a prior
 torch.cuda.synchronize()
 out = F.fuse_detections(dets, "probEn-log", temperatures=T)

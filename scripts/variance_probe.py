@@ -45,9 +45,9 @@ goff = torch.arange(0, B * G + 1, G, dtype=torch.int32, device="cuda")
 gcls = torch.from_numpy(rng.integers(0, K, B * G).astype(np.int32)).cuda()
 T, S = (1.5, 0.8), (0.4, 2.5)
 for it in range(50):
-    F.pack_rows(dets, 2)                                             # proben_pack_kernel
-    F.pack_rows(dets, 2, variance_scales=S)                          # proben_pack_kernel + proben_scale_vars_kernel
-    F.pack_rows(dets, 2, temperatures=T, variance_scales=S)          # proben_pack_logits_kernel<false> + proben_scale_vars_kernel
+    F.pack_rows(dets, 2)                                             # proben_pack_kernel<PROBS>
+    F.pack_rows(dets, 2, variance_scales=S)                          # proben_pack_kernel<PROBS>, scaled (one launch)
+    F.pack_rows(dets, 2, temperatures=T, variance_scales=S)          # proben_pack_kernel<LOGITS>, scaled (one launch)
     lab, match, iou = C.match_rows_device(db, doff, gb, goff, gcls, None, 0.5, K)     # match_ground_truth_kernel
     st = C.variance_stats(db, match, gb, dv)                         # variance_stats_kernel + variance_stats_finish_kernel
 torch.cuda.synchronize()
