@@ -223,6 +223,43 @@ int pe_proben_pack_calibrated(const float* const* det_boxes_host, const float* c
                               void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Reliability statistics of a score (csrc/reliability.hip): what a reliability diagram, the expected and the maximum calibration error
+ * (ECE, MCE) and the Brier score are made of, for the rows a calibration was NOT fitted on.  Not in the reference.
+ *
+ * Bins: num_bins = B in [1, PE_RELIABILITY_MAX_BINS] bins of equal width on [0, 1]; a row with confidence conf falls into
+ *   bin = min((int)(conf * B), B - 1)  (one float64 multiply), so conf == 1.0 lies in the last bin.
+ * Outputs: out_counts i64 [B, 2]: [b][0] = rows in the bin, [b][1] = correct rows (both exact); out_sums f64 [B, 2]: [b][0] = sum of
+ *   conf, [b][1] = sum of the Brier term d * d, d = conf - (correct ? 1.0 : 0.0) (two IEEE operations, no contraction).
+ *   ECE = sum_b (n_b / N) |correct_b / n_b - sum conf_b / n_b|, MCE = the largest of those gaps, Brier = sum_b sum term_b / N
+ *   (calibration.summarise_reliability).
+ * pe_reliability_logits: logits f32 [num_rows, num_columns] (K + 1 columns, background last), labels i32 [num_rows] in [0, K].
+ *   p = softmax(logits / temperature) as in pe_calibrated_softmax: the same row arithmetic (csrc/softmax_row.h), the same bits.
+ *   classes i32 [num_rows] given: conf = p[classes[i]], correct = (labels[i] == classes[i]) - the detection's own score, the one
+ *   pe_proben_pack_logits writes to out_scores.  classes NULL (top label): conf = max_k p_k over all K + 1 columns, the predicted class
+ *   is the FIRST index that attains it, correct = (that index == labels[i]).
+ *   A row is excluded - it adds nothing - when its label or its class is outside [0, K] or its conf is NaN (a NaN or +inf logit).
+ * pe_reliability_scores: conf f64 [num_rows], correct i32 [num_rows] (non-zero = correct): the same bins, outputs and flags for scores
+ *   that do not come from a softmax (the fused detections).  A conf that is NaN or outside [0, 1] excludes the row.
+ * out_flags i32 [2], as pe_temperature_nll's: [0] = excluded rows, [1] = 1 + the largest excluded row index.
+ * Deterministic like pe_temperature_nll and pe_variance_stats - no floating-point atomics, the same input gives the same bits:
+ *   min(ceil(num_rows / 256), PE_RELIABILITY_MAX_BLOCKS) workgroups of 4 wavefronts, a function of num_rows alone.  Wavefront v of the
+ *   grid takes row groups v, v + (4 * workgroups), ... (a group = the 64 / G rows of calibrated_softmax_kernel's lane groups for
+ *   K + 1 <= 64, G the power of two >= K + 1; 64 rows otherwise) and adds their rows in ascending row order into its own table of B
+ *   bins; a workgroup adds its 4 tables in wavefront order into workspace[workgroup][bin][4]; a one-workgroup second kernel adds, per
+ *   bin, 16 contiguous segments of the workgroups, each in workgroup order, then the 16 segment sums in segment order.
+ *   workspace: PE_RELIABILITY_MAX_BLOCKS * num_bins * 4 eight-byte values.
+ * Arguments are checked before any device work (temperature finite and > 0, num_bins, num_columns >= 2, num_rows >= 0, null
+ * pointers).  num_rows == 0 reads nothing: the outputs that are given are zeroed and no pointer is required.
+ * ------------------------------------------------------------------------------------------- */
+#define PE_RELIABILITY_MAX_BINS 64
+#define PE_RELIABILITY_MAX_BLOCKS 1024
+int pe_reliability_logits(const float* logits, const int32_t* labels, const int32_t* classes /* optional */, int64_t num_rows,
+                          int32_t num_columns, double temperature, int32_t num_bins, double* workspace, int64_t* out_counts,
+                          double* out_sums, int32_t* out_flags, void* stream);
+int pe_reliability_scores(const double* conf, const int32_t* correct, int64_t num_rows, int32_t num_bins, double* workspace,
+                          int64_t* out_counts, double* out_sums, int32_t* out_flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused convolution / GEMM: NHWC fp16 activations, [Cout][KH][KW][Cin] fp16 weights, fp32 accumulate
  * on MFMA, epilogue = + bias[Cout] (fp32) + residual + ReLU, fp16 (or fp32) NHWC output.
  * Replaces, per layer, detectron2.layers.Conv2d.forward (layers/wrappers.py:62-98) + FrozenBatchNorm2d

@@ -16,6 +16,10 @@ Variance calibration (csrc/variance.hip): one scale s per detector, variance' = 
   variance_stats / fit_variance_scale      the Gaussian NLL's statistics of the matched rows (pe_variance_stats) and the closed-form fit
   check_variance_scale / parse_variance_scales / resolve_variance_scales / scale_j1_vars
   save_variance / load_variance            the "variance_*" keys of the calibration file (save / load above do not know them)
+
+Reliability of a score on rows the fit did not see (csrc/reliability.hip; the driver is cli/calibration_report):
+  reliability / reliability_scores         per-bin counts and sums from pe_reliability_logits / pe_reliability_scores, one launch each
+  summarise_reliability                    ECE, MCE and the Brier score from those, on the host
 """
 import ctypes
 import json
@@ -29,6 +33,8 @@ from . import _lib
 NLL_CANDIDATES = 64          # pe_temperature_nll's limit: one launch evaluates this many temperatures
 NLL_MAX_BLOCKS = 1024        # PE_TEMPERATURE_NLL_MAX_BLOCKS (include/proben_hip.h): sizes the partial-sum workspace
 VARIANCE_MAX_BLOCKS = 1024   # PE_VARIANCE_STATS_MAX_BLOCKS: 5 partial values per workgroup
+RELIABILITY_MAX_BINS = 64    # PE_RELIABILITY_MAX_BINS
+RELIABILITY_MAX_BLOCKS = 1024     # PE_RELIABILITY_MAX_BLOCKS: 4 partial values per workgroup and bin
 BBOX_REG_WEIGHTS = (10.0, 10.0, 5.0, 5.0)      # cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS: the units the variance head is trained in
 
 
@@ -466,3 +472,92 @@ def scale_j1_vars(det, s):
     out = dict(det)
     out["vars"] = [(np.asarray(v, dtype=np.float64) * s).tolist() for v in det["vars"]]
     return out
+
+
+# ---- reliability ---------------------------------------------------------------------------------------------------------------
+
+def summarise_reliability(counts, sums):
+    """The per-bin statistics of pe_reliability_logits / pe_reliability_scores -> the figures, float64 on the host, in bin order.
+    counts [B, 2] integers (rows, correct rows), sums [B, 2] (sum of conf, sum of the Brier term).  With N = all rows and, per
+    non-empty bin, acc_b = correct_b / n_b and conf_b = conf_sum_b / n_b:
+        ece = sum_b (n_b / N) |acc_b - conf_b|,   mce = max_b |acc_b - conf_b|,   brier = sum_b brier_sum_b / N;
+    empty bins are skipped (their accuracy and confidence are NaN in the table) and N = 0 gives NaN for all three.
+    Returns {"rows", "bins": [{"count", "correct", "conf_sum", "brier_sum", "accuracy", "confidence"}], "ece", "mce", "brier"}."""
+    counts = np.asarray(counts).reshape(-1, 2)
+    sums = np.asarray(sums, dtype=np.float64).reshape(-1, 2)
+    if counts.shape != sums.shape:
+        raise ValueError(f"summarise_reliability: counts {counts.shape} and sums {sums.shape} do not list the same bins")
+    N = sum(int(c) for c in counts[:, 0])
+    nan = float("nan")
+    bins, ece, mce, brier = [], 0.0, 0.0, 0.0
+    for (n, k), (sc, sb) in zip(counts.tolist(), sums.tolist()):
+        n, k = int(n), int(k)
+        acc, conf = (k / n, sc / n) if n else (nan, nan)
+        bins.append({"count": n, "correct": k, "conf_sum": sc, "brier_sum": sb, "accuracy": acc, "confidence": conf})
+        if n:
+            gap = abs(acc - conf)
+            ece += (n / N) * gap
+            mce = max(mce, gap)
+            brier += sb / N
+    if N == 0:
+        ece = mce = brier = nan
+    return {"rows": N, "bins": bins, "ece": ece, "mce": mce, "brier": brier}
+
+
+def _check_bins(bins, who):
+    if int(bins) != bins or not 1 <= int(bins) <= RELIABILITY_MAX_BINS:
+        raise ValueError(f"{who}: bins {bins!r} is not an integer in [1, {RELIABILITY_MAX_BINS}]")
+    return int(bins)
+
+
+def _reliability_call(who, M, B, dev, launch):
+    """Allocate [counts i64 B x 2 | sums f64 B x 2 | flags (2 x i32 in one slot)] as one buffer, launch, download once."""
+    res = torch.empty((4 * B + 1,), dtype=torch.float64, device=dev)
+    work = torch.empty((RELIABILITY_MAX_BLOCKS * B * 4,), dtype=torch.float64, device=dev)
+    p = res.data_ptr()
+    st = launch(_lib.ptr(work), ctypes.c_void_p(p), ctypes.c_void_p(p + 16 * B), ctypes.c_void_p(p + 32 * B), _lib.stream())
+    _lib.check(st, who)
+    host = res.cpu()
+    out = summarise_reliability(host[:2 * B].view(torch.int64).numpy().reshape(B, 2), host[2 * B:4 * B].numpy().reshape(B, 2))
+    bad, last = host[4 * B:].view(torch.int32).tolist()
+    out["excluded"], out["last_excluded"] = bad, last - 1
+    assert out["rows"] + bad == M, f"{who}: {out['rows']} rows binned and {bad} excluded of {M}"
+    return out
+
+
+def reliability(logits, labels, T=1.0, classes=None, bins=15):
+    """Reliability of softmax(logits / T) against the labels: logits CUDA f32 [M, K+1] (background last), labels CUDA i32 [M] in
+    [0, K].  classes CUDA i32 [M]: the confidence is the row's own p[class] and it is correct when label == class (the score ProbEn
+    consumes); classes None: the top label over all K + 1 columns, the first index among equal maxima.  One pe_reliability_logits
+    call and one download (synchronises).  Returns summarise_reliability's dict plus "excluded" (rows with a label or class outside
+    [0, K], or a NaN confidence: they add nothing; reported, not raised) and "last_excluded" (such a row's index, -1 without one)."""
+    _lib.require_cuda(logits, labels, classes)
+    T, B = check_temperature(T), _check_bins(bins, "reliability")
+    if logits.dim() != 2 or logits.shape[1] < 2:
+        raise ValueError(f"reliability: logits must be [M, K+1] with K >= 1, got {tuple(logits.shape)}")
+    logits = logits.contiguous().float()
+    M, k1 = logits.shape
+    labels = labels.reshape(-1).contiguous().to(torch.int32)
+    if classes is not None:
+        classes = classes.reshape(-1).contiguous().to(torch.int32)
+    if labels.numel() != M or (classes is not None and classes.numel() != M):
+        raise ValueError(f"reliability: {labels.numel()} labels{'' if classes is None else f' and {classes.numel()} classes'} for {M} rows")
+    L = _lib.lib()
+    return _reliability_call("pe_reliability_logits", M, B, logits.device, lambda work, cnt, sums, flags, stream: L.pe_reliability_logits(
+        _lib.ptr(logits) if M else None, _lib.ptr(labels) if M else None, _lib.ptr(classes) if (M and classes is not None) else None,
+        M, k1, T, B, work, cnt, sums, flags, stream))
+
+
+def reliability_scores(conf, correct, bins=15):
+    """The same dict for scores that come with their own verdict: conf CUDA f64 [M] in [0, 1], correct CUDA [M] (non-zero = correct).
+    A conf that is NaN or outside [0, 1] excludes the row.  One pe_reliability_scores call and one download."""
+    _lib.require_cuda(conf, correct)
+    B = _check_bins(bins, "reliability_scores")
+    conf = conf.reshape(-1).contiguous().double()
+    correct = correct.reshape(-1).contiguous().to(torch.int32)
+    M = conf.numel()
+    if correct.numel() != M:
+        raise ValueError(f"reliability_scores: {correct.numel()} verdicts for {M} scores")
+    L = _lib.lib()
+    return _reliability_call("pe_reliability_scores", M, B, conf.device, lambda work, cnt, sums, flags, stream: L.pe_reliability_scores(
+        _lib.ptr(conf) if M else None, _lib.ptr(correct) if M else None, M, B, work, cnt, sums, flags, stream))

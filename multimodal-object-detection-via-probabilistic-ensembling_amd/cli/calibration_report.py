@@ -1,0 +1,246 @@
+"""Held-out calibration report: does what cli/fit_temperature fitted help on the images it did not see?
+
+    python -m proben_amd.cli.calibration_report --dataset_path DATA/FLIR/val \\
+        --predictions out/val_thermal_only_predictions.json out/val_early_fusion_predictions.json \\
+        --calibration calibration.json [--bins 15] [--iou 0.5] [--on heldout|fitted|all] \\
+        [--score_fusion probEn --box_fusion v-avg] [--out report.json]
+
+--on heldout (the default) takes the dataset's images that are not among the calibration file's "fitted_image_ids"; `fitted` takes
+those, `all` every image.  A file fitted with --holdout 1.0 leaves nothing held out: that is refused, choose --on fitted or --on all.
+
+Per detector (the <name> of val_<name>_predictions.json), once at T = 1 ("before") and once at the file's T ("after"): the detections
+of the chosen images are labelled on the device in one launch (calibration.match_rows_device; a ground-truth class the head has no
+column for is background, as in the fit), then the NLL per row (calibration.temperature_nll) and ECE, MCE and the Brier score of the
+detection's own score p[class] - the score ProbEn consumes - from calibration.reliability; "top_label" holds the same for the top label
+over all K + 1 columns.  When the file has "variance_scales": the Gaussian NLL per matched row and the 1-sigma / 2-sigma coverage of
+the box residuals (calibration.variance_stats) at s = 1 and at the file's s, beside a Gaussian's 0.6827 / 0.9545.
+For the fused detections: late_fusion over the chosen images without any calibration ("before") and with the file's temperatures,
+variance scales and - for --score_fusion probEn-log - class prior ("after"); the fused boxes are matched the same way, a fused row is
+correct when its label is its fused class, and its confidence is its fused score (calibration.reliability_scores).
+Rows that cannot be binned (a NaN score, a label outside the columns) are counted as "excluded" and printed, never dropped silently.
+
+What the detection-level figures are not.  A detection is "correct" when the ground-truth box it overlaps most, at IoU >= --iou, has
+its class: two detections on one box are both correct.  That is the temperature fit's labelling, not COCO's one-to-one matching, so
+the figures describe the scores as the fit sees them, not AP.  And with no trained weights or FLIR frames offline, whatever this
+prints on synthetic detectors says nothing about real FLIR data.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+from .. import calibration
+from ..data import load_coco_json
+from ..late_fusion import late_fusion, read_j1
+from .fit_temperature import detector_name
+
+ON = ("heldout", "fitted", "all")
+GAUSSIAN_COVERAGE = (0.682689492137086, 0.954499736103642)
+
+
+def parse(argv):
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--predictions", nargs="+", required=True, help="val_<method>_predictions.json files, one per detector")
+    p.add_argument("--dataset_path", required=True, help="FLIR val folder (FLIR_thermal_RGBT_pairs_val.json)")
+    p.add_argument("--calibration", required=True, help="the file cli/fit_temperature wrote")
+    p.add_argument("--bins", type=int, default=15, help="confidence bins of equal width on [0, 1]")
+    p.add_argument("--iou", type=float, default=0.5, help="IoU from which a detection takes a ground-truth box's class")
+    p.add_argument("--on", choices=ON, default="heldout", help="which images: those the file was not fitted on, those it was, or all")
+    p.add_argument("--score_fusion", default="probEn", help="score fusion of the fused detections (avg / max / probEn / probEn-log)")
+    p.add_argument("--box_fusion", default="v-avg", help="box fusion of the fused detections (v-avg / s-avg / avg / argmax)")
+    p.add_argument("--out", default=None, help="write the report as JSON")
+    p.add_argument("--device", default="cuda")
+    args = p.parse_args(argv)
+    if not 1 <= args.bins <= calibration.RELIABILITY_MAX_BINS:
+        p.error(f"--bins {args.bins} is not in [1, {calibration.RELIABILITY_MAX_BINS}]")
+    if not 0.0 <= args.iou <= 1.0:
+        p.error(f"--iou {args.iou} is not in [0, 1]")
+    if not 2 <= len(args.predictions) <= 3:
+        p.error(f"--predictions lists {len(args.predictions)} files: late fusion takes 2 or 3")
+    return args
+
+
+def select_images(order, fitted_ids, on, source="the calibration file"):
+    """The dataset's image ids (dataset order) that --on names.  An empty choice is refused."""
+    if on not in ON:
+        raise ValueError(f"--on {on!r} is not one of {', '.join(ON)}")
+    fitted = set(fitted_ids)
+    ids = [i for i in order if on == "all" or (i in fitted) == (on == "fitted")]
+    if not ids:
+        what = ("lists every image of the dataset among its fitted_image_ids (fit_temperature --holdout 1.0): nothing is held out"
+                if on == "heldout" else "lists none of the dataset's images among its fitted_image_ids" if on == "fitted"
+                else "is beside an empty dataset")
+        raise ValueError(f"{source} {what}.  Choose the images with --on {' / --on '.join(o for o in ON if o != on)}")
+    return ids
+
+
+def take_j1(det, index):
+    """shard_j1 for a list of positions: the prediction dict of those images."""
+    return {k: [v[i] for i in index] for k, v in det.items()}
+
+
+def positions(pred, ids, name):
+    where = {iid: i for i, iid in enumerate(pred["image_id"])}
+    missing = [i for i in ids if i not in where]
+    if missing:
+        raise ValueError(f"{name}: no entry for {len(missing)} of the {len(ids)} chosen images (image id {missing[0]} is one)")
+    return [where[i] for i in ids]
+
+
+def ground_truth(records, ids, device):
+    """(boxes f64 [G,4] XYXY, offsets i32 [B+1], classes i32 [G], crowd i32 [G]) of the chosen images on the device."""
+    gt, cls, crowd, off = [], [], [], [0]
+    for iid in ids:
+        for a in records[iid]["annotations"]:
+            x, y, w, h = a["bbox"]                        # COCO XYWH -> XYXY
+            gt.append([x, y, x + w, y + h])
+            cls.append(a["category_id"])
+            crowd.append(a["iscrowd"])
+        off.append(len(gt))
+    t = lambda x, dt, shape: torch.tensor(x, dtype=dt).reshape(shape).to(device)
+    return t(gt, torch.float64, (-1, 4)), t(off, torch.int32, (-1,)), t(cls, torch.int32, (-1,)), t(crowd, torch.int32, (-1,))
+
+
+def match_device(boxes, offsets, gt, iou, k, device):
+    """Labels in [0, k] (a class outside the head's columns folds to k, as fit_temperature.labelled_rows does) and the match index."""
+    db = torch.tensor(boxes, dtype=torch.float64).reshape(-1, 4).to(device)
+    doff = torch.tensor(offsets, dtype=torch.int32).to(device)
+    labels, match, _ = calibration.match_rows_device(db, doff, gt[0], gt[1], gt[2], gt[3], iou, k)
+    labels = torch.where((labels < 0) | (labels > k), torch.full_like(labels, k), labels)
+    return db, labels, match
+
+
+def _figures(rel):
+    return {k: rel[k] for k in ("rows", "excluded", "ece", "mce", "brier", "bins")}
+
+
+def detector_report(pred, name, gt, T, bins, iou, device):
+    """{"before", "after"} of one (already sliced) prediction dict, plus the tensors the variance block reuses."""
+    calibration.require_logits(pred, name)
+    flat = lambda key: [r for rows in pred[key] for r in rows]
+    logits, classes = flat("class_logits"), flat("classes")
+    if not logits:
+        raise ValueError(f"{name}: no detections on the chosen images: nothing to report")
+    k = len(logits[0]) - 1
+    offsets = np.cumsum([0] + [len(b) for b in pred["boxes"]]).tolist()
+    db, labels, match = match_device(flat("boxes"), offsets, gt, iou, k, device)
+    lg = torch.tensor(logits, dtype=torch.float32, device=device).reshape(len(logits), k + 1)
+    cls = torch.tensor(classes, dtype=torch.int32, device=device)
+    out = {}
+    for tag, t in (("before", 1.0), ("after", T)):
+        nll, _ = calibration.temperature_nll(lg, labels, [t])
+        rec = {"T": t, "nll": float(nll[0]) / len(logits)}
+        rec.update(_figures(calibration.reliability(lg, labels, t, cls, bins)))
+        rec["top_label"] = _figures(calibration.reliability(lg, labels, t, None, bins))
+        out[tag] = rec
+    return out, (db, match)
+
+
+def variance_report(pred, rows, gt_boxes, s, device):
+    """Gaussian NLL per matched row and the coverage of the box residuals at s = 1 and at the file's s."""
+    db, match = rows
+    var = torch.tensor([v[0] if isinstance(v, (list, tuple)) else v for r in pred["vars"] for v in r], dtype=torch.float64, device=device)
+    if var.numel() != db.shape[0]:
+        raise ValueError(f"{var.numel()} vars for {db.shape[0]} detections: the variance report needs the box head's vars")
+    hit = match >= 0
+    out = {}
+    for tag, scale in (("before", 1.0), ("after", s)):
+        st = calibration.variance_stats(db[hit], match[hit], gt_boxes, var[hit], scale)
+        n = st["n"]
+        out[tag] = {"scale": scale, "rows": n, "excluded": st["excluded"],
+                    "nll": calibration.variance_nll(st, scale) / n if n else float("nan"),
+                    "coverage": [st["cover1"] / (4 * n), st["cover2"] / (4 * n)] if n else [float("nan")] * 2}
+    return out
+
+
+def fused_report(dets, names, method, gt, k, bins, iou, device, **calibrated):
+    """Reliability of the fused score of late_fusion(dets, method, **calibrated) on the chosen images."""
+    boxes, conf, cls, offsets = [], [], [], [0]
+    for r in late_fusion(dets, method, device, names=names, **calibrated):
+        if r is not None:
+            boxes += np.asarray(r[0], dtype=np.float64).reshape(-1, 4).tolist()
+            conf += r[1].double().tolist()
+            cls += r[2].tolist()
+        offsets.append(len(boxes))
+    _, labels, _ = match_device(boxes, offsets, gt, iou, k, device)
+    correct = labels == torch.tensor(cls, dtype=torch.float64, device=device).to(torch.int32)
+    return _figures(calibration.reliability_scores(torch.tensor(conf, dtype=torch.float64, device=device), correct, bins))
+
+
+def table(report):
+    head = ("", "", "rows", "excl", "NLL/row", "ECE", "MCE", "Brier", "1 sigma", "2 sigma")
+    rows = [head]
+    f = lambda x: "-" if x is None else f"{x:.6f}"
+    for name, d in report["detectors"].items():
+        for tag in ("before", "after"):
+            r = d[tag]
+            rows.append((name, f"{tag} (T = {r['T']:.4g})", str(r["rows"]), str(r["excluded"]), f(r["nll"]), f(r["ece"]), f(r["mce"]), f(r["brier"]), "", ""))
+            t = r["top_label"]
+            rows.append((name, "  top label", str(t["rows"]), str(t["excluded"]), "", f(t["ece"]), f(t["mce"]), f(t["brier"]), "", ""))
+    for name, d in report["variance"].items():
+        for tag in ("before", "after"):
+            r = d[tag]
+            rows.append((name, f"variance {tag} (s = {r['scale']:.4g})", str(r["rows"]), str(r["excluded"]), f(r["nll"]), "", "", "",
+                         f(r["coverage"][0]), f(r["coverage"][1])))
+    if report["variance"]:
+        rows.append(("", "a Gaussian", "", "", "", "", "", "", f(GAUSSIAN_COVERAGE[0]), f(GAUSSIAN_COVERAGE[1])))
+    for tag in ("before", "after"):
+        r = report["fused"][tag]
+        rows.append(("fused", f"{tag} ({'/'.join(report['method'])})", str(r["rows"]), str(r["excluded"]), "", f(r["ece"]), f(r["mce"]), f(r["brier"]), "", ""))
+    width = [max(len(r[c]) for r in rows) for c in range(len(head))]
+    return "\n".join("  ".join(x.ljust(w) if c < 2 else x.rjust(w) for c, (x, w) in enumerate(zip(r, width))).rstrip() for r in rows)
+
+
+def main(cmd=None):
+    args = parse(list(cmd) if cmd is not None else sys.argv[1:])
+    rec = calibration.load(args.calibration)
+    scales = calibration.load_variance(args.calibration)
+    records = load_coco_json(os.path.join(args.dataset_path, "FLIR_thermal_RGBT_pairs_val.json"),
+                             os.path.join(args.dataset_path, "thermal_8_bit"))
+    ids = select_images([r["image_id"] for r in records], rec.get("fitted_image_ids", []), args.on, args.calibration)
+    by_id = {r["image_id"]: r for r in records}
+    names = [detector_name(p) for p in args.predictions]
+    if len(set(names)) != len(names):
+        raise ValueError(f"two prediction files for one detector ({', '.join(names)})")
+    temps = calibration.resolve(rec["detectors"], names, args.calibration)
+    svals = None if scales is None else calibration.resolve_variance_scales(scales, names, args.calibration)
+    gt = ground_truth(by_id, ids, args.device)
+    report = {"images": ids, "on": args.on, "bins": args.bins, "iou": args.iou, "method": [args.score_fusion, args.box_fusion],
+              "detectors": {}, "variance": {}}
+    dets, k1 = [], set()
+    for d, (path, name) in enumerate(zip(args.predictions, names)):
+        full = read_j1(path)
+        pred = take_j1(full, positions(full, ids, path))
+        report["detectors"][name], rows = detector_report(pred, path, gt, temps[d], args.bins, args.iou, args.device)
+        if svals is not None:
+            try:
+                report["variance"][name] = variance_report(pred, rows, gt[0], svals[d], args.device)
+            except ValueError as e:
+                raise ValueError(f"{path}: {e}") from None
+        k1.add(len(next(r for rows_ in pred["class_logits"] for r in rows_)))
+        dets.append(pred)
+    if len(k1) != 1:
+        raise ValueError(f"the prediction files have {sorted(k1)} class columns: they cannot be fused")
+    k = k1.pop() - 1
+    method = [args.score_fusion, args.box_fusion]
+    prior = rec.get("class_prior") if args.score_fusion == "probEn-log" else None
+    fuse = lambda **kw: fused_report(dets, args.predictions, method, gt, k, args.bins, args.iou, args.device, **kw)
+    report["fused"] = {"before": fuse(), "after": fuse(temperatures=temps, variance_scales=svals, class_prior=prior)}
+    print(f"{len(ids)} images ({args.on}) of {len(records)}, {args.bins} bins, IoU >= {args.iou}")
+    print(table(report))
+    excluded = sum(d[t]["excluded"] + d[t]["top_label"]["excluded"] for d in report["detectors"].values() for t in ("before", "after")) \
+        + sum(report["fused"][t]["excluded"] for t in ("before", "after"))
+    if excluded:
+        print("excluded rows (a NaN score, a label or class outside the columns) are not in the figures above: see the excl column")
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(report, f, indent=1)
+        print("report:", args.out)
+    return report
+
+
+if __name__ == "__main__":
+    main()
