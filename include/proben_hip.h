@@ -260,6 +260,73 @@ int pe_reliability_scores(const double* conf, const int32_t* correct, int64_t nu
                           int64_t* out_counts, double* out_sums, int32_t* out_flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Pooling weights of log-posterior ProbEn: the logarithmic opinion pool, one exponent w_d >= 0 per detector INSIDE the fusion.  ProbEn's
+ * product assumes detectors that are conditionally independent given the class; detectors that share evidence (two that look at the
+ * same thermal frame, several rows of one detector in a cluster) count it twice and the fused score is over-confident although every
+ * detector is calibrated on its own.  Not in the reference.  For a cluster of m > 1 rows in cluster order (matches first, pivot last),
+ * d(t) the detector row t came from:
+ *     a_j = (sum_t w_d(t) * log_probs[t][j]) - (W - 1) * log_prior[j],   W = sum_t w_d(t)   (both sums sequential, in that order; the
+ *                                                                                            prior term only when log_prior != NULL)
+ *     s_j = exp(a_j - max_j a_j) / sum_j exp(a_j - max_j a_j)                               (column order)
+ * With every w = 1 this is PE_SCORE_PROBEN_LOGP bit for bit (1.0 * x is x, W is the integer m); with sum w = 1 over a cluster it is a
+ * weighted geometric mean.  Unlike a temperature, w leaves the row's own score alone: the clustering order, clusters of one and s-avg.
+ *
+ * pe_proben_fuse_batch_pooled: pe_proben_fuse_batch_logp plus row_source i32 [Ntot] (the detector index of each row), pool_weights
+ *   DEVICE f64 [num_detectors], num_detectors in [1, PE_POOL_MAX_DETECTORS], and the optional output out_cluster i32 [Ntot].  Same
+ *   kernel (a template instantiation), clustering (both forms), box modes, score / class rule (maximum over the K + 1 columns, first
+ *   index, NaN wins), K <= 62, out_counts = -1 and passthrough rules; a cluster of one keeps its row's score and class, whatever the
+ *   weights.  The weight is staged in LDS beside the row: 8 more bytes per row than pe_proben_fuse_batch_logp in the LDS budget.
+ *   pool_weights is a device pointer and cannot be checked here: entries must be finite and >= 0, not all 0 - the caller's contract
+ *   (fusion.pool_weight_tensor validates it).  A row whose source is outside [0, num_detectors) takes a NaN weight (a NaN score for its
+ *   cluster); 0 * -inf is NaN as in NumPy.
+ *   out_cluster[offsets[b] + r], r an input row of image b: the output row k of the cluster the row ended in, as pivot or as member;
+ *   -1 when the row left the pool without joining one (a NaN IoU); r on a passthrough image; untouched when out_counts[b] is -1.
+ * pe_proben_pack_pooled: pe_proben_pack_calibrated plus out_source i32 [num_images * row_stride] (required): the detector index d
+ *   of every written row, stored where the row is stored, in the one walk.  Every other output is pe_proben_pack_calibrated's bits.
+ * pe_pool_nll: the objective of the weights' fit.  log_probs f64 [num_rows, num_columns] (K + 1 columns in [2, 64]), row_source i32
+ *   [num_rows]; the clusters in CSR form, member_rows i32 [num_members] (row indices) and cluster_offsets i32 [num_clusters + 1];
+ *   labels i32 [num_clusters] in [0, K]; log_prior optional DEVICE f64 [K + 1]; weights_host: num_candidates <= 64 candidate vectors,
+ *   host doubles [num_candidates, num_detectors], each finite and >= 0 (checked; the array is free again on return).  Per candidate c,
+ *   out f64 [num_candidates, 1 + num_detectors]:
+ *     out[c][0]     = sum over clusters of -log s_label(w_c)
+ *     out[c][1 + d] = its derivative in w_d = sum over clusters of  sum_j s_j G_dj - G_d,label,
+ *     G_dj = S_dj - n_d lp_j,  S_dj = the sum of log_probs[t][j] over the cluster's rows of detector d (member order), n_d their
+ *     number, lp the log prior (0 when NULL); a_j is evaluated as (sum_d w_d G_dj) + lp_j, d ascending - the same value as the fusion's
+ *     member-order sum up to rounding.  The NLL is convex in w (a is linear in w).
+ *   Lane = candidate, wavefront = cluster: a wavefront reads its cluster's rows once (lane = column) into the table G in LDS and the 64
+ *   candidates work from it.  A cluster is excluded - it adds nothing - when it has fewer than 2 rows (the product does not fuse
+ *   those), its label is outside [0, K], one of its rows has a source outside [0, num_detectors), or its offsets / one of its row
+ *   indices point outside the arrays; out_flags i32 [2]: [0] = excluded clusters, [1] = 1 + the largest excluded cluster index.
+ *   Deterministic like pe_temperature_nll: min(ceil(num_clusters / 4), PE_POOL_NLL_MAX_BLOCKS) workgroups, a function of num_clusters
+ *   alone, per-workgroup partials in a fixed order, one fixed-order finishing pass, no floating-point atomics.
+ *   workspace: f64, num_candidates * (num_detectors + PE_POOL_NLL_MAX_BLOCKS * (1 + num_detectors)) values.
+ * Arguments are checked before any device work.
+ * ------------------------------------------------------------------------------------------- */
+#define PE_POOL_MAX_DETECTORS 8
+#define PE_POOL_NLL_MAX_BLOCKS 1024
+int pe_proben_fuse_batch_pooled(const double* boxes, const double* scores, const double* log_probs, /* [Ntot,K+1] */
+                                const double* variances, const int32_t* classes, const int32_t* row_source, /* [Ntot] */
+                                const int32_t* offsets, const int32_t* row_counts, const int32_t* passthrough, int32_t num_images,
+                                int32_t num_classes, int32_t max_rows_per_image, int32_t box_mode, double iou_thresh, double frame_w,
+                                double frame_h, const double* log_prior, /* optional [K+1] */
+                                const double* pool_weights,              /* DEVICE [num_detectors] */
+                                int32_t num_detectors, double* out_boxes, float* out_scores, float* out_classes, int32_t* out_keep,
+                                int32_t* out_counts, int32_t* out_cluster /* optional [Ntot] */, void* stream);
+int pe_proben_pack_pooled(const float* const* det_boxes_host, const float* const* det_scores_host,
+                          const int32_t* const* det_classes_host, const float* const* det_probs_host,
+                          const float* const* det_logits_host, const float* const* det_vars_host,
+                          const int32_t* const* det_counts_host, const double* temperatures_host,
+                          const double* var_scales_host /* optional */, int32_t num_detectors, int32_t num_images,
+                          int32_t det_stride, int32_t num_classes, int32_t max_class, int32_t row_stride, double* out_boxes,
+                          double* out_scores, double* out_probs, double* out_log_probs /* optional */, double* out_vars,
+                          int32_t* out_classes, int32_t* out_offsets, int32_t* out_counts, int32_t* out_single_source,
+                          int32_t* out_source, void* stream);
+int pe_pool_nll(const double* log_probs, const int32_t* row_source, int64_t num_rows, int32_t num_columns,
+                const int32_t* member_rows, int64_t num_members, const int32_t* cluster_offsets, const int32_t* labels,
+                int32_t num_clusters, const double* log_prior /* optional */, const double* weights_host, int32_t num_candidates,
+                int32_t num_detectors, double* workspace, double* out, int32_t* out_flags /* [2] */, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused convolution / GEMM: NHWC fp16 activations, [Cout][KH][KW][Cin] fp16 weights, fp32 accumulate
  * on MFMA, epilogue = + bias[Cout] (fp32) + residual + ReLU, fp16 (or fp32) NHWC output.
  * Replaces, per layer, detectron2.layers.Conv2d.forward (layers/wrappers.py:62-98) + FrozenBatchNorm2d

@@ -20,6 +20,12 @@ Variance calibration (csrc/variance.hip): one scale s per detector, variance' = 
 Reliability of a score on rows the fit did not see (csrc/reliability.hip; the driver is cli/calibration_report):
   reliability / reliability_scores         per-bin counts and sums from pe_reliability_logits / pe_reliability_scores, one launch each
   summarise_reliability                    ECE, MCE and the Brier score from those, on the host
+
+Pooling weights (csrc/pool.hip, csrc/proben.hip): one exponent w per detector inside score_fusion "probEn-log", for detectors that
+share evidence.
+  pool_nll / fit_pool_weights              the fused posterior's NLL and gradient for up to 64 candidates (pe_pool_nll); the safeguarded fit
+  check_pool_weights / parse_pool_weights / resolve_pool_weights
+  save / load                              carry the optional key "pool_weights" {name: w}
 """
 import ctypes
 import json
@@ -35,6 +41,8 @@ NLL_MAX_BLOCKS = 1024        # PE_TEMPERATURE_NLL_MAX_BLOCKS (include/proben_hip
 VARIANCE_MAX_BLOCKS = 1024   # PE_VARIANCE_STATS_MAX_BLOCKS: 5 partial values per workgroup
 RELIABILITY_MAX_BINS = 64    # PE_RELIABILITY_MAX_BINS
 RELIABILITY_MAX_BLOCKS = 1024     # PE_RELIABILITY_MAX_BLOCKS: 4 partial values per workgroup and bin
+POOL_MAX_DETECTORS = 8       # PE_POOL_MAX_DETECTORS
+POOL_NLL_MAX_BLOCKS = 1024   # PE_POOL_NLL_MAX_BLOCKS: 1 + num_detectors partial values per workgroup and candidate
 BBOX_REG_WEIGHTS = (10.0, 10.0, 5.0, 5.0)      # cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS: the units the variance head is trained in
 
 
@@ -191,14 +199,17 @@ def fit_temperature(logits, labels, lo=0.05, hi=20.0, tol=1e-6):
             "rounds": rounds, "rows": int(logits.shape[0]), "at_bound": at}
 
 
-def save(path, detectors, nll=None, rows=None, class_prior=None, **extra):
+def save(path, detectors, nll=None, rows=None, class_prior=None, pool_weights=None, **extra):
     """Write the calibration file.  detectors {name: T}; nll {name: {"before": .., "after": ..}}; rows {name: fitted rows};
     class_prior (optional, K + 1 probabilities, background last: the prior of score_fusion "probEn-log") is written normalised -
-    without it the file has no such key; extra keys (cli/fit_temperature adds "holdout" and "fitted_image_ids") are kept as given."""
+    without it the file has no such key; pool_weights (optional, {name: w}: the pooling weights of "probEn-log") likewise; extra keys
+    (cli/fit_temperature adds "holdout" and "fitted_image_ids") are kept as given."""
     rec = {"detectors": {k: check_temperature(v, f"temperature of {k}") for k, v in detectors.items()},
            "nll": nll or {}, "rows": rows or {}}
     if class_prior is not None:
         rec["class_prior"] = check_class_prior(class_prior).tolist()
+    if pool_weights is not None:
+        rec["pool_weights"] = _check_pool_table(pool_weights, "pool_weights")
     rec.update(extra)
     with open(path, "w") as f:
         json.dump(rec, f, indent=1)
@@ -214,6 +225,8 @@ def load(path):
         check_temperature(v, f"{path}: temperature of {k}")
     if "class_prior" in rec:
         rec["class_prior"] = check_class_prior(rec["class_prior"], what=f"{path}: class_prior").tolist()
+    if "pool_weights" in rec:
+        rec["pool_weights"] = _check_pool_table(rec["pool_weights"], f"{path}: pool_weights")
     return rec
 
 
@@ -561,3 +574,179 @@ def reliability_scores(conf, correct, bins=15):
     L = _lib.lib()
     return _reliability_call("pe_reliability_scores", M, B, conf.device, lambda work, cnt, sums, flags, stream: L.pe_reliability_scores(
         _lib.ptr(conf) if M else None, _lib.ptr(correct) if M else None, M, B, work, cnt, sums, flags, stream))
+
+
+# ---- pooling weights -----------------------------------------------------------------------------------------------------------
+
+def check_pool_weight(w, what="pool weight"):
+    try:
+        w = float(w)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} {w!r} is not a number") from None
+    if not (math.isfinite(w) and w >= 0):
+        raise ValueError(f"{what} {w!r} is not finite and >= 0")
+    return w
+
+
+def check_pool_weights(weights, num_detectors, who):
+    """pool_weights argument of the fusion entry points -> [w per detector] or None.  Every w finite and >= 0, not all of them 0
+    (the pooled posterior would be the prior), one per detector, at most POOL_MAX_DETECTORS."""
+    if weights is None:
+        return None
+    if isinstance(weights, torch.Tensor):
+        weights = weights.detach().cpu().reshape(-1).tolist()
+    weights = list(weights)
+    if len(weights) != num_detectors:
+        raise ValueError(f"{who}: {len(weights)} pool weights for {num_detectors} detectors")
+    if not 1 <= num_detectors <= POOL_MAX_DETECTORS:
+        raise ValueError(f"{who}: pool weights for {num_detectors} detectors (1 to {POOL_MAX_DETECTORS})")
+    out = [check_pool_weight(w, f"{who}: pool weight of detector {k + 1}") for k, w in enumerate(weights)]
+    if not any(w > 0 for w in out):
+        raise ValueError(f"{who}: pool weights {out} are all 0")
+    return out
+
+
+def _check_pool_table(table, what):
+    if not isinstance(table, dict) or not table:
+        raise ValueError(f"{what} is not a table of detector names")
+    out = {k: check_pool_weight(v, f"{what}: pool weight of {k}") for k, v in table.items()}
+    if not any(w > 0 for w in out.values()):
+        raise ValueError(f"{what}: the pool weights are all 0")
+    return out
+
+
+def parse_pool_weights(text, names):
+    """--pool_weights value -> [w per name].  'a,b[,c]' is matched by position, 'name=a,name=b' by name; not both."""
+    items = [x.strip() for x in str(text).split(",") if x.strip()]
+    named = ["=" in x for x in items]
+    if any(named) != all(named):
+        raise ValueError(f"--pool_weights {text!r} mixes positional and name=value entries")
+    if not all(named):
+        if len(items) != len(names):
+            raise ValueError(f"--pool_weights lists {len(items)} values for {len(names)} --detectors ({','.join(names)})")
+        return check_pool_weights(items, len(names), "--pool_weights")
+    table = {}
+    for x in items:
+        k, v = x.split("=", 1)
+        if k in table:
+            raise ValueError(f"--pool_weights names {k} twice")
+        table[k] = v
+    return resolve_pool_weights(table, names, "--pool_weights")
+
+
+def resolve_pool_weights(table, names, source):
+    """{name: w} -> [w per name]; every name must be there."""
+    missing = [n for n in names if n not in table]
+    if missing:
+        raise ValueError(f"{source} has no pool weight for {','.join(missing)} (it lists {','.join(sorted(table)) or 'nothing'})")
+    return check_pool_weights([table[n] for n in names], len(names), source)
+
+
+def pool_nll(log_probs, row_source, member_rows, cluster_offsets, labels, weights, log_prior=None):
+    """One pe_pool_nll launch.  Device tensors: log_probs f64 [N, K+1], row_source i32 [N], the clusters in CSR form (member_rows i32
+    [M] row indices, cluster_offsets i32 [C+1]), labels i32 [C] in [0, K], log_prior f64 [K+1] or None.  weights: [n_c, D] candidate
+    vectors (n_c <= 64), finite and >= 0.  Returns (nll f64 ndarray [n_c], grad f64 ndarray [n_c, D], excluded clusters,
+    last excluded cluster index or -1); an excluded cluster (fewer than 2 rows, a label outside [0, K], a row source outside [0, D))
+    adds nothing.  Synchronises (one download)."""
+    _lib.require_cuda(log_probs, row_source, member_rows, cluster_offsets, labels, log_prior)
+    W = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+    if W.ndim != 2 or W.shape[0] < 1 or W.shape[1] < 1:
+        raise ValueError(f"pool_nll: weights must be [candidates, detectors], got {W.shape}")
+    n_c, D = W.shape
+    if log_probs.dim() != 2 or log_probs.shape[1] < 2:
+        raise ValueError(f"pool_nll: log_probs must be [N, K+1] with K >= 1, got {tuple(log_probs.shape)}")
+    log_probs = log_probs.contiguous().double()
+    N, k1 = log_probs.shape
+    row_source = row_source.reshape(-1).contiguous().to(torch.int32)
+    member_rows = member_rows.reshape(-1).contiguous().to(torch.int32)
+    cluster_offsets = cluster_offsets.reshape(-1).contiguous().to(torch.int32)
+    labels = labels.reshape(-1).contiguous().to(torch.int32)
+    C, M = labels.numel(), member_rows.numel()
+    if row_source.numel() != N or cluster_offsets.numel() != C + 1:
+        raise ValueError(f"pool_nll: {row_source.numel()} sources for {N} rows, {cluster_offsets.numel()} offsets for {C} clusters")
+    if log_prior is not None:
+        log_prior = log_prior.reshape(-1).contiguous().double()
+        if log_prior.numel() != k1:
+            raise ValueError(f"pool_nll: log_prior lists {log_prior.numel()} entries for K + 1 = {k1} columns")
+    dev = log_probs.device
+    nv = n_c * (1 + D)
+    res = torch.empty((nv + 1,), dtype=torch.float64, device=dev)       # [out | flags (2 x i32 in one f64 slot)]: one download
+    work = torch.empty((n_c * (D + POOL_NLL_MAX_BLOCKS * (1 + D)),), dtype=torch.float64, device=dev)
+    flags = res[nv:].view(torch.int32)
+    st = _lib.lib().pe_pool_nll(_lib.ptr(log_probs) if N else None, _lib.ptr(row_source) if N else None, N, k1,
+                               _lib.ptr(member_rows) if M else None, M, _lib.ptr(cluster_offsets), _lib.ptr(labels) if C else None, C,
+                               _lib.ptr(log_prior), W.ctypes.data_as(ctypes.c_void_p), n_c, D, _lib.ptr(work), _lib.ptr(res),
+                               ctypes.c_void_p(flags.data_ptr()), _lib.stream())
+    _lib.check(st, "pe_pool_nll")
+    host = res.cpu()
+    bad, last = host[nv:].view(torch.int32).tolist()
+    out = host[:nv].numpy().reshape(n_c, 1 + D)
+    return out[:, 0].copy(), out[:, 1:].copy(), bad, last - 1
+
+
+def fit_pool_weights(log_probs, row_source, member_rows, cluster_offsets, labels, num_detectors, log_prior=None, hi=64.0,
+                     gtol=1e-7, max_rounds=60):
+    """w in [0, hi]^D that minimises the NLL of the pooled posterior against the clusters' labels (pool_nll's inputs).  The NLL is
+    convex in w, so a projected Newton iteration with a line search finds its minimum: per round one launch evaluates the gradient at
+    w and at w + h e_d (the Hessian's columns by forward differences, h = 1e-4, symmetrised), the Newton system is solved over the
+    coordinates that are not held at a bound (a coordinate is held at 0 / hi when the gradient pushes it outwards), and a second
+    launch evaluates up to 40 step lengths 2, 1, 1/2, ... along the clipped direction; the step with the lowest NLL is taken if
+    it is lower than the current one.  A direction that is not a descent direction (a nearly singular Hessian: two detectors that
+    are copies of each other) is replaced by the negative gradient.
+    Stops when the projected gradient satisfies max_d |pg_d| <= gtol * clusters used (pg_d = the gradient entry, 0 for a coordinate
+    held at a bound), when no step length lowers the NLL (float64 resolution of the NLL reached), or after max_rounds.
+    Returns a dict: weights [D], nll (at weights), nll_at_1, grad [D] (at weights), clusters (used), excluded, rounds, converged
+    (the gradient criterion was met), at_bound [D]: "lo" / "hi" where the NLL still falls beyond that end of [0, hi], else None."""
+    D = int(num_detectors)
+    if not 1 <= D <= POOL_MAX_DETECTORS:
+        raise ValueError(f"fit_pool_weights: {D} detectors (1 to {POOL_MAX_DETECTORS})")
+    hi = check_pool_weight(hi, "hi")
+    if not hi > 1.0:
+        raise ValueError(f"fit_pool_weights: hi {hi} <= 1 (the start of the search)")
+    C = int(labels.numel())
+    args = (log_probs, row_source, member_rows, cluster_offsets, labels)
+    h = 1e-4
+    w = np.ones(D)
+    f1, _, bad, _ = pool_nll(*args, [w], log_prior)
+    used = C - bad
+    if used <= 0:
+        raise ValueError(f"fit_pool_weights: no usable cluster ({bad} of {C} excluded: fewer than 2 rows, a label or a row source "
+                         "out of range)")
+    if not math.isfinite(f1[0]):
+        raise ValueError("fit_pool_weights: the NLL at w = 1 is not finite (non-finite log-posteriors?)")
+    rounds, converged = 0, False
+    f, g = float(f1[0]), None
+    while rounds < max_rounds:
+        rounds += 1
+        cand = np.vstack([w] + [w + h * np.eye(D)[d] for d in range(D)])
+        fs, gs, _, _ = pool_nll(*args, cand, log_prior)
+        f, g = float(fs[0]), gs[0]
+        held = ((w <= 0) & (g > 0)) | ((w >= hi) & (g < 0))
+        pg = np.where(held, 0.0, g)
+        if np.max(np.abs(pg)) <= gtol * used:
+            converged = True
+            break
+        H = (gs[1:] - g[None, :]) / h
+        H = 0.5 * (H + H.T)
+        free = ~held
+        p = np.zeros(D)
+        try:
+            Hf = H[np.ix_(free, free)] + 1e-10 * max(np.trace(H), 1.0) * np.eye(int(free.sum()))
+            p[free] = -np.linalg.solve(Hf, g[free])
+        except np.linalg.LinAlgError:
+            p[free] = -g[free]
+        if not (np.all(np.isfinite(p)) and p @ g < 0):
+            p = np.where(free, -g, 0.0) / max(np.max(np.abs(np.diag(H))), 1e-300)
+        steps = 2.0 ** (1 - np.arange(40))
+        trial = np.clip(w[None, :] + steps[:, None] * p[None, :], 0.0, hi)
+        ft, _, _, _ = pool_nll(*args, trial, log_prior)
+        ft = np.where(np.isfinite(ft), ft, np.inf)
+        i = int(np.argmin(ft))
+        if not ft[i] < f:
+            break
+        w, f = trial[i], float(ft[i])
+    fs, gs, _, _ = pool_nll(*args, [w], log_prior)
+    f, g = float(fs[0]), gs[0]
+    at = ["lo" if (w[d] <= 0 and g[d] > 0) else "hi" if (w[d] >= hi and g[d] < 0) else None for d in range(D)]
+    return {"weights": [float(x) for x in w], "nll": f, "nll_at_1": float(f1[0]), "grad": [float(x) for x in g], "clusters": used,
+            "excluded": bad, "rounds": rounds, "converged": converged, "at_bound": at}

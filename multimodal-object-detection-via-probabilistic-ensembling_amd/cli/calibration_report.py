@@ -17,6 +17,10 @@ the box residuals (calibration.variance_stats) at s = 1 and at the file's s, bes
 For the fused detections: late_fusion over the chosen images without any calibration ("before") and with the file's temperatures,
 variance scales and - for --score_fusion probEn-log - class prior ("after"); the fused boxes are matched the same way, a fused row is
 correct when its label is its fused class, and its confidence is its fused score (calibration.reliability_scores).
+When the file has "pool_weights" (fit_temperature --with-pool-weights): the "after" fusion of --score_fusion probEn-log uses them,
+and the report prints the NLL per cluster of the fused posterior against the label of the fused box, at w = 1 and at the file's
+weights, over the clusters of two or more rows that probEn-log forms on the chosen images at the file's temperatures, prior and
+variance scales (fit_temperature.pool_clusters: the fit's own labelling; calibration.pool_nll, both in one launch).
 Rows that cannot be binned (a NaN score, a label outside the columns) are counted as "excluded" and printed, never dropped silently.
 
 What the detection-level figures are not.  A detection is "correct" when the ground-truth box it overlaps most, at IoU >= --iou, has
@@ -35,7 +39,7 @@ import torch
 from .. import calibration
 from ..data import load_coco_json
 from ..late_fusion import late_fusion, read_j1
-from .fit_temperature import detector_name
+from .fit_temperature import detector_name, pool_clusters
 
 ON = ("heldout", "fitted", "all")
 GAUSSIAN_COVERAGE = (0.682689492137086, 0.954499736103642)
@@ -170,6 +174,25 @@ def fused_report(dets, names, method, gt, k, bins, iou, device, **calibrated):
     return _figures(calibration.reliability_scores(torch.tensor(conf, dtype=torch.float64, device=device), correct, bins))
 
 
+def pool_report(dets, names, records, ids, weights, iou, box_fusion, device, temperatures, class_prior, variance_scales):
+    """NLL per cluster of probEn-log's fused posterior on the chosen images, at w = 1 ("before") and at `weights` ("after")."""
+    from ..fusion import log_class_prior
+    out = {"clusters": 0, "excluded": 0, "nll": {"before": float("nan"), "after": float("nan")}}
+    got = pool_clusters(dets, names, records, ids, iou, box_fusion, device, temperatures, class_prior, variance_scales)
+    if got is None:
+        return out
+    cl, labels = got
+    lp = cl["log_probs"]
+    prior = None if class_prior is None else log_class_prior(class_prior, lp.shape[1], lp.device)
+    nll, _, bad, _ = calibration.pool_nll(lp, cl["row_source"], cl["member_rows"], cl["cluster_offsets"], labels,
+                                          [[1.0] * len(weights), weights], prior)
+    used = int(labels.numel()) - bad
+    out["clusters"], out["excluded"] = used, bad
+    if used:
+        out["nll"] = {"before": float(nll[0]) / used, "after": float(nll[1]) / used}
+    return out
+
+
 def table(report):
     head = ("", "", "rows", "excl", "NLL/row", "ECE", "MCE", "Brier", "1 sigma", "2 sigma")
     rows = [head]
@@ -226,11 +249,27 @@ def main(cmd=None):
         raise ValueError(f"the prediction files have {sorted(k1)} class columns: they cannot be fused")
     k = k1.pop() - 1
     method = [args.score_fusion, args.box_fusion]
-    prior = rec.get("class_prior") if args.score_fusion == "probEn-log" else None
+    logp = args.score_fusion == "probEn-log"
+    prior = rec.get("class_prior") if logp else None
+    pvals = None if "pool_weights" not in rec else calibration.resolve_pool_weights(rec["pool_weights"], names, args.calibration)
     fuse = lambda **kw: fused_report(dets, args.predictions, method, gt, k, args.bins, args.iou, args.device, **kw)
-    report["fused"] = {"before": fuse(), "after": fuse(temperatures=temps, variance_scales=svals, class_prior=prior)}
+    report["fused"] = {"before": fuse(), "after": fuse(temperatures=temps, variance_scales=svals, class_prior=prior,
+                                                       pool_weights=pvals if logp else None)}
+    if pvals is not None:
+        report["pool"] = pool_report(dets, args.predictions, by_id, ids, pvals, args.iou, args.box_fusion, args.device, temps,
+                                     rec.get("class_prior"), svals)
+        report["pool"]["weights"] = dict(zip(names, pvals))
+        report["pool"]["applied"] = logp
     print(f"{len(ids)} images ({args.on}) of {len(records)}, {args.bins} bins, IoU >= {args.iou}")
     print(table(report))
+    if pvals is not None:
+        r = report["pool"]
+        print(f"fused NLL per cluster (probEn-log/{args.box_fusion}, {r['clusters']} clusters of >= 2 rows, {r['excluded']} excluded): "
+              f"{r['nll']['before']:.6f} at w = 1, {r['nll']['after']:.6f} at the file's pool weights "
+              f"({', '.join(f'{n} = {w:.6g}' for n, w in zip(names, pvals))})")
+        if not logp:
+            print(f"the file's pool weights are not in the fused rows above: --score_fusion {args.score_fusion} has no pooled form "
+                  "(they belong to probEn-log)")
     excluded = sum(d[t]["excluded"] + d[t]["top_label"]["excluded"] for d in report["detectors"].values() for t in ("before", "after")) \
         + sum(report["fused"][t]["excluded"] for t in ("before", "after"))
     if excluded:

@@ -23,6 +23,10 @@ normalises in the log domain: ProbEn's rule, defined where probEn's `1 - sum(p)`
 --variance_scales 0.5,2 (by position) or thermal_only=0.5,early_fusion=2 (by name) multiplies every detector's box variances by its
 scale ahead of the fusion (either route): the 1 / variance weights of --box_fusion v-avg.  Without the flag a --calibration file
 written by `fit_temperature --with-variance` supplies them, and the run says so; a file without them changes nothing.
+
+--pool_weights 0.6,0.5 (by position) or thermal_only=0.6,early_fusion=0.5 (by name), with --score_fusion probEn-log on either route:
+one exponent per detector inside the fusion (the logarithmic opinion pool, pe_proben_fuse_batch_pooled) for detectors that share
+evidence.  Without the flag a --calibration file that carries "pool_weights" supplies them; 1,1 is the plain product bit for bit.
 """
 import json
 import os
@@ -50,8 +54,9 @@ def main(cmd=None):
     if logp and temps is None:
         temps = {"values": [1.0] * len(names), "fitted": set()}
     vscales = _variance_scales(args, names)
+    pool = _pool_weights(args, names) if logp else None
     if args.one_pass:
-        return one_pass(args, names, world, dev, temps, prior, vscales)
+        return one_pass(args, names, world, dev, temps, prior, vscales, pool)
     files = [os.path.join(args.prediction_path, f"val_{n}_predictions.json") for n in names]
     if comm.is_main_process():
         for i, f in enumerate(files):
@@ -79,8 +84,8 @@ def main(cmd=None):
     res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
                                          det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev),
                                          temperatures=None if temps is None else temps["values"], names=files, class_prior=prior,
-                                         variance_scales=vscales)
-    _name_options(res, names, temps, prior, vscales)
+                                         variance_scales=vscales, pool_weights=pool)
+    _name_options(res, names, temps, prior, vscales, pool)
     if main_rank:
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
@@ -114,6 +119,21 @@ def _variance_scales(args, names):
     return None
 
 
+def _pool_weights(args, names):
+    """--pool_weights, else the calibration file's "pool_weights" (fit_temperature --with-pool-weights), else None; a list."""
+    from .. import calibration
+    if getattr(args, "pool_weights", None) is not None:
+        return calibration.parse_pool_weights(args.pool_weights, names)
+    if args.calibration is not None:
+        table = calibration.load(args.calibration).get("pool_weights")
+        if table is not None:
+            vals = calibration.resolve_pool_weights(table, names, args.calibration)
+            if comm.is_main_process():
+                print(f"pool weights of {args.calibration}:", ", ".join(f"{n}={v:.6g}" for n, v in zip(names, vals)))
+            return vals
+    return None
+
+
 def _class_prior(args):
     """--class_prior, else the calibration file's "class_prior" (fit_temperature --with-prior), else None (uniform); a list."""
     from .. import calibration
@@ -124,7 +144,7 @@ def _class_prior(args):
     return None
 
 
-def _name_options(res, names, temps, prior, vscales):
+def _name_options(res, names, temps, prior, vscales, pool=None):
     """The printed result names the calibration it was made with; a run without any carries none of the keys."""
     if temps is not None:
         res["temperatures"] = dict(zip(names, temps["values"]))
@@ -132,6 +152,8 @@ def _name_options(res, names, temps, prior, vscales):
         res["class_prior"] = prior
     if vscales is not None:
         res["variance_scales"] = dict(zip(names, vscales))
+    if pool is not None:
+        res["pool_weights"] = dict(zip(names, pool))
 
 
 def _warn_fitted(temps, image_ids):
@@ -154,7 +176,7 @@ def _register(args):
     return cfg
 
 
-def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None):
+def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool=None):
     """loader -> FramePairPipeline (one DefaultPredictor model per --detectors entry, cfg as save_predictions.build_cfg) ->
     ProbEn -> evaluation rows on the device (late_fusion.fused_rows_device) -> one all-gather -> FLIREvaluator on rank 0."""
     import argparse
@@ -188,7 +210,8 @@ def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None):
     if temps is not None:
         _warn_fitted(temps, [loader.items[i]["id"] for i in loader.mine])
     pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion,
-                             temperatures=None if temps is None else temps["values"], class_prior=prior, variance_scales=vscales)
+                             temperatures=None if temps is None else temps["values"], class_prior=prior, variance_scales=vscales,
+                             pool_weights=pool)
     j1 = [([], [], []) for _ in names]       # per detector: names, ids, instances
     rows = []
     feeder, feed_key, host = None, None, None
@@ -253,7 +276,7 @@ def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None):
         ev.process_rows(all_rows.numpy())
         res = ev.evaluate()
         res["one_pass"] = stats
-        _name_options(res, names, temps, prior, vscales)
+        _name_options(res, names, temps, prior, vscales, pool)
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
         launch.shutdown()

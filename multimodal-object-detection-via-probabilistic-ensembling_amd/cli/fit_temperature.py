@@ -21,6 +21,15 @@ detections are rows of the fit, so "variance_rows" + "variance_excluded" is the 
 printed one) is over matched rows - a degenerate box, a variance that is not finite and > 0 - and never includes unmatched detections.  Matching at
 IoU >= --iou cuts off the residuals' tails: s is biased low for a detector whose misses are large.  The fit
 takes the vars the file carries: fit and fuse under the same PROBEN.FIX_VARS setting.
+--with-pool-weights (2 or 3 prediction files) also fits one pooling weight per detector for score_fusion "probEn-log" (DESIGN.md
+section 15).  After everything above is fitted, the fitted images are fused once with probEn-log at those temperatures (and prior and
+variance scales, when asked for) at w = 1, with --box_fusion (default v-avg), and every cluster of two or more rows is labelled by
+matching its fused box to the ground truth on the device (--iou; unmatched = background, a class without a column folds to
+background, as above).  The clusters go to the device in CSR form and calibration.fit_pool_weights minimises the NLL of the pooled
+posterior against those labels.  The file gains "pool_weights" {name: w}, "pool_nll" {"before", "after"} (per cluster, at w = 1 and
+at the fit), "pool_clusters" (used), "pool_excluded" (clusters of one row, which the product does not fuse), "pool_at_bound"
+{name: "lo" / "hi" / null} and "pool_fit" (the box fusion, IoU, rounds and whether the gradient criterion was met);
+`demo_probEn --score_fusion probEn-log --calibration FILE` then fuses with the weights.
 """
 import argparse
 import json
@@ -32,7 +41,7 @@ import torch
 
 from .. import calibration
 from ..data import load_coco_json
-from ..late_fusion import read_j1
+from ..late_fusion import fused_clusters, read_j1
 
 
 def detector_name(path):
@@ -54,7 +63,12 @@ def parse(argv):
                    help="also fit one box-variance scale per detector on the fitted images and write the variance_* keys")
     p.add_argument("--bbox_reg_weights", type=str, default="10,10,5,5",
                    help="--with-variance: the box head's BBOX_REG_WEIGHTS 'wx,wy,ww,wh' (the units of the predicted variance)")
+    p.add_argument("--with-pool-weights", action="store_true",
+                   help="also fit one pooling weight per detector for score_fusion probEn-log and write the pool_* keys")
+    p.add_argument("--box_fusion", default="v-avg", help="--with-pool-weights: box fusion of the fused boxes that are labelled")
     args = p.parse_args(argv)
+    if args.with_pool_weights and not 2 <= len(args.predictions) <= 3:
+        p.error(f"--with-pool-weights: --predictions lists {len(args.predictions)} files: late fusion takes 2 or 3")
     if not 0.0 < args.holdout <= 1.0:
         p.error(f"--holdout {args.holdout} is not in (0, 1]")
     try:
@@ -95,6 +109,35 @@ def variance_fit(pred, records, fitted_ids, iou, name, weights, device):
     return calibration.fit_variance_scale(db[hit], match[hit], gb, t(var, torch.float64, (-1,))[hit], weights)
 
 
+def pool_clusters(dets, names, records, ids, iou, box_fusion, device, temperatures=None, class_prior=None, variance_scales=None):
+    """The labelled clusters of the pooling-weight fit (and of calibration_report's fused NLL): dets = the prediction dicts sliced to
+    the images `ids`, in that order.  late_fusion.fused_clusters fuses them once at w = 1; every fused box is matched to the ground
+    truth of its image on the device (pe_match_ground_truth at `iou`): an unmatched cluster is background, and so is a class the
+    head has no column for.  Returns (clusters, labels i32 [C] on the device), or None when no image has two live detectors."""
+    from .calibration_report import ground_truth
+    cl = fused_clusters(dets, box_fusion, device, temperatures, names, class_prior, variance_scales)
+    if cl is None:
+        return None
+    k = cl["log_probs"].shape[1] - 1
+    gt = ground_truth(records, [ids[i] for i in cl["images"]], device)
+    labels, _, _ = calibration.match_rows_device(cl["boxes"], cl["box_offsets"], gt[0], gt[1], gt[2], gt[3], iou, k)
+    return cl, torch.where((labels < 0) | (labels > k), torch.full_like(labels, k), labels)
+
+
+def pool_fit(preds, names, records, fitted, iou, box_fusion, device, temperatures, class_prior, variance_scales):
+    """calibration.fit_pool_weights over the clusters of the fitted images."""
+    from .calibration_report import positions, take_j1
+    from ..fusion import log_class_prior
+    dets = [take_j1(p, positions(p, fitted, n)) for p, n in zip(preds, names)]
+    got = pool_clusters(dets, names, records, fitted, iou, box_fusion, device, temperatures, class_prior, variance_scales)
+    if got is None:
+        raise ValueError(f"no image among the {len(fitted)} fitted ones on which two detectors fired: no cluster to fit pooling weights on")
+    cl, labels = got
+    lp = cl["log_probs"]
+    prior = None if class_prior is None else log_class_prior(class_prior, lp.shape[1], lp.device)
+    return calibration.fit_pool_weights(lp, cl["row_source"], cl["member_rows"], cl["cluster_offsets"], labels, len(preds), prior)
+
+
 def labelled_rows(pred, records, fitted_ids, iou, name):
     """(logits [M, K+1] list, labels [M] list) of the file's detections on the fitted images."""
     calibration.require_logits(pred, name)
@@ -124,13 +167,14 @@ def main(cmd=None):
     fitted = order[:n_fit]
     by_id = {r["image_id"]: r for r in records}
     temps, nll, rows, bound = {}, {}, {}, {}
-    vfit = {}
+    vfit, preds = {}, []
     counts = None
     for path in args.predictions:
         name = detector_name(path)
         if name in temps:
             raise ValueError(f"{path}: a second prediction file for detector {name}")
         pred = read_j1(path)
+        preds.append(pred)
         logits, labels = labelled_rows(pred, by_id, set(fitted), args.iou, path)
         if not logits:
             raise ValueError(f"{path}: no detections on the {n_fit} fitted images: nothing to fit")
@@ -153,12 +197,26 @@ def main(cmd=None):
             print(f"{name}: variance scale = {v['scale']:.6f}  NLL {v['nll_before']:.6f} -> {v['nll_after']:.6f} over {v['rows']} matched rows "
                   f"({v['excluded']} excluded), within 1 / 2 sigma {v['coverage_before'][0]:.4f} / {v['coverage_before'][1]:.4f} -> "
                   f"{v['coverage_after'][0]:.4f} / {v['coverage_after'][1]:.4f} (a Gaussian: 0.6827 / 0.9545)")
+    pool = {}
+    if args.with_pool_weights:
+        names = list(temps)
+        fit = pool_fit(preds, args.predictions, by_id, fitted, args.iou, args.box_fusion, args.device, [temps[n] for n in names],
+                       [c + 1 for c in counts] if args.with_prior else None, [vfit[n]["scale"] for n in names] if args.with_variance else None)
+        n = fit["clusters"]
+        pool = {"pool_weights": dict(zip(names, fit["weights"])), "pool_nll": {"before": fit["nll_at_1"] / n, "after": fit["nll"] / n},
+                "pool_clusters": n, "pool_excluded": fit["excluded"], "pool_at_bound": dict(zip(names, fit["at_bound"])),
+                "pool_fit": {"box_fusion": args.box_fusion, "iou": args.iou, "rounds": fit["rounds"], "converged": fit["converged"]}}
+        held = [f"{m} on the {a} end" for m, a in zip(names, fit["at_bound"]) if a]
+        note = f"  (minimum on the search range's bound: {', '.join(held)}: not a fitted value)" if held else ""
+        print("pool weights:", ", ".join(f"{m} = {w:.6f}" for m, w in zip(names, fit["weights"])),
+              f" NLL per cluster {fit['nll_at_1'] / n:.6f} -> {fit['nll'] / n:.6f} over {n} clusters of >= 2 rows ({fit['excluded']} excluded)"
+              f"{'' if fit['converged'] else '  (the gradient criterion was not met)'}{note}")
     if args.with_prior:
         calibration.save(args.out, temps, nll, rows, class_prior=[c + 1 for c in counts], holdout=args.holdout, fitted_image_ids=fitted,
-                         at_bound=bound, class_prior_counts=counts)
+                         at_bound=bound, class_prior_counts=counts, **pool)
         print("class prior (background last):", ", ".join(f"{c + 1}/{sum(counts) + len(counts)}" for c in counts))
     else:
-        calibration.save(args.out, temps, nll, rows, holdout=args.holdout, fitted_image_ids=fitted, at_bound=bound)
+        calibration.save(args.out, temps, nll, rows, holdout=args.holdout, fitted_image_ids=fitted, at_bound=bound, **pool)
     if args.with_variance:
         calibration.save_variance(args.out, {n: v["scale"] for n, v in vfit.items()},
                                   {n: {"before": v["nll_before"], "after": v["nll_after"]} for n, v in vfit.items()},

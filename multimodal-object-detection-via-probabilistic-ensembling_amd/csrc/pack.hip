@@ -3,6 +3,7 @@
 //   pe_proben_pack_logits         : LOGITS       p = softmax(logits / T_d) in float64 (csrc/softmax_row.h), score = p[class]
 //   pe_proben_pack_log_posteriors : LOGITS_LOGP  the same plus the row's K+1 log-posteriors (the input of pe_proben_fuse_batch_logp)
 //   pe_proben_pack_calibrated     : whichever of the three its arguments select, with out_vars = (double)var * s_d
+//   pe_proben_pack_pooled         : pe_proben_pack_calibrated plus out_source, the detector index of every written row
 // Built with -ffp-contract=off like the other ProbEn code.
 #include "common.h"
 #include "softmax_row.h"
@@ -31,6 +32,7 @@ struct PackRows {
     int32_t* osingle;
     double* olp;               // LOGITS_LOGP: [rows, K+1] log-posteriors
     double s[4];               // read when scaled
+    int32_t* osrc;             // pe_proben_pack_pooled: [rows] detector index of the row; NULL: not written
 };
 
 // One wavefront per image.  The ordered compaction: per detector the first min(counts, D) rows in chunks of 64, a row is kept when
@@ -69,6 +71,7 @@ __global__ __launch_bounds__(64) void proben_pack_kernel(PackRows a) {
                 const double v = (double)a.vars[d][src];
                 a.ov[dst] = a.scaled ? v * a.s[d] : v;      // wave-uniform
                 a.oc[dst] = cls;
+                if (a.osrc) a.osrc[dst] = d;                // wave-uniform
             }
             if (ROUTE != PROBS) {
                 if (G) {
@@ -111,14 +114,14 @@ __global__ __launch_bounds__(64) void proben_pack_kernel(PackRows a) {
 const char* const kRouteName[] = {"pe_proben_pack_detections", "pe_proben_pack_logits", "pe_proben_pack_log_posteriors"};
 
 // All four entry points: every argument check and the launch.  The messages carry the name of the route's own entry point, also
-// when pe_proben_pack_calibrated (the only caller with var_scales_host) selected it.
+// when pe_proben_pack_calibrated or pe_proben_pack_pooled (the only callers with var_scales_host / out_source) selected it.
 int pack_impl(PackRoute route, const float* const* det_boxes_host, const float* const* det_scores_host,
               const int32_t* const* det_classes_host, const float* const* det_probs_host, const float* const* det_logits_host,
               const float* const* det_vars_host, const int32_t* const* det_counts_host, const double* temperatures_host,
               const double* var_scales_host, int32_t num_detectors, int32_t num_images, int32_t det_stride, int32_t num_classes,
               int32_t max_class, int32_t row_stride, double* out_boxes, double* out_scores, double* out_probs, double* out_log_probs,
               double* out_vars, int32_t* out_classes, int32_t* out_offsets, int32_t* out_counts, int32_t* out_single_source,
-              void* stream) {
+              int32_t* out_source, void* stream) {
     const char* what = kRouteName[route];
     const bool probs = route == PROBS;
     PE_CHECK_ARG(num_detectors >= 1 && num_detectors <= 4, "%s: num_detectors %d", what, num_detectors);
@@ -150,10 +153,32 @@ int pack_impl(PackRoute route, const float* const* det_boxes_host, const float* 
     a.nd = num_detectors; a.B = num_images; a.D = det_stride; a.K = num_classes; a.max_class = max_class;
     a.stride = row_stride; a.ob = out_boxes; a.os = out_scores; a.op = out_probs; a.ov = out_vars; a.oc = out_classes;
     a.ooff = out_offsets; a.ocnt = out_counts; a.osingle = out_single_source; a.olp = out_log_probs;
+    a.osrc = out_source;
     void (*kernel)(PackRows) = probs ? proben_pack_kernel<PROBS> : route == LOGITS ? proben_pack_kernel<LOGITS> : proben_pack_kernel<LOGITS_LOGP>;
     hipLaunchKernelGGL(kernel, dim3(num_images), dim3(64), 0, (hipStream_t)stream, a);
     PE_CHECK_LAUNCH(what);
     return PE_OK;
+}
+
+// pe_proben_pack_calibrated / pe_proben_pack_pooled: their own checks - which route the arguments select.  Everything else is the route's.
+int pack_select(const char* what, const float* const* det_boxes_host, const float* const* det_scores_host,
+                const int32_t* const* det_classes_host, const float* const* det_probs_host, const float* const* det_logits_host,
+                const float* const* det_vars_host, const int32_t* const* det_counts_host, const double* temperatures_host,
+                const double* var_scales_host, int32_t num_detectors, int32_t num_images, int32_t det_stride, int32_t num_classes,
+                int32_t max_class, int32_t row_stride, double* out_boxes, double* out_scores, double* out_probs, double* out_log_probs,
+                double* out_vars, int32_t* out_classes, int32_t* out_offsets, int32_t* out_counts, int32_t* out_single_source,
+                int32_t* out_source, void* stream) {
+    if (det_logits_host) {
+        PE_CHECK_ARG(temperatures_host, "%s: null pointer (temperatures: the logits route needs one per detector)", what);
+        PE_CHECK_ARG(!det_scores_host && !det_probs_host, "%s: both probabilities and logits given: one route at a time", what);
+    } else {
+        PE_CHECK_ARG(det_scores_host && det_probs_host, "%s: null pointer (neither probabilities nor logits)", what);
+        PE_CHECK_ARG(!temperatures_host && !out_log_probs, "%s: temperatures / out_log_probs belong to the logits route", what);
+    }
+    return pack_impl(!det_logits_host ? PROBS : out_log_probs ? LOGITS_LOGP : LOGITS, det_boxes_host, det_scores_host, det_classes_host,
+                     det_probs_host, det_logits_host, det_vars_host, det_counts_host, temperatures_host, var_scales_host, num_detectors,
+                     num_images, det_stride, num_classes, max_class, row_stride, out_boxes, out_scores, out_probs, out_log_probs, out_vars,
+                     out_classes, out_offsets, out_counts, out_single_source, out_source, stream);
 }
 
 }  // namespace
@@ -168,7 +193,7 @@ extern "C" int pe_proben_pack_detections(const float* const* det_boxes_host, con
                                          int32_t* out_single_source, void* stream) {
     return pack_impl(PROBS, det_boxes_host, det_scores_host, det_classes_host, det_probs_host, nullptr, det_vars_host, det_counts_host,
                      nullptr, nullptr, num_detectors, num_images, det_stride, num_classes, max_class, row_stride, out_boxes, out_scores,
-                     out_probs, nullptr, out_vars, out_classes, out_offsets, out_counts, out_single_source, stream);
+                     out_probs, nullptr, out_vars, out_classes, out_offsets, out_counts, out_single_source, nullptr, stream);
 }
 
 extern "C" int pe_proben_pack_logits(const float* const* det_boxes_host, const int32_t* const* det_classes_host,
@@ -180,7 +205,7 @@ extern "C" int pe_proben_pack_logits(const float* const* det_boxes_host, const i
                                      int32_t* out_counts, int32_t* out_single_source, void* stream) {
     return pack_impl(LOGITS, det_boxes_host, nullptr, det_classes_host, nullptr, det_logits_host, det_vars_host, det_counts_host,
                      temperatures_host, nullptr, num_detectors, num_images, det_stride, num_classes, max_class, row_stride, out_boxes,
-                     out_scores, out_probs, nullptr, out_vars, out_classes, out_offsets, out_counts, out_single_source, stream);
+                     out_scores, out_probs, nullptr, out_vars, out_classes, out_offsets, out_counts, out_single_source, nullptr, stream);
 }
 
 extern "C" int pe_proben_pack_log_posteriors(const float* const* det_boxes_host, const int32_t* const* det_classes_host,
@@ -192,7 +217,7 @@ extern "C" int pe_proben_pack_log_posteriors(const float* const* det_boxes_host,
                                              int32_t* out_offsets, int32_t* out_counts, int32_t* out_single_source, void* stream) {
     return pack_impl(LOGITS_LOGP, det_boxes_host, nullptr, det_classes_host, nullptr, det_logits_host, det_vars_host, det_counts_host,
                      temperatures_host, nullptr, num_detectors, num_images, det_stride, num_classes, max_class, row_stride, out_boxes,
-                     out_scores, out_probs, out_log_probs, out_vars, out_classes, out_offsets, out_counts, out_single_source, stream);
+                     out_scores, out_probs, out_log_probs, out_vars, out_classes, out_offsets, out_counts, out_single_source, nullptr, stream);
 }
 
 extern "C" int pe_proben_pack_calibrated(const float* const* det_boxes_host, const float* const* det_scores_host,
@@ -204,17 +229,24 @@ extern "C" int pe_proben_pack_calibrated(const float* const* det_boxes_host, con
                                          double* out_boxes, double* out_scores, double* out_probs, double* out_log_probs,
                                          double* out_vars, int32_t* out_classes, int32_t* out_offsets, int32_t* out_counts,
                                          int32_t* out_single_source, void* stream) {
-    // its own checks: which route the arguments select.  Everything else is the route's.
-    const char* what = "pe_proben_pack_calibrated";
-    if (det_logits_host) {
-        PE_CHECK_ARG(temperatures_host, "%s: null pointer (temperatures: the logits route needs one per detector)", what);
-        PE_CHECK_ARG(!det_scores_host && !det_probs_host, "%s: both probabilities and logits given: one route at a time", what);
-    } else {
-        PE_CHECK_ARG(det_scores_host && det_probs_host, "%s: null pointer (neither probabilities nor logits)", what);
-        PE_CHECK_ARG(!temperatures_host && !out_log_probs, "%s: temperatures / out_log_probs belong to the logits route", what);
-    }
-    return pack_impl(!det_logits_host ? PROBS : out_log_probs ? LOGITS_LOGP : LOGITS, det_boxes_host, det_scores_host, det_classes_host,
-                     det_probs_host, det_logits_host, det_vars_host, det_counts_host, temperatures_host, var_scales_host, num_detectors,
-                     num_images, det_stride, num_classes, max_class, row_stride, out_boxes, out_scores, out_probs, out_log_probs, out_vars,
-                     out_classes, out_offsets, out_counts, out_single_source, stream);
+    return pack_select("pe_proben_pack_calibrated", det_boxes_host, det_scores_host, det_classes_host, det_probs_host, det_logits_host,
+                       det_vars_host, det_counts_host, temperatures_host, var_scales_host, num_detectors, num_images, det_stride,
+                       num_classes, max_class, row_stride, out_boxes, out_scores, out_probs, out_log_probs, out_vars, out_classes,
+                       out_offsets, out_counts, out_single_source, nullptr, stream);
+}
+
+extern "C" int pe_proben_pack_pooled(const float* const* det_boxes_host, const float* const* det_scores_host,
+                                     const int32_t* const* det_classes_host, const float* const* det_probs_host,
+                                     const float* const* det_logits_host, const float* const* det_vars_host,
+                                     const int32_t* const* det_counts_host, const double* temperatures_host,
+                                     const double* var_scales_host, int32_t num_detectors, int32_t num_images, int32_t det_stride,
+                                     int32_t num_classes, int32_t max_class, int32_t row_stride, double* out_boxes,
+                                     double* out_scores, double* out_probs, double* out_log_probs, double* out_vars,
+                                     int32_t* out_classes, int32_t* out_offsets, int32_t* out_counts, int32_t* out_single_source,
+                                     int32_t* out_source, void* stream) {
+    PE_CHECK_ARG(out_source, "pe_proben_pack_pooled: null output (out_source)");
+    return pack_select("pe_proben_pack_pooled", det_boxes_host, det_scores_host, det_classes_host, det_probs_host, det_logits_host,
+                       det_vars_host, det_counts_host, temperatures_host, var_scales_host, num_detectors, num_images, det_stride,
+                       num_classes, max_class, row_stride, out_boxes, out_scores, out_probs, out_log_probs, out_vars, out_classes,
+                       out_offsets, out_counts, out_single_source, out_source, stream);
 }

@@ -32,6 +32,10 @@ struct ProbenArgs {
     int32_t* out_keep;
     int32_t* out_counts;
     const double* log_prior;   // LOGP only: optional [K+1] log class prior (NULL = uniform)
+    const int32_t* row_source;    // POOL only: [Ntot] detector index of each row
+    const double* pool_weights;   // POOL only: [num_detectors] fusion exponents
+    int32_t num_detectors;        // POOL only
+    int32_t* out_cluster;         // POOL only, optional: [Ntot] output row of the cluster each input row ended in
 };
 
 // Sort rule shared with oracle/proben.py: NaN first, score descending, ties by ORIGINAL index
@@ -56,6 +60,11 @@ __device__ __forceinline__ bool precedes(double sa, int ia, double sb, int ib) {
 // LOGP (pe_proben_fuse_batch_logp, PE_SCORE_PROBEN_LOGP): a.probs holds the rows' K+1 LOG-posteriors, background column included.  Phase 2
 // copies them into glog instead of taking logs of p and of 1 - sum(p), phase 4 normalises the cluster's summed columns with a
 // max-subtracted log-sum-exp.  A template parameter, not a run-time branch: the four other score modes compile to what they were.
+// POOL (pe_proben_fuse_batch_pooled, LOGP only): the logarithmic opinion pool.  Phase 2 stages the weight of the row's detector in gw
+// beside glog (a source outside [0, num_detectors) stages NaN), phase 4 multiplies each member's log-posterior by it before the same
+// sequential sum and takes the prior (W - 1) times, W the sequential sum of the members' weights.  1.0 * x is x and W is then the
+// integer m, so weights of 1.0 give the LOGP bits.  out_cluster goes through LDS (the clustering's dead geometry array gx1) so that
+// every input row is written once, by the thread that owns it.
 constexpr int kFuseThreads = 1024;
 
 __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int l) {
@@ -63,7 +72,7 @@ __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, i
     return ((unsigned long long)hi << 32) | lo;
 }
 
-template <bool BITS, bool LOGP>
+template <bool BITS, bool LOGP, bool POOL>
 __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int ncl_s;
@@ -82,6 +91,7 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
             a.out_scores[o] = (float)a.scores[o];
             a.out_classes[o] = (float)a.classes[o];
             a.out_keep[o] = r;
+            if (POOL && a.out_cluster) a.out_cluster[o] = r;
         }
         if (tid == 0) a.out_counts[img] = n;
         return;
@@ -103,7 +113,8 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
     double* glog = gsc + R;  // [L][R]
     double* gob = glog + (size_t)L * R;                       // [4][R] original coordinates
     double* ginv = gob + 4 * (size_t)R;                       // 1 / variance (v-avg only)
-    int* ord = reinterpret_cast<int*>(ginv + R);              // sorted position -> original row
+    double* gw = ginv + R;                                    // POOL: the pool weight of the row's detector
+    int* ord = reinterpret_cast<int*>(gw + (POOL ? R : 0));   // sorted position -> original row
     int* gcls = ord + R;                                      // class id
     unsigned short* members = reinterpret_cast<unsigned short*>(gcls + R);   // all clusters' matches, back to back
     unsigned short* cl_piv = members + R;      // per cluster: pivot position, first member, number of matches
@@ -136,6 +147,10 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
         gob[p] = b[0]; gob[R + p] = b[1]; gob[2 * (size_t)R + p] = b[2]; gob[3 * (size_t)R + p] = b[3];
         gcls[p] = a.classes[beg + r];
         if (a.box_mode == PE_BOX_VAVG) ginv[p] = 1.0 / a.vars[beg + r];
+        if (POOL) {
+            const int src = a.row_source[beg + r];
+            gw[p] = (src >= 0 && src < a.num_detectors) ? a.pool_weights[src] : __builtin_nan("");
+        }
         if (LOGP) {
             const double* lp = a.probs + (size_t)(beg + r) * (K + 1);
             for (int j = 0; j <= K; ++j) glog[(size_t)j * R + p] = lp[j];
@@ -243,6 +258,11 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
     }
     __syncthreads();
     const int ncl = ncl_s;
+    int* rcl = reinterpret_cast<int*>(gx1);      // POOL + out_cluster: sorted position -> output row of its cluster (gx1 is dead now)
+    if (POOL && a.out_cluster) {                 // block-uniform
+        for (int p = tid; p < n; p += kFuseThreads) rcl[p] = -1;
+        __syncthreads();
+    }
     // ---- 4. fusion: one lane per cluster (cluster = matches in sorted order + the pivot LAST), output row = cluster index.
     // The per-cluster arithmetic is the sequence the reference runs per pivot (sums over the members in cluster order, the
     // normaliser summed over the columns in column order, first-maximum / first-NaN rules); it used to sit inside the pivot loop
@@ -257,6 +277,10 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
         }
         const int m = cnt + 1;
         const int piv_row = ord[pos];
+        if (POOL && a.out_cluster) {
+            for (int t = 0; t < cnt; ++t) rcl[mem[t]] = k;
+            rcl[pos] = k;
+        }
         auto at = [&](int t) { return t < cnt ? (int)mem[t] : pos; };
         auto coord = [&](int c4, int p) { return gob[(size_t)c4 * R + p]; };
         double out_score = gsc[pos];
@@ -270,11 +294,14 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
                 // a_j = sum over the members (cluster order) of log p_j, less (m - 1) log prior_j; s = softmax(a) with the maximum
                 // subtracted first, so the largest term is exp(0) and nothing under- or overflows before the division.  np.max /
                 // np.argmax over the K+1 entries INCLUDING background, NaN wins, first index - the rule of PE_SCORE_PROBEN below.
+                // POOL: a_j = sum of w log p_j, less (W - 1) log prior_j, W = the members' weights summed in the same order
+                double wsum = 0.0;
+                if (POOL) for (int t = 0; t < m; ++t) wsum += gw[at(t)];
                 auto column = [&](int j) {
                     double acc = 0.0;
                     const double* col = glog + (size_t)j * R;
-                    for (int t = 0; t < m; ++t) acc += col[at(t)];
-                    if (a.log_prior) acc -= (double)(m - 1) * a.log_prior[j];
+                    for (int t = 0; t < m; ++t) acc += POOL ? gw[at(t)] * col[at(t)] : col[at(t)];
+                    if (a.log_prior) acc -= (POOL ? wsum - 1.0 : (double)(m - 1)) * a.log_prior[j];
                     return acc;
                 };
                 double top = column(0);
@@ -370,16 +397,24 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
         a.out_keep[o] = piv_row;
         for (int c4 = 0; c4 < 4; ++c4) a.out_boxes[o * 4 + c4] = out_coord[c4];
     }
+    if (POOL && a.out_cluster) {
+        __syncthreads();
+        for (int p = tid; p < n; p += kFuseThreads) a.out_cluster[beg + ord[p]] = rcl[p];
+    }
     if (tid == 0) a.out_counts[img] = ncl;
 }
 
 // pe_proben_fuse_batch / pe_proben_fuse_batch_logp: the argument checks, LDS sizing, clustering form, launch.  logp: a.probs holds the
-// K+1 log-posteriors (required), a.score_mode is PE_SCORE_PROBEN_LOGP and is not the caller's to choose.
-int fuse_impl(const char* what, bool logp, ProbenArgs a, int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, void* stream) {
+// K+1 log-posteriors (required), a.score_mode is PE_SCORE_PROBEN_LOGP and is not the caller's to choose.  pool (implies logp):
+// pe_proben_fuse_batch_pooled, a.row_source / a.pool_weights required, 8 more bytes of LDS per row for the staged weight.
+int fuse_impl(const char* what, bool logp, bool pool, ProbenArgs a, int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, void* stream) {
     PE_CHECK_ARG(num_images >= 0, "%s: num_images < 0", what);
     if (num_images == 0) return PE_OK;
     PE_CHECK_ARG(a.boxes && a.scores && (a.probs || !logp) && a.vars && a.classes && a.offsets, "%s: null input pointer", what);
     PE_CHECK_ARG(a.out_boxes && a.out_scores && a.out_classes && a.out_keep && a.out_counts, "%s: null output pointer", what);
+    PE_CHECK_ARG(!pool || (a.row_source && a.pool_weights), "%s: null input pointer (row_source / pool_weights)", what);
+    PE_CHECK_ARG(!pool || (a.num_detectors >= 1 && a.num_detectors <= PE_POOL_MAX_DETECTORS), "%s: num_detectors %d not in [1,%d]", what,
+                 a.num_detectors, PE_POOL_MAX_DETECTORS);
     PE_CHECK_ARG(logp || (a.score_mode >= 0 && a.score_mode <= 3), "%s: bad score_mode %d", what, a.score_mode);
     PE_CHECK_ARG(a.box_mode >= 0 && a.box_mode <= 3, "%s: bad box_mode %d", what, a.box_mode);
     // K <= 62: a wavefront keeps a cluster's per-class log-odds in lanes (K + background in 64 lanes).  Enough for every fusion the
@@ -391,22 +426,25 @@ int fuse_impl(const char* what, bool logp, ProbenArgs a, int32_t num_images, int
                  max_rows_per_image);
     const int R = (max_rows_per_image + 1) & ~1;  // keep the int/short/byte carves 8-byte aligned
     const int L = (logp || a.score_mode == PE_SCORE_PROBEN) ? num_classes + 1 : (a.score_mode == PE_SCORE_PROBEN_BINARY ? 2 : 0);
-    const size_t lds_seq = (size_t)R * (8 * (6 + L + 5) + 4 + 4 + 4 * 2 + 1) + 16;
+    const size_t per_row = 8 * (6 + L + 5 + (pool ? 1 : 0)) + 4 + 4 + 4 * 2 + 1;
+    const size_t lds_seq = (size_t)R * per_row + 16;
     const size_t lds_bits = lds_seq + (size_t)R * ((R + 63) / 64) * 16;        // + the two bit matrices
     constexpr size_t kStatic = 512;                                            // the kernels' static __shared__ scratch (ncl_s, reductions)
     const bool bits = lds_bits + kStatic <= 160 * 1024;
     const size_t lds = bits ? lds_bits : lds_seq;
     if (lds + kStatic > 160 * 1024) {
-        // a whole image's rows live in LDS (boxes, 1 / variance, class ids, log-odds, cluster tables: 8 (11 + L) + 17 bytes per row);
+        // a whole image's rows live in LDS (boxes, 1 / variance, class ids, log-odds, cluster tables: 8 (11 + L) + 17 bytes per row,
+        // 8 more for the pooled form's weight);
         // capacity at K = 3: 1 195 rows per image (probEn), 1 400 (other score modes) - a detector contributes at most 100
         pe::set_error("%s: %zu bytes of LDS needed (> 160 KiB): max_rows_per_image %d is above the per-image capacity of %zu rows "
                       "for this score mode / class count", what, lds + kStatic, max_rows_per_image,
-                      (size_t)(160 * 1024 - kStatic - 16) / (size_t)(8 * (6 + L + 5) + 4 + 4 + 4 * 2 + 1));
+                      (size_t)(160 * 1024 - kStatic - 16) / per_row);
         return PE_ERR_UNSUPPORTED;
     }
     a.max_rows = R;
-    void (*kernel)(ProbenArgs) = logp ? (bits ? proben_fuse_kernel<true, true> : proben_fuse_kernel<false, true>)
-                                      : (bits ? proben_fuse_kernel<true, false> : proben_fuse_kernel<false, false>);
+    void (*kernel)(ProbenArgs) = pool ? (bits ? proben_fuse_kernel<true, true, true> : proben_fuse_kernel<false, true, true>)
+                                 : logp ? (bits ? proben_fuse_kernel<true, true, false> : proben_fuse_kernel<false, true, false>)
+                                        : (bits ? proben_fuse_kernel<true, false, false> : proben_fuse_kernel<false, false, false>);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
@@ -429,8 +467,8 @@ extern "C" int pe_proben_fuse_batch(const double* boxes, const double* scores, c
                                     int32_t* out_keep, int32_t* out_counts, void* stream) {
     ProbenArgs a{boxes, scores, probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
                  score_mode, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, nullptr};
-    return fuse_impl("pe_proben_fuse_batch", false, a, num_images, num_classes, max_rows_per_image, stream);
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, nullptr, nullptr, nullptr, 0, nullptr};
+    return fuse_impl("pe_proben_fuse_batch", false, false, a, num_images, num_classes, max_rows_per_image, stream);
 }
 
 extern "C" int pe_proben_fuse_batch_logp(const double* boxes, const double* scores, const double* log_probs,
@@ -441,6 +479,20 @@ extern "C" int pe_proben_fuse_batch_logp(const double* boxes, const double* scor
                                          float* out_scores, float* out_classes, int32_t* out_keep, int32_t* out_counts, void* stream) {
     ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
                  PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior};
-    return fuse_impl("pe_proben_fuse_batch_logp", true, a, num_images, num_classes, max_rows_per_image, stream);
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, nullptr, nullptr, 0, nullptr};
+    return fuse_impl("pe_proben_fuse_batch_logp", true, false, a, num_images, num_classes, max_rows_per_image, stream);
+}
+
+extern "C" int pe_proben_fuse_batch_pooled(const double* boxes, const double* scores, const double* log_probs,
+                                           const double* variances, const int32_t* classes, const int32_t* row_source,
+                                           const int32_t* offsets, const int32_t* row_counts, const int32_t* passthrough,
+                                           int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, int32_t box_mode,
+                                           double iou_thresh, double frame_w, double frame_h, const double* log_prior,
+                                           const double* pool_weights, int32_t num_detectors, double* out_boxes, float* out_scores,
+                                           float* out_classes, int32_t* out_keep, int32_t* out_counts, int32_t* out_cluster,
+                                           void* stream) {
+    ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
+                 PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, row_source, pool_weights, num_detectors, out_cluster};
+    return fuse_impl("pe_proben_fuse_batch_pooled", true, true, a, num_images, num_classes, max_rows_per_image, stream);
 }

@@ -9,6 +9,8 @@ The arithmetic lives in csrc/proben.hip behind pe_proben_fuse_batch.
 score_fusion "probEn-log" (not in the reference) is ProbEn on the detectors' log-posteriors, log_softmax(class_logits / T) over all
 K + 1 columns with the background column kept, normalised by a max-subtracted log-sum-exp (pe_proben_fuse_batch_logp): the same Bayes
 rule, defined on saturated rows and large clusters where "probEn" gives NaN, with an optional class prior (`class_prior`).
+`pool_weights` (one exponent w_d >= 0 per detector, "probEn-log" only) turns its product into the logarithmic opinion pool
+a_j = sum_t w_d(t) log p_t[j] - (W - 1) log prior_j (pe_proben_fuse_batch_pooled); every weight 1 is "probEn-log" bit for bit.
 """
 import numpy as np
 import torch
@@ -35,9 +37,26 @@ def log_class_prior(class_prior, num_columns, device):
     return torch.from_numpy(np.log(check_class_prior(class_prior, num_columns))).to(device)
 
 
-def _check_mode(score_fusion, class_prior, who):
+def pool_weight_tensor(pool_weights, num_detectors, device):
+    """pool_weights (one exponent per detector; calibration.check_pool_weights validates: finite, >= 0, not all 0) -> the DEVICE f64
+    [num_detectors] tensor pe_proben_fuse_batch_pooled takes.  None -> None.  A CUDA tensor is taken as the result of an earlier call
+    (FramePairPipeline uploads once, not per batch)."""
+    if pool_weights is None:
+        return None
+    if isinstance(pool_weights, torch.Tensor) and pool_weights.is_cuda:
+        if pool_weights.dtype != torch.float64 or tuple(pool_weights.shape) != (num_detectors,):
+            raise ValueError(f"pool-weight tensor {tuple(pool_weights.shape)} {pool_weights.dtype} is not float64 [{num_detectors}]")
+        return pool_weights.contiguous()
+    from .calibration import check_pool_weights
+    return torch.tensor(check_pool_weights(pool_weights, num_detectors, "pool_weights"), dtype=torch.float64).to(device)
+
+
+def _check_mode(score_fusion, class_prior, who, pool_weights=None):
     if score_fusion not in SCORE_MODES:
         raise ValueError(f"{who}: unknown score_fusion {score_fusion!r} (one of {', '.join(SCORE_MODES)})")
+    if pool_weights is not None and score_fusion != LOGP:
+        raise ValueError(f"{who}: pool_weights belong to score_fusion '{LOGP}' (got {score_fusion!r}): the other score fusions "
+                         "have no pooled form")
     if class_prior is not None and score_fusion != LOGP:
         raise ValueError(f"{who}: class_prior belongs to score_fusion '{LOGP}' (got {score_fusion!r}): the other score fusions "
                          "have no prior term")
@@ -45,11 +64,14 @@ def _check_mode(score_fusion, class_prior, who):
 
 def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="probEn", box_fusion="v-avg",
                max_rows=None, iou_thresh=0.5, frame=(FRAME_W, FRAME_H), row_counts=None, passthrough=None, log_probs=None,
-               class_prior=None):
+               class_prior=None, pool_weights=None, row_source=None):
     """Fuse B images in one launch.
 
     score_fusion "probEn-log": log_probs f64 [Ntot,K+1] (calibration.log_posteriors / pack_rows(log_posteriors=True)) replaces
     probs (ignored, may be None); class_prior: K + 1 probabilities, background last, or None = uniform.
+    pool_weights ("probEn-log" only; one w_d per detector or pool_weight_tensor's device tensor) with row_source i32 [Ntot] (each
+    row's detector index): pe_proben_fuse_batch_pooled; the result then also holds "cluster" i32 [Ntot], the output row of the
+    cluster each input row ended in (-1: it left the pool without one; -2 where nothing was written: counts == -1, padding).
 
     boxes f64 [Ntot,4], scores f64 [Ntot], probs f64 [Ntot,K], variances f64 [Ntot],
     classes i32 [Ntot], offsets i32 [B+1] - all CUDA tensors, rows of each image already
@@ -57,14 +79,18 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
       boxes f64 [Ntot,4], scores f32 [Ntot], classes f32 [Ntot], keep i32 [Ntot], counts i32 [B];
     image b's fused rows are [offsets[b], offsets[b]+counts[b]).
     """
-    _check_mode(score_fusion, class_prior, "fuse_batch")
+    _check_mode(score_fusion, class_prior, "fuse_batch", pool_weights)
     logp = score_fusion == LOGP
+    pool = pool_weights is not None
+    if pool and (row_source is None or row_source.dim() != 1 or row_source.shape[0] != boxes.shape[0]):
+        raise ValueError(f"fuse_batch: pool_weights need row_source [Ntot] for the {boxes.shape[0]} rows, got "
+                         f"{None if row_source is None else tuple(row_source.shape)}")
     if logp:
         if log_probs is None or log_probs.dim() != 2 or log_probs.shape[1] < 2 or log_probs.shape[0] != boxes.shape[0]:
             raise ValueError(f"fuse_batch: score_fusion '{LOGP}' needs log_probs [Ntot, K+1] for the {boxes.shape[0]} rows, got "
                              f"{None if log_probs is None else tuple(log_probs.shape)}")
         probs = log_probs
-    _lib.require_cuda(boxes, scores, probs, variances, classes, offsets)
+    _lib.require_cuda(boxes, scores, probs, variances, classes, offsets, row_source if pool else None)
     if score_fusion == "max" and box_fusion == "argmax":
         raise ValueError("('max','argmax') is the class-aware NMS route: use fusion()/nms_fuse_batch")
     B = offsets.numel() - (0 if row_counts is not None else 1)
@@ -83,6 +109,9 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
         max_rows = int((offsets[1:] - offsets[:-1]).max().item()) if B > 0 else 1
     max_rows = max(int(max_rows), 1)
     dev = boxes.device
+    if pool:
+        weights = pool_weight_tensor(pool_weights, len(pool_weights), dev)
+        row_source = row_source.contiguous().to(torch.int32)
     out = {
         "boxes": torch.empty((ntot, 4), dtype=torch.float64, device=dev),
         "scores": torch.empty((ntot,), dtype=torch.float32, device=dev),
@@ -90,23 +119,28 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
         "keep": torch.empty((ntot,), dtype=torch.int32, device=dev),
         "counts": torch.zeros((max(B, 1),), dtype=torch.int32, device=dev)[:B],
     }
-    name = "pe_proben_fuse_batch_logp" if logp else "pe_proben_fuse_batch"
-    head = (_lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(probs), _lib.ptr(variances), _lib.ptr(classes), _lib.ptr(offsets),
-            _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows)
+    name = "pe_proben_fuse_batch_pooled" if pool else "pe_proben_fuse_batch_logp" if logp else "pe_proben_fuse_batch"
+    head = (_lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(probs), _lib.ptr(variances), _lib.ptr(classes),
+            *([_lib.ptr(row_source)] if pool else []), _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows)
     geometry = (BOX_MODES[box_fusion], float(iou_thresh), float(frame[0]), float(frame[1]))
     mode = geometry + (_lib.ptr(log_prior),) if logp else (SCORE_MODES[score_fusion],) + geometry
+    tail = ()
+    if pool:
+        mode += (_lib.ptr(weights), int(weights.numel()))
+        out["cluster"] = torch.full((ntot,), -2, dtype=torch.int32, device=dev)     # -2: never written (padding, counts == -1)
+        tail = (_lib.ptr(out["cluster"]),)
     st = getattr(_lib.lib(), name)(*head, *mode, _lib.ptr(out["boxes"]), _lib.ptr(out["scores"]), _lib.ptr(out["classes"]),
-                                   _lib.ptr(out["keep"]), _lib.ptr(out["counts"]), _lib.stream())
+                                   _lib.ptr(out["keep"]), _lib.ptr(out["counts"]), *tail, _lib.stream())
     _lib.check(st, name)
     return out
 
 
-def pack_infos(per_image_infos, device="cuda", with_log_probs=False):
+def pack_infos(per_image_infos, device="cuda", with_log_probs=False, with_sources=False):
     """per_image_infos: list (images) of lists (detectors) of reference-style dicts
     {bbox, score, class, prob, vars}.  Returns the flat device tensors + offsets (with_log_probs: + the rows' "log_prob"
-    [n][K+1] as a seventh tensor)."""
+    [n][K+1] as a seventh tensor; with_sources: + each row's position in its image's detector list, i32, as the last)."""
     bb, ss, cc, pp, vv, offs = [], [], [], [], [], [0]
-    ll = []
+    ll, src = [], []
     K = None
     for infos in per_image_infos:
         for d in infos:
@@ -118,7 +152,7 @@ def pack_infos(per_image_infos, device="cuda", with_log_probs=False):
     K = K or 3
     for infos in per_image_infos:
         n = 0
-        for d in infos:
+        for k, d in enumerate(infos):
             if not d or len(d["bbox"]) == 0:
                 continue
             bb.append(np.asarray(d["bbox"], dtype=np.float64).reshape(-1, 4))
@@ -128,6 +162,7 @@ def pack_infos(per_image_infos, device="cuda", with_log_probs=False):
             vv.append(np.asarray(d["vars"], dtype=np.float64).reshape(-1))
             if with_log_probs:
                 ll.append(np.asarray(d["log_prob"], dtype=np.float64).reshape(-1, K + 1))
+            src.append(np.full(len(ss[-1]), k, dtype=np.int32))
             n += len(ss[-1])
         offs.append(offs[-1] + n)
 
@@ -137,10 +172,11 @@ def pack_infos(per_image_infos, device="cuda", with_log_probs=False):
     out = (cat(bb, (0, 4), np.float64), cat(ss, (0,), np.float64), cat(pp, (0, K), np.float64),
            cat(vv, (0,), np.float64), cat(cc, (0,), np.int32),
            torch.tensor(offs, dtype=torch.int32, device=device))
-    return out + (cat(ll, (0, K + 1), np.float64),) if with_log_probs else out
+    out = out + (cat(ll, (0, K + 1), np.float64),) if with_log_probs else out
+    return out + (cat(src, (0,), np.int32),) if with_sources else out
 
 
-def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=None, variance_scales=None):
+def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=None, variance_scales=None, pool_weights=None):
     """Drop-in for the reference's ``fusion`` (demo_probEn.py:189-196).
 
     Returns (out_boxes, out_scores, out_class): boxes as a list of float64 ndarrays [4]
@@ -151,9 +187,14 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=Non
     method[0] "probEn-log": the rows' log-posteriors come from their class_logits too (temperatures None = 1 for every info) and
     are fused by pe_proben_fuse_batch_logp, with class_prior (K + 1 probabilities, background last) when given.
     variance_scales (one s per info): the rows' vars are multiplied by s in float64 (one multiply, as pe_proben_pack_calibrated does
-    on the device route); only box rule "v-avg" reads them."""
+    on the device route); only box rule "v-avg" reads them.
+    pool_weights (one w per info, method[0] "probEn-log" only): the pooled rule of pe_proben_fuse_batch_pooled; a row's detector is
+    its info's position."""
     infos = [info_1, info_2] + ([info_3] if info_3 else [])
-    _check_mode(method[0], class_prior, "fusion")
+    _check_mode(method[0], class_prior, "fusion", pool_weights)
+    if pool_weights is not None:
+        from .calibration import check_pool_weights
+        pool_weights = check_pool_weights(pool_weights, len(infos), "fusion")
     if variance_scales is not None:
         from .calibration import check_variance_scales
         variance_scales = check_variance_scales(variance_scales, len(infos), "fusion")
@@ -183,7 +224,11 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=Non
         classes = torch.tensor(sum([list(d["class"]) for d in infos], []), dtype=torch.float32)
         keep = batched_nms(boxes.cuda(), scores.cuda(), classes.cuda(), 0.5).cpu()
         return boxes[keep], scores[keep], classes[keep]
-    if logp:
+    if logp and pool_weights is not None:
+        b, s, p, v, c, offs, lp, src = pack_infos([infos], with_log_probs=True, with_sources=True)
+        out = fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior, pool_weights=pool_weights,
+                         row_source=src)
+    elif logp:
         b, s, p, v, c, offs, lp = pack_infos([infos], with_log_probs=True)
         out = fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior)
     else:
@@ -196,16 +241,23 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=Non
     return [boxes[i] for i in range(m)], out["scores"][:m].cpu(), out["classes"][:m].cpu()
 
 
-def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, variance_scales=None):
+def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, variance_scales=None, pool_weights=None):
     """The detectors' padded outputs -> ProbEn input rows on the device (pe_proben_pack_detections; with temperatures
     pe_proben_pack_logits: probabilities and scores from class_logits as softmax(logits / T_d) in float64).
     Returns (boxes f64 [B*S,4], scores f64, probs f64 [B*S,K], vars f64, classes i32, offsets i32 [B], counts i32 [B],
     single-source flags i32 [B]), S = len(dets) * D.  log_posteriors (needs temperatures): pe_proben_pack_log_posteriors, the
     same eight plus the rows' log-posteriors f64 [B*S,K+1] as a ninth.
     variance_scales (one s per detector): pe_proben_pack_calibrated, whichever of the three routes the other arguments select, with
-    vars = (double)var * s_d; None calls the three entry points above as before."""
+    vars = (double)var * s_d; None calls the three entry points above as before.
+    pool_weights (one w per detector; only their presence and count matter here): pe_proben_pack_pooled, the same route with each
+    written row's detector index i32 [B*S] appended as the LAST element of the result."""
     import ctypes
     nd = len(dets)
+    if pool_weights is not None and not (isinstance(pool_weights, torch.Tensor) and pool_weights.is_cuda):
+        from .calibration import check_pool_weights
+        check_pool_weights(pool_weights, nd, "pack_rows")
+    elif pool_weights is not None and pool_weights.numel() != nd:
+        raise ValueError(f"pack_rows: {pool_weights.numel()} pool weights for {nd} detectors")
     if variance_scales is not None:
         from .calibration import check_variance_scales
         variance_scales = check_variance_scales(variance_scales, nd, "pack_rows")
@@ -238,10 +290,12 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, varian
     scores, probs, lg = (None, None, arr("class_logits")) if logits else (arr("scores"), arr("prob_score"), None)
     dims = (nd, B, D, K, max_class, S)
     head, tail = [_lib.ptr(t) for t in (ob, os_, op)], [_lib.ptr(t) for t in (ov, oc, ooff, ocnt, osingle)]
-    if variance_scales is not None:
-        name = "pe_proben_pack_calibrated"
+    osrc = torch.empty((B * S,), dtype=torch.int32, device=dev) if pool_weights is not None else None
+    if variance_scales is not None or osrc is not None:
+        name = "pe_proben_pack_pooled" if osrc is not None else "pe_proben_pack_calibrated"
         args = (arr("boxes"), scores, arr("classes"), probs, lg, arr("vars"), arr("counts"), temps,
-                (ctypes.c_double * nd)(*variance_scales), *dims, *head, _lib.ptr(olp), *tail)
+                (ctypes.c_double * nd)(*variance_scales) if variance_scales is not None else None, *dims, *head, _lib.ptr(olp), *tail,
+                *([_lib.ptr(osrc)] if osrc is not None else []))
     elif not logits:
         name = "pe_proben_pack_detections"
         args = (arr("boxes"), scores, arr("classes"), probs, arr("vars"), arr("counts"), *dims, *head, *tail)
@@ -251,11 +305,11 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, varian
                 *([_lib.ptr(olp)] if log_posteriors else []), *tail)
     st = getattr(_lib.lib(), name)(*args, _lib.stream())
     _lib.check(st, name)
-    return (ob, os_, op, ov, oc, ooff, ocnt, osingle) + ((olp,) if log_posteriors else ())
+    return (ob, os_, op, ov, oc, ooff, ocnt, osingle) + ((olp,) if log_posteriors else ()) + ((osrc,) if osrc is not None else ())
 
 
 def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=0.5, temperatures=None,
-                    class_prior=None, variance_scales=None):
+                    class_prior=None, variance_scales=None, pool_weights=None):
     """Device-to-device stage fusion: `dets` = the result dicts of 2 or 3 detectors run on the SAME batch
     (rcnn.GeneralizedRCNN.forward_batch).  Packs their detections into ProbEn rows (classes <= max_class,
     like the JSON writer demo_FLIR_save_predictions.py:148-155), applies the reference's per-image case
@@ -266,11 +320,13 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     class_prior: K + 1 probabilities, background last, or the device tensor of log_class_prior).
     variance_scales (one s per detector): the rows' variances are (double)var * s_d (pe_proben_pack_calibrated); they weight the
     member boxes of box_fusion "v-avg" and nothing else, so every other box rule and the NMS route give the bits they gave.
+    pool_weights (one w per detector or pool_weight_tensor's device tensor, "probEn-log" only): pe_proben_pack_pooled +
+    pe_proben_fuse_batch_pooled; the result then also holds "cluster" and "row_source".
     No host synchronisation.  Returns a dict: boxes f64 [B*S,4], scores f32, classes f32, counts i32 [B],
     offsets i32 [B], stride S = len(dets) * D."""
     # the box heads' candidate-cap bookkeeping travels with the result (no kernel here): check_candidate_overflow() looks
     # at it at the consumer's first host synchronisation
-    _check_mode(score_fusion, class_prior, "fuse_detections")
+    _check_mode(score_fusion, class_prior, "fuse_detections", pool_weights)
     overflow_src = [(d["cand_total"], d["cand_max"]) for d in dets if "cand_total" in d]
     B, D = dets[0]["scores"].shape
     S = len(dets) * D
@@ -279,7 +335,8 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     if logp and temperatures is None:
         temperatures = [1.0] * len(dets)
     ob, os_, op, ov, oc, ooff, ocnt, osingle, *olp = pack_rows(dets, max_class, temperatures, log_posteriors=logp,
-                                                               variance_scales=variance_scales)
+                                                               variance_scales=variance_scales, pool_weights=pool_weights)
+    osrc = olp.pop() if pool_weights is not None else None
     if score_fusion == "max" and box_fusion == "argmax":
         from .layers import nms_batched_raw
         b32 = ob.float().view(B, S, 4)
@@ -294,7 +351,10 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
         return {"boxes": ob[g], "scores": os_.float()[g], "classes": oc.float()[g], "counts": kcnt, "keep": keep,
                 "offsets": ooff, "stride": S, "in_counts": ocnt, "nms_route": True, "cand_overflow_src": overflow_src}
     out = fuse_batch(ob, os_, op, ov, oc, ooff, score_fusion, box_fusion, max_rows=S, iou_thresh=iou_thresh,
-                     row_counts=ocnt, passthrough=osingle, log_probs=olp[0] if logp else None, class_prior=class_prior)
+                     row_counts=ocnt, passthrough=osingle, log_probs=olp[0] if logp else None, class_prior=class_prior,
+                     pool_weights=pool_weights, row_source=osrc)
+    if osrc is not None:
+        out["row_source"] = osrc
     out["offsets"], out["stride"], out["in_counts"] = ooff, S, ocnt
     out["cand_overflow_src"] = overflow_src
     return out

@@ -66,7 +66,8 @@ def _info(det, i):
     return d
 
 
-def late_fusion(dets, method, device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None):
+def late_fusion(dets, method, device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None,
+                pool_weights=None):
     """dets: 2 or 3 J1 dicts over the same images (order = detector order).  Returns per-image
     (boxes float64 [m,4] | None, scores f32, classes f32); None = skipped image (no detector fired).
     Case split of demo_probEn.py:237-267: 0 detectors -> skip, 1 -> passthrough, >= 2 -> fusion of the
@@ -77,8 +78,13 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
     method[0] "probEn-log": the files' log-posteriors log_softmax(class_logits / T) (temperatures None = 1 per file) go through
     pe_proben_fuse_batch_logp, with class_prior (K + 1 probabilities, background last) when given.
     variance_scales (one s per detector): every file's vars are multiplied by s in float64 (calibration.scale_j1_vars), the single
-    multiply of the device route's pe_proben_pack_calibrated, so both routes fuse identical variances."""
-    F._check_mode(method[0], class_prior, "late_fusion")
+    multiply of the device route's pe_proben_pack_calibrated, so both routes fuse identical variances.
+    pool_weights (one w per detector, "probEn-log" only): the pooled rule of pe_proben_fuse_batch_pooled; a row's detector is its
+    file's position in dets, what pe_proben_pack_pooled writes on the device route."""
+    F._check_mode(method[0], class_prior, "late_fusion", pool_weights)
+    if pool_weights is not None:
+        from . import calibration
+        pool_weights = calibration.check_pool_weights(pool_weights, len(dets), "late_fusion")
     if variance_scales is not None:
         from . import calibration
         variance_scales = calibration.check_variance_scales(variance_scales, len(dets), "late_fusion")
@@ -107,7 +113,7 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
             results[i] = (np.array(x["bbox"], dtype=np.float64), torch.tensor(x["score"], dtype=torch.float32),
                           torch.tensor(x["class"], dtype=torch.float32))
             continue
-        batch.append(live)
+        batch.append(infos if pool_weights is not None else live)      # pack_infos skips the empty ones; the positions stay
         where.append(i)
     if batch:
         if method[0] == "max" and method[1] == "argmax":
@@ -115,7 +121,11 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
                 b, s, c = F.fusion(method, *live)
                 results[i] = (b.double().numpy(), s, c)
         else:
-            if logp:
+            if logp and pool_weights is not None:
+                b, s, p, v, c, offs, lp, src = F.pack_infos(batch, device, with_log_probs=True, with_sources=True)
+                out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior,
+                                   pool_weights=pool_weights, row_source=src)
+            elif logp:
                 b, s, p, v, c, offs, lp = F.pack_infos(batch, device, with_log_probs=True)
                 out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior)
             else:
@@ -130,9 +140,57 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
     return results
 
 
+def fused_clusters(dets, box_fusion="v-avg", device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None):
+    """The clusters "probEn-log" forms over dets (late_fusion's arguments), for the pooling-weight fit and its report: the images
+    where two or more detectors fired go through ONE pe_proben_fuse_batch_pooled launch at w = 1 - which is probEn-log bit for bit -
+    with out_cluster, and the clusters come back in CSR form, built with torch on the device.  Clustering and the fused boxes do not
+    depend on the weights, so the clusters are those of every w.  Returns None when no image has two live detectors, else a dict
+    of device tensors: log_probs f64 [N, K+1] and row_source i32 [N] (the packed rows), member_rows i32 [M] / cluster_offsets i32
+    [C+1] (cluster c = fused row c, image-major; its rows in packed order), boxes f64 [C, 4] (the fused boxes), box_offsets i32
+    [B'+1] (the clusters of fused image j), and "images": the B' positions of the fused images in dets."""
+    from . import calibration
+    D = len(dets)
+    if variance_scales is not None:
+        variance_scales = calibration.check_variance_scales(variance_scales, D, "fused_clusters")
+        dets = [calibration.scale_j1_vars(d, s) for d, s in zip(dets, variance_scales)]
+    temperatures = [1.0] * D if temperatures is None else list(temperatures)
+    if len(temperatures) != D:
+        raise ValueError(f"fused_clusters: {len(temperatures)} temperatures for {D} detectors")
+    names = names or [f"prediction file {k + 1}" for k in range(D)]
+    for d, n in zip(dets, names):
+        calibration.require_logits(d, n)
+    dets = [calibration.calibrate_j1(d, t, n, device, log_probs=True) for d, t, n in zip(dets, temperatures, names)]
+    batch, where = [], []
+    for i in range(len(dets[0]["image"])):
+        infos = [_info(d, i) for d in dets]
+        if sum(len(x["bbox"]) > 0 for x in infos) >= 2:
+            batch.append(infos)
+            where.append(i)
+    if not batch:
+        return None
+    b, s, p, v, c, offs, lp, src = F.pack_infos(batch, device, with_log_probs=True, with_sources=True)
+    out = F.fuse_batch(b, s, p, v, c, offs, F.LOGP, box_fusion, log_probs=lp, class_prior=class_prior, pool_weights=[1.0] * D,
+                       row_source=src)
+    dev = b.device
+    cnt, in_off = out["counts"].long(), offs.long()
+    assert int(cnt.min()) >= 0, "fused_clusters: an image over the row bound"       # max_rows is the longest image: cannot happen
+    C = int(cnt.sum())
+    base = torch.cumsum(cnt, 0) - cnt                                               # the first cluster of every image
+    img = torch.repeat_interleave(torch.arange(len(batch), device=dev), in_off[1:] - in_off[:-1])
+    cl = out["cluster"].long()
+    rows = torch.nonzero(cl >= 0).flatten()                                         # -1: the row left the pool without a cluster
+    gid = base[img[rows]] + cl[rows]
+    order = torch.sort(gid, stable=True).indices
+    zero = torch.zeros((1,), dtype=torch.long, device=dev)
+    first = torch.repeat_interleave(in_off[:-1] - base, cnt) + torch.arange(C, device=dev)      # cluster c's fused row
+    return {"log_probs": lp, "row_source": src, "member_rows": rows[order].to(torch.int32),
+            "cluster_offsets": torch.cat([zero, torch.cumsum(torch.bincount(gid, minlength=C), 0)]).to(torch.int32),
+            "boxes": out["boxes"][first], "box_offsets": torch.cat([zero, torch.cumsum(cnt, 0)]).to(torch.int32), "images": where}
+
+
 def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="", image_hw=None, device="cuda",
                                    img_folder="../../../Datasets/FLIR/val/thermal_8_bit/", temperatures=None, names=None,
-                                   class_prior=None, variance_scales=None):
+                                   class_prior=None, variance_scales=None, pool_weights=None):
     """Same call as the reference (demo_probEn.py:198).  `image_hw`: {image_id: (H, W)} from the dataset
     json (the reference re-reads every thermal JPEG just for its shape); default 512 x 640 (FLIR).
     `img_folder`: the prefix the reference hard-codes into the `file_name` it hands to the evaluator (:200,271).
@@ -142,7 +200,7 @@ def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="
     print("Method: ", method)
     start = time.time()
     dets = [det_1, det_2] + ([det_3] if det_3 else [])
-    fused = late_fusion(dets, method, device, temperatures, names, class_prior, variance_scales)
+    fused = late_fusion(dets, method, device, temperatures, names, class_prior, variance_scales, pool_weights)
     for i, r in enumerate(fused):
         if r is None:
             continue

@@ -43,7 +43,13 @@ def config_parser(cmd=None):
     p.add_argument("--class_prior", type=str, default=None,
                    help="demo_probEn --score_fusion probEn-log: class prior 'p_0,...,p_K' (K + 1 numbers > 0, background last; normalised); "
                         "default: the calibration file's class_prior if it has one, else uniform")
+    p.add_argument("--pool_weights", type=str, default=None,
+                   help="demo_probEn --score_fusion probEn-log: one pooling weight per --detectors entry, 'a,b[,c]' by position or "
+                        "'name=a,name=b' by name (a_j = sum_t w_d(t) log p_t[j]: the logarithmic opinion pool); default: the calibration "
+                        "file's pool_weights if it has them (fit_temperature --with-pool-weights), else the plain product")
     args = p.parse_args(cmd) if cmd is not None else p.parse_args()
+    if args.pool_weights is not None and args.score_fusion != "probEn-log":
+        p.error(f"--pool_weights belongs to --score_fusion probEn-log (got {args.score_fusion})")
     if args.class_prior is not None:
         if args.score_fusion != "probEn-log":
             p.error(f"--class_prior belongs to --score_fusion probEn-log (got {args.score_fusion})")

@@ -22,7 +22,8 @@ class FramePairPipeline:
     synchronisation); inputs must not be modified before that either."""
 
     def __init__(self, models, score_fusion="probEn", box_fusion="v-avg", max_class=2, concurrent=True,
-                 staggered=False, stagger_stage=4, fuse=True, temperatures=None, class_prior=None, variance_scales=None):
+                 staggered=False, stagger_stage=4, fuse=True, temperatures=None, class_prior=None, variance_scales=None,
+                 pool_weights=None):
         self.models = list(models)
         self.fuse = fuse and len(self.models) > 1   # a single detector has nothing to fuse (configs[1])
         self.method = (score_fusion, box_fusion)
@@ -33,7 +34,11 @@ class FramePairPipeline:
             raise ValueError(f"FramePairPipeline: {len(self.temperatures)} temperatures for {len(self.models)} detectors")
         # score_fusion "probEn-log": ProbEn on log_softmax(class_logits / T) with the background column kept (pe_proben_pack_log_posteriors,
         # pe_proben_fuse_batch_logp); T = 1 without temperatures; class_prior = K + 1 probabilities (background last) or None = uniform
-        F._check_mode(score_fusion, class_prior, "FramePairPipeline")
+        F._check_mode(score_fusion, class_prior, "FramePairPipeline", pool_weights)
+        # one w per detector ("probEn-log" only): the pooled rule (pe_proben_pack_pooled, pe_proben_fuse_batch_pooled); None = the product
+        from .calibration import check_pool_weights
+        self.pool_weights = check_pool_weights(pool_weights, len(self.models), "FramePairPipeline")
+        self._pool = None           # the weights on the device, uploaded at the first batch
         self.logp = score_fusion == F.LOGP
         if self.logp and self.temperatures is None:
             self.temperatures = [1.0] * len(self.models)
@@ -135,8 +140,10 @@ class FramePairPipeline:
         # every option is None unless it was asked for (a class prior exists with "probEn-log" only), and None is fuse_detections' default
         if self.class_prior is not None and self._log_prior is None:
             self._log_prior = F.log_class_prior(self.class_prior, len(self.class_prior), dets[0]["scores"].device)
+        if self.pool_weights is not None and self._pool is None:
+            self._pool = F.pool_weight_tensor(self.pool_weights, len(self.pool_weights), dets[0]["scores"].device)
         return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class, temperatures=self.temperatures,
-                                 class_prior=self._log_prior, variance_scales=self.variance_scales)
+                                 class_prior=self._log_prior, variance_scales=self.variance_scales, pool_weights=self._pool)
 
 
 class HostFeeder:
