@@ -245,8 +245,8 @@ int pe_proben_pack_calibrated(const float* const* det_boxes_host, const float* c
  *   min(ceil(num_rows / 256), PE_RELIABILITY_MAX_BLOCKS) workgroups of 4 wavefronts, a function of num_rows alone.  Wavefront v of the
  *   grid takes row groups v, v + (4 * workgroups), ... (a group = the 64 / G rows of calibrated_softmax_kernel's lane groups for
  *   K + 1 <= 64, G the power of two >= K + 1; 64 rows otherwise) and adds their rows in ascending row order into its own table of B
- *   bins; a workgroup adds its 4 tables in wavefront order into workspace[workgroup][bin][4]; a one-workgroup second kernel adds, per
- *   bin, 16 contiguous segments of the workgroups, each in workgroup order, then the 16 segment sums in segment order.
+ *   bins; a workgroup adds its 4 tables in wavefront order into its 4 * num_bins slots of the workspace; a second kernel
+ *   adds the workgroups in the one order that csrc/reduce2.h states.
  *   workspace: PE_RELIABILITY_MAX_BLOCKS * num_bins * 4 eight-byte values.
  * Arguments are checked before any device work (temperature finite and > 0, num_bins, num_columns >= 2, num_rows >= 0, null
  * pointers).  num_rows == 0 reads nothing: the outputs that are given are zeroed and no pointer is required.

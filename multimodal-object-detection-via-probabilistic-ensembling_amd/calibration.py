@@ -46,11 +46,65 @@ POOL_NLL_MAX_BLOCKS = 1024   # PE_POOL_NLL_MAX_BLOCKS: 1 + num_detectors partial
 BBOX_REG_WEIGHTS = (10.0, 10.0, 5.0, 5.0)      # cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS: the units the variance head is trained in
 
 
+def _finite_positive(x, what):
+    """The rule for a temperature and for a variance scale."""
+    x = float(x)
+    if not (math.isfinite(x) and x > 0):
+        raise ValueError(f"{what} {x!r} is not finite and > 0")
+    return x
+
+
 def check_temperature(t, what="temperature"):
-    t = float(t)
-    if not (math.isfinite(t) and t > 0):
-        raise ValueError(f"{what} {t!r} is not finite and > 0")
-    return t
+    return _finite_positive(t, what)
+
+
+def _statistic(who, nv, work_values, dev, launch):
+    """The device side of the four statistic calls (csrc/reduce2.h): allocate [nv result slots | the two int32 flags in one f64 slot]
+    as one buffer and a workspace of work_values f64, run launch(work, out, flags, stream) -> status, download once.
+    Returns (the nv result slots on the host, excluded items, the last excluded index or -1)."""
+    res = torch.empty((nv + 1,), dtype=torch.float64, device=dev)
+    work = torch.empty((work_values,), dtype=torch.float64, device=dev)
+    st = launch(_lib.ptr(work), _lib.ptr(res), ctypes.c_void_p(res.data_ptr() + 8 * nv), _lib.stream())
+    _lib.check(st, who)
+    host = res.cpu()
+    bad, last = host[nv:].view(torch.int32).tolist()
+    return host[:nv], bad, last - 1
+
+
+# ---- one value per detector, from the command line ('a,b[,c]' by position, 'name=a,name=b' by name) or from a {name: value} table.
+# kind = (the noun of the messages, values in the order of names -> the validated list).  Temperatures and variance scales validate
+# entry by entry; pool weights validate as a list (the count limits, "all 0").
+
+def _resolve(kind, table, names, source):
+    noun, validate = kind
+    missing = [n for n in names if n not in table]
+    if missing:
+        raise ValueError(f"{source} has no {noun} for {','.join(missing)} (it lists {','.join(sorted(table)) or 'nothing'})")
+    return validate([table[n] for n in names], names, source)
+
+
+def _parse(kind, flag, text, names):
+    items = [x.strip() for x in text.split(",") if x.strip()]
+    named = ["=" in x for x in items]
+    if any(named) != all(named):
+        raise ValueError(f"{flag} {text!r} mixes positional and name=value entries")
+    if not all(named):
+        if len(items) != len(names):
+            raise ValueError(f"{flag} lists {len(items)} values for {len(names)} --detectors ({','.join(names)})")
+        return kind[1](items, names, flag)
+    table = {}
+    for x in items:
+        k, v = x.split("=", 1)
+        if k in table:
+            raise ValueError(f"{flag} names {k} twice")
+        table[k] = v
+    return _resolve(kind, table, names, flag)
+
+
+_TEMPERATURES = ("temperature", lambda vals, names, source: [check_temperature(v, f"temperature of {n}") for v, n in zip(vals, names)])
+_VARIANCE_SCALES = ("variance scale",
+                    lambda vals, names, source: [check_variance_scale(v, f"variance scale of {n}") for v, n in zip(vals, names)])
+_POOL_WEIGHTS = ("pool weight", lambda vals, names, source: check_pool_weights(vals, len(names), source))
 
 
 def calibrated_probs(logits, T):
@@ -143,20 +197,13 @@ def temperature_nll(logits, labels, temperatures):
     assert labels.shape == (M,), f"temperature_nll: {tuple(labels.shape)} labels for {M} rows"
     ts = [float(t) for t in temperatures]
     n_t = len(ts)
-    dev = logits.device
-    # [out 2 n_t | flags (2 x i32 in one f64 slot)] in one buffer: one download
-    res = torch.empty((2 * n_t + 1,), dtype=torch.float64, device=dev)
-    work = torch.empty((NLL_MAX_BLOCKS * max(n_t, 1) * 2,), dtype=torch.float64, device=dev)
-    flags = res[2 * n_t:].view(torch.int32)
-    st = _lib.lib().pe_temperature_nll(_lib.ptr(logits), _lib.ptr(labels), M, k1, (ctypes.c_double * max(n_t, 1))(*ts), n_t,
-                                      _lib.ptr(work), _lib.ptr(res), ctypes.c_void_p(flags.data_ptr()), _lib.stream())
-    _lib.check(st, "pe_temperature_nll")
-    host = res.cpu()
-    bad, last = host[2 * n_t:].view(torch.int32).tolist()
+    host, bad, last = _statistic("pe_temperature_nll", 2 * n_t, NLL_MAX_BLOCKS * max(n_t, 1) * 2, logits.device,
+                                 lambda work, out, flags, stream: _lib.lib().pe_temperature_nll(
+                                     _lib.ptr(logits), _lib.ptr(labels), M, k1, (ctypes.c_double * max(n_t, 1))(*ts), n_t, work, out, flags, stream))
     if bad:
-        raise ValueError(f"temperature_nll: {bad} of {M} rows have a label outside [0, {k1 - 1}] (row {last - 1} is one, "
-                         f"label {int(labels[last - 1])})")
-    out = host[:2 * n_t].numpy().reshape(n_t, 2)
+        raise ValueError(f"temperature_nll: {bad} of {M} rows have a label outside [0, {k1 - 1}] (row {last} is one, "
+                         f"label {int(labels[last])})")
+    out = host.numpy().reshape(n_t, 2)
     return out[:, 0].copy(), out[:, 1].copy()
 
 
@@ -232,29 +279,12 @@ def load(path):
 
 def parse_temperatures(text, names):
     """--temperatures value -> [T per name].  'a,b[,c]' is matched by position, 'name=a,name=b' by name; not both."""
-    items = [x.strip() for x in text.split(",") if x.strip()]
-    named = ["=" in x for x in items]
-    if any(named) != all(named):
-        raise ValueError(f"--temperatures {text!r} mixes positional and name=value entries")
-    if not all(named):
-        if len(items) != len(names):
-            raise ValueError(f"--temperatures lists {len(items)} values for {len(names)} --detectors ({','.join(names)})")
-        return [check_temperature(x, f"temperature of {n}") for x, n in zip(items, names)]
-    table = {}
-    for x in items:
-        k, v = x.split("=", 1)
-        if k in table:
-            raise ValueError(f"--temperatures names {k} twice")
-        table[k] = v
-    return resolve(table, names, "--temperatures")
+    return _parse(_TEMPERATURES, "--temperatures", text, names)
 
 
 def resolve(table, names, source):
     """{name: T} -> [T per name]; every name must be there."""
-    missing = [n for n in names if n not in table]
-    if missing:
-        raise ValueError(f"{source} has no temperature for {','.join(missing)} (it lists {','.join(sorted(table)) or 'nothing'})")
-    return [check_temperature(table[n], f"temperature of {n}") for n in names]
+    return _resolve(_TEMPERATURES, table, names, source)
 
 
 def require_logits(det, name):
@@ -322,10 +352,7 @@ def calibrate_j1(det, T, name="prediction file", device="cuda", log_probs=False)
 # ---- variance calibration ------------------------------------------------------------------------------------------------------
 
 def check_variance_scale(s, what="variance scale"):
-    s = float(s)
-    if not (math.isfinite(s) and s > 0):
-        raise ValueError(f"{what} {s!r} is not finite and > 0")
-    return s
+    return _finite_positive(s, what)
 
 
 def check_variance_scales(scales, num_detectors, who):
@@ -384,18 +411,12 @@ def variance_stats(det_boxes, match, gt_boxes, variances, scale=1.0, bbox_reg_we
     w = [float(x) for x in bbox_reg_weights]
     if len(w) != 4:
         raise ValueError(f"variance_stats: bbox_reg_weights {bbox_reg_weights!r} is not 4 numbers")
-    dev = det_boxes.device
-    res = torch.empty((6,), dtype=torch.float64, device=dev)           # [out 5 | flags (2 x i32 in one f64 slot)]: one download
-    work = torch.empty((VARIANCE_MAX_BLOCKS * 5,), dtype=torch.float64, device=dev)
-    flags = res[5:].view(torch.int32)
-    st = _lib.lib().pe_variance_stats(_lib.ptr(det_boxes) if M else None, _lib.ptr(match) if M else None, _lib.ptr(gt_boxes) if G else None,
-                                     _lib.ptr(variances) if M else None, M, G, (ctypes.c_float * 4)(*w), scale, _lib.ptr(work),
-                                     _lib.ptr(res), ctypes.c_void_p(flags.data_ptr()), _lib.stream())
-    _lib.check(st, "pe_variance_stats")
-    host = res.cpu()
-    bad, last = host[5:].view(torch.int32).tolist()
-    n, sq, sl, c1, c2 = host[:5].tolist()
-    return {"n": int(n), "sum_q": sq, "sum_log_var": sl, "cover1": int(c1), "cover2": int(c2), "excluded": bad, "last_excluded": last - 1}
+    host, bad, last = _statistic("pe_variance_stats", 5, VARIANCE_MAX_BLOCKS * 5, det_boxes.device,
+                                 lambda work, out, flags, stream: _lib.lib().pe_variance_stats(
+                                     _lib.ptr(det_boxes) if M else None, _lib.ptr(match) if M else None, _lib.ptr(gt_boxes) if G else None,
+                                     _lib.ptr(variances) if M else None, M, G, (ctypes.c_float * 4)(*w), scale, work, out, flags, stream))
+    n, sq, sl, c1, c2 = host.tolist()
+    return {"n": int(n), "sum_q": sq, "sum_log_var": sl, "cover1": int(c1), "cover2": int(c2), "excluded": bad, "last_excluded": last}
 
 
 def variance_nll(stats, s):
@@ -424,29 +445,12 @@ def fit_variance_scale(det_boxes, match, gt_boxes, variances, bbox_reg_weights=B
 
 def parse_variance_scales(text, names):
     """--variance_scales value -> [s per name].  'a,b[,c]' is matched by position, 'name=a,name=b' by name; not both."""
-    items = [x.strip() for x in text.split(",") if x.strip()]
-    named = ["=" in x for x in items]
-    if any(named) != all(named):
-        raise ValueError(f"--variance_scales {text!r} mixes positional and name=value entries")
-    if not all(named):
-        if len(items) != len(names):
-            raise ValueError(f"--variance_scales lists {len(items)} values for {len(names)} --detectors ({','.join(names)})")
-        return [check_variance_scale(x, f"variance scale of {n}") for x, n in zip(items, names)]
-    table = {}
-    for x in items:
-        k, v = x.split("=", 1)
-        if k in table:
-            raise ValueError(f"--variance_scales names {k} twice")
-        table[k] = v
-    return resolve_variance_scales(table, names, "--variance_scales")
+    return _parse(_VARIANCE_SCALES, "--variance_scales", text, names)
 
 
 def resolve_variance_scales(table, names, source):
     """{name: s} -> [s per name]; every name must be there."""
-    missing = [n for n in names if n not in table]
-    if missing:
-        raise ValueError(f"{source} has no variance scale for {','.join(missing)} (it lists {','.join(sorted(table)) or 'nothing'})")
-    return [check_variance_scale(table[n], f"variance scale of {n}") for n in names]
+    return _resolve(_VARIANCE_SCALES, table, names, source)
 
 
 def save_variance(path, scales, nll=None, rows=None, excluded=None, coverage=None):
@@ -524,16 +528,11 @@ def _check_bins(bins, who):
 
 
 def _reliability_call(who, M, B, dev, launch):
-    """Allocate [counts i64 B x 2 | sums f64 B x 2 | flags (2 x i32 in one slot)] as one buffer, launch, download once."""
-    res = torch.empty((4 * B + 1,), dtype=torch.float64, device=dev)
-    work = torch.empty((RELIABILITY_MAX_BLOCKS * B * 4,), dtype=torch.float64, device=dev)
-    p = res.data_ptr()
-    st = launch(_lib.ptr(work), ctypes.c_void_p(p), ctypes.c_void_p(p + 16 * B), ctypes.c_void_p(p + 32 * B), _lib.stream())
-    _lib.check(st, who)
-    host = res.cpu()
-    out = summarise_reliability(host[:2 * B].view(torch.int64).numpy().reshape(B, 2), host[2 * B:4 * B].numpy().reshape(B, 2))
-    bad, last = host[4 * B:].view(torch.int32).tolist()
-    out["excluded"], out["last_excluded"] = bad, last - 1
+    """The result slots are [counts i64 B x 2 | sums f64 B x 2]; launch(work, counts, sums, flags, stream) -> status."""
+    host, bad, last = _statistic(who, 4 * B, RELIABILITY_MAX_BLOCKS * B * 4, dev, lambda work, out, flags, stream: launch(
+        work, out, ctypes.c_void_p(out.value + 16 * B), flags, stream))
+    out = summarise_reliability(host[:2 * B].view(torch.int64).numpy().reshape(B, 2), host[2 * B:].numpy().reshape(B, 2))
+    out["excluded"], out["last_excluded"] = bad, last
     assert out["rows"] + bad == M, f"{who}: {out['rows']} rows binned and {bad} excluded of {M}"
     return out
 
@@ -617,29 +616,12 @@ def _check_pool_table(table, what):
 
 def parse_pool_weights(text, names):
     """--pool_weights value -> [w per name].  'a,b[,c]' is matched by position, 'name=a,name=b' by name; not both."""
-    items = [x.strip() for x in str(text).split(",") if x.strip()]
-    named = ["=" in x for x in items]
-    if any(named) != all(named):
-        raise ValueError(f"--pool_weights {text!r} mixes positional and name=value entries")
-    if not all(named):
-        if len(items) != len(names):
-            raise ValueError(f"--pool_weights lists {len(items)} values for {len(names)} --detectors ({','.join(names)})")
-        return check_pool_weights(items, len(names), "--pool_weights")
-    table = {}
-    for x in items:
-        k, v = x.split("=", 1)
-        if k in table:
-            raise ValueError(f"--pool_weights names {k} twice")
-        table[k] = v
-    return resolve_pool_weights(table, names, "--pool_weights")
+    return _parse(_POOL_WEIGHTS, "--pool_weights", str(text), names)          # as before, anything with a str() is taken
 
 
 def resolve_pool_weights(table, names, source):
     """{name: w} -> [w per name]; every name must be there."""
-    missing = [n for n in names if n not in table]
-    if missing:
-        raise ValueError(f"{source} has no pool weight for {','.join(missing)} (it lists {','.join(sorted(table)) or 'nothing'})")
-    return check_pool_weights([table[n] for n in names], len(names), source)
+    return _resolve(_POOL_WEIGHTS, table, names, source)
 
 
 def pool_nll(log_probs, row_source, member_rows, cluster_offsets, labels, weights, log_prior=None):
@@ -668,20 +650,13 @@ def pool_nll(log_probs, row_source, member_rows, cluster_offsets, labels, weight
         log_prior = log_prior.reshape(-1).contiguous().double()
         if log_prior.numel() != k1:
             raise ValueError(f"pool_nll: log_prior lists {log_prior.numel()} entries for K + 1 = {k1} columns")
-    dev = log_probs.device
-    nv = n_c * (1 + D)
-    res = torch.empty((nv + 1,), dtype=torch.float64, device=dev)       # [out | flags (2 x i32 in one f64 slot)]: one download
-    work = torch.empty((n_c * (D + POOL_NLL_MAX_BLOCKS * (1 + D)),), dtype=torch.float64, device=dev)
-    flags = res[nv:].view(torch.int32)
-    st = _lib.lib().pe_pool_nll(_lib.ptr(log_probs) if N else None, _lib.ptr(row_source) if N else None, N, k1,
-                               _lib.ptr(member_rows) if M else None, M, _lib.ptr(cluster_offsets), _lib.ptr(labels) if C else None, C,
-                               _lib.ptr(log_prior), W.ctypes.data_as(ctypes.c_void_p), n_c, D, _lib.ptr(work), _lib.ptr(res),
-                               ctypes.c_void_p(flags.data_ptr()), _lib.stream())
-    _lib.check(st, "pe_pool_nll")
-    host = res.cpu()
-    bad, last = host[nv:].view(torch.int32).tolist()
-    out = host[:nv].numpy().reshape(n_c, 1 + D)
-    return out[:, 0].copy(), out[:, 1:].copy(), bad, last - 1
+    host, bad, last = _statistic("pe_pool_nll", n_c * (1 + D), n_c * (D + POOL_NLL_MAX_BLOCKS * (1 + D)), log_probs.device,
+                                 lambda work, out, flags, stream: _lib.lib().pe_pool_nll(
+                                     _lib.ptr(log_probs) if N else None, _lib.ptr(row_source) if N else None, N, k1,
+                                     _lib.ptr(member_rows) if M else None, M, _lib.ptr(cluster_offsets), _lib.ptr(labels) if C else None, C,
+                                     _lib.ptr(log_prior), W.ctypes.data_as(ctypes.c_void_p), n_c, D, work, out, flags, stream))
+    out = host.numpy().reshape(n_c, 1 + D)
+    return out[:, 0].copy(), out[:, 1:].copy(), bad, last
 
 
 def fit_pool_weights(log_probs, row_source, member_rows, cluster_offsets, labels, num_detectors, log_prior=None, hi=64.0,

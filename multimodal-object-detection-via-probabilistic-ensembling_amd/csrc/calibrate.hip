@@ -5,6 +5,7 @@
 // The row arithmetic is csrc/softmax_row.h, shared with the pack kernel (csrc/pack.hip: pe_proben_pack_logits,
 // pe_proben_pack_log_posteriors), so a row gets the same bits from either.  Built with -ffp-contract=off like the other ProbEn code.
 #include "common.h"
+#include "reduce2.h"
 #include "softmax_row.h"
 
 namespace {
@@ -38,8 +39,8 @@ struct NllArgs {
     long long M;
     int k1, n_t;
     double T[64];
-    double* partial;     // [blocks, n_t, 2]
-    int32_t* flags;      // [0] rows with a label outside [0, K], [1] 1 + the largest such row index (saturating)
+    double* partial;     // [blocks, n_t, 2], added up by pe::launch_finish (csrc/reduce2.h)
+    int32_t* flags;      // pe::flag_excluded: rows with a label outside [0, K]
 };
 
 // Lane = candidate temperature, wavefront = row: the 64 lanes read the same logits (one cache line, broadcast) and each keeps its own
@@ -53,10 +54,7 @@ __global__ __launch_bounds__(kNllThreads) void temperature_nll_kernel(NllArgs a)
     for (long long r = (long long)blockIdx.x * kNllWaves + w; r < a.M; r += step) {
         const int y = a.labels[r];
         if (y < 0 || y >= a.k1) {
-            if (lane == 0) {
-                atomicAdd(&a.flags[0], 1);
-                atomicMax(&a.flags[1], (int)min(r + 1, (long long)0x7fffffff));
-            }
+            if (lane == 0) pe::flag_excluded(a.flags, r);
             continue;
         }
         const float* row = a.logits + r * a.k1;
@@ -85,34 +83,6 @@ __global__ __launch_bounds__(kNllThreads) void temperature_nll_kernel(NllArgs a)
         double* o = a.partial + ((size_t)blockIdx.x * a.n_t + lane) * 2;
         o[0] = s0;
         o[1] = s1;
-    }
-}
-
-// second pass, one workgroup: segment g of the 16 adds its share of the blocks in block order, then candidate t adds the 16 segment
-// sums in segment order - fixed for a fixed block count
-constexpr int kFinishSegments = 16;
-
-__global__ __launch_bounds__(64 * kFinishSegments) void temperature_nll_finish_kernel(const double* partial, int blocks, int n_t, double* out) {
-    __shared__ double seg[kFinishSegments][64][2];
-    const int t = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int per = (blocks + kFinishSegments - 1) / kFinishSegments;
-    double s0 = 0.0, s1 = 0.0;
-    if (t < n_t) {
-        const int end = min(blocks, (g + 1) * per);
-        for (int k = g * per; k < end; ++k) {
-            s0 += partial[((size_t)k * n_t + t) * 2];
-            s1 += partial[((size_t)k * n_t + t) * 2 + 1];
-        }
-    }
-    seg[g][t][0] = s0;
-    seg[g][t][1] = s1;
-    __syncthreads();
-    if (g == 0 && t < n_t) {
-        s0 = seg[0][t][0];
-        s1 = seg[0][t][1];
-        for (int k = 1; k < kFinishSegments; ++k) { s0 += seg[k][t][0]; s1 += seg[k][t][1]; }
-        out[t * 2] = s0;
-        out[t * 2 + 1] = s1;
     }
 }
 
@@ -168,14 +138,8 @@ extern "C" int pe_temperature_nll(const float* logits, const int32_t* labels, in
     // the grid is a function of num_rows alone: same input, same partition, same bits
     const int blocks = (int)std::max<long long>(1, std::min<long long>((num_rows + kNllWaves - 1) / kNllWaves,
                                                                         PE_TEMPERATURE_NLL_MAX_BLOCKS));
-    if (hipMemsetAsync(out_flags, 0, 2 * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) {
-        pe::set_error("pe_temperature_nll: hipMemsetAsync of the flags failed");
-        return PE_ERR_HIP;
-    }
+    if (int st = pe::zero_flags(out_flags, (hipStream_t)stream, "pe_temperature_nll")) return st;
     hipLaunchKernelGGL(temperature_nll_kernel, dim3(blocks), dim3(kNllThreads), 0, (hipStream_t)stream, a);
     PE_CHECK_LAUNCH("pe_temperature_nll");
-    hipLaunchKernelGGL(temperature_nll_finish_kernel, dim3(1), dim3(64 * kFinishSegments), 0, (hipStream_t)stream, workspace, blocks,
-                       (int)num_temperatures, out);
-    PE_CHECK_LAUNCH("pe_temperature_nll (finish)");
-    return PE_OK;
+    return pe::launch_finish(workspace, blocks, 2 * num_temperatures, 0, nullptr, out, (hipStream_t)stream, "pe_temperature_nll");
 }

@@ -7,6 +7,7 @@
 // and all 64 candidates work from that table (every lane reads the same address: a broadcast).  d NLL / d w_d = sum_j s_j G_dj - G_d,label.
 // Built with -ffp-contract=off like the other ProbEn code.
 #include "common.h"
+#include "reduce2.h"
 
 namespace {
 
@@ -23,8 +24,8 @@ struct PoolArgs {
     const double* weights;          // [nc, D] (the head of the workspace)
     long long N, M;
     int C, k1, D, nc;
-    double* partial;                // [blocks, nc, 1 + D]
-    int32_t* flags;                 // [0] excluded clusters, [1] 1 + the largest excluded cluster index
+    double* partial;                // [blocks, nc, 1 + D], added up by pe::launch_finish (csrc/reduce2.h)
+    int32_t* flags;                 // pe::flag_excluded: excluded clusters
 };
 
 // the candidates travel as kernel arguments, 256 doubles a launch, into the head of the workspace: stream-ordered, and the host
@@ -75,10 +76,7 @@ __global__ __launch_bounds__(kPoolThreads) void pool_nll_kernel(PoolArgs a) {
             }
         }
         if (bad) {
-            if (lane == 0) {
-                atomicAdd(&a.flags[0], 1);
-                atomicMax(&a.flags[1], c + 1);
-            }
+            if (lane == 0) pe::flag_excluded(a.flags, c);
             continue;
         }
         // ---- the table: lane j sums column j of the cluster's rows per detector, in member order; then G = S - n_d lp ----
@@ -145,32 +143,6 @@ __global__ __launch_bounds__(kPoolThreads) void pool_nll_kernel(PoolArgs a) {
     }
 }
 
-// second pass, one workgroup: per output value, segment g of the 16 adds its share of the blocks in block order, then the 16 segment
-// sums are added in segment order - fixed for a fixed block count
-constexpr int kFinishSegments = 16;
-
-__global__ __launch_bounds__(64 * kFinishSegments) void pool_nll_finish_kernel(const double* partial, int blocks, int nv, double* out) {
-    __shared__ double seg[kFinishSegments][64];
-    const int t = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int per = (blocks + kFinishSegments - 1) / kFinishSegments;
-    for (int v0 = 0; v0 < nv; v0 += 64) {      // block-uniform
-        const int v = v0 + t;
-        double s = 0.0;
-        if (v < nv) {
-            const int end = min(blocks, (g + 1) * per);
-            for (int k = g * per; k < end; ++k) s += partial[(size_t)k * nv + v];
-        }
-        seg[g][t] = s;
-        __syncthreads();
-        if (g == 0 && v < nv) {
-            s = seg[0][t];
-            for (int k = 1; k < kFinishSegments; ++k) s += seg[k][t];
-            out[v] = s;
-        }
-        __syncthreads();
-    }
-}
-
 }  // namespace
 
 extern "C" int pe_pool_nll(const double* log_probs, const int32_t* row_source, int64_t num_rows, int32_t num_columns,
@@ -212,13 +184,8 @@ extern "C" int pe_pool_nll(const double* log_probs, const int32_t* row_source, i
     a.k1 = num_columns; a.D = num_detectors; a.nc = num_candidates; a.partial = workspace + nw; a.flags = out_flags;
     // the grid is a function of num_clusters alone: same input, same partition, same bits
     const int blocks = std::max(1, std::min((num_clusters + kPoolWaves - 1) / kPoolWaves, PE_POOL_NLL_MAX_BLOCKS));
-    if (hipMemsetAsync(out_flags, 0, 2 * sizeof(int32_t), st) != hipSuccess) {
-        pe::set_error("%s: hipMemsetAsync of the flags failed", what);
-        return PE_ERR_HIP;
-    }
+    if (int rc = pe::zero_flags(out_flags, st, what)) return rc;
     hipLaunchKernelGGL(pool_nll_kernel, dim3(blocks), dim3(kPoolThreads), 0, st, a);
     PE_CHECK_LAUNCH(what);
-    hipLaunchKernelGGL(pool_nll_finish_kernel, dim3(1), dim3(64 * kFinishSegments), 0, st, a.partial, blocks, nv, out);
-    PE_CHECK_LAUNCH("pe_pool_nll (finish)");
-    return PE_OK;
+    return pe::launch_finish(a.partial, blocks, nv, 0, nullptr, out, st, what);
 }

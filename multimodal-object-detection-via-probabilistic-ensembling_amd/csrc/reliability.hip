@@ -11,19 +11,18 @@
 //      the grid (v = 4 * workgroup + wave) takes row groups v, v + waves, ... in that order; inside a group the owner lanes take turns in
 //      lane order, which is row order: the row's (bin, conf, term) is broadcast and the one lane whose index is the bin adds it.
 //      So a wavefront adds its rows in ascending row order.
-//   2. A workgroup adds its 4 wavefronts in wavefront order (LDS) into workspace[workgroup][bin][4] = (rows, correct, sum conf, sum term);
-//      the two counts are int64 kept in the 8-byte slots.
-//   3. reliability_finish_kernel, one workgroup: segment g of 16 adds its share of the workgroups in workgroup order, bin b then adds the
-//      16 segment sums in segment order.
+//   2. A workgroup adds its 4 wavefronts in wavefront order (LDS) into its 4 B slots of the workspace: [counts B x 2 | sums B x 2] =
+//      per bin (rows, correct) as int64, then per bin (sum conf, sum term).
+//   3. pe::launch_finish (csrc/reduce2.h) adds the workgroups: the order is stated there.
 // The grid is min(ceil(num_rows / 256), PE_RELIABILITY_MAX_BLOCKS), a function of num_rows alone.  Counts are integers: exact in any order.
 #include "common.h"
+#include "reduce2.h"
 #include "softmax_row.h"
 
 namespace {
 
 constexpr int kRelThreads = 256, kRelWaves = kRelThreads / 64;
 constexpr int kRelRowsPerBlock = 256;          // sizes the grid only: which rows a wavefront takes is the source's row grouping
-constexpr int kRelSegments = 16;
 
 enum RowState { kNoRow = 0, kRowUsed = 1, kRowExcluded = 2 };
 
@@ -136,10 +135,7 @@ __global__ __launch_bounds__(kRelThreads) void reliability_kernel(Source src, lo
         double conf = 0.0;
         int correct = 0;
         const int state = src.fetch(r0, M, lane, &r, &conf, &correct);
-        if (state == kRowExcluded) {
-            atomicAdd(&flags[0], 1);
-            atomicMax(&flags[1], (int)min(r + 1, (long long)0x7fffffff));
-        }
+        if (state == kRowExcluded) pe::flag_excluded(flags, r);
         const bool used = state == kRowUsed;
         const double d = conf - (correct ? 1.0 : 0.0);
         const double term = d * d;
@@ -171,46 +167,11 @@ __global__ __launch_bounds__(kRelThreads) void reliability_kernel(Source src, lo
             c0 += wave_counts[v][lane][0]; c1 += wave_counts[v][lane][1];
             s0 += wave_sums[v][lane][0]; s1 += wave_sums[v][lane][1];
         }
-        double* o = workspace + ((size_t)blockIdx.x * B + lane) * 4;
+        double* o = workspace + (size_t)blockIdx.x * B * 4 + lane * 2;
         reinterpret_cast<long long*>(o)[0] = c0;
         reinterpret_cast<long long*>(o)[1] = c1;
-        o[2] = s0;
-        o[3] = s1;
-    }
-}
-
-// second pass, one workgroup: segment g of the 16 adds its share of the workgroups in workgroup order, then bin b adds the 16 segment
-// sums in segment order - fixed for a fixed workgroup count
-__global__ __launch_bounds__(64 * kRelSegments) void reliability_finish_kernel(const double* workspace, int blocks, int B,
-                                                                               long long* out_counts, double* out_sums) {
-    __shared__ long long seg_counts[kRelSegments][64][2];
-    __shared__ double seg_sums[kRelSegments][64][2];
-    const int b = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int per = (blocks + kRelSegments - 1) / kRelSegments;
-    long long c0 = 0, c1 = 0;
-    double s0 = 0.0, s1 = 0.0;
-    if (b < B) {
-        const int end = min(blocks, (g + 1) * per);
-        for (int k = g * per; k < end; ++k) {
-            const double* p = workspace + ((size_t)k * B + b) * 4;
-            c0 += reinterpret_cast<const long long*>(p)[0];
-            c1 += reinterpret_cast<const long long*>(p)[1];
-            s0 += p[2];
-            s1 += p[3];
-        }
-    }
-    seg_counts[g][b][0] = c0; seg_counts[g][b][1] = c1;
-    seg_sums[g][b][0] = s0; seg_sums[g][b][1] = s1;
-    __syncthreads();
-    if (g == 0 && b < B) {
-        c0 = seg_counts[0][b][0]; c1 = seg_counts[0][b][1];
-        s0 = seg_sums[0][b][0]; s1 = seg_sums[0][b][1];
-        for (int k = 1; k < kRelSegments; ++k) {
-            c0 += seg_counts[k][b][0]; c1 += seg_counts[k][b][1];
-            s0 += seg_sums[k][b][0]; s1 += seg_sums[k][b][1];
-        }
-        out_counts[b * 2] = c0; out_counts[b * 2 + 1] = c1;
-        out_sums[b * 2] = s0; out_sums[b * 2 + 1] = s1;
+        o[2 * B] = s0;
+        o[2 * B + 1] = s1;
     }
 }
 
@@ -235,17 +196,11 @@ int reliability_impl(const char* what, const Source& src, bool data_ok, int64_t 
     PE_CHECK_ARG(workspace && out_counts && out_sums && out_flags, "%s: null pointer (workspace / out_counts / out_sums / out_flags)", what);
     // the grid is a function of num_rows alone: same input, same partition, same bits
     const int blocks = (int)std::min<long long>((num_rows + kRelRowsPerBlock - 1) / kRelRowsPerBlock, PE_RELIABILITY_MAX_BLOCKS);
-    if (hipMemsetAsync(out_flags, 0, 2 * sizeof(int32_t), st) != hipSuccess) {
-        pe::set_error("%s: hipMemsetAsync of the flags failed", what);
-        return PE_ERR_HIP;
-    }
+    if (int rc = pe::zero_flags(out_flags, st, what)) return rc;
     hipLaunchKernelGGL(reliability_kernel<Source>, dim3(blocks), dim3(kRelThreads), 0, st, src, (long long)num_rows, (int)num_bins,
                        workspace, out_flags);
     PE_CHECK_LAUNCH(what);
-    hipLaunchKernelGGL(reliability_finish_kernel, dim3(1), dim3(64 * kRelSegments), 0, st, workspace, blocks, (int)num_bins,
-                       reinterpret_cast<long long*>(out_counts), out_sums);
-    PE_CHECK_LAUNCH(what);
-    return PE_OK;
+    return pe::launch_finish(workspace, blocks, 4 * num_bins, 2 * num_bins, reinterpret_cast<long long*>(out_counts), out_sums, st, what);
 }
 
 }  // namespace

@@ -12,6 +12,8 @@
 // (blocks * 256)), the workgroup adds its 256 threads in a stride-halving tree, the second kernel adds the (at most 1 024) workgroup
 // partials in the same tree.  The grid is a function of the row count alone: same input, same bits.
 #include "common.h"
+#define PE_REDUCE2_FLAGS_ONLY          // the flags, not the finish kernel: see the note at variance_stats_finish_kernel
+#include "reduce2.h"
 
 namespace {
 
@@ -82,7 +84,7 @@ struct StatArgs {
     double w[4];
     double s;
     double* partial;      // [blocks, 5]
-    int32_t* flags;       // [0] excluded rows, [1] 1 + the largest excluded row index (saturating)
+    int32_t* flags;       // pe::flag_excluded (csrc/reduce2.h): excluded rows
 };
 
 // x[0..255] of the five values -> x[0], stride-halving tree: level by level, the same pairs whatever the data
@@ -111,8 +113,7 @@ __global__ __launch_bounds__(kStatThreads) void variance_stats_kernel(StatArgs a
             ok = sw > 0.0 && sh > 0.0 && tw > 0.0 && th > 0.0;
         }
         if (!ok) {
-            atomicAdd(&a.flags[0], 1);
-            atomicMax(&a.flags[1], (int)min(r + 1, (long long)0x7fffffff));
+            pe::flag_excluded(a.flags, r);
             continue;
         }
         // Box2BoxTransform.get_deltas(detection, ground truth): w[:2] * (tc - sc) / swh, w[2:] * log(twh / swh)
@@ -142,6 +143,7 @@ __global__ __launch_bounds__(kStatThreads) void variance_stats_kernel(StatArgs a
 }
 
 // second pass, one workgroup: thread k holds workgroup k's partial (0 beyond the grid: adding it is exact), 1 024 -> 1 in the same tree
+// (not pe::launch_finish of csrc/reduce2.h: its segment order would change the low bits of sum_q and sum_log_var)
 __global__ __launch_bounds__(PE_VARIANCE_STATS_MAX_BLOCKS) void variance_stats_finish_kernel(const double* partial, int blocks,
                                                                                              double* out) {
     __shared__ double x[PE_VARIANCE_STATS_MAX_BLOCKS][kStatValues];
@@ -194,10 +196,7 @@ extern "C" int pe_variance_stats(const double* det_boxes, const int32_t* match, 
     // the grid is a function of num_rows alone: same input, same partition, same bits
     const int blocks = (int)std::max<long long>(1, std::min<long long>((num_rows + kStatThreads - 1) / kStatThreads,
                                                                         PE_VARIANCE_STATS_MAX_BLOCKS));
-    if (hipMemsetAsync(out_flags, 0, 2 * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) {
-        pe::set_error("pe_variance_stats: hipMemsetAsync of the flags failed");
-        return PE_ERR_HIP;
-    }
+    if (int st = pe::zero_flags(out_flags, (hipStream_t)stream, "pe_variance_stats")) return st;
     hipLaunchKernelGGL(variance_stats_kernel, dim3(blocks), dim3(kStatThreads), 0, (hipStream_t)stream, a);
     PE_CHECK_LAUNCH("pe_variance_stats");
     hipLaunchKernelGGL(variance_stats_finish_kernel, dim3(1), dim3(PE_VARIANCE_STATS_MAX_BLOCKS), 0, (hipStream_t)stream, workspace, blocks,

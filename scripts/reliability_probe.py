@@ -24,9 +24,9 @@ conf = torch.rand((M,), generator=g, device="cuda", dtype=torch.float64)
 correct = (torch.rand((M,), generator=g, device="cuda", dtype=torch.float64) < conf).to(torch.int32)
 torch.cuda.synchronize()
 for it in range(10):
-    own = C.reliability(logits, labels, 1.3, classes, bins=B)            # reliability_kernel<LogitsSource> + reliability_finish_kernel
+    own = C.reliability(logits, labels, 1.3, classes, bins=B)            # reliability_kernel<LogitsSource> + pe::finish_kernel (csrc/reduce2.h)
     top = C.reliability(logits, labels, 1.3, None, bins=B)
-    sc = C.reliability_scores(conf, correct, bins=B)                     # reliability_kernel<ScoresSource> + reliability_finish_kernel
+    sc = C.reliability_scores(conf, correct, bins=B)                     # reliability_kernel<ScoresSource> + pe::finish_kernel
 nll, _ = C.temperature_nll(logits, labels, np.exp(np.linspace(np.log(0.05), np.log(20.0), 64)))
 torch.cuda.synchronize()
 print("rows", own["rows"], top["rows"], sc["rows"], "ECE own / top / scores", own["ece"], top["ece"], sc["ece"], "NLL candidates", len(nll))

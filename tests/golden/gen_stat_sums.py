@@ -1,0 +1,316 @@
+"""Generate tests/golden/stat_sums_parent.npz: what the four device-side calibration statistics returned for a set of small cases,
+recorded on the GPU at the commit BEFORE their second passes became one kernel (DESIGN.md names it).
+tests/test_stat_sums_golden_gpu.py holds the same calls to these bits.
+
+    python tests/golden/gen_stat_sums.py [--out FILE]        on the GPU, at that commit
+    python tests/golden/gen_stat_sums.py --check-inputs      anywhere: the coverage condition below on the host alone
+
+Only the public Python surface is used (calibration.temperature_nll, pool_nll, reliability, reliability_scores, variance_stats) and
+the file holds OUTPUTS ONLY: per case `<name>_f64` (every returned float64, in order) and `<name>_i64` (every returned integer, the
+two flag values last).  The inputs are closed-form integer formulas (multipliers modulo the prime 8191, scaled) that the test
+rebuilds by importing this file: no random generator is involved.
+
+Cases, by what the shared second pass sees:
+  workgroups   1, 5 (one per segment, 11 segments empty), 17 (two per segment, the last used segment short), 1024 at the cap with
+               one more unit of work behind it: 3 / 20 / 68 / 4100 rows or clusters at 4 a workgroup (temperature, pool),
+               200 / 1280 / 4352 / 262400 rows at 256 a workgroup (reliability, variance)
+  values       temperature n_t = 1, 32, 64 (2, 64, 128 values a workgroup); pool (candidates, detectors) = (1, 1), (64, 8) (2, 576),
+               with and without log_prior; reliability bins = 1, 15, 64 (4, 60, 256), both sources, with and without `classes`,
+               K + 1 = 4 and 65
+  excluded     every case has excluded items and the last index is one of them (3 items: the last only), so both flag values are
+               non-trivial; a variance case holds each of its exclusion causes once.  temperature_nll raises on an excluded row, so
+               a temperature case is two calls: the clean labels give the sums, the labels with bad rows give the message, whose two
+               numbers are the flags.
+
+Coverage condition (asserted before writing): every returned sum is finite, excluded < items / 2, and in each family at least one
+double sum differs in bits from the plain ascending float64 sum of the host's terms - otherwise the file could not tell one order
+from another.  Wherever this file restates the terms, the same terms added in the kernels' two-pass order must equal the device's sum
+bit for bit (asserted too), so that difference is the order's and not the terms'.  --check-inputs shows the same of the inputs without a GPU: it adds the host's terms once in ascending order and once
+in the kernels' two-pass order and requires the two to differ.
+"""
+import os
+import re
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+
+P = 8191
+K1 = 4
+REL_T = 1.25
+POOL_PRIOR = [-(0.5 + 0.25 * j) for j in range(K1)]
+
+TEMPERATURE = [(M, n) for M in (3, 20, 68, 4100) for n in (1, 32, 64)]
+POOL = ([(C, 1, 1, prior) for C in (3, 20, 68, 4100) for prior in (False, True)] +
+        [(3, 64, 8, True), (20, 64, 8, False), (68, 64, 8, True), (4100, 64, 8, False), (4100, 64, 8, True)])
+RELIABILITY = [("own", 200, 1, 4), ("own", 1280, 15, 65), ("own", 4352, 64, 4), ("own", 262400, 15, 4),        # (source, M, bins, K + 1)
+               ("top", 200, 64, 65), ("top", 1280, 1, 4), ("top", 4352, 15, 65), ("top", 262400, 64, 4),
+               ("scores", 200, 15, 0), ("scores", 1280, 64, 0), ("scores", 4352, 1, 0), ("scores", 262400, 15, 0),
+               ("scores", 262400, 1, 0)]
+VARIANCE = [(200, 1.0), (1280, 1.0), (4352, 0.75), (262400, 0.75)]                                           # (M, scale)
+CASES = ([("temperature", c) for c in TEMPERATURE] + [("pool", c) for c in POOL] + [("reliability", c) for c in RELIABILITY] +
+         [("variance", c) for c in VARIANCE])
+
+
+def case_name(family, c):
+    return family[0] + "_" + "_".join(str(int(x) if isinstance(x, bool) else x).replace(".", "p") for x in c)
+
+
+def frac(i, a=1, c=0):
+    """((a * i + c) mod P) / P in [0, 1): exact integer arithmetic, one float64 division."""
+    return ((np.asarray(i, np.int64) * a + c) % P) / P
+
+
+def planted(n):
+    """The indices of the excluded items: the last always, two more where n leaves room."""
+    return [n - 1] if n < 8 else [n // 3, n // 2, n - 1]
+
+
+def logits_input(M, k1):
+    r, k = np.arange(M, dtype=np.int64)[:, None], np.arange(k1, dtype=np.int64)[None]
+    return (frac(r * 613 + k * 2731 + r * k * 29, 1, 17) * 12.0 - 6.0).astype(np.float32)
+
+
+def temperature_input(M, n_t):
+    """logits f32 [M, 4], labels i32 [M], the same labels with the planted rows out of range, temperatures [n_t]."""
+    labels = ((np.arange(M) * 7 + 3) % K1).astype(np.int32)
+    bad = labels.copy()
+    for j, r in enumerate(planted(M)):
+        bad[r] = K1 if r == M - 1 else (-1, K1 + 3)[j % 2]
+    return logits_input(M, K1), labels, bad, [0.5 + 0.0625 * t for t in range(n_t)]
+
+
+def pool_input(C, nc, D, prior):
+    """log_probs f64 [N, 4], row_source, member_rows, cluster_offsets, labels, weights [nc, D], log_prior or None: clusters of 2 or 3
+    rows; excluded: the last cluster (label 4), and with room a label -1 and a row whose source is D."""
+    c = np.arange(C, dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(2 + c % 2)]).astype(np.int32)
+    N = int(offs[-1])
+    r, k = np.arange(N, dtype=np.int64)[:, None], np.arange(K1, dtype=np.int64)[None]
+    lp = -(0.05 + 6.0 * frac(r * 389 + k * 1277 + r * k * 31, 1, 5))
+    src = ((np.arange(N) * 3 + np.repeat(c, 2 + c % 2)) % D).astype(np.int32)
+    labels = ((c * 3 + 1) % K1).astype(np.int32)
+    ex = planted(C)
+    labels[ex[-1]] = K1
+    if len(ex) == 3:
+        labels[ex[0]] = -1
+        src[offs[ex[1]]] = D
+    W = 0.25 + ((np.arange(nc)[:, None] * 5 + np.arange(D)[None] * 3) % 16) / 8.0
+    return lp, src, np.arange(N, dtype=np.int32), offs, labels, W, (np.asarray(POOL_PRIOR) if prior else None)
+
+
+def reliability_input(source, M, k1):
+    """scores: conf f64 [M], correct i32 [M]; excluded: NaN (the last row), 1.5, -0.25.  own / top: logits f32 [M, k1], labels, classes;
+    excluded: a label of -1 (the last row), a class of k1 (a label of k1 for the top label), a NaN logit."""
+    r = np.arange(M, dtype=np.int64)
+    ex = planted(M)
+    if source == "scores":
+        conf = frac(r, 2731, 5)
+        conf[ex[-1]] = np.nan
+        if len(ex) == 3:
+            conf[ex[0]], conf[ex[1]] = 1.5, -0.25
+        return conf, ((r * 13 + 1) % 3 == 0).astype(np.int32)
+    lg = logits_input(M, k1)
+    labels, classes = ((r * 7 + 3) % k1).astype(np.int32), ((r * 5 + 1) % k1).astype(np.int32)
+    labels[ex[-1]] = -1
+    if len(ex) == 3:
+        classes[ex[0]] = k1
+        if source == "top":
+            labels[ex[0]] = k1
+        lg[ex[1], 1] = np.nan
+    return lg, labels, classes
+
+
+VARIANCE_GT = 38          # ground-truth boxes; the last is degenerate (zero width) and only the planted row matches it
+
+
+def variance_input(M):
+    """det f64 [M, 4], match i32 [M], gt f64 [38, 4], variances f64 [M].  Excluded, one row each: no match, a match beyond the table,
+    a variance of 0 / NaN / inf, a degenerate detection, a degenerate ground-truth box; and the last row (no match)."""
+    def boxes(i, a):
+        x1, y1 = 500.0 * frac(i, 613 + a, 1), 400.0 * frac(i, 1277 + a, 2)
+        return np.stack([x1, y1, x1 + 20.0 + 100.0 * frac(i, 71 + a, 3), y1 + 20.0 + 80.0 * frac(i, 97 + a, 4)], 1)
+    r = np.arange(M, dtype=np.int64)
+    det, gt = boxes(r, 0), boxes(np.arange(VARIANCE_GT, dtype=np.int64), 100)
+    gt[-1, 2] = gt[-1, 0]
+    match = (r % (VARIANCE_GT - 1)).astype(np.int32)
+    var = 0.001 + 2.0 * frac(r, 389, 7)
+    match[10], match[20], match[70], match[M - 1] = -1, VARIANCE_GT, VARIANCE_GT - 1, -1
+    var[30], var[40], var[50] = 0.0, np.nan, np.inf
+    det[60, 2] = det[60, 0] - 1.0
+    return det, match, gt, var
+
+
+VARIANCE_EXCLUDED = (10, 20, 30, 40, 50, 60, 70)          # and M - 1
+
+
+def run_case(family, c):
+    """The case on the GPU through the public calls -> (float64 array, int64 array)."""
+    import torch
+    from proben_amd import calibration as C
+    dev = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).cuda()  # noqa: E731
+    if family == "temperature":
+        M, n_t = c
+        lg, labels, bad, ts = temperature_input(M, n_t)
+        nll, dnll = C.temperature_nll(dev(lg), dev(labels), ts)
+        try:
+            C.temperature_nll(dev(lg), dev(bad), ts)
+            raise AssertionError("temperature_nll did not raise on labels out of range")
+        except ValueError as e:
+            msg = str(e)
+        ex = planted(M)
+        assert msg == (f"temperature_nll: {len(ex)} of {M} rows have a label outside [0, {K1 - 1}] (row {M - 1} is one, label {K1})"), msg
+        flags = re.match(r"temperature_nll: (\d+) of \d+ rows .* \(row (\d+) is one", msg)
+        return np.concatenate([nll, dnll]), np.asarray([int(flags[1]), int(flags[2])], np.int64)
+    if family == "pool":
+        lp, src, mem, offs, labels, W, prior = pool_input(*c)
+        nll, grad, bad, last = C.pool_nll(dev(lp), dev(src), dev(mem), dev(offs), dev(labels), W, dev(prior))
+        return np.concatenate([nll, grad.reshape(-1)]), np.asarray([bad, last], np.int64)
+    if family == "reliability":
+        source, M, B, k1 = c
+        if source == "scores":
+            conf, correct = reliability_input(source, M, k1)
+            out = C.reliability_scores(dev(conf), dev(correct), bins=B)
+        else:
+            lg, labels, classes = reliability_input(source, M, k1)
+            out = C.reliability(dev(lg), dev(labels), REL_T, dev(classes) if source == "own" else None, bins=B)
+        f = [x for b in out["bins"] for x in (b["conf_sum"], b["brier_sum"])] + [out["ece"], out["mce"], out["brier"]]
+        i = [x for b in out["bins"] for x in (b["count"], b["correct"])] + [out["rows"], out["excluded"], out["last_excluded"]]
+        return np.asarray(f, np.float64), np.asarray(i, np.int64)
+    M, scale = c
+    det, match, gt, var = variance_input(M)
+    s = C.variance_stats(dev(det), dev(match), dev(gt), dev(var), scale)
+    return (np.asarray([s["sum_q"], s["sum_log_var"]], np.float64),
+            np.asarray([s["n"], s["cover1"], s["cover2"], s["excluded"], s["last_excluded"]], np.int64))
+
+
+def items_and_excluded(family, c, i64):
+    """(items of the case, excluded items it reported, the last excluded index it reported)."""
+    if family == "temperature":
+        return c[0], int(i64[0]), int(i64[1])
+    if family == "pool":
+        return c[0], int(i64[0]), int(i64[1])
+    if family == "reliability":
+        return c[1], int(i64[-2]), int(i64[-1])
+    return c[0], int(i64[3]), int(i64[4])
+
+
+# ---- the coverage condition: the host's terms of one sum per family, added in ascending order and in the kernels' order ------------
+
+def _seq(x, axis=0):
+    return np.add.accumulate(x, axis=axis).take(-1, axis=axis)          # strictly one after the other
+
+
+def _padded(terms, step):
+    return np.concatenate([terms, np.zeros((-len(terms)) % step)])     # + 0.0 is exact
+
+
+def _segments(partial):
+    blocks = len(partial)
+    per = -(-blocks // 16)
+    return _seq(np.asarray([_seq(partial[g * per:min(blocks, (g + 1) * per)]) if g * per < blocks else 0.0 for g in range(16)]))
+
+
+def _tree(x):
+    x = x.copy()
+    s = x.shape[1] // 2
+    while s:
+        x[:, :s] += x[:, s:2 * s]
+        s //= 2
+    return x[:, 0]
+
+
+def two_pass_sum(family, terms):
+    """`terms` (one per item, 0.0 for an excluded one) in the order the family's kernels add them."""
+    n = len(terms)
+    if family in ("temperature", "pool"):          # wavefront = item, 4 wavefronts a workgroup
+        blocks = max(1, min(-(-n // 4), 1024))
+        waves = _seq(_padded(terms, 4 * blocks).reshape(-1, 4 * blocks), 0)
+        return _segments(_seq(waves.reshape(blocks, 4), 1))
+    blocks = max(1, min(-(-n // 256), 1024))
+    if family == "reliability":                    # wavefront = groups of 64 rows, one bin
+        x = _padded(terms, 256 * blocks).reshape(-1, 4 * blocks, 64).transpose(1, 0, 2).reshape(4 * blocks, -1)
+        return _segments(_seq(_seq(x, 1).reshape(blocks, 4), 1))
+    threads = _seq(_padded(terms, 256 * blocks).reshape(-1, 256 * blocks), 0)          # variance: thread = row mod the grid, trees
+    return _tree(_padded(_tree(threads.reshape(blocks, 256)), 1024)[None])[0]
+
+
+def host_terms(family, c):
+    """The float64 terms of the case's first double sum as the host computes them, or None where this file does not restate them."""
+    if family == "temperature":
+        lg, labels, _, ts = temperature_input(*c)
+        z = lg.astype(np.float64) / ts[0]
+        m = z.max(1)
+        zy = z[np.arange(len(z)), labels] - m
+        return np.log(np.exp(z - m[:, None]).sum(1)) - zy
+    if family == "pool":
+        if c[1:] != (1, 1, False):
+            return None
+        lp, src, _, offs, labels, W, _ = pool_input(*c)
+        a = W[0, 0] * np.add.reduceat(lp, offs[:-1], axis=0)
+        ok = (labels >= 0) & (labels < K1) & (np.add.reduceat((src >= 1).astype(np.int64), offs[:-1]) == 0)
+        top = a.max(1)
+        t = np.log(np.exp(a - top[:, None]).sum(1)) - (a[np.arange(len(a)), np.clip(labels, 0, K1 - 1)] - top)
+        return np.where(ok, t, 0.0)
+    if family == "reliability":
+        if c[0] != "scores" or c[2] != 1:
+            return None
+        conf, _ = reliability_input(*c[:2], c[3])
+        return np.where((conf >= 0) & (conf <= 1), conf, 0.0)
+    det, match, gt, var = variance_input(c[0])
+    ok = np.ones(c[0], bool)
+    ok[list(VARIANCE_EXCLUDED) + [c[0] - 1]] = False
+    t = gt[np.where(ok, match, 0)]
+    sw, sh, tw, th = det[:, 2] - det[:, 0], det[:, 3] - det[:, 1], t[:, 2] - t[:, 0], t[:, 3] - t[:, 1]
+    with np.errstate(all="ignore"):
+        res = np.stack([10.0 * ((t[:, 0] + 0.5 * tw) - (det[:, 0] + 0.5 * sw)) / sw, 10.0 * ((t[:, 1] + 0.5 * th) - (det[:, 1] + 0.5 * sh)) / sh,
+                        5.0 * np.log(tw / sw), 5.0 * np.log(th / sh)], 1)
+        q = _seq(res * res / var[:, None], 1)
+    return np.where(ok, q, 0.0)
+
+
+def check_inputs():
+    """Host only: per family, the cases whose terms add up differently in ascending order and in the kernels' order."""
+    told = {}
+    for family, c in CASES:
+        t = host_terms(family, c)
+        if t is None:
+            continue
+        assert np.isfinite(t).all(), (family, c)
+        asc, dev = float(_seq(t)), float(two_pass_sum(family, t))
+        told.setdefault(family, []).append(asc != dev)
+        print(f"{case_name(family, c):28s} ascending {asc!r:24s} two-pass order {dev!r:24s} {'differ' if asc != dev else 'equal'}")
+    assert set(told) == {"temperature", "pool", "reliability", "variance"} and all(any(v) for v in told.values()), told
+    return told
+
+
+def main():
+    if "--check-inputs" in sys.argv:
+        check_inputs()
+        return
+    import proben_amd  # noqa: F401
+    path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(HERE, "stat_sums_parent.npz")
+    z, told = {}, {}
+    for family, c in CASES:
+        name = case_name(family, c)
+        f64, i64 = run_case(family, c)
+        items, bad, last = items_and_excluded(family, c, i64)
+        assert np.isfinite(f64).all(), (name, f64)
+        assert 0 < bad < items / 2 and last == items - 1, (name, items, bad, last)
+        z[name + "_f64"], z[name + "_i64"] = f64, i64
+        t = host_terms(family, c)
+        if t is not None:
+            # the host's terms in the kernels' order give the device's bits, so a difference from ascending order is the order's alone
+            assert float(two_pass_sum(family, t)) == float(f64[0]), (name, float(two_pass_sum(family, t)), float(f64[0]))
+            told.setdefault(family, []).append(float(_seq(t)) != float(f64[0]))
+            print(f"{name:28s} device {float(f64[0])!r:24s} host ascending {float(_seq(t))!r:24s} host two-pass order "
+                  f"{float(two_pass_sum(family, t))!r}", flush=True)
+    assert set(told) == {"temperature", "pool", "reliability", "variance"} and all(any(v) for v in told.values()), told
+    np.savez_compressed(path, **z)
+    print("wrote", path, os.path.getsize(path), "bytes,", len(CASES), "cases")
+
+
+if __name__ == "__main__":
+    main()
