@@ -327,6 +327,37 @@ int pe_pool_nll(const double* log_probs, const int32_t* row_source, int64_t num_
                 int32_t num_detectors, double* workspace, double* out, int32_t* out_flags /* [2] */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The fused detection as a full prediction: what phase 4 of the fusion kernel forms and pe_proben_fuse_batch_logp / _pooled drop.  Not in
+ * the reference.
+ * pe_proben_fuse_batch_posterior: the arguments of pe_proben_fuse_batch_pooled - row_source and pool_weights may be NULL TOGETHER, which is
+ *   the unpooled rule of pe_proben_fuse_batch_logp (num_detectors is then not looked at) - and three more outputs, indexed like out_scores
+ *   (image b's fused rows are [offsets[b], offsets[b] + out_counts[b])).  Same kernel (a template instantiation); out_boxes, out_scores,
+ *   out_classes, out_keep, out_counts and out_cluster (optional, with or without weights) are the bits of the entry point it stands for.
+ *   out_log_posterior f64 [Ntot, K + 1]: for a cluster of m >= 2 rows lq_j = (a_j - top) - log(tot), a_j the cluster's summed column (member
+ *     order, prior and pool weights included), top = max_j a_j, tot = sum_j exp(a_j - top) in column order - the quantities the score is made
+ *     of, so exp(lq_class) is the fused score up to rounding.  A cluster of one row and a passed-through row: the row's input log_probs, copied.
+ *   out_vars f64 [Ntot]: the variance of the fused box under the independence its box rule assumes, sum_t lambda_t^2 var_t with lambda_t the
+ *     weight the rule gives member t.  v-avg: 1.0 / wsum, wsum the box fusion's own sequential sum of 1 / var_t (= 1 / sum 1 / var);
+ *     s-avg: lambda_t = s_t / sum s; avg: lambda_t = 1 / m - both summed sequentially in cluster order (matches in sorted order, pivot last)
+ *     as (lambda_t * lambda_t) * var_t; argmax: the chosen member's variance.  A cluster of one and a passed-through row: the row's own.
+ *   out_members i32 [Ntot]: the rows in the cluster; 1 for a cluster of one and for a passed-through row.
+ *   Every element of a live fused row is written exactly once, by the thread that owns the cluster (the row, on passthrough); nothing is
+ *   written for an image with out_counts -1 or beyond out_counts[b] (fusion.fuse_batch pre-fills NaN / NaN / 0).  No atomics.
+ *   Checked before any device work, on top of every check of pe_proben_fuse_batch_pooled: row_source and pool_weights both NULL or both
+ *   set; the three new pointers non-NULL.
+ * ------------------------------------------------------------------------------------------- */
+int pe_proben_fuse_batch_posterior(const double* boxes, const double* scores, const double* log_probs, /* [Ntot,K+1] */
+                                   const double* variances, const int32_t* classes, const int32_t* row_source, /* [Ntot] or NULL */
+                                   const int32_t* offsets, const int32_t* row_counts, const int32_t* passthrough, int32_t num_images,
+                                   int32_t num_classes, int32_t max_rows_per_image, int32_t box_mode, double iou_thresh, double frame_w,
+                                   double frame_h, const double* log_prior, /* optional [K+1] */
+                                   const double* pool_weights,              /* DEVICE [num_detectors] or NULL */
+                                   int32_t num_detectors, double* out_boxes, float* out_scores, float* out_classes, int32_t* out_keep,
+                                   int32_t* out_counts, int32_t* out_cluster /* optional [Ntot] */,
+                                   double* out_log_posterior /* [Ntot,K+1] */, double* out_vars /* [Ntot] */,
+                                   int32_t* out_members /* [Ntot] */, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused convolution / GEMM: NHWC fp16 activations, [Cout][KH][KW][Cin] fp16 weights, fp32 accumulate
  * on MFMA, epilogue = + bias[Cout] (fp32) + residual + ReLU, fp16 (or fp32) NHWC output.
  * Replaces, per layer, detectron2.layers.Conv2d.forward (layers/wrappers.py:62-98) + FrozenBatchNorm2d

@@ -3,7 +3,7 @@
     python -m proben_amd.cli.calibration_report --dataset_path DATA/FLIR/val \\
         --predictions out/val_thermal_only_predictions.json out/val_early_fusion_predictions.json \\
         --calibration calibration.json [--bins 15] [--iou 0.5] [--on heldout|fitted|all] \\
-        [--score_fusion probEn --box_fusion v-avg] [--out report.json]
+        [--score_fusion probEn --box_fusion v-avg] [--fused-posterior] [--out report.json]
 
 --on heldout (the default) takes the dataset's images that are not among the calibration file's "fitted_image_ids"; `fitted` takes
 those, `all` every image.  A file fitted with --holdout 1.0 leaves nothing held out: that is refused, choose --on fitted or --on all.
@@ -21,6 +21,13 @@ When the file has "pool_weights" (fit_temperature --with-pool-weights): the "aft
 and the report prints the NLL per cluster of the fused posterior against the label of the fused box, at w = 1 and at the file's
 weights, over the clusters of two or more rows that probEn-log forms on the chosen images at the file's temperatures, prior and
 variance scales (fit_temperature.pool_clusters: the fit's own labelling; calibration.pool_nll, both in one launch).
+--fused-posterior (with --score_fusion probEn-log) judges the fused detections as full predictions (late_fusion with_posterior,
+pe_proben_fuse_batch_posterior), before and after: under "posterior" the NLL per fused row of the fused posterior against the label of
+the fused box (calibration.temperature_nll at T = 1 on the fused log-posterior) and ECE / MCE / Brier of its top label over all K + 1
+columns; under "variance" the Gaussian NLL per matched fused row and the 1-sigma / 2-sigma coverage of the fused boxes' residuals under
+the fused variance (calibration.variance_stats), as printed per detector.  The posterior figures go through the statistics the detectors'
+logits go through, which take float32: they are those of the float32 cast of the float64 fused log-posterior (6e-8 relative on a
+log-probability), renormalised - a report's precision, not the fusion's.  Only new keys: everything else is what it is without the flag.
 Rows that cannot be binned (a NaN score, a label outside the columns) are counted as "excluded" and printed, never dropped silently.
 
 What the detection-level figures are not.  A detection is "correct" when the ground-truth box it overlaps most, at IoU >= --iou, has
@@ -55,6 +62,9 @@ def parse(argv):
     p.add_argument("--on", choices=ON, default="heldout", help="which images: those the file was not fitted on, those it was, or all")
     p.add_argument("--score_fusion", default="probEn", help="score fusion of the fused detections (avg / max / probEn / probEn-log)")
     p.add_argument("--box_fusion", default="v-avg", help="box fusion of the fused detections (v-avg / s-avg / avg / argmax)")
+    p.add_argument("--fused-posterior", action="store_true",
+                   help="--score_fusion probEn-log: also report the fused posterior (NLL per row, top-label ECE / MCE / Brier) and the "
+                        "fused box variance (Gaussian NLL, 1-sigma / 2-sigma coverage)")
     p.add_argument("--out", default=None, help="write the report as JSON")
     p.add_argument("--device", default="cuda")
     args = p.parse_args(argv)
@@ -64,6 +74,8 @@ def parse(argv):
         p.error(f"--iou {args.iou} is not in [0, 1]")
     if not 2 <= len(args.predictions) <= 3:
         p.error(f"--predictions lists {len(args.predictions)} files: late fusion takes 2 or 3")
+    if args.fused_posterior and args.score_fusion != "probEn-log":
+        p.error(f"--fused-posterior belongs to --score_fusion probEn-log (got {args.score_fusion}): the other score fusions form no posterior")
     return args
 
 
@@ -160,18 +172,36 @@ def variance_report(pred, rows, gt_boxes, s, device):
     return out
 
 
-def fused_report(dets, names, method, gt, k, bins, iou, device, **calibrated):
-    """Reliability of the fused score of late_fusion(dets, method, **calibrated) on the chosen images."""
-    boxes, conf, cls, offsets = [], [], [], [0]
-    for r in late_fusion(dets, method, device, names=names, **calibrated):
+def fused_report(dets, names, method, gt, k, bins, iou, device, posterior=False, **calibrated):
+    """Reliability of the fused score of late_fusion(dets, method, **calibrated) on the chosen images.  posterior: plus "posterior"
+    (NLL per row and top-label reliability of the fused posterior, of its float32 cast: the statistics take float32 logits) and "variance" (the fused boxes' residuals under the fused variance)."""
+    boxes, conf, cls, offsets, lq, var = [], [], [], [0], [], []
+    for r in late_fusion(dets, method, device, names=names, with_posterior=posterior, **calibrated):
         if r is not None:
             boxes += np.asarray(r[0], dtype=np.float64).reshape(-1, 4).tolist()
             conf += r[1].double().tolist()
             cls += r[2].tolist()
+            if posterior:
+                lq.append(r[3])
+                var.append(r[4])
         offsets.append(len(boxes))
-    _, labels, _ = match_device(boxes, offsets, gt, iou, k, device)
+    db, labels, match = match_device(boxes, offsets, gt, iou, k, device)
     correct = labels == torch.tensor(cls, dtype=torch.float64, device=device).to(torch.int32)
-    return _figures(calibration.reliability_scores(torch.tensor(conf, dtype=torch.float64, device=device), correct, bins))
+    out = _figures(calibration.reliability_scores(torch.tensor(conf, dtype=torch.float64, device=device), correct, bins))
+    if posterior:
+        n = len(boxes)
+        out["posterior"] = {"rows": n, "nll": float("nan"), "top_label": None}
+        out["variance"] = {"rows": 0, "excluded": 0, "nll": float("nan"), "coverage": [float("nan")] * 2}
+        if n:
+            lg = torch.from_numpy(np.concatenate(lq).reshape(n, k + 1)).to(device)       # the fused log-posterior is its own logits at T = 1
+            nll, _ = calibration.temperature_nll(lg, labels, [1.0])
+            out["posterior"] = {"rows": n, "nll": float(nll[0]) / n, "top_label": _figures(calibration.reliability(lg, labels, 1.0, None, bins))}
+            hit = match >= 0
+            st = calibration.variance_stats(db[hit], match[hit], gt[0], torch.from_numpy(np.concatenate(var)).to(device)[hit], 1.0)
+            m = st["n"]
+            out["variance"] = {"rows": m, "excluded": st["excluded"], "nll": calibration.variance_nll(st, 1.0) / m if m else float("nan"),
+                               "coverage": [st["cover1"] / (4 * m), st["cover2"] / (4 * m)] if m else [float("nan")] * 2}
+    return out
 
 
 def pool_report(dets, names, records, ids, weights, iou, box_fusion, device, temperatures, class_prior, variance_scales):
@@ -213,6 +243,11 @@ def table(report):
     for tag in ("before", "after"):
         r = report["fused"][tag]
         rows.append(("fused", f"{tag} ({'/'.join(report['method'])})", str(r["rows"]), str(r["excluded"]), "", f(r["ece"]), f(r["mce"]), f(r["brier"]), "", ""))
+        if "posterior" in r and r["posterior"]["rows"]:       # no fused row: nothing to print (the keys hold NaN / None)
+            q, t, v = r["posterior"], r["posterior"]["top_label"], r["variance"]
+            rows.append(("fused", "  posterior, top label", str(q["rows"]), str(t["excluded"]), f(q["nll"]), f(t["ece"]), f(t["mce"]), f(t["brier"]), "", ""))
+            rows.append(("fused", "  fused box variance", str(v["rows"]), str(v["excluded"]), f(v["nll"]), "", "", "",
+                         f(v["coverage"][0]), f(v["coverage"][1])))
     width = [max(len(r[c]) for r in rows) for c in range(len(head))]
     return "\n".join("  ".join(x.ljust(w) if c < 2 else x.rjust(w) for c, (x, w) in enumerate(zip(r, width))).rstrip() for r in rows)
 
@@ -252,7 +287,8 @@ def main(cmd=None):
     logp = args.score_fusion == "probEn-log"
     prior = rec.get("class_prior") if logp else None
     pvals = None if "pool_weights" not in rec else calibration.resolve_pool_weights(rec["pool_weights"], names, args.calibration)
-    fuse = lambda **kw: fused_report(dets, args.predictions, method, gt, k, args.bins, args.iou, args.device, **kw)
+    fuse = lambda **kw: fused_report(dets, args.predictions, method, gt, k, args.bins, args.iou, args.device,
+                                     posterior=args.fused_posterior, **kw)
     report["fused"] = {"before": fuse(), "after": fuse(temperatures=temps, variance_scales=svals, class_prior=prior,
                                                        pool_weights=pvals if logp else None)}
     if pvals is not None:

@@ -27,6 +27,12 @@ written by `fit_temperature --with-variance` supplies them, and the run says so;
 --pool_weights 0.6,0.5 (by position) or thermal_only=0.6,early_fusion=0.5 (by name), with --score_fusion probEn-log on either route:
 one exponent per detector inside the fusion (the logarithmic opinion pool, pe_proben_fuse_batch_pooled) for detectors that share
 evidence.  Without the flag a --calibration file that carries "pool_weights" supplies them; 1,1 is the plain product bit for bit.
+
+--write_fused FILE, with --score_fusion probEn-log on either route: the fused detections leave as a prediction file of the schema the
+detectors' files have (late_fusion.fused_to_j1): class_logits = the fused log-posterior over all K + 1 columns, probs / scores / classes,
+vars = the variance of the fused box under its box rule.  Fused rows whose class is the background column are not detections and are
+not written; the run prints how many.  The file is a detector's file: name it val_<name>_predictions.json and list <name> in
+--detectors to fuse it with a further detector, or hand it to fit_temperature / calibration_report.
 """
 import json
 import os
@@ -80,12 +86,16 @@ def main(cmd=None):
                        out_eval_path=os.path.join(args.outfolder, "FLIR_probEn_eval.json"))
     if temps is not None:
         _warn_fitted(temps, [i for d in dets for i in d["image_id"]])
+    fused = [] if args.write_fused else None
     # every option is None unless it was asked for, and None is the callee's default
     res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
                                          det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev),
                                          temperatures=None if temps is None else temps["values"], names=files, class_prior=prior,
-                                         variance_scales=vscales, pool_weights=pool)
+                                         variance_scales=vscales, pool_weights=pool, fused_out=fused)
     _name_options(res, names, temps, prior, vscales, pool)
+    if fused is not None:
+        from ..late_fusion import fused_to_j1
+        _write_fused(args.write_fused, [fused_to_j1(dets, fused)], main_rank)
     if main_rank:
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
@@ -156,6 +166,23 @@ def _name_options(res, names, temps, prior, vscales, pool=None):
         res["pool_weights"] = dict(zip(names, pool))
 
 
+def _write_fused(path, parts, main_rank):
+    """--write_fused: this rank's (prediction dict, dropped rows) parts, in image order, gathered to rank 0 (rank order == dataset
+    order) and written as one prediction file."""
+    from ..late_fusion import J1_KEYS, write_j1
+    gathered = comm.gather(parts, dst=0)
+    if not main_rank:
+        return
+    parts = [p for g in gathered for p in g]
+    pred = {k: sum((p[k] for p, _ in parts), []) for k in J1_KEYS}
+    folder = os.path.dirname(path)
+    if folder:
+        os.makedirs(folder, exist_ok=True)
+    write_j1(path, pred)
+    print(f"fused detections: {path}: {sum(len(r) for r in pred['scores'])} rows on {len(pred['image'])} images written, "
+          f"{sum(d for _, d in parts)} background rows dropped")
+
+
 def _warn_fitted(temps, image_ids):
     """The calibration file records the images its temperatures were fitted on: say so when the evaluation includes them."""
     seen = temps["fitted"] & set(image_ids)
@@ -183,7 +210,7 @@ def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool
     import time
     import torch
     from ..data import PairFrames, resize_shortest_edge_shape
-    from ..late_fusion import fused_rows_device, predictions_to_j1, write_j1
+    from ..late_fusion import fused_device_to_j1, fused_rows_device, predictions_to_j1, write_j1
     from ..pipeline import FramePairPipeline, HostFeeder
     from ..predictor import DefaultPredictor
     from ..stream import FlirPairLoader, check_workers
@@ -211,7 +238,8 @@ def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool
         _warn_fitted(temps, [loader.items[i]["id"] for i in loader.mine])
     pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion,
                              temperatures=None if temps is None else temps["values"], class_prior=prior, variance_scales=vscales,
-                             pool_weights=pool)
+                             pool_weights=pool, with_posterior=bool(args.write_fused))
+    fused_parts = []
     j1 = [([], [], []) for _ in names]       # per detector: names, ids, instances
     rows = []
     feeder, feed_key, host = None, None, None
@@ -221,6 +249,8 @@ def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool
     def finish(p):
         dets, fused, batch = p
         rows.append(fused_rows_device(fused, batch.ids))        # the batch's one host synchronisation
+        if args.write_fused:
+            fused_parts.append(fused_device_to_j1(fused, batch.names, batch.ids))
         if args.write_predictions:
             for d, det, (nm, ids, insts) in zip(preds, dets, j1):
                 nm += batch.names
@@ -267,6 +297,8 @@ def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool
             if main_rank:
                 os.makedirs(pdir, exist_ok=True)
                 write_j1(os.path.join(pdir, f"val_{m}_predictions.json"), {k: sum((g[k] for g in gathered), []) for k in pred})
+    if args.write_fused:
+        _write_fused(args.write_fused, fused_parts, main_rank)
     res = {}
     if main_rank:
         print(f"one-pass: {stats['timed_pairs']} pairs timed, {stats['pairs_per_s']:.1f} pairs/s, GPU side waited on decode "

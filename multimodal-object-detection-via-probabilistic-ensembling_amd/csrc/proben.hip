@@ -35,7 +35,10 @@ struct ProbenArgs {
     const int32_t* row_source;    // POOL only: [Ntot] detector index of each row
     const double* pool_weights;   // POOL only: [num_detectors] fusion exponents
     int32_t num_detectors;        // POOL only
-    int32_t* out_cluster;         // POOL only, optional: [Ntot] output row of the cluster each input row ended in
+    int32_t* out_cluster;         // POOL / POST, optional: [Ntot] output row of the cluster each input row ended in
+    double* out_log_posterior;    // POST only: [Ntot, K+1] the fused rows' normalised log-posterior
+    double* out_vars;             // POST only: [Ntot] the fused boxes' variance
+    int32_t* out_members;         // POST only: [Ntot] rows in the cluster
 };
 
 // Sort rule shared with oracle/proben.py: NaN first, score descending, ties by ORIGINAL index
@@ -65,6 +68,13 @@ __device__ __forceinline__ bool precedes(double sa, int ia, double sb, int ib) {
 // sequential sum and takes the prior (W - 1) times, W the sequential sum of the members' weights.  1.0 * x is x and W is then the
 // integer m, so weights of 1.0 give the LOGP bits.  out_cluster goes through LDS (the clustering's dead geometry array gx1) so that
 // every input row is written once, by the thread that owns it.
+// POST (pe_proben_fuse_batch_posterior, LOGP only, with or without POOL): the fused row keeps what phase 4 forms and used to drop.
+// out_log_posterior[j] = (a_j - top) - log(tot), the K + 1 columns walked once more; out_vars = sum_t lambda_t^2 var_t, lambda_t the
+// weight the box rule gives member t (v-avg: 1 / wsum with the box fusion's own wsum); out_members = m.  The rows' variances are
+// staged (by sorted position) in the clustering's dead geometry array gy1 between phases 3 and 4, so phase 4 reads no more global
+// memory than it did; a cluster of one and a passed-through row copy their input log-posterior and variance.  Every element is
+// written once, by the thread that owns the cluster (or the row).  A template parameter: the other instantiations compile to what
+// they were.
 constexpr int kFuseThreads = 1024;
 
 __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int l) {
@@ -72,8 +82,9 @@ __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, i
     return ((unsigned long long)hi << 32) | lo;
 }
 
-template <bool BITS, bool LOGP, bool POOL>
+template <bool BITS, bool LOGP, bool POOL, bool POST>
 __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a) {
+    static_assert(LOGP || !POST, "the posterior output belongs to the log-posterior rule");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int ncl_s;
     const int img = blockIdx.x;
@@ -91,7 +102,12 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
             a.out_scores[o] = (float)a.scores[o];
             a.out_classes[o] = (float)a.classes[o];
             a.out_keep[o] = r;
-            if (POOL && a.out_cluster) a.out_cluster[o] = r;
+            if ((POOL || POST) && a.out_cluster) a.out_cluster[o] = r;
+            if (POST) {
+                for (int j = 0; j <= a.K; ++j) a.out_log_posterior[o * (a.K + 1) + j] = a.probs[o * (a.K + 1) + j];
+                a.out_vars[o] = a.vars[o];
+                a.out_members[o] = 1;
+            }
         }
         if (tid == 0) a.out_counts[img] = n;
         return;
@@ -259,10 +275,13 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
     __syncthreads();
     const int ncl = ncl_s;
     int* rcl = reinterpret_cast<int*>(gx1);      // POOL + out_cluster: sorted position -> output row of its cluster (gx1 is dead now)
-    if (POOL && a.out_cluster) {                 // block-uniform
+    double* gvar = gy1;                          // POST: sorted position -> the row's variance (gy1 is dead now)
+    const bool want_cluster = (POOL || POST) && a.out_cluster;      // block-uniform
+    if (want_cluster)
         for (int p = tid; p < n; p += kFuseThreads) rcl[p] = -1;
-        __syncthreads();
-    }
+    if (POST)
+        for (int p = tid; p < n; p += kFuseThreads) gvar[p] = a.vars[beg + ord[p]];
+    if (want_cluster || POST) __syncthreads();
     // ---- 4. fusion: one lane per cluster (cluster = matches in sorted order + the pivot LAST), output row = cluster index.
     // The per-cluster arithmetic is the sequence the reference runs per pivot (sums over the members in cluster order, the
     // normaliser summed over the columns in column order, first-maximum / first-NaN rules); it used to sit inside the pivot loop
@@ -277,7 +296,7 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
         }
         const int m = cnt + 1;
         const int piv_row = ord[pos];
-        if (POOL && a.out_cluster) {
+        if (want_cluster) {
             for (int t = 0; t < cnt; ++t) rcl[mem[t]] = k;
             rcl[pos] = k;
         }
@@ -286,8 +305,12 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
         double out_score = gsc[pos];
         double out_class = (double)gcls[pos];
         double out_coord[4];
+        const size_t o = (size_t)beg + k;
+        double out_var = POST ? gvar[pos] : 0.0;
         if (cnt == 0) {
             for (int c4 = 0; c4 < 4; ++c4) out_coord[c4] = coord(c4, pos);
+            if (POST)
+                for (int j = 0; j < L; ++j) a.out_log_posterior[o * L + j] = glog[(size_t)j * R + pos];
         } else {
             // ---------- score fusion ----------
             if (LOGP) {
@@ -320,6 +343,10 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
                 }
                 out_score = best;
                 out_class = (double)bi;
+                if (POST) {
+                    const double ltot = log(tot);
+                    for (int j = 0; j < L; ++j) a.out_log_posterior[o * L + j] = (column(j) - top) - ltot;
+                }
             } else if (L > 0) {
                 auto column = [&](int j) {       // exp of the cluster's summed log-probability of column j
                     double acc = 0.0;
@@ -373,11 +400,28 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
                     }
                     out_coord[c4] = acc;
                 }
+                if (POST) {
+                    if (a.box_mode == PE_BOX_VAVG) {
+                        out_var = 1.0 / wsum;
+                    } else {
+                        out_var = 0.0;
+                        for (int t = 0; t < m; ++t) {
+                            const int p = at(t);
+                            const double lam = weight(p) / wsum;
+                            out_var += (lam * lam) * gvar[p];
+                        }
+                    }
+                }
             } else if (a.box_mode == PE_BOX_AVG) {
                 for (int c4 = 0; c4 < 4; ++c4) {
                     double acc = 0.0;
                     for (int t = 0; t < m; ++t) acc += coord(c4, at(t));
                     out_coord[c4] = acc / (double)m;
+                }
+                if (POST) {
+                    const double lam = 1.0 / (double)m;
+                    out_var = 0.0;
+                    for (int t = 0; t < m; ++t) out_var += (lam * lam) * gvar[at(t)];
                 }
             } else {  // argmax: box of the first maximal score in cluster order
                 int bp = at(0);
@@ -389,15 +433,19 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
                     if (!bnan && (v != v || v > best)) { best = v; bp = p; bnan = v != v; }
                 }
                 for (int c4 = 0; c4 < 4; ++c4) out_coord[c4] = coord(c4, bp);
+                if (POST) out_var = gvar[bp];
             }
         }
-        const size_t o = (size_t)beg + k;
+        if (POST) {
+            a.out_vars[o] = out_var;
+            a.out_members[o] = m;
+        }
         a.out_scores[o] = (float)out_score;
         a.out_classes[o] = (float)out_class;
         a.out_keep[o] = piv_row;
         for (int c4 = 0; c4 < 4; ++c4) a.out_boxes[o * 4 + c4] = out_coord[c4];
     }
-    if (POOL && a.out_cluster) {
+    if (want_cluster) {
         __syncthreads();
         for (int p = tid; p < n; p += kFuseThreads) a.out_cluster[beg + ord[p]] = rcl[p];
     }
@@ -407,12 +455,16 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
 // pe_proben_fuse_batch / pe_proben_fuse_batch_logp: the argument checks, LDS sizing, clustering form, launch.  logp: a.probs holds the
 // K+1 log-posteriors (required), a.score_mode is PE_SCORE_PROBEN_LOGP and is not the caller's to choose.  pool (implies logp):
 // pe_proben_fuse_batch_pooled, a.row_source / a.pool_weights required, 8 more bytes of LDS per row for the staged weight.
-int fuse_impl(const char* what, bool logp, bool pool, ProbenArgs a, int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, void* stream) {
+// post (implies logp, pool = the caller gave row_source): pe_proben_fuse_batch_posterior, the three more outputs required.
+int fuse_impl(const char* what, bool logp, bool pool, bool post, ProbenArgs a, int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, void* stream) {
     PE_CHECK_ARG(num_images >= 0, "%s: num_images < 0", what);
     if (num_images == 0) return PE_OK;
     PE_CHECK_ARG(a.boxes && a.scores && (a.probs || !logp) && a.vars && a.classes && a.offsets, "%s: null input pointer", what);
     PE_CHECK_ARG(a.out_boxes && a.out_scores && a.out_classes && a.out_keep && a.out_counts, "%s: null output pointer", what);
     PE_CHECK_ARG(!pool || (a.row_source && a.pool_weights), "%s: null input pointer (row_source / pool_weights)", what);
+    PE_CHECK_ARG(!post || (!a.row_source == !a.pool_weights), "%s: row_source and pool_weights go together (both NULL = the unpooled rule)", what);
+    PE_CHECK_ARG(!post || (a.out_log_posterior && a.out_vars && a.out_members),
+                 "%s: null output pointer (out_log_posterior / out_vars / out_members)", what);
     PE_CHECK_ARG(!pool || (a.num_detectors >= 1 && a.num_detectors <= PE_POOL_MAX_DETECTORS), "%s: num_detectors %d not in [1,%d]", what,
                  a.num_detectors, PE_POOL_MAX_DETECTORS);
     PE_CHECK_ARG(logp || (a.score_mode >= 0 && a.score_mode <= 3), "%s: bad score_mode %d", what, a.score_mode);
@@ -442,9 +494,12 @@ int fuse_impl(const char* what, bool logp, bool pool, ProbenArgs a, int32_t num_
         return PE_ERR_UNSUPPORTED;
     }
     a.max_rows = R;
-    void (*kernel)(ProbenArgs) = pool ? (bits ? proben_fuse_kernel<true, true, true> : proben_fuse_kernel<false, true, true>)
-                                 : logp ? (bits ? proben_fuse_kernel<true, true, false> : proben_fuse_kernel<false, true, false>)
-                                        : (bits ? proben_fuse_kernel<true, false, false> : proben_fuse_kernel<false, false, false>);
+    void (*kernel)(ProbenArgs) =
+        post   ? (pool ? (bits ? proben_fuse_kernel<true, true, true, true> : proben_fuse_kernel<false, true, true, true>)
+                       : (bits ? proben_fuse_kernel<true, true, false, true> : proben_fuse_kernel<false, true, false, true>))
+        : pool ? (bits ? proben_fuse_kernel<true, true, true, false> : proben_fuse_kernel<false, true, true, false>)
+        : logp ? (bits ? proben_fuse_kernel<true, true, false, false> : proben_fuse_kernel<false, true, false, false>)
+               : (bits ? proben_fuse_kernel<true, false, false, false> : proben_fuse_kernel<false, false, false, false>);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
@@ -467,8 +522,8 @@ extern "C" int pe_proben_fuse_batch(const double* boxes, const double* scores, c
                                     int32_t* out_keep, int32_t* out_counts, void* stream) {
     ProbenArgs a{boxes, scores, probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
                  score_mode, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, nullptr, nullptr, nullptr, 0, nullptr};
-    return fuse_impl("pe_proben_fuse_batch", false, false, a, num_images, num_classes, max_rows_per_image, stream);
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    return fuse_impl("pe_proben_fuse_batch", false, false, false, a, num_images, num_classes, max_rows_per_image, stream);
 }
 
 extern "C" int pe_proben_fuse_batch_logp(const double* boxes, const double* scores, const double* log_probs,
@@ -479,8 +534,8 @@ extern "C" int pe_proben_fuse_batch_logp(const double* boxes, const double* scor
                                          float* out_scores, float* out_classes, int32_t* out_keep, int32_t* out_counts, void* stream) {
     ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
                  PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, nullptr, nullptr, 0, nullptr};
-    return fuse_impl("pe_proben_fuse_batch_logp", true, false, a, num_images, num_classes, max_rows_per_image, stream);
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    return fuse_impl("pe_proben_fuse_batch_logp", true, false, false, a, num_images, num_classes, max_rows_per_image, stream);
 }
 
 extern "C" int pe_proben_fuse_batch_pooled(const double* boxes, const double* scores, const double* log_probs,
@@ -493,6 +548,22 @@ extern "C" int pe_proben_fuse_batch_pooled(const double* boxes, const double* sc
                                            void* stream) {
     ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
                  PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, row_source, pool_weights, num_detectors, out_cluster};
-    return fuse_impl("pe_proben_fuse_batch_pooled", true, true, a, num_images, num_classes, max_rows_per_image, stream);
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, row_source, pool_weights, num_detectors, out_cluster, nullptr, nullptr, nullptr};
+    return fuse_impl("pe_proben_fuse_batch_pooled", true, true, false, a, num_images, num_classes, max_rows_per_image, stream);
+}
+
+extern "C" int pe_proben_fuse_batch_posterior(const double* boxes, const double* scores, const double* log_probs,
+                                              const double* variances, const int32_t* classes, const int32_t* row_source,
+                                              const int32_t* offsets, const int32_t* row_counts, const int32_t* passthrough,
+                                              int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, int32_t box_mode,
+                                              double iou_thresh, double frame_w, double frame_h, const double* log_prior,
+                                              const double* pool_weights, int32_t num_detectors, double* out_boxes, float* out_scores,
+                                              float* out_classes, int32_t* out_keep, int32_t* out_counts, int32_t* out_cluster,
+                                              double* out_log_posterior, double* out_vars, int32_t* out_members, void* stream) {
+    ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
+                 PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, row_source, pool_weights, num_detectors, out_cluster,
+                 out_log_posterior, out_vars, out_members};
+    return fuse_impl("pe_proben_fuse_batch_posterior", true, row_source != nullptr && pool_weights != nullptr, true, a, num_images,
+                     num_classes, max_rows_per_image, stream);
 }

@@ -11,6 +11,9 @@ K + 1 columns with the background column kept, normalised by a max-subtracted lo
 rule, defined on saturated rows and large clusters where "probEn" gives NaN, with an optional class prior (`class_prior`).
 `pool_weights` (one exponent w_d >= 0 per detector, "probEn-log" only) turns its product into the logarithmic opinion pool
 a_j = sum_t w_d(t) log p_t[j] - (W - 1) log prior_j (pe_proben_fuse_batch_pooled); every weight 1 is "probEn-log" bit for bit.
+`with_posterior` ("probEn-log" only, with or without pool weights) keeps what the fusion forms and the plain entry points drop: the
+fused rows' normalised log-posterior over all K + 1 columns, the variance of the fused box under its box rule and the size of the
+cluster (pe_proben_fuse_batch_posterior) - the fused detection as a full prediction, a valid "probEn-log" input itself.
 """
 import numpy as np
 import torch
@@ -51,9 +54,12 @@ def pool_weight_tensor(pool_weights, num_detectors, device):
     return torch.tensor(check_pool_weights(pool_weights, num_detectors, "pool_weights"), dtype=torch.float64).to(device)
 
 
-def _check_mode(score_fusion, class_prior, who, pool_weights=None):
+def _check_mode(score_fusion, class_prior, who, pool_weights=None, with_posterior=False):
     if score_fusion not in SCORE_MODES:
         raise ValueError(f"{who}: unknown score_fusion {score_fusion!r} (one of {', '.join(SCORE_MODES)})")
+    if with_posterior and score_fusion != LOGP:
+        raise ValueError(f"{who}: with_posterior belongs to score_fusion '{LOGP}' (got {score_fusion!r}): the other score fusions "
+                         "form no normalised posterior")
     if pool_weights is not None and score_fusion != LOGP:
         raise ValueError(f"{who}: pool_weights belong to score_fusion '{LOGP}' (got {score_fusion!r}): the other score fusions "
                          "have no pooled form")
@@ -64,7 +70,7 @@ def _check_mode(score_fusion, class_prior, who, pool_weights=None):
 
 def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="probEn", box_fusion="v-avg",
                max_rows=None, iou_thresh=0.5, frame=(FRAME_W, FRAME_H), row_counts=None, passthrough=None, log_probs=None,
-               class_prior=None, pool_weights=None, row_source=None):
+               class_prior=None, pool_weights=None, row_source=None, with_posterior=False):
     """Fuse B images in one launch.
 
     score_fusion "probEn-log": log_probs f64 [Ntot,K+1] (calibration.log_posteriors / pack_rows(log_posteriors=True)) replaces
@@ -72,6 +78,9 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
     pool_weights ("probEn-log" only; one w_d per detector or pool_weight_tensor's device tensor) with row_source i32 [Ntot] (each
     row's detector index): pe_proben_fuse_batch_pooled; the result then also holds "cluster" i32 [Ntot], the output row of the
     cluster each input row ended in (-1: it left the pool without one; -2 where nothing was written: counts == -1, padding).
+    with_posterior ("probEn-log" only): pe_proben_fuse_batch_posterior; the result then also holds "log_posterior" f64 [Ntot, K+1]
+    (the fused rows' normalised log-posterior), "vars" f64 [Ntot] (the fused boxes' variance under the box rule) and "members" i32
+    [Ntot] (rows in the cluster), indexed like "scores"; rows nothing was written to hold NaN / NaN / 0.
 
     boxes f64 [Ntot,4], scores f64 [Ntot], probs f64 [Ntot,K], variances f64 [Ntot],
     classes i32 [Ntot], offsets i32 [B+1] - all CUDA tensors, rows of each image already
@@ -79,7 +88,7 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
       boxes f64 [Ntot,4], scores f32 [Ntot], classes f32 [Ntot], keep i32 [Ntot], counts i32 [B];
     image b's fused rows are [offsets[b], offsets[b]+counts[b]).
     """
-    _check_mode(score_fusion, class_prior, "fuse_batch", pool_weights)
+    _check_mode(score_fusion, class_prior, "fuse_batch", pool_weights, with_posterior)
     logp = score_fusion == LOGP
     pool = pool_weights is not None
     if pool and (row_source is None or row_source.dim() != 1 or row_source.shape[0] != boxes.shape[0]):
@@ -119,9 +128,10 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
         "keep": torch.empty((ntot,), dtype=torch.int32, device=dev),
         "counts": torch.zeros((max(B, 1),), dtype=torch.int32, device=dev)[:B],
     }
-    name = "pe_proben_fuse_batch_pooled" if pool else "pe_proben_fuse_batch_logp" if logp else "pe_proben_fuse_batch"
+    name = ("pe_proben_fuse_batch_posterior" if with_posterior else "pe_proben_fuse_batch_pooled" if pool
+            else "pe_proben_fuse_batch_logp" if logp else "pe_proben_fuse_batch")
     head = (_lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(probs), _lib.ptr(variances), _lib.ptr(classes),
-            *([_lib.ptr(row_source)] if pool else []), _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows)
+            *([_lib.ptr(row_source) if pool else None] if pool or with_posterior else []), _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows)
     geometry = (BOX_MODES[box_fusion], float(iou_thresh), float(frame[0]), float(frame[1]))
     mode = geometry + (_lib.ptr(log_prior),) if logp else (SCORE_MODES[score_fusion],) + geometry
     tail = ()
@@ -129,6 +139,14 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
         mode += (_lib.ptr(weights), int(weights.numel()))
         out["cluster"] = torch.full((ntot,), -2, dtype=torch.int32, device=dev)     # -2: never written (padding, counts == -1)
         tail = (_lib.ptr(out["cluster"]),)
+    elif with_posterior:
+        mode += (None, 0)          # row_source and pool_weights NULL together: the unpooled rule
+        tail = (None,)
+    if with_posterior:
+        out["log_posterior"] = torch.full((ntot, K + 1), float("nan"), dtype=torch.float64, device=dev)
+        out["vars"] = torch.full((ntot,), float("nan"), dtype=torch.float64, device=dev)
+        out["members"] = torch.zeros((ntot,), dtype=torch.int32, device=dev)
+        tail += (_lib.ptr(out["log_posterior"]), _lib.ptr(out["vars"]), _lib.ptr(out["members"]))
     st = getattr(_lib.lib(), name)(*head, *mode, _lib.ptr(out["boxes"]), _lib.ptr(out["scores"]), _lib.ptr(out["classes"]),
                                    _lib.ptr(out["keep"]), _lib.ptr(out["counts"]), *tail, _lib.stream())
     _lib.check(st, name)
@@ -309,7 +327,7 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, varian
 
 
 def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=0.5, temperatures=None,
-                    class_prior=None, variance_scales=None, pool_weights=None):
+                    class_prior=None, variance_scales=None, pool_weights=None, with_posterior=False):
     """Device-to-device stage fusion: `dets` = the result dicts of 2 or 3 detectors run on the SAME batch
     (rcnn.GeneralizedRCNN.forward_batch).  Packs their detections into ProbEn rows (classes <= max_class,
     like the JSON writer demo_FLIR_save_predictions.py:148-155), applies the reference's per-image case
@@ -322,11 +340,13 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     member boxes of box_fusion "v-avg" and nothing else, so every other box rule and the NMS route give the bits they gave.
     pool_weights (one w per detector or pool_weight_tensor's device tensor, "probEn-log" only): pe_proben_pack_pooled +
     pe_proben_fuse_batch_pooled; the result then also holds "cluster" and "row_source".
+    with_posterior ("probEn-log" only): the fusion is pe_proben_fuse_batch_posterior and the result also holds fuse_batch's
+    "log_posterior", "vars" and "members".
     No host synchronisation.  Returns a dict: boxes f64 [B*S,4], scores f32, classes f32, counts i32 [B],
     offsets i32 [B], stride S = len(dets) * D."""
     # the box heads' candidate-cap bookkeeping travels with the result (no kernel here): check_candidate_overflow() looks
     # at it at the consumer's first host synchronisation
-    _check_mode(score_fusion, class_prior, "fuse_detections", pool_weights)
+    _check_mode(score_fusion, class_prior, "fuse_detections", pool_weights, with_posterior)
     overflow_src = [(d["cand_total"], d["cand_max"]) for d in dets if "cand_total" in d]
     B, D = dets[0]["scores"].shape
     S = len(dets) * D
@@ -352,7 +372,7 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
                 "offsets": ooff, "stride": S, "in_counts": ocnt, "nms_route": True, "cand_overflow_src": overflow_src}
     out = fuse_batch(ob, os_, op, ov, oc, ooff, score_fusion, box_fusion, max_rows=S, iou_thresh=iou_thresh,
                      row_counts=ocnt, passthrough=osingle, log_probs=olp[0] if logp else None, class_prior=class_prior,
-                     pool_weights=pool_weights, row_source=osrc)
+                     pool_weights=pool_weights, row_source=osrc, with_posterior=with_posterior)
     if osrc is not None:
         out["row_source"] = osrc
     out["offsets"], out["stride"], out["in_counts"] = ooff, S, ocnt

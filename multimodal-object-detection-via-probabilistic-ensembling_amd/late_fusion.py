@@ -67,7 +67,7 @@ def _info(det, i):
 
 
 def late_fusion(dets, method, device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None,
-                pool_weights=None):
+                pool_weights=None, with_posterior=False):
     """dets: 2 or 3 J1 dicts over the same images (order = detector order).  Returns per-image
     (boxes float64 [m,4] | None, scores f32, classes f32); None = skipped image (no detector fired).
     Case split of demo_probEn.py:237-267: 0 detectors -> skip, 1 -> passthrough, >= 2 -> fusion of the
@@ -80,8 +80,11 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
     variance_scales (one s per detector): every file's vars are multiplied by s in float64 (calibration.scale_j1_vars), the single
     multiply of the device route's pe_proben_pack_calibrated, so both routes fuse identical variances.
     pool_weights (one w per detector, "probEn-log" only): the pooled rule of pe_proben_fuse_batch_pooled; a row's detector is its
-    file's position in dets, what pe_proben_pack_pooled writes on the device route."""
-    F._check_mode(method[0], class_prior, "late_fusion", pool_weights)
+    file's position in dets, what pe_proben_pack_pooled writes on the device route.
+    with_posterior ("probEn-log" only): every per-image result is a 6-tuple, the three above plus (log_posterior f64 [m, K+1], vars f64
+    [m], members i32 [m]) of pe_proben_fuse_batch_posterior; a passed-through image takes its log-posterior from the calibrated file
+    ("log_probs") and its vars from the scaled file, what the device route's passthrough copies."""
+    F._check_mode(method[0], class_prior, "late_fusion", pool_weights, with_posterior)
     if pool_weights is not None:
         from . import calibration
         pool_weights = calibration.check_pool_weights(pool_weights, len(dets), "late_fusion")
@@ -112,6 +115,10 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
             x = live[0]
             results[i] = (np.array(x["bbox"], dtype=np.float64), torch.tensor(x["score"], dtype=torch.float32),
                           torch.tensor(x["class"], dtype=torch.float32))
+            if with_posterior:
+                m = len(x["bbox"])
+                results[i] += (np.asarray(x["log_prob"], dtype=np.float64).reshape(m, -1),
+                               np.asarray(x["vars"], dtype=np.float64).reshape(m), np.ones(m, dtype=np.int32))
             continue
         batch.append(infos if pool_weights is not None else live)      # pack_infos skips the empty ones; the positions stay
         where.append(i)
@@ -124,20 +131,86 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
             if logp and pool_weights is not None:
                 b, s, p, v, c, offs, lp, src = F.pack_infos(batch, device, with_log_probs=True, with_sources=True)
                 out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior,
-                                   pool_weights=pool_weights, row_source=src)
+                                   pool_weights=pool_weights, row_source=src, with_posterior=with_posterior)
             elif logp:
                 b, s, p, v, c, offs, lp = F.pack_infos(batch, device, with_log_probs=True)
-                out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior)
+                out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior,
+                                   with_posterior=with_posterior)
             else:
                 b, s, p, v, c, offs = F.pack_infos(batch, device)
                 out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1])
             cnt = out["counts"].cpu().numpy()
             ob, os_, oc = out["boxes"].cpu().numpy(), out["scores"].cpu(), out["classes"].cpu()
             oh = offs.cpu().numpy()
+            post = [out[k].cpu().numpy() for k in ("log_posterior", "vars", "members")] if with_posterior else []
             for j, i in enumerate(where):
                 sl = slice(oh[j], oh[j] + cnt[j])
-                results[i] = (ob[sl], os_[sl], oc[sl])
+                results[i] = (ob[sl], os_[sl], oc[sl]) + tuple(x[sl] for x in post)
     return results
+
+
+def _fused_j1_rows(out, boxes, scores, classes, log_posterior, variances):
+    """One image's fused rows appended to the J1 lists of `out`; returns the background rows left out."""
+    if len(scores) == 0:
+        for key in ("boxes", "scores", "classes", "class_logits", "probs", "vars"):
+            out[key].append([])
+        return 0
+    lq = np.asarray(log_posterior, dtype=np.float64).reshape(len(scores), -1)
+    k = lq.shape[1] - 1
+    cls = np.asarray(classes).astype(np.int64)
+    keep = np.nonzero(cls != k)[0]
+    out["boxes"].append(np.asarray(boxes, dtype=np.float64).reshape(-1, 4)[keep].tolist())
+    out["scores"].append([float(x) for x in np.asarray(scores, dtype=np.float32)[keep]])
+    out["classes"].append(cls[keep].tolist())
+    out["class_logits"].append(lq[keep].tolist())
+    out["probs"].append(np.exp(lq[keep, :k]).tolist())
+    out["vars"].append([[float(v)] for v in np.asarray(variances, dtype=np.float64)[keep]])
+    return len(cls) - len(keep)
+
+
+def fused_to_j1(dets, fused):
+    """The fused detections of late_fusion(dets, ..., with_posterior=True) as a prediction dict (J1 schema) over the same images - a
+    detector's file in its own right, so a fusion can be cascaded, refitted or reported on.  class_logits = the fused log-posterior
+    (softmax(class_logits / 1) is the fused posterior: a valid "probEn-log" input at T = 1), probs = exp of its first K columns,
+    scores / classes = the float32 score and the class the fusion wrote, vars = [[the fused box's variance]]; image / image_id are
+    dets[1]'s, as the driver pairs them.  A skipped image (no detector fired) gets empty lists.  Rows whose fused class is the
+    background column K are not detections and are not written.  Returns (the dict, the number of background rows dropped)."""
+    ref = dets[1] if len(dets) > 1 else dets[0]
+    out = {k: [] for k in J1_KEYS}
+    dropped = 0
+    for i, r in enumerate(fused):
+        out["image"].append(ref["image"][i])
+        out["image_id"].append(ref["image_id"][i])
+        if r is None:
+            for k in ("boxes", "scores", "classes", "class_logits", "probs", "vars"):
+                out[k].append([])
+            continue
+        if len(r) != 6:
+            raise ValueError("fused_to_j1: the fused rows carry no posterior (late_fusion(..., with_posterior=True) writes it)")
+        dropped += _fused_j1_rows(out, r[0], r[1].numpy() if isinstance(r[1], torch.Tensor) else r[1],
+                                  r[2].numpy() if isinstance(r[2], torch.Tensor) else r[2], r[3], r[4])
+    return out, dropped
+
+
+def fused_device_to_j1(fused, file_names, image_ids):
+    """fused_to_j1 for the device route: `fused` = the result of fusion.fuse_detections(..., with_posterior=True) on one batch,
+    file_names / image_ids the batch's.  The same dict the file route builds from the same detections; synchronises (the rows leave
+    for the host).  Returns (the dict, the number of background rows dropped)."""
+    if "log_posterior" not in fused:
+        raise ValueError("fused_device_to_j1: the fused rows carry no posterior (fuse_detections(..., with_posterior=True) writes it)")
+    S = fused["stride"]
+    cnt = fused["counts"].cpu().numpy()
+    host = {k: fused[k].cpu().numpy() for k in ("boxes", "scores", "classes", "log_posterior", "vars")}
+    out = {k: [] for k in J1_KEYS}
+    dropped = 0
+    for b, (name, iid) in enumerate(zip(file_names, image_ids)):
+        out["image"].append(name)
+        out["image_id"].append(iid)
+        if cnt[b] < 0:
+            raise RuntimeError(f"fused_device_to_j1: image {name} has more rows than the fusion's bound")
+        sl = slice(b * S, b * S + int(cnt[b]))
+        dropped += _fused_j1_rows(out, *(host[k][sl] for k in ("boxes", "scores", "classes", "log_posterior", "vars")))
+    return out, dropped
 
 
 def fused_clusters(dets, box_fusion="v-avg", device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None):
@@ -190,23 +263,28 @@ def fused_clusters(dets, box_fusion="v-avg", device="cuda", temperatures=None, n
 
 def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="", image_hw=None, device="cuda",
                                    img_folder="../../../Datasets/FLIR/val/thermal_8_bit/", temperatures=None, names=None,
-                                   class_prior=None, variance_scales=None, pool_weights=None):
+                                   class_prior=None, variance_scales=None, pool_weights=None, fused_out=None):
     """Same call as the reference (demo_probEn.py:198).  `image_hw`: {image_id: (H, W)} from the dataset
     json (the reference re-reads every thermal JPEG just for its shape); default 512 x 640 (FLIR).
     `img_folder`: the prefix the reference hard-codes into the `file_name` it hands to the evaluator (:200,271).
+    `fused_out`: a list; when given ("probEn-log" only) the fusion keeps its posterior and the per-image 6-tuples of late_fusion are
+    appended to it, for fused_to_j1 - the evaluator receives what it receives without it.
     What the evaluator receives per image is pinned by tests/golden/p5_cases.json (the reference's function run with a recording
     evaluator): tests/test_pipeline_gpu.py::test_late_fusion_driver_reproduces_the_references_records."""
     evaluator.reset()
     print("Method: ", method)
     start = time.time()
     dets = [det_1, det_2] + ([det_3] if det_3 else [])
-    fused = late_fusion(dets, method, device, temperatures, names, class_prior, variance_scales, pool_weights)
+    fused = late_fusion(dets, method, device, temperatures, names, class_prior, variance_scales, pool_weights,
+                        with_posterior=fused_out is not None)
+    if fused_out is not None:
+        fused_out.extend(fused)
     for i, r in enumerate(fused):
         if r is None:
             continue
         iid = det_2["image_id"][i]
         H, W = (image_hw or {}).get(iid, (512, 640))
-        boxes, scores, classes = r
+        boxes, scores, classes = r[:3]
         inst = Instances((H, W))
         inst.pred_boxes = Boxes(torch.as_tensor(np.asarray(boxes), dtype=torch.float32).reshape(-1, 4))
         inst.scores = scores

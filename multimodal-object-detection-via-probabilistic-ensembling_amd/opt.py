@@ -47,7 +47,13 @@ def config_parser(cmd=None):
                    help="demo_probEn --score_fusion probEn-log: one pooling weight per --detectors entry, 'a,b[,c]' by position or "
                         "'name=a,name=b' by name (a_j = sum_t w_d(t) log p_t[j]: the logarithmic opinion pool); default: the calibration "
                         "file's pool_weights if it has them (fit_temperature --with-pool-weights), else the plain product")
+    p.add_argument("--write_fused", type=str, default=None, metavar="FILE",
+                   help="demo_probEn --score_fusion probEn-log (either route): write the fused detections as a prediction file (the "
+                        "schema of val_<method>_predictions.json: class_logits = the fused log-posterior, vars = the fused box's "
+                        "variance), a detector's file for a later fusion, fit_temperature or calibration_report")
     args = p.parse_args(cmd) if cmd is not None else p.parse_args()
+    if args.write_fused is not None and args.score_fusion != "probEn-log":
+        p.error(f"--write_fused belongs to --score_fusion probEn-log (got {args.score_fusion}): the other score fusions form no posterior")
     if args.pool_weights is not None and args.score_fusion != "probEn-log":
         p.error(f"--pool_weights belongs to --score_fusion probEn-log (got {args.score_fusion})")
     if args.class_prior is not None:

@@ -23,7 +23,7 @@ class FramePairPipeline:
 
     def __init__(self, models, score_fusion="probEn", box_fusion="v-avg", max_class=2, concurrent=True,
                  staggered=False, stagger_stage=4, fuse=True, temperatures=None, class_prior=None, variance_scales=None,
-                 pool_weights=None):
+                 pool_weights=None, with_posterior=False):
         self.models = list(models)
         self.fuse = fuse and len(self.models) > 1   # a single detector has nothing to fuse (configs[1])
         self.method = (score_fusion, box_fusion)
@@ -34,7 +34,9 @@ class FramePairPipeline:
             raise ValueError(f"FramePairPipeline: {len(self.temperatures)} temperatures for {len(self.models)} detectors")
         # score_fusion "probEn-log": ProbEn on log_softmax(class_logits / T) with the background column kept (pe_proben_pack_log_posteriors,
         # pe_proben_fuse_batch_logp); T = 1 without temperatures; class_prior = K + 1 probabilities (background last) or None = uniform
-        F._check_mode(score_fusion, class_prior, "FramePairPipeline", pool_weights)
+        F._check_mode(score_fusion, class_prior, "FramePairPipeline", pool_weights, with_posterior)
+        # "probEn-log" only: the fused rows keep their log-posterior, box variance and cluster size (pe_proben_fuse_batch_posterior)
+        self.with_posterior = bool(with_posterior)
         # one w per detector ("probEn-log" only): the pooled rule (pe_proben_pack_pooled, pe_proben_fuse_batch_pooled); None = the product
         from .calibration import check_pool_weights
         self.pool_weights = check_pool_weights(pool_weights, len(self.models), "FramePairPipeline")
@@ -143,7 +145,8 @@ class FramePairPipeline:
         if self.pool_weights is not None and self._pool is None:
             self._pool = F.pool_weight_tensor(self.pool_weights, len(self.pool_weights), dets[0]["scores"].device)
         return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class, temperatures=self.temperatures,
-                                 class_prior=self._log_prior, variance_scales=self.variance_scales, pool_weights=self._pool)
+                                 class_prior=self._log_prior, variance_scales=self.variance_scales, pool_weights=self._pool,
+                                 with_posterior=self.with_posterior)
 
 
 class HostFeeder:

@@ -1,0 +1,432 @@
+"""The fused detection as a full prediction on the GPU: pe_proben_fuse_batch_posterior (log-posterior, box variance, cluster size)
+against the np.longdouble restatement of tests/test_posterior_cpu.py, byte for byte against the entry points it stands for, a cascade
+((A, B), C) against the direct three-way fusion, and the routes (fuse_detections, late_fusion, demo_probEn --write_fused,
+calibration_report --fused-posterior).  The comparator is never the code under test; clusters come from oracle.proben.order_desc plus
+the greedy rule (tests/test_proben_logp_gpu.py::_clusters).  u = 2^-53."""
+import json
+
+import numpy as np
+import pytest
+import torch
+
+from test_posterior_cpu import BOX, LD, U, restate, var_bound
+
+pytestmark = pytest.mark.gpu
+
+POOL = np.array([0.6, 0.5])
+
+
+def _ulp32(x):
+    x = np.abs(np.asarray(x, np.float64))
+    return np.exp2(np.maximum(np.floor(np.log2(np.maximum(x, 2.0 ** -126))), -126.0) - 23.0)
+
+
+def _log_softmax(lg):
+    d = lg - lg.max(1, keepdims=True)
+    return d - np.log(np.exp(d).sum(1, keepdims=True))
+
+
+# anchors 70 x 62 apart hold boxes of 60 x 50 jittered by <= 2 px: members of one anchor overlap with IoU > 0.8, anchors never meet
+ANCHORS = [(4 + 70 * ix, 4 + 62 * iy) for iy in range(8) for ix in range(9)]
+
+
+def _image(rng, K1, sizes):
+    """One image's rows (shuffled): an anchor per entry of `sizes`, that many rows of one class on it, from detectors 0 / 1 at random.
+    Log-posteriors are float64 log_softmax of logits with margins from flat to saturated (up to ~40)."""
+    K = K1 - 1
+    n = sum(sizes)
+    boxes, cls = np.empty((n, 4)), np.empty(n, np.int32)
+    r = 0
+    for a, size in zip(rng.permutation(len(ANCHORS))[:len(sizes)], sizes):
+        x, y = ANCHORS[a]
+        boxes[r:r + size] = np.array([x, y, x + 60.0, y + 50.0]) + rng.uniform(-2.0, 2.0, (size, 4))
+        cls[r:r + size] = rng.integers(0, K)
+        r += size
+    lg = rng.normal(0.0, 3.0, (n, K1))
+    lg[np.arange(n), cls] += rng.uniform(2.0, 12.0, n) * rng.choice([1.0, 3.0], n)
+    lp = _log_softmax(lg)
+    perm = rng.permutation(n)
+    boxes, cls, lp = boxes[perm], cls[perm], lp[perm]
+    return {"boxes": boxes, "classes": cls, "lp": lp, "scores": np.exp(lp[np.arange(n), cls]), "vars": rng.uniform(0.5, 4.0, n),
+            "src": rng.integers(0, 2, n).astype(np.int32)}
+
+
+def _sizes(total):
+    out, k = [], 0
+    while sum(out) < total:
+        out.append(min(1 + k % 6, total - sum(out)))          # clusters of 1 .. 6 rows
+        k += 1
+    return out
+
+
+_SETS = {}
+
+
+def image_set(K1):
+    """Images of 1, 2, 64 and 65 rows (65 crosses the 64-row word of the bit matrices), one of 0 rows, one passed through (5 rows) and
+    one of 70 rows for the launches whose bound is 65 (counts == -1).  Computed once per K + 1 and left unchanged."""
+    if K1 not in _SETS:
+        rng = np.random.default_rng(1000 + K1)
+        imgs = [_image(rng, K1, [1]), _image(rng, K1, [2]), _image(rng, K1, _sizes(64)), _image(rng, K1, _sizes(65)), _image(rng, K1, []),
+                _image(rng, K1, [2, 1, 2]), _image(rng, K1, _sizes(70))]
+        _SETS[K1] = (imgs, [0, 0, 0, 0, 0, 1, 0])
+    return _SETS[K1]
+
+
+def _launch(imgs, passthrough, box, max_rows, prior=None, pool=False, with_posterior=True):
+    from proben_amd import fusion as F
+    cat = lambda k, dt: torch.from_numpy(np.ascontiguousarray(np.concatenate([i[k] for i in imgs]).astype(dt))).cuda()  # noqa: E731
+    offs = torch.tensor(np.cumsum([0] + [len(i["scores"]) for i in imgs]), dtype=torch.int32).cuda()
+    out = F.fuse_batch(cat("boxes", np.float64), cat("scores", np.float64), None, cat("vars", np.float64), cat("classes", np.int32), offs,
+                       "probEn-log", box, max_rows=max_rows, log_probs=cat("lp", np.float64), class_prior=prior,
+                       passthrough=None if passthrough is None else torch.tensor(passthrough, dtype=torch.int32).cuda(),
+                       pool_weights=POOL.tolist() if pool else None, row_source=cat("src", np.int32) if pool else None,
+                       with_posterior=with_posterior)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}, offs.cpu().numpy()
+
+
+# ---- 1. parity with the restatement ---------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("box", BOX)
+@pytest.mark.parametrize("K1", [2, 4, 63])
+def test_parity_with_the_restatement(K1, box):
+    """Every fused row of pe_proben_fuse_batch_posterior against test_posterior_cpu.restate on the image's own (reference) clustering,
+    with and without a non-uniform prior, with and without pool weights (0.6, 0.5); bound 65 rows, so the 70-row image gives counts -1.
+      lq:   |lq_j - (a_j - logsumexp(a))| <= (D_j + T + 2 |log tot| + |lq_j|) u, absolute (restate's docstring);
+      vars: relative (m + 3) u for v-avg, (3 m + 4) u for s-avg / avg, exact for argmax and single rows (var_bound);
+      members: exact.  Rows nothing was written to keep the pre-fill NaN / NaN / 0."""
+    from test_proben_logp_gpu import _clusters
+    imgs, passthrough = image_set(K1)
+    rng = np.random.default_rng(K1)
+    prior = rng.dirichlet(np.full(K1, 2.0)) + 0.01
+    prior = prior / prior.sum()
+    sizes_seen = set()
+    for use_prior in (False, True):
+        for pool in (False, True):
+            out, offs = _launch(imgs, passthrough, box, 65, prior.tolist() if use_prior else None, pool)
+            lprior = np.log(prior / prior.sum()) if use_prior else None
+            worst_lq = worst_var = 0.0
+            assert out["counts"].tolist()[4:] == [0, 5, -1]
+            written = np.zeros(offs[-1], bool)
+            for i, im in enumerate(imgs[:6]):
+                o = offs[i]
+                if passthrough[i]:
+                    cl = [(r, [r]) for r in range(len(im["scores"]))]
+                else:
+                    cl = _clusters(im["boxes"], im["scores"], im["classes"].astype(np.float64))
+                assert out["counts"][i] == len(cl), (i, out["counts"][i], len(cl))
+                np.testing.assert_array_equal(out["keep"][o:o + len(cl)], [p for p, _ in cl])
+                for r, (piv, mem) in enumerate(cl):
+                    m = len(mem)
+                    sizes_seen.add(m)
+                    written[o + r] = True
+                    assert out["members"][o + r] == m
+                    lq, _, v, bound = restate(im["lp"], im["boxes"], im["scores"], im["vars"], mem, box, lprior, POOL[im["src"]] if pool else None)
+                    got_lq, got_v = out["log_posterior"][o + r], out["vars"][o + r]
+                    if m == 1:
+                        assert got_lq.tobytes() == im["lp"][piv].tobytes() and got_v == im["vars"][piv]
+                        continue
+                    err = np.abs(got_lq.astype(LD) - lq).astype(np.float64)
+                    tol = bound * U
+                    worst_lq = max(worst_lq, float((err / tol).max()))
+                    assert (err <= tol).all(), (i, r, m, err / U, bound)
+                    vb = var_bound(box, m)
+                    rel = float(abs(LD(got_v) - v) / v)
+                    if vb == 0:
+                        assert got_v == float(v)
+                    else:
+                        worst_var = max(worst_var, rel / (vb * U))
+                        assert rel <= vb * U, (i, r, m, rel / U, vb)
+            assert np.isnan(out["log_posterior"][~written]).all() and np.isnan(out["vars"][~written]).all() and (out["members"][~written] == 0).all()
+            assert (out["members"][written] >= 1).all() and np.isfinite(out["log_posterior"][written]).all()
+            print(f"K+1={K1} {box} prior={use_prior} pool={pool}: largest lq error {worst_lq:.3f} of its bound, largest variance error "
+                  f"{worst_var:.3f} of its bound")
+    assert {1, 2, 3, 4, 5, 6} <= sizes_seen, sizes_seen
+
+
+# ---- 2. consistency with the existing entry points ---------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("pool", [False, True])
+@pytest.mark.parametrize("box", ["v-avg", "s-avg"])
+def test_plain_outputs_are_the_existing_entry_points_bytes(box, pool):
+    """boxes, scores, classes, keep, counts (and cluster) of the new entry point equal pe_proben_fuse_batch_logp / _pooled on the same input
+    byte for byte, in both clustering forms (bound = the longest image: bit matrices; 1100: the sequential walk); the posterior outputs
+    do not depend on the form either; float32(exp(lq[class])) is within one float32 ulp of the score; the same input twice gives the
+    same bytes."""
+    imgs, passthrough = image_set(4)
+    prior = [0.3, 0.2, 0.1, 0.4]
+    first = None
+    for bound in (None, 1100):
+        new, offs = _launch(imgs, passthrough, box, bound, prior, pool)
+        old, _ = _launch(imgs, passthrough, box, bound, prior, pool, with_posterior=False)
+        again, _ = _launch(imgs, passthrough, box, bound, prior, pool)
+        assert new["counts"].tobytes() == old["counts"].tobytes() and (new["counts"] >= 0).all() and new["counts"].sum() > 60
+        assert set(new) - set(old) == {"log_posterior", "vars", "members"}
+        if pool:
+            assert new["cluster"].tobytes() == old["cluster"].tobytes()
+        live = np.concatenate([np.arange(offs[i], offs[i] + new["counts"][i]) for i in range(len(imgs))])
+        for k in ("boxes", "scores", "classes", "keep"):
+            assert new[k][live].tobytes() == old[k][live].tobytes(), k
+        for k in ("boxes", "scores", "classes", "keep", "log_posterior", "vars", "members"):
+            assert new[k][live].tobytes() == again[k][live].tobytes(), k
+        cls = new["classes"][live].astype(np.int64)
+        back = np.exp(new["log_posterior"][live, cls]).astype(np.float32)
+        assert (np.abs(back.astype(np.float64) - new["scores"][live].astype(np.float64)) <= _ulp32(new["scores"][live])).all()
+        if first is None:
+            first = new
+        else:
+            for k in ("boxes", "scores", "classes", "keep", "log_posterior", "vars", "members"):
+                assert new[k][live].tobytes() == first[k][live].tobytes(), k
+
+
+# ---- 3. cascade ---------------------------------------------------------------------------------------------------------------------
+
+def _cascade_detectors():
+    """Three detectors on two images of six objects each (12 objects on a 200-px grid inside the 640 x 512 frame, boxes about 60 x 80):
+    each detector sees every object once, jittered by <= 2 px (member pairs IoU > 0.85, objects never overlap), own-class probability
+    >= 0.6, variances in [0.5, 4].  J1 dicts with float32 logits, as a detector's file carries them."""
+    rng = np.random.default_rng(31)
+    grid = [(20.0 + 200 * ix, 20.0 + 200 * iy) for iy in range(2) for ix in range(3)]
+    cls = [rng.integers(0, 3, 6) for _ in range(2)]
+    dets = []
+    for _ in range(3):
+        d = {k: [] for k in ("image", "boxes", "scores", "classes", "image_id", "class_logits", "probs", "vars")}
+        for b in range(2):
+            order = rng.permutation(6)
+            boxes = np.array([[grid[o][0], grid[o][1], grid[o][0] + 60, grid[o][1] + 80] for o in order]) + rng.uniform(-2, 2, (6, 4))
+            c = cls[b][order]
+            lg = rng.uniform(-1.0, 0.0, (6, 4)).astype(np.float32)
+            lg[np.arange(6), c] = np.float32(2.0) + rng.uniform(0, 4, 6).astype(np.float32)      # own p >= e^2 / (e^2 + 3) = 0.71
+            p = np.exp(_log_softmax(lg.astype(np.float64)))
+            assert (p[np.arange(6), c] >= 0.6).all()
+            d["image"].append(f"c{b}.jpeg")
+            d["image_id"].append(b)
+            d["boxes"].append(boxes.tolist())
+            d["scores"].append(p[np.arange(6), c].tolist())
+            d["classes"].append(c.tolist())
+            d["class_logits"].append(lg.tolist())
+            d["probs"].append(p[:, :3].tolist())
+            d["vars"].append(rng.uniform(0.5, 4.0, (6, 1)).tolist())
+        dets.append(d)
+    return dets
+
+
+@pytest.mark.parametrize("with_prior", [False, True])
+def test_cascade_equals_the_three_way_fusion(with_prior):
+    """Stage one fuses (A, B) with probEn-log / v-avg into a prediction dict (fused_to_j1), stage two fuses (F, C); posteriors, boxes and
+    variances equal the direct fusion of (A, B, C) within the sum of the two routes' bounds against the same longdouble value (not the
+    same bytes: the member order differs).  With a prior too: (1 + 1) prior terms are the (3 - 1) of the direct fusion.
+    Stage two takes the dict's float64 numbers as they are (class_logits as log_probs); through a FILE the float32 cast of the logits
+    that every prediction file goes through (calibration.calibrate_j1) adds 6e-8 relative; that route, late_fusion([F, C]), is compared
+    too, at a tolerance derived from the cast: the float32 rounding moves F's column j by at most |lqF_j| 2^-24 (the renormalisation
+    shifts all columns alike and cancels), which moves the result by dlq_j - sum_k s_k dlq_k: (|lqF_j| + sum_k s_k |lqF_k|) 2^-24 on top
+    of the float64 bounds.  Boxes and variances do not read the logits under v-avg and keep their float64 bounds.
+    Bounds (units of u).  Direct: restate's lq bound at m = 3; box (2 m + 1) X = 7 X, X = sum_t |c_t lambda_t| (weights (m + 1) u, a
+    product, m - 1 additions); variance m + 1 = 4 relative.  Cascade: stage two's own bound on its float64 inputs (lq: restate at m = 2;
+    box 5 X; variance 3) plus what stage one's error does to it: dlq_j - sum_k s_k dlq_k, so b1_j + sum_k s_k b1_k with b1 stage one's lq
+    bound; stage one's box error 5 X lambda_F <= 5 X and its variance error (3 relative) moving the weights, <= 3 X; variance 3 more."""
+    from test_proben_logp_gpu import _clusters
+    from proben_amd import fusion as F
+    from proben_amd.calibration import calibrated_probs, log_posteriors
+    from proben_amd.late_fusion import fused_to_j1, late_fusion
+    A, B, C = _cascade_detectors()
+    prior = [0.15, 0.35, 0.2, 0.3] if with_prior else None
+    lprior = np.log(np.asarray(prior)) if with_prior else None
+    method = ["probEn-log", "v-avg"]
+    direct = late_fusion([A, B, C], method, class_prior=prior, with_posterior=True)
+    stage1 = late_fusion([A, B], method, class_prior=prior, with_posterior=True)
+    Fd, dropped = fused_to_j1([A, B], stage1)
+    assert dropped == 0 and [len(r) for r in Fd["scores"]] == [6, 6]
+    lp_of = lambda d, b: log_posteriors(torch.tensor(d["class_logits"][b], dtype=torch.float32).cuda(), 1.0).cpu().numpy()  # noqa: E731
+    via_file = late_fusion([Fd, C], method, class_prior=prior, with_posterior=True)      # stage two as a file's rows go: float32 logits
+    worst = {"lq": 0.0, "box": 0.0, "var": 0.0, "lq32": 0.0}
+
+    def own_score(d, b):          # the score late_fusion sorts a file's rows by: the calibrated p[class] at T = 1, float64 on the device
+        p = calibrated_probs(torch.tensor(d["class_logits"][b], dtype=torch.float32).cuda(), 1.0)[0].cpu().numpy()
+        return p[np.arange(len(p)), d["classes"][b]]
+    for b in range(2):
+        rows = lambda d, lp, sc: {"boxes": np.asarray(d["boxes"][b]), "scores": np.asarray(sc, np.float64), "lp": lp,  # noqa: E731
+                                  "classes": np.asarray(d["classes"][b], np.int32), "vars": np.asarray(d["vars"][b]).reshape(-1)}
+        ra, rb, rc = (rows(d, lp_of(d, b), own_score(d, b)) for d in (A, B, C))
+        rf = rows(Fd, np.asarray(Fd["class_logits"][b]), Fd["scores"][b])
+        cat = lambda parts: {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}  # noqa: E731
+        abc, ab, fc = cat([ra, rb, rc]), cat([ra, rb]), cat([rf, rc])
+        # the precondition, on the reference clustering: the cascade's stage-two clusters are the three-way clusters
+        cl3 = _clusters(abc["boxes"], abc["scores"], abc["classes"].astype(np.float64))
+        cl1 = _clusters(ab["boxes"], ab["scores"], ab["classes"].astype(np.float64))
+        cl2 = _clusters(fc["boxes"], fc["scores"], fc["classes"].astype(np.float64))
+        assert len(cl3) == len(cl1) == len(cl2) == 6 and all(len(m) == 3 for _, m in cl3) and all(len(m) == 2 for _, m in cl1 + cl2)
+        obj3 = {frozenset(m): k for k, (_, m) in enumerate(cl3)}
+        stage1_rows = [m for _, m in cl1]                                  # fused row r of stage one = cluster r of (A, B)
+        out2, _ = _launch([fc], None, "v-avg", None, prior)
+        assert out2["counts"][0] == 6
+        for r2, (_, mem2) in enumerate(cl2):
+            f_row, c_row = [x for x in mem2 if x < 6][0], [x for x in mem2 if x >= 6][0]
+            mem3 = frozenset(stage1_rows[f_row]) | {c_row + 6}
+            assert mem3 in obj3, "the cascade's stage-two cluster is not a three-way cluster"
+            k3 = obj3[mem3]
+            lq3, b3, v3, bd3 = restate(abc["lp"], abc["boxes"], abc["scores"], abc["vars"], cl3[k3][1], "v-avg", lprior)
+            _, _, _, bd1 = restate(ab["lp"], ab["boxes"], ab["scores"], ab["vars"], stage1_rows[f_row], "v-avg", lprior)
+            _, _, _, bd2 = restate(fc["lp"], fc["boxes"], fc["scores"], fc["vars"], mem2, "v-avg", lprior)
+            s3 = np.exp(lq3.astype(np.float64))
+            casc = bd2 + bd1 + float((s3 * bd1).sum())
+            got_d = (direct[b][3][k3], direct[b][0][k3], direct[b][4][k3])
+            got_c = (out2["log_posterior"][r2], out2["boxes"][r2], out2["vars"][r2])
+            assert direct[b][5][k3] == 3 and out2["members"][r2] == 2
+            X = np.abs(b3.astype(np.float64))
+            for got, blq, bbox, bvar in ((got_d, bd3, 7.0, 4.0), (got_c, casc, 13.0, 6.0)):
+                assert (np.abs(got[0].astype(LD) - lq3) <= blq * U).all()
+                assert (np.abs(got[1].astype(LD) - b3) <= bbox * X * U).all()
+                assert abs(LD(got[2]) - v3) <= bvar * U * float(v3)
+            e_lq = np.abs(got_c[0] - got_d[0]) / ((bd3 + casc) * U)
+            e_box = np.abs(got_c[1] - got_d[1]) / (20.0 * X * U)
+            e_var = abs(got_c[2] - got_d[2]) / (10.0 * U * float(v3))
+            assert (e_lq <= 1).all() and (e_box <= 1).all() and e_var <= 1
+            worst.update(lq=max(worst["lq"], float(e_lq.max())), box=max(worst["box"], float(e_box.max())), var=max(worst["var"], float(e_var)))
+            # the same cluster through late_fusion: its rows may come in another order (the scores are recomputed from the logits)
+            rv = int(np.argmin(np.abs(via_file[b][0] - got_c[1]).sum(1)))
+            assert via_file[b][5][rv] == 2 and len(via_file[b][1]) == 6
+            lqF = np.abs(fc["lp"][f_row])
+            tol32 = (lqF + float((s3 * lqF).sum())) * 2.0 ** -24 + (bd3 + casc) * U
+            e32 = np.abs(via_file[b][3][rv] - got_d[0]) / tol32
+            assert (e32 <= 1).all(), (b, r2, e32)
+            assert (np.abs(via_file[b][0][rv].astype(LD) - b3) <= 13.0 * X * U).all() and abs(LD(via_file[b][4][rv]) - v3) <= 6.0 * U * float(v3)
+            worst["lq32"] = max(worst["lq32"], float(e32.max()))
+    print(f"cascade against direct, prior {with_prior}: largest difference / summed bound: lq {worst['lq']:.3f}, box {worst['box']:.3f}, "
+          f"variance {worst['var']:.3f}; through late_fusion (float32 logits) lq {worst['lq32']:.3f} of its bound")
+
+
+# ---- 4. routes ----------------------------------------------------------------------------------------------------------------------
+
+def test_fuse_detections_is_pack_plus_fuse_and_equals_the_file_route():
+    """fuse_detections(with_posterior=True) on two pseudo-head detectors = pack_rows + fuse_batch byte for byte, and the file route
+    (late_fusion over prediction dicts holding the same detections) gives the same six arrays; fused_device_to_j1 and fused_to_j1 then
+    build the same prediction dict."""
+    from test_calibration_gpu import detector_rows
+    from proben_amd import fusion as F
+    from proben_amd.late_fusion import fused_device_to_j1, fused_to_j1, late_fusion
+    dets = detector_rows(3)
+    B, D = dets[0]["scores"].shape
+    S = 2 * D
+    keys = ("boxes", "scores", "classes", "log_posterior", "vars", "members")
+    for tp, pr, vs, pw in (((1.5, 0.8), [0.1, 0.3, 0.2, 0.4], [0.5, 2.0], None), (None, None, None, [0.6, 0.5])):
+        dev = F.fuse_detections(dets, "probEn-log", "v-avg", temperatures=tp, class_prior=pr, variance_scales=vs, pool_weights=pw,
+                                with_posterior=True)
+        ob, os_, op, ov, oc, ooff, ocnt, osingle, olp, *osrc = F.pack_rows(dets, 2, tp or [1.0, 1.0], log_posteriors=True,
+                                                                             variance_scales=vs, pool_weights=pw)
+        two = F.fuse_batch(ob, os_, op, ov, oc, ooff, "probEn-log", "v-avg", max_rows=S, row_counts=ocnt, passthrough=osingle, log_probs=olp,
+                           class_prior=pr, pool_weights=pw, row_source=osrc[0] if osrc else None, with_posterior=True)
+        torch.cuda.synchronize()
+        cnt = dev["counts"].cpu().numpy()
+        assert cnt.sum() > 0 and torch.equal(dev["counts"], two["counts"])
+        live = (torch.arange(S, device="cuda")[None] < dev["counts"][:, None]).reshape(-1)
+        for k in keys + ("keep",):
+            assert dev[k][live].contiguous().cpu().numpy().tobytes() == two[k][live].contiguous().cpu().numpy().tobytes(), k
+        j1 = []
+        for d in dets:
+            c = d["counts"].cpu().numpy()
+            rec = {k: [] for k in ("image", "boxes", "scores", "classes", "image_id", "class_logits", "probs", "vars")}
+            for b in range(B):
+                keep = [j for j in range(c[b]) if int(d["classes"][b, j]) <= 2]
+                rec["image"].append(f"f{b}.jpeg")
+                rec["image_id"].append(b)
+                for key, src in (("boxes", "boxes"), ("scores", "scores"), ("classes", "classes"), ("class_logits", "class_logits"), ("probs", "prob_score")):
+                    rec[key].append([d[src][b, j].tolist() for j in keep])
+                rec["vars"].append([[float(d["vars"][b, j])] for j in keep])
+            j1.append(json.loads(json.dumps(rec)))
+        via = late_fusion(j1, ["probEn-log", "v-avg"], temperatures=tp, class_prior=pr, variance_scales=vs, pool_weights=pw, with_posterior=True)
+        host = {k: dev[k].cpu().numpy() for k in keys}
+        for b in range(B):
+            if via[b] is None:
+                assert cnt[b] == 0
+                continue
+            sl = slice(b * S, b * S + cnt[b])
+            assert len(via[b]) == 6 and len(via[b][1]) == cnt[b]
+            for k, got in zip(keys, via[b]):
+                got = got.numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
+                assert got.dtype == host[k].dtype and got.tobytes() == host[k][sl].tobytes(), (b, k)
+        from_dev, drop_d = fused_device_to_j1(dev, [f"f{b}.jpeg" for b in range(B)], list(range(B)))
+        from_file, drop_f = fused_to_j1(j1, via)
+        assert from_dev == from_file and drop_d == drop_f
+        assert sum(len(r) for r in from_dev["scores"]) + drop_d == cnt.sum()
+    plain = F.fuse_detections(dets, "probEn-log", "v-avg")
+    assert "log_posterior" not in plain and "vars" not in plain and "members" not in plain
+
+
+def test_drivers_write_read_back_and_report(tmp_path, capsys):
+    """demo_probEn --write_fused: the two-stage route and --one-pass write equal files on a synthetic dataset of a few pairs; the file read
+    back as a detector beside a second file runs and evaluates; calibration_report --fused-posterior prints the new keys and without
+    the flag its JSON is the one with the flag minus those keys."""
+    from test_stream_gpu import _weights, _write_flir
+    from proben_amd.cli import calibration_report, demo_probEn, fit_temperature, save_predictions
+    from proben_amd.late_fusion import read_j1
+    root = tmp_path / "val"
+    _write_flir(root, 6, 96, 120, (150, 180))
+    names = ["thermal_only", "early_fusion"]
+    paths = [_weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
+    pdir = tmp_path / "pred"
+    for m, p in zip(names, paths):
+        save_predictions.main(["--dataset_path", str(root), "--fusion_method", m, "--model_path", p, "--prediction_path", str(pdir), "--batch", "4"])
+    files = [str(pdir / f"val_{m}_predictions.json") for m in names]
+    log = ["--score_fusion", "probEn-log", "--temperatures", "1.4,0.9", "--class_prior", "0.3,0.2,0.1,0.4"]
+    f2, f1 = pdir / "val_fused2_predictions.json", pdir / "val_fused1_predictions.json"
+    capsys.readouterr()
+    res2 = demo_probEn.main(["--dataset_path", str(root), "--prediction_path", str(pdir), "--detectors", ",".join(names), "--outfolder",
+                             str(tmp_path / "o2"), "--dataset_name", "flir_post2", "--write_fused", str(f2)] + log)
+    printed = capsys.readouterr().out
+    assert f"fused detections: {f2}" in printed and "rows on 6 images written" in printed and "background rows dropped" in printed
+    res1 = demo_probEn.main(["--one-pass", "--dataset_path", str(root), "--detectors", ",".join(names), "--model_paths", ",".join(paths), "--workers",
+                             "2", "--batch", "4", "--outfolder", str(tmp_path / "o1"), "--dataset_name", "flir_post1", "--write_fused", str(f1)] + log)
+    assert f"fused detections: {f1}" in capsys.readouterr().out
+    d2, d1 = read_j1(f2), read_j1(f1)
+    assert d2 == d1 and f2.read_bytes() == f1.read_bytes()
+    rows = sum(len(r) for r in d2["scores"])
+    assert rows > 0 and d2["image_id"] == json.load(open(files[1]))["image_id"]
+    for lg, pr, sc, cl, vr in zip(d2["class_logits"], d2["probs"], d2["scores"], d2["classes"], d2["vars"]):
+        for l, p, s, c, v in zip(lg, pr, sc, cl, vr):
+            assert len(l) == 4 and len(p) == 3 and c in (0, 1, 2) and len(v) == 1 and v[0] > 0
+            assert abs(np.exp(l).sum() - 1.0) < 1e-12 and abs(np.float32(np.exp(l[c])) - np.float32(s)) <= _ulp32(s)
+    # without the flag nothing changes: the evaluation is the plain run's
+    plain = demo_probEn.main(["--dataset_path", str(root), "--prediction_path", str(pdir), "--detectors", ",".join(names), "--outfolder",
+                              str(tmp_path / "o0"), "--dataset_name", "flir_post0"] + log)
+    assert (tmp_path / "o0" / "FLIR_probEn_eval.json").read_bytes() == (tmp_path / "o2" / "FLIR_probEn_eval.json").read_bytes()
+    assert {k: v for k, v in plain.items()} == {k: v for k, v in res2.items()} and res1
+    # the fused file is a detector's file: fuse it with a second one
+    back = demo_probEn.main(["--dataset_path", str(root), "--prediction_path", str(pdir), "--detectors", "fused2,early_fusion", "--outfolder",
+                             str(tmp_path / "o3"), "--dataset_name", "flir_post3", "--score_fusion", "probEn-log"])
+    assert "bbox" in back and (tmp_path / "o3" / "FLIR_probEn_eval.json").exists()
+    # the report (annotations rewritten from the detections so that rows match, the recipe of tests/test_reliability_gpu.py)
+    preds = [json.load(open(f)) for f in files]
+    val = root / "FLIR_thermal_RGBT_pairs_val.json"
+    ds = json.load(open(val))
+    anns = []
+    for i, iid in enumerate(preds[0]["image_id"]):
+        for k, p in enumerate(preds):
+            if p["boxes"][i]:
+                x1, y1, x2, y2 = p["boxes"][i][0]
+                anns.append({"id": len(anns) + 1, "image_id": iid, "category_id": 1 + int(p["classes"][i][0]) % 3,
+                             "bbox": [x1 + 0.03 * (1 + k) * (x2 - x1), y1 - 0.02 * (y2 - y1), (x2 - x1) * 1.05, (y2 - y1) * 0.97],
+                             "area": (x2 - x1) * (y2 - y1), "iscrowd": 0})
+    assert anns
+    ds["annotations"] = anns
+    json.dump(ds, open(val, "w"))
+    cal = tmp_path / "cal.json"
+    fit_temperature.main(["--predictions", *files, "--dataset_path", str(root), "--holdout", "0.5", "--out", str(cal), "--with-variance", "--with-prior"])
+    base = ["--dataset_path", str(root), "--predictions", *files, "--calibration", str(cal), "--score_fusion", "probEn-log", "--on", "all"]
+    capsys.readouterr()
+    with_flag = calibration_report.main(base + ["--fused-posterior", "--out", str(tmp_path / "rep1.json")])
+    printed = capsys.readouterr().out
+    assert "posterior, top label" in printed and "fused box variance" in printed
+    without = calibration_report.main(base + ["--out", str(tmp_path / "rep0.json")])
+    assert "posterior, top label" not in capsys.readouterr().out
+    r1, r0 = json.load(open(tmp_path / "rep1.json")), json.load(open(tmp_path / "rep0.json"))
+    for tag in ("before", "after"):
+        f = r1["fused"][tag]
+        assert set(f) - set(r0["fused"][tag]) == {"posterior", "variance"}
+        assert f["posterior"]["rows"] == f["rows"] + f["excluded"] > 0 and np.isfinite(f["posterior"]["nll"]) and f["posterior"]["nll"] >= 0
+        assert set(f["posterior"]["top_label"]) == {"rows", "excluded", "ece", "mce", "brier", "bins"}
+        assert len(f["variance"]["coverage"]) == 2 and set(f["variance"]) == {"rows", "excluded", "nll", "coverage"}
+        assert f["variance"]["rows"] > 0 and np.isfinite(f["variance"]["nll"]) and all(0.0 <= c <= 1.0 for c in f["variance"]["coverage"])
+        del f["posterior"], f["variance"]
+    assert json.dumps(r1, sort_keys=True) == json.dumps(r0, sort_keys=True) and with_flag["method"] == without["method"]
