@@ -40,7 +40,7 @@ __device__ __forceinline__ void decode(const float* d, float bx1, float by1, flo
     const float wd = bx2 - bx1, ht = by2 - by1;
     const float cx = bx1 + 0.5f * wd, cy = by1 + 0.5f * ht;
     const float dx = d[0] / a.wx, dy = d[1] / a.wy;
-    const float dw = fminf(d[2] / a.ww, a.scale_clamp), dh = fminf(d[3] / a.wh, a.scale_clamp);
+    const float dw = pe::clamp_max_nan(d[2] / a.ww, a.scale_clamp), dh = pe::clamp_max_nan(d[3] / a.wh, a.scale_clamp);
     const float pcx = dx * wd + cx, pcy = dy * ht + cy;
     const float pw = expf(dw) * wd, ph = expf(dh) * ht;
     o[0] = pcx - 0.5f * pw; o[1] = pcy - 0.5f * ph; o[2] = pcx + 0.5f * pw; o[3] = pcy + 0.5f * ph;

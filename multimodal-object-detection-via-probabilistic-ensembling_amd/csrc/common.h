@@ -51,6 +51,9 @@ __device__ __forceinline__ unsigned long long lanemask_lt() {
 // NaN and would turn a poisoned activation into a clean 0: the reference's robustness contract - NaN / inf features give no
 // proposals and no detections, tests/test_model_e2e.py:91-120 - depends on NaN surviving).  gfx950: one v_maximum3_f32.
 __device__ __forceinline__ float relu_nan(float x) { return __builtin_elementwise_maximum(x, 0.f); }
+// The box decoders' upper clamp of dw / dh, NaN-propagating like torch.clamp(max=) (fminf(NaN, hi) is hi: a row whose only bad
+// value is dw or dh would decode to a finite box and be kept where the reference drops it).  The same bits as fminf otherwise.
+__device__ __forceinline__ float clamp_max_nan(float x, float hi) { return x > hi ? hi : x; }
 
 // the rule for a temperature or a variance scale
 inline bool finite_positive(double x) { return x == x && x > 0.0 && x < __builtin_huge_val(); }

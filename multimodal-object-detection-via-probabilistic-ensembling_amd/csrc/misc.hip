@@ -365,7 +365,7 @@ __global__ void apply_deltas_kernel(const float* deltas, const float* boxes, int
     const float wd = b[2] - b[0], ht = b[3] - b[1];
     const float cx = b[0] + 0.5f * wd, cy = b[1] + 0.5f * ht;
     const float dx = d[0] / wx, dy = d[1] / wy;
-    const float dw = fminf(d[2] / ww, clamp), dh = fminf(d[3] / wh, clamp);
+    const float dw = pe::clamp_max_nan(d[2] / ww, clamp), dh = pe::clamp_max_nan(d[3] / wh, clamp);
     const float pcx = dx * wd + cx, pcy = dy * ht + cy;
     const float pw = expf(dw) * wd, ph = expf(dh) * ht;
     float* o = out + (size_t)idx * 4;

@@ -43,7 +43,10 @@ struct RpnArgs {
     int slice_level[64], slice_begin[64];
 };
 
+// Smaller key = better.  Every NaN gets the best key, whatever its sign or payload: NaNs come first and tie by index, like the
+// reference's stable descending sort - and no key of a real anchor is 0xFFFFFFFF, stage 2's padding (the bits of a negative NaN).
 __device__ __forceinline__ unsigned ordered_desc(float s) {
+    if (s != s) return 0u;
     s += 0.0f;
     unsigned u = __float_as_uint(s);
     u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;
@@ -210,7 +213,7 @@ __global__ __launch_bounds__(kThreads) void rpn_select_kernel(RpnArgs a) {
         const float wd = ax2 - ax1, ht = ay2 - ay1;
         const float cx = ax1 + 0.5f * wd, cy = ay1 + 0.5f * ht;
         const float dx = row[3 + an * 4], dy = row[3 + an * 4 + 1];
-        const float dw = fminf(row[3 + an * 4 + 2], a.scale_clamp), dh = fminf(row[3 + an * 4 + 3], a.scale_clamp);
+        const float dw = pe::clamp_max_nan(row[3 + an * 4 + 2], a.scale_clamp), dh = pe::clamp_max_nan(row[3 + an * 4 + 3], a.scale_clamp);
         const float pcx = dx * wd + cx, pcy = dy * ht + cy;
         const float pw = expf(dw) * wd, ph = expf(dh) * ht;
         float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
