@@ -358,6 +358,66 @@ int pe_proben_fuse_batch_posterior(const double* boxes, const double* scores, co
                                    int32_t* out_members /* [Ntot] */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Presence evidence for log-posterior ProbEn: WHICH detectors produced a row of a cluster is an observation about the class that the
+ * product of posteriors never uses (each posterior is conditioned on "this detector produced a row").  Not in the reference.  With D
+ * detectors, D <= PE_PRESENCE_MAX_DETECTORS, a cluster's pattern is P = OR over its rows of (1 << row_source[row]), in [1, 2^D), and
+ *     a_j = (the a_j of pe_proben_fuse_batch_logp / _pooled, prior and pool weights included) + presence[P * (K + 1) + j]
+ * - the addition last, once per column -, then the max-subtracted softmax and the score / class rule as before (maximum over the K + 1
+ * columns, first index, NaN wins).  presence is a table of float64 log-evidence [2^D][K + 1] (row 0 unused), indexed by the pattern and
+ * not a miss probability per detector: detectors that share a frame do not fire independently given the class.
+ * pe_proben_fuse_batch_presence: the arguments of pe_proben_fuse_batch_posterior with row_source REQUIRED, pool_weights optional (NULL =
+ *   the unpooled rule) and out_log_posterior / out_vars / out_members optional TOGETHER (all NULL = a score-only run); presence DEVICE f64
+ *   [(1 << num_detectors) * (K + 1)], every entry finite (a device pointer, not checked here: calibration.presence_table validates it);
+ *   num_detectors in [1, PE_PRESENCE_MAX_DETECTORS] (it also sizes pool_weights); out_pattern optional i32 [Ntot], indexed like
+ *   out_scores: the fused row's pattern, written once by the thread that owns the cluster (the row, on passthrough).  Same kernel (a
+ *   template instantiation), clustering (both forms), box modes, K <= 62 and out_counts = -1 rules.
+ *   A cluster of ONE row is fused: a_j = log_probs[row][j] + presence[1 << source][j] - no pool weight and no prior, which is what those
+ *   rules give a lone row -, its score the normalised maximum, its class the argmax over all K + 1 columns (a lone row whose largest
+ *   column becomes background leaves as a background row), out_log_posterior normalised; box, keep and variance stay the row's own.
+ *   A passthrough image is rescored, not clustered: each row is such a cluster of one, output row = input row, keep = r, count = n; rows
+ *   of one detector are never merged with each other there.
+ *   Nothing before the fusion phase reads the table: the row's own scores decide the clustering order, s-avg's weights and argmax's box,
+ *   so the clusters at a zero table are the clusters at every table.  At a zero table every output of a cluster of m >= 2 rows equals
+ *   pe_proben_fuse_batch_logp / _pooled / _posterior (x + 0.0 is x); lone and passthrough rows are normalised and differ from the copied
+ *   score by rounding.
+ *   A row whose source is outside [0, num_detectors) makes every column of its cluster NaN (a NaN score, class 0 by the NaN rule) and adds
+ *   no bit to out_pattern (0 for a lone such row).
+ *   The row's detector index is staged in LDS beside the row: 4 more bytes per row in the LDS budget.
+ * pe_bias_nll: the objective of the table's fit.  One row b of the table is a bias-only softmax regression over the clusters of its
+ *   pattern, convex in b: base f64 [num_clusters, num_columns] (the fused log-posterior at a zero table), labels i32 [num_clusters] in
+ *   [0, K]; candidates_host: num_candidates <= 64 candidate rows, host doubles [num_candidates, num_columns], each finite (checked; the
+ *   array is free again on return).  Per candidate c, out f64 [num_candidates, 1 + num_columns]:
+ *     out[c][0]     = sum over clusters of -log softmax(base + b_c)[label] = log(tot) - (a_label - top),
+ *     out[c][1 + j] = its derivative in b_j = sum over clusters of e_j / tot - [label == j],
+ *     a_j = base_j + b_j, top = max_j a_j, e_j = exp(a_j - top), tot = sum_j e_j in column order.
+ *   Lane = candidate, wavefront = cluster; a lane's candidate and accumulators live in registers, so num_columns <=
+ *   PE_BIAS_NLL_MAX_COLUMNS (FLIR has 4, KAIST 2); more returns PE_ERR_UNSUPPORTED.  A cluster is excluded - it adds nothing - when its
+ *   label is outside [0, K] or its base holds a non-finite entry; out_flags i32 [2]: [0] = excluded clusters, [1] = 1 + the largest
+ *   excluded index.  num_clusters == 0 is valid: zeros, no kernel.  Deterministic like pe_pool_nll: min(ceil(num_clusters / 4),
+ *   PE_BIAS_NLL_MAX_BLOCKS) workgroups, a function of num_clusters alone, per-workgroup partials [workgroup][candidate][1 + num_columns]
+ *   in a fixed order, the fixed-order finishing pass, no floating-point atomics.
+ *   workspace: f64, num_candidates * (num_columns + PE_BIAS_NLL_MAX_BLOCKS * (1 + num_columns)) values.
+ * Arguments are checked before any device work.
+ * ------------------------------------------------------------------------------------------- */
+#define PE_PRESENCE_MAX_DETECTORS 4
+#define PE_BIAS_NLL_MAX_COLUMNS 16
+#define PE_BIAS_NLL_MAX_BLOCKS 1024
+int pe_proben_fuse_batch_presence(const double* boxes, const double* scores, const double* log_probs, /* [Ntot,K+1] */
+                                  const double* variances, const int32_t* classes, const int32_t* row_source, /* [Ntot] */
+                                  const int32_t* offsets, const int32_t* row_counts, const int32_t* passthrough, int32_t num_images,
+                                  int32_t num_classes, int32_t max_rows_per_image, int32_t box_mode, double iou_thresh, double frame_w,
+                                  double frame_h, const double* log_prior, /* optional [K+1] */
+                                  const double* pool_weights,              /* DEVICE [num_detectors] or NULL */
+                                  const double* presence,                  /* DEVICE [(1 << num_detectors) * (K+1)] */
+                                  int32_t num_detectors, double* out_boxes, float* out_scores, float* out_classes, int32_t* out_keep,
+                                  int32_t* out_counts, int32_t* out_cluster /* optional [Ntot] */,
+                                  double* out_log_posterior /* [Ntot,K+1] */, double* out_vars /* [Ntot] */,
+                                  int32_t* out_members /* [Ntot]; the three NULL together = score only */,
+                                  int32_t* out_pattern /* optional [Ntot] */, void* stream);
+int pe_bias_nll(const double* base, const int32_t* labels, int32_t num_clusters, int32_t num_columns, const double* candidates_host,
+                int32_t num_candidates, double* workspace, double* out, int32_t* out_flags /* [2] */, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused convolution / GEMM: NHWC fp16 activations, [Cout][KH][KW][Cin] fp16 weights, fp32 accumulate
  * on MFMA, epilogue = + bias[Cout] (fp32) + residual + ReLU, fp16 (or fp32) NHWC output.
  * Replaces, per layer, detectron2.layers.Conv2d.forward (layers/wrappers.py:62-98) + FrozenBatchNorm2d

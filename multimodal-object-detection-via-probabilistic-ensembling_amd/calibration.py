@@ -26,6 +26,12 @@ share evidence.
   pool_nll / fit_pool_weights              the fused posterior's NLL and gradient for up to 64 candidates (pe_pool_nll); the safeguarded fit
   check_pool_weights / parse_pool_weights / resolve_pool_weights
   save / load                              carry the optional key "pool_weights" {name: w}
+
+Presence evidence (csrc/presence.hip, csrc/proben.hip): one row of log-evidence per presence pattern (which detectors put a row into
+the cluster) inside score_fusion "probEn-log", added to the fused columns last; clusters of one row and passthrough images included.
+  check_presence / presence_table / parse_presence / resolve_presence
+  bias_nll / fit_presence                  a table row's NLL and gradient for up to 64 candidates (pe_bias_nll); the per-pattern fit
+  save / load                              carry the optional key "presence" {"detectors", "columns", "table", "hi"}
 """
 import ctypes
 import json
@@ -43,6 +49,9 @@ RELIABILITY_MAX_BINS = 64    # PE_RELIABILITY_MAX_BINS
 RELIABILITY_MAX_BLOCKS = 1024     # PE_RELIABILITY_MAX_BLOCKS: 4 partial values per workgroup and bin
 POOL_MAX_DETECTORS = 8       # PE_POOL_MAX_DETECTORS
 POOL_NLL_MAX_BLOCKS = 1024   # PE_POOL_NLL_MAX_BLOCKS: 1 + num_detectors partial values per workgroup and candidate
+PRESENCE_MAX_DETECTORS = 4   # PE_PRESENCE_MAX_DETECTORS
+BIAS_NLL_MAX_COLUMNS = 16    # PE_BIAS_NLL_MAX_COLUMNS: a lane of pe_bias_nll keeps 1 + (K + 1) accumulators in registers
+BIAS_NLL_MAX_BLOCKS = 1024   # PE_BIAS_NLL_MAX_BLOCKS: 1 + (K + 1) partial values per workgroup and candidate
 BBOX_REG_WEIGHTS = (10.0, 10.0, 5.0, 5.0)      # cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS: the units the variance head is trained in
 
 
@@ -246,10 +255,12 @@ def fit_temperature(logits, labels, lo=0.05, hi=20.0, tol=1e-6):
             "rounds": rounds, "rows": int(logits.shape[0]), "at_bound": at}
 
 
-def save(path, detectors, nll=None, rows=None, class_prior=None, pool_weights=None, **extra):
+def save(path, detectors, nll=None, rows=None, class_prior=None, pool_weights=None, presence=None, **extra):
     """Write the calibration file.  detectors {name: T}; nll {name: {"before": .., "after": ..}}; rows {name: fitted rows};
     class_prior (optional, K + 1 probabilities, background last: the prior of score_fusion "probEn-log") is written normalised -
-    without it the file has no such key; pool_weights (optional, {name: w}: the pooling weights of "probEn-log") likewise; extra keys
+    without it the file has no such key; pool_weights (optional, {name: w}: the pooling weights of "probEn-log") likewise; presence
+    (optional, {"detectors": [names in bit order], "columns": K + 1, "table": [2^D][K + 1], "hi": the fit's search bound or None}: the
+    presence table of "probEn-log") likewise; extra keys
     (cli/fit_temperature adds "holdout" and "fitted_image_ids") are kept as given."""
     rec = {"detectors": {k: check_temperature(v, f"temperature of {k}") for k, v in detectors.items()},
            "nll": nll or {}, "rows": rows or {}}
@@ -257,6 +268,8 @@ def save(path, detectors, nll=None, rows=None, class_prior=None, pool_weights=No
         rec["class_prior"] = check_class_prior(class_prior).tolist()
     if pool_weights is not None:
         rec["pool_weights"] = _check_pool_table(pool_weights, "pool_weights")
+    if presence is not None:
+        rec["presence"] = _check_presence_record(presence, "presence")
     rec.update(extra)
     with open(path, "w") as f:
         json.dump(rec, f, indent=1)
@@ -274,6 +287,8 @@ def load(path):
         rec["class_prior"] = check_class_prior(rec["class_prior"], what=f"{path}: class_prior").tolist()
     if "pool_weights" in rec:
         rec["pool_weights"] = _check_pool_table(rec["pool_weights"], f"{path}: pool_weights")
+    if "presence" in rec:
+        rec["presence"] = _check_presence_record(rec["presence"], f"{path}: presence")
     return rec
 
 
@@ -725,3 +740,242 @@ def fit_pool_weights(log_probs, row_source, member_rows, cluster_offsets, labels
     at = ["lo" if (w[d] <= 0 and g[d] > 0) else "hi" if (w[d] >= hi and g[d] < 0) else None for d in range(D)]
     return {"weights": [float(x) for x in w], "nll": f, "nll_at_1": float(f1[0]), "grad": [float(x) for x in g], "clusters": used,
             "excluded": bad, "rounds": rounds, "converged": converged, "at_bound": at}
+
+
+# ---- presence evidence ---------------------------------------------------------------------------------------------------------
+
+def check_presence(table, num_detectors=None, num_columns=None, what="presence"):
+    """The presence table -> float64 ndarray [2^D, K + 1]: one row of log-evidence per presence pattern P = OR of (1 << detector), row
+    0 (no detector: no cluster has it) present and ignored.  1 <= D <= PRESENCE_MAX_DETECTORS, K + 1 >= 2, every entry finite (row 0
+    too: it is uploaded with the rest); anything else, or a shape other than the one asked for, raises ValueError."""
+    if isinstance(table, torch.Tensor):
+        table = table.detach().cpu().numpy()
+    try:
+        t = np.asarray(table, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} {table!r} is not a table of numbers") from None
+    if t.ndim != 2 or t.shape[1] < 2:
+        raise ValueError(f"{what} must be a table [2^D][K + 1] with K + 1 >= 2 columns, got shape {t.shape}")
+    rows = [2 ** d for d in range(1, PRESENCE_MAX_DETECTORS + 1)]
+    if t.shape[0] not in rows:
+        raise ValueError(f"{what} has {t.shape[0]} rows: one per presence pattern, row 0 included, is {' / '.join(map(str, rows))} "
+                         f"(1 to {PRESENCE_MAX_DETECTORS} detectors)")
+    if num_detectors is not None and t.shape[0] != 2 ** int(num_detectors):
+        raise ValueError(f"{what} has {t.shape[0]} rows for {num_detectors} detectors ({2 ** int(num_detectors)} patterns, row 0 included)")
+    if num_columns is not None and t.shape[1] != num_columns:
+        raise ValueError(f"{what} has {t.shape[1]} columns for K + 1 = {num_columns} (background last)")
+    if not np.all(np.isfinite(t)):
+        r, c = np.argwhere(~np.isfinite(t))[0]
+        raise ValueError(f"{what}: entry {t[r, c]!r} (pattern {r}, column {c}) is not finite")
+    return np.ascontiguousarray(t)
+
+
+def presence_table(table, num_detectors, num_columns, device):
+    """The presence table (check_presence validates: shape, finite entries, row 0 present and ignored) -> the DEVICE f64 [2^D, K + 1]
+    tensor pe_proben_fuse_batch_presence takes.  None -> None.  A CUDA tensor is taken as the result of an earlier call
+    (FramePairPipeline uploads once, not per batch); num_detectors None takes D from the table's rows."""
+    if table is None:
+        return None
+    if isinstance(table, torch.Tensor) and table.is_cuda:
+        want = (None if num_detectors is None else 2 ** int(num_detectors), num_columns)
+        if table.dtype != torch.float64 or table.dim() != 2 or (want[0] is not None and table.shape[0] != want[0]) or table.shape[1] != num_columns \
+                or table.shape[0] not in [2 ** d for d in range(1, PRESENCE_MAX_DETECTORS + 1)]:
+            raise ValueError(f"presence tensor {tuple(table.shape)} {table.dtype} is not float64 [{want[0] or '2^D'}, {num_columns}]")
+        return table.contiguous()
+    return torch.from_numpy(check_presence(table, num_detectors, num_columns)).to(device)
+
+
+def presence_detectors(table):
+    """D of a table (host or device) with 2^D rows."""
+    return int(table.shape[0]).bit_length() - 1
+
+
+def _pattern_of(text, names, flag):
+    parts = [x.strip() for x in text.split("+")]
+    mask = 0
+    for n in parts:
+        if n not in names:
+            raise ValueError(f"{flag}: unknown detector {n!r} in pattern {text!r} (the detectors are {','.join(names)})")
+        if mask & (1 << names.index(n)):
+            raise ValueError(f"{flag}: pattern {text!r} names {n} twice")
+        mask |= 1 << names.index(n)
+    return mask
+
+
+def parse_presence(text, names, num_columns=None):
+    """--presence value -> float64 ndarray [2^D, K + 1], D = len(names).  One entry per pattern, 'name[+name...]=v:v:...:v' (K + 1
+    numbers, background last), entries separated by commas; a detector's bit is its position in names; patterns not listed get zeros."""
+    names = list(names)
+    flag = "--presence"
+    if not 1 <= len(names) <= PRESENCE_MAX_DETECTORS:
+        raise ValueError(f"{flag}: {len(names)} detectors (1 to {PRESENCE_MAX_DETECTORS})")
+    rows = {}
+    for item in [x.strip() for x in str(text).split(",") if x.strip()]:
+        if "=" not in item:
+            raise ValueError(f"{flag}: entry {item!r} is not pattern=v:v:...")
+        k, v = item.split("=", 1)
+        mask = _pattern_of(k, names, flag)
+        if mask in rows:
+            raise ValueError(f"{flag} lists pattern {'+'.join(n for d, n in enumerate(names) if mask >> d & 1)} twice")
+        try:
+            vals = [float(x) for x in v.split(":")]
+        except ValueError:
+            raise ValueError(f"{flag}: entry {item!r} is not a ':' separated list of numbers") from None
+        rows[mask] = (vals, k)
+    if not rows:
+        raise ValueError(f"{flag} {text!r} lists no pattern")
+    k1 = num_columns if num_columns is not None else len(next(iter(rows.values()))[0])
+    table = np.zeros((2 ** len(names), k1))
+    for mask, (vals, k) in rows.items():
+        if len(vals) != k1:
+            raise ValueError(f"{flag}: pattern {k} lists {len(vals)} entries for K + 1 = {k1} columns (background last)")
+        if not all(math.isfinite(x) for x in vals):
+            raise ValueError(f"{flag}: pattern {k} has an entry that is not finite ({vals})")
+        table[mask] = vals
+    return check_presence(table, len(names), k1, flag)
+
+
+def _check_presence_record(rec, what):
+    if not isinstance(rec, dict) or not isinstance(rec.get("detectors"), list) or "table" not in rec:
+        raise ValueError(f"{what} is not a presence record (\"detectors\": names in bit order, \"columns\", \"table\")")
+    names = [str(n) for n in rec["detectors"]]
+    if len(set(names)) != len(names):
+        raise ValueError(f"{what}: detectors {names} repeat a name")
+    t = check_presence(rec["table"], len(names), rec.get("columns"), f"{what}: table")
+    hi = rec.get("hi")
+    out = dict(rec)
+    out.update({"detectors": names, "columns": int(t.shape[1]), "table": t.tolist(), "hi": None if hi is None else float(hi)})
+    return out
+
+
+def resolve_presence(rec, names, source):
+    """The calibration file's "presence" record -> float64 ndarray [2^D, K + 1] with the bits in the order of `names`.  The file's
+    detectors must be exactly `names` (in any order): a table over other detectors is a table about other observations."""
+    rec = _check_presence_record(rec, f"{source}: presence")
+    names = list(names)
+    if sorted(rec["detectors"]) != sorted(names):
+        raise ValueError(f"{source}: the presence table is over {','.join(rec['detectors'])}, not {','.join(names)}")
+    src = np.asarray(rec["table"], dtype=np.float64)
+    bit = [names.index(n) for n in rec["detectors"]]          # file bit d -> bit of this run
+    out = np.zeros_like(src)
+    for p in range(src.shape[0]):
+        q = sum(1 << bit[d] for d in range(len(names)) if p >> d & 1)
+        out[q] = src[p]
+    return out
+
+
+def bias_nll(base, labels, candidates):
+    """One pe_bias_nll launch.  Device tensors: base f64 [C, K+1] (the fused log-posteriors of one pattern's clusters at a zero table),
+    labels i32 [C] in [0, K].  candidates: [n_c, K+1] candidate table rows (n_c <= 64), finite.  Returns (nll f64 ndarray [n_c], grad f64
+    ndarray [n_c, K+1], excluded clusters, last excluded cluster index or -1); an excluded cluster (a label outside [0, K], a non-finite
+    base entry) adds nothing.  K + 1 <= BIAS_NLL_MAX_COLUMNS.  Synchronises (one download)."""
+    _lib.require_cuda(base, labels)
+    cand = np.ascontiguousarray(np.asarray(candidates, dtype=np.float64))
+    if cand.ndim != 2 or cand.shape[0] < 1:
+        raise ValueError(f"bias_nll: candidates must be [candidates, K+1], got {cand.shape}")
+    n_c, k1 = cand.shape
+    if base.dim() != 2 or base.shape[1] != k1:
+        raise ValueError(f"bias_nll: base must be [C, {k1}] for candidates of {k1} columns, got {tuple(base.shape)}")
+    base = base.contiguous().double()
+    labels = labels.reshape(-1).contiguous().to(torch.int32)
+    C = base.shape[0]
+    if labels.numel() != C:
+        raise ValueError(f"bias_nll: {labels.numel()} labels for {C} clusters")
+    host, bad, last = _statistic("pe_bias_nll", n_c * (1 + k1), n_c * (k1 + BIAS_NLL_MAX_BLOCKS * (1 + k1)), base.device,
+                                 lambda work, out, flags, stream: _lib.lib().pe_bias_nll(
+                                     _lib.ptr(base) if C else None, _lib.ptr(labels) if C else None, C, k1,
+                                     cand.ctypes.data_as(ctypes.c_void_p), n_c, work, out, flags, stream))
+    out = host.numpy().reshape(n_c, 1 + k1)
+    return out[:, 0].copy(), out[:, 1:].copy(), bad, last
+
+
+def _fit_bias(base, labels, hi, gtol, max_rounds):
+    """One row of the table: b in [-hi, hi]^K x {0} that minimises bias_nll, by fit_pool_weights' projected Newton scheme."""
+    C, k1 = base.shape
+    K = k1 - 1
+    h = 1e-4
+    b = np.zeros(k1)
+    f0, _, bad, _ = bias_nll(base, labels, [b])
+    used = C - bad
+    rec = {"clusters": used, "excluded": bad, "nll_at_0": float(f0[0]), "nll": float(f0[0]), "rounds": 0, "converged": used == 0,
+           "at_bound": [None] * K, "grad": [0.0] * K}
+    if used == 0:
+        return b, rec
+    if not math.isfinite(f0[0]):
+        raise ValueError("fit_presence: the NLL at a zero row is not finite")
+    eye = np.eye(k1)[:K]
+    rounds, converged, f = 0, False, float(f0[0])
+    while rounds < max_rounds:
+        rounds += 1
+        fs, gs, _, _ = bias_nll(base, labels, np.vstack([b] + [b + h * eye[d] for d in range(K)]))
+        f, g = float(fs[0]), gs[0, :K]
+        x = b[:K]
+        held = ((x <= -hi) & (g > 0)) | ((x >= hi) & (g < 0))
+        pg = np.where(held, 0.0, g)
+        if np.max(np.abs(pg)) <= gtol * used:
+            converged = True
+            break
+        H = (gs[1:, :K] - g[None, :]) / h
+        H = 0.5 * (H + H.T)
+        free = ~held
+        p = np.zeros(K)
+        try:
+            Hf = H[np.ix_(free, free)] + 1e-10 * max(np.trace(H), 1.0) * np.eye(int(free.sum()))
+            p[free] = -np.linalg.solve(Hf, g[free])
+        except np.linalg.LinAlgError:
+            p[free] = -g[free]
+        if not (np.all(np.isfinite(p)) and p @ g < 0):
+            p = np.where(free, -g, 0.0) / max(np.max(np.abs(np.diag(H))), 1e-300)
+        steps = 2.0 ** (1 - np.arange(40))
+        trial = np.zeros((40, k1))
+        trial[:, :K] = np.clip(x[None, :] + steps[:, None] * p[None, :], -hi, hi)
+        ft, _, _, _ = bias_nll(base, labels, trial)
+        ft = np.where(np.isfinite(ft), ft, np.inf)
+        i = int(np.argmin(ft))
+        if not ft[i] < f:
+            break
+        b, f = trial[i], float(ft[i])
+    fs, gs, _, _ = bias_nll(base, labels, [b])
+    g = gs[0, :K]
+    rec.update({"nll": float(fs[0]), "rounds": rounds, "converged": converged, "grad": [float(v) for v in g],
+                "at_bound": ["lo" if (b[d] <= -hi and g[d] > 0) else "hi" if (b[d] >= hi and g[d] < 0) else None for d in range(K)]})
+    return b, rec
+
+
+def fit_presence(base, patterns, labels, num_detectors, hi=16.0, gtol=1e-7, max_rounds=60):
+    """The presence table that minimises the NLL of softmax(base + presence[pattern]) against the clusters' labels.  Device tensors:
+    base f64 [C, K+1] (the fused log-posterior of every cluster at a ZERO table: pe_proben_fuse_batch_presence's out_log_posterior,
+    clusters of one and passthrough rows included), patterns i32 [C] (its out_pattern), labels i32 [C] in [0, K].  Patterns do not
+    interact: per pattern P in [1, 2^D) its clusters are selected with torch indexing on the device and the row b = presence[P] is a
+    bias-only softmax regression, convex, gauge b_K = 0 (background is the reference column), fitted by fit_pool_weights' projected
+    Newton scheme over b[:K] in the box [-hi, hi]^K: per round one launch evaluates the gradient at b and at b + h e_j (the Hessian's
+    columns by forward differences, h = 1e-4, symmetrised), a second one 40 step lengths 2, 1, 1/2, ...; it stops when the projected
+    gradient satisfies max_j |pg_j| <= gtol * clusters used, when no step lowers the NLL, or after max_rounds.  hi is a search domain,
+    not a prior: a pattern in which some label never occurs has its minimum at infinity and stops there, reported in at_bound.
+    A pattern without clusters (or with every cluster excluded) keeps a zero row.  Clusters whose pattern is outside [1, 2^D) (a row
+    with a bad source) belong to no row and are counted in "unassigned".
+    Returns {"table": [2^D][K+1], "hi", "unassigned", "patterns": {P: {"clusters", "excluded", "nll_at_0", "nll", "rounds",
+    "converged", "at_bound" [K], "grad" [K]}}}."""
+    D = int(num_detectors)
+    if not 1 <= D <= PRESENCE_MAX_DETECTORS:
+        raise ValueError(f"fit_presence: {D} detectors (1 to {PRESENCE_MAX_DETECTORS})")
+    hi = float(hi)
+    if not (math.isfinite(hi) and hi > 0):
+        raise ValueError(f"fit_presence: hi {hi!r} is not finite and > 0")
+    _lib.require_cuda(base, patterns, labels)
+    if base.dim() != 2 or not 2 <= base.shape[1] <= BIAS_NLL_MAX_COLUMNS:
+        raise ValueError(f"fit_presence: base must be [C, K+1] with 2 <= K + 1 <= {BIAS_NLL_MAX_COLUMNS}, got {tuple(base.shape)}")
+    C, k1 = base.shape
+    patterns, labels = patterns.reshape(-1), labels.reshape(-1)
+    if patterns.numel() != C or labels.numel() != C:
+        raise ValueError(f"fit_presence: {patterns.numel()} patterns and {labels.numel()} labels for {C} clusters")
+    table = np.zeros((2 ** D, k1))
+    report = {}
+    assigned = 0
+    for P in range(1, 2 ** D):
+        idx = torch.nonzero(patterns == P).flatten()
+        assigned += int(idx.numel())
+        b, rec = _fit_bias(base[idx], labels[idx], hi, gtol, max_rounds)
+        table[P] = b
+        report[P] = rec
+    return {"table": table.tolist(), "hi": hi, "unassigned": C - assigned, "patterns": report}

@@ -21,6 +21,11 @@ When the file has "pool_weights" (fit_temperature --with-pool-weights): the "aft
 and the report prints the NLL per cluster of the fused posterior against the label of the fused box, at w = 1 and at the file's
 weights, over the clusters of two or more rows that probEn-log forms on the chosen images at the file's temperatures, prior and
 variance scales (fit_temperature.pool_clusters: the fit's own labelling; calibration.pool_nll, both in one launch).
+When the file has "presence" (fit_temperature --with-presence): the "after" fusion of --score_fusion probEn-log uses the table, and
+the report prints the NLL per fused row of the fused posterior against the label of the fused box, without the table (the candidate
+b = 0) and with it, per presence pattern and overall, over every fused row probEn-log forms on the chosen images at the file's
+temperatures, prior, variance scales and pool weights - clusters of one row and passthrough rows included
+(fit_temperature.presence_labelled: the fit's own labelling; calibration.bias_nll, both candidates in one launch per pattern).
 --fused-posterior (with --score_fusion probEn-log) judges the fused detections as full predictions (late_fusion with_posterior,
 pe_proben_fuse_batch_posterior), before and after: under "posterior" the NLL per fused row of the fused posterior against the label of
 the fused box (calibration.temperature_nll at T = 1 on the fused log-posterior) and ECE / MCE / Brier of its top label over all K + 1
@@ -46,7 +51,7 @@ import torch
 from .. import calibration
 from ..data import load_coco_json
 from ..late_fusion import late_fusion, read_j1
-from .fit_temperature import detector_name, pool_clusters
+from .fit_temperature import detector_name, pattern_name, pool_clusters, presence_labelled
 
 ON = ("heldout", "fitted", "all")
 GAUSSIAN_COVERAGE = (0.682689492137086, 0.954499736103642)
@@ -223,6 +228,30 @@ def pool_report(dets, names, records, ids, weights, iou, box_fusion, device, tem
     return out
 
 
+def presence_report(dets, names, files, records, ids, table, iou, box_fusion, device, temperatures, class_prior, variance_scales, pool_weights):
+    """NLL per fused row of probEn-log's fused posterior on the chosen images, without the presence table ("before": b = 0) and with it
+    ("after"), per pattern and overall; both from pe_bias_nll over the rows fused at a zero table."""
+    nan = float("nan")
+    out = {"rows": 0, "excluded": 0, "nll": {"before": nan, "after": nan}, "patterns": {}}
+    got = presence_labelled(dets, files, records, ids, iou, box_fusion, device, temperatures, class_prior, variance_scales, pool_weights)
+    if got is None:
+        return out
+    rows, labels = got
+    tot = [0.0, 0.0]
+    for P in range(1, len(table)):
+        idx = torch.nonzero(rows["pattern"] == P).flatten()
+        nll, _, bad, _ = calibration.bias_nll(rows["log_posterior"][idx], labels[idx], [np.zeros(len(table[P])), table[P]])
+        used = int(idx.numel()) - bad
+        out["patterns"][pattern_name(P, names)] = {"pattern": P, "rows": used, "excluded": bad,
+                                                   "nll": {"before": float(nll[0]) / used if used else nan, "after": float(nll[1]) / used if used else nan}}
+        out["rows"] += used
+        out["excluded"] += bad
+        tot = [tot[0] + float(nll[0]), tot[1] + float(nll[1])]
+    if out["rows"]:
+        out["nll"] = {"before": tot[0] / out["rows"], "after": tot[1] / out["rows"]}
+    return out
+
+
 def table(report):
     head = ("", "", "rows", "excl", "NLL/row", "ECE", "MCE", "Brier", "1 sigma", "2 sigma")
     rows = [head]
@@ -287,15 +316,22 @@ def main(cmd=None):
     logp = args.score_fusion == "probEn-log"
     prior = rec.get("class_prior") if logp else None
     pvals = None if "pool_weights" not in rec else calibration.resolve_pool_weights(rec["pool_weights"], names, args.calibration)
+    ptable = None if "presence" not in rec else calibration.resolve_presence(rec["presence"], names, args.calibration)
     fuse = lambda **kw: fused_report(dets, args.predictions, method, gt, k, args.bins, args.iou, args.device,
                                      posterior=args.fused_posterior, **kw)
     report["fused"] = {"before": fuse(), "after": fuse(temperatures=temps, variance_scales=svals, class_prior=prior,
-                                                       pool_weights=pvals if logp else None)}
+                                                       pool_weights=pvals if logp else None,
+                                                       **({"presence": ptable} if logp and ptable is not None else {}))}
     if pvals is not None:
         report["pool"] = pool_report(dets, args.predictions, by_id, ids, pvals, args.iou, args.box_fusion, args.device, temps,
                                      rec.get("class_prior"), svals)
         report["pool"]["weights"] = dict(zip(names, pvals))
         report["pool"]["applied"] = logp
+    if ptable is not None:
+        report["presence"] = presence_report(dets, names, args.predictions, by_id, ids, ptable, args.iou, args.box_fusion, args.device, temps,
+                                             rec.get("class_prior"), svals, pvals)
+        report["presence"]["table"] = ptable.tolist()
+        report["presence"]["applied"] = logp
     print(f"{len(ids)} images ({args.on}) of {len(records)}, {args.bins} bins, IoU >= {args.iou}")
     print(table(report))
     if pvals is not None:
@@ -306,6 +342,15 @@ def main(cmd=None):
         if not logp:
             print(f"the file's pool weights are not in the fused rows above: --score_fusion {args.score_fusion} has no pooled form "
                   "(they belong to probEn-log)")
+    if ptable is not None:
+        r = report["presence"]
+        print(f"fused NLL per row (probEn-log/{args.box_fusion}, {r['rows']} fused rows, {r['excluded']} excluded): "
+              f"{r['nll']['before']:.6f} without the presence table, {r['nll']['after']:.6f} with the file's")
+        for pname, q in r["patterns"].items():
+            print(f"  presence {pname}: {q['nll']['before']:.6f} -> {q['nll']['after']:.6f} over {q['rows']} rows ({q['excluded']} excluded)")
+        if not logp:
+            print(f"the file's presence table is not in the fused rows above: --score_fusion {args.score_fusion} has no log-evidence to add "
+                  "it to (it belongs to probEn-log)")
     excluded = sum(d[t]["excluded"] + d[t]["top_label"]["excluded"] for d in report["detectors"].values() for t in ("before", "after")) \
         + sum(report["fused"][t]["excluded"] for t in ("before", "after"))
     if excluded:

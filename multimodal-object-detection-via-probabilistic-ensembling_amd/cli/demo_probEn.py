@@ -28,6 +28,13 @@ written by `fit_temperature --with-variance` supplies them, and the run says so;
 one exponent per detector inside the fusion (the logarithmic opinion pool, pe_proben_fuse_batch_pooled) for detectors that share
 evidence.  Without the flag a --calibration file that carries "pool_weights" supplies them; 1,1 is the plain product bit for bit.
 
+--presence 'thermal_only=-0.1:-0.9:0:0,early_fusion=-1.3:0:0.3:0,thermal_only+early_fusion=1.6:1.5:1.1:0', with --score_fusion
+probEn-log on either route: presence evidence (pe_proben_fuse_batch_presence), one row of K + 1 log-evidence values (background last)
+per presence pattern - the detectors that put a row into the cluster, names joined by + -, added to the fused columns; patterns not
+listed get zeros.  Detections only one detector made, and images on which one detector fired, are rescored too.  Without the flag a
+--calibration file that carries "presence" (fit_temperature --with-presence) supplies the table.  With --write_fused the fused
+log-posterior includes the presence term.
+
 --write_fused FILE, with --score_fusion probEn-log on either route: the fused detections leave as a prediction file of the schema the
 detectors' files have (late_fusion.fused_to_j1): class_logits = the fused log-posterior over all K + 1 columns, probs / scores / classes,
 vars = the variance of the fused box under its box rule.  Fused rows whose class is the background column are not detections and are
@@ -61,8 +68,9 @@ def main(cmd=None):
         temps = {"values": [1.0] * len(names), "fitted": set()}
     vscales = _variance_scales(args, names)
     pool = _pool_weights(args, names) if logp else None
+    presence = _presence(args, names) if logp else None
     if args.one_pass:
-        return one_pass(args, names, world, dev, temps, prior, vscales, pool)
+        return one_pass(args, names, world, dev, temps, prior, vscales, pool, presence)
     files = [os.path.join(args.prediction_path, f"val_{n}_predictions.json") for n in names]
     if comm.is_main_process():
         for i, f in enumerate(files):
@@ -91,8 +99,8 @@ def main(cmd=None):
     res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
                                          det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev),
                                          temperatures=None if temps is None else temps["values"], names=files, class_prior=prior,
-                                         variance_scales=vscales, pool_weights=pool, fused_out=fused)
-    _name_options(res, names, temps, prior, vscales, pool)
+                                         variance_scales=vscales, pool_weights=pool, fused_out=fused, presence=presence)
+    _name_options(res, names, temps, prior, vscales, pool, presence)
     if fused is not None:
         from ..late_fusion import fused_to_j1
         _write_fused(args.write_fused, [fused_to_j1(dets, fused)], main_rank)
@@ -144,6 +152,23 @@ def _pool_weights(args, names):
     return None
 
 
+def _presence(args, names):
+    """--presence, else the calibration file's "presence" (fit_temperature --with-presence), else None; a float64 ndarray [2^D, K+1]."""
+    from .. import calibration
+    if getattr(args, "presence", None) is not None:
+        return calibration.parse_presence(args.presence, names)
+    if args.calibration is not None:
+        rec = calibration.load(args.calibration).get("presence")
+        if rec is not None:
+            table = calibration.resolve_presence(rec, names, args.calibration)
+            if comm.is_main_process():
+                print(f"presence table of {args.calibration}:", ", ".join(
+                    "+".join(n for d, n in enumerate(names) if p >> d & 1) + "=" + ":".join(f"{v:.6g}" for v in table[p])
+                    for p in range(1, len(table))))
+            return table
+    return None
+
+
 def _class_prior(args):
     """--class_prior, else the calibration file's "class_prior" (fit_temperature --with-prior), else None (uniform); a list."""
     from .. import calibration
@@ -154,7 +179,7 @@ def _class_prior(args):
     return None
 
 
-def _name_options(res, names, temps, prior, vscales, pool=None):
+def _name_options(res, names, temps, prior, vscales, pool=None, presence=None):
     """The printed result names the calibration it was made with; a run without any carries none of the keys."""
     if temps is not None:
         res["temperatures"] = dict(zip(names, temps["values"]))
@@ -164,6 +189,8 @@ def _name_options(res, names, temps, prior, vscales, pool=None):
         res["variance_scales"] = dict(zip(names, vscales))
     if pool is not None:
         res["pool_weights"] = dict(zip(names, pool))
+    if presence is not None:
+        res["presence"] = {"detectors": list(names), "table": presence.tolist()}
 
 
 def _write_fused(path, parts, main_rank):
@@ -203,7 +230,7 @@ def _register(args):
     return cfg
 
 
-def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool=None):
+def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool=None, presence=None):
     """loader -> FramePairPipeline (one DefaultPredictor model per --detectors entry, cfg as save_predictions.build_cfg) ->
     ProbEn -> evaluation rows on the device (late_fusion.fused_rows_device) -> one all-gather -> FLIREvaluator on rank 0."""
     import argparse
@@ -238,7 +265,7 @@ def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool
         _warn_fitted(temps, [loader.items[i]["id"] for i in loader.mine])
     pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion,
                              temperatures=None if temps is None else temps["values"], class_prior=prior, variance_scales=vscales,
-                             pool_weights=pool, with_posterior=bool(args.write_fused))
+                             pool_weights=pool, with_posterior=bool(args.write_fused), presence=presence)
     fused_parts = []
     j1 = [([], [], []) for _ in names]       # per detector: names, ids, instances
     rows = []
@@ -308,7 +335,7 @@ def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool
         ev.process_rows(all_rows.numpy())
         res = ev.evaluate()
         res["one_pass"] = stats
-        _name_options(res, names, temps, prior, vscales, pool)
+        _name_options(res, names, temps, prior, vscales, pool, presence)
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
         launch.shutdown()

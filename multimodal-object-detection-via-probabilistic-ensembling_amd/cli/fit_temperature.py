@@ -30,6 +30,14 @@ posterior against those labels.  The file gains "pool_weights" {name: w}, "pool_
 at the fit), "pool_clusters" (used), "pool_excluded" (clusters of one row, which the product does not fuse), "pool_at_bound"
 {name: "lo" / "hi" / null} and "pool_fit" (the box fusion, IoU, rounds and whether the gradient criterion was met);
 `demo_probEn --score_fusion probEn-log --calibration FILE` then fuses with the weights.
+--with-presence (2 or 3 prediction files) also fits the presence table of score_fusion "probEn-log" (DESIGN.md section 18): one row
+of log-evidence per presence pattern - which detectors put a row into a cluster.  It runs last, so its base includes the
+temperatures, prior, variance scales and pool weights of the same run: the fitted images are fused once through
+pe_proben_fuse_batch_presence at a zero table with the posterior outputs (late_fusion.presence_rows), every fused box - clusters of
+one row and the rows of images on which one detector fired included - is labelled by matching it to the ground truth on the device
+(--iou; unmatched = background), and calibration.fit_presence fits each pattern's row to its clusters.  The file gains "presence"
+{"detectors", "columns", "table", "hi", "patterns": per pattern the clusters used / excluded, the NLL per cluster at 0 and at the fit,
+rounds, converged, at_bound, "box_fusion", "iou"}; `demo_probEn --score_fusion probEn-log --calibration FILE` then fuses with the table.
 """
 import argparse
 import json
@@ -41,7 +49,7 @@ import torch
 
 from .. import calibration
 from ..data import load_coco_json
-from ..late_fusion import fused_clusters, read_j1
+from ..late_fusion import fused_clusters, presence_rows, read_j1
 
 
 def detector_name(path):
@@ -65,8 +73,12 @@ def parse(argv):
                    help="--with-variance: the box head's BBOX_REG_WEIGHTS 'wx,wy,ww,wh' (the units of the predicted variance)")
     p.add_argument("--with-pool-weights", action="store_true",
                    help="also fit one pooling weight per detector for score_fusion probEn-log and write the pool_* keys")
-    p.add_argument("--box_fusion", default="v-avg", help="--with-pool-weights: box fusion of the fused boxes that are labelled")
+    p.add_argument("--with-presence", action="store_true",
+                   help="also fit the presence table of score_fusion probEn-log (one row per pattern of detectors) and write the presence key")
+    p.add_argument("--box_fusion", default="v-avg", help="--with-pool-weights / --with-presence: box fusion of the fused boxes that are labelled")
     args = p.parse_args(argv)
+    if args.with_presence and not 2 <= len(args.predictions) <= 3:
+        p.error(f"--with-presence: --predictions lists {len(args.predictions)} files: late fusion takes 2 or 3")
     if args.with_pool_weights and not 2 <= len(args.predictions) <= 3:
         p.error(f"--with-pool-weights: --predictions lists {len(args.predictions)} files: late fusion takes 2 or 3")
     if not 0.0 < args.holdout <= 1.0:
@@ -136,6 +148,37 @@ def pool_fit(preds, names, records, fitted, iou, box_fusion, device, temperature
     lp = cl["log_probs"]
     prior = None if class_prior is None else log_class_prior(class_prior, lp.shape[1], lp.device)
     return calibration.fit_pool_weights(lp, cl["row_source"], cl["member_rows"], cl["cluster_offsets"], labels, len(preds), prior)
+
+
+def presence_labelled(dets, names, records, ids, iou, box_fusion, device, temperatures=None, class_prior=None, variance_scales=None,
+                      pool_weights=None, presence=None):
+    """The labelled fused rows of the presence fit (and of calibration_report's per-pattern NLL): dets = the prediction dicts sliced to
+    the images `ids`, in that order.  late_fusion.presence_rows fuses them once (a zero table unless `presence` is given); every fused
+    box is matched to the ground truth of its image on the device: an unmatched row is background, and so is a class the head has no
+    column for.  Returns (rows, labels i32 [C] on the device), or None when no detector fired."""
+    from .calibration_report import ground_truth
+    rows = presence_rows(dets, box_fusion, device, temperatures, names, class_prior, variance_scales, pool_weights, presence)
+    if rows is None:
+        return None
+    k = rows["log_posterior"].shape[1] - 1
+    gt = ground_truth(records, [ids[i] for i in rows["images"]], device)
+    labels, _, _ = calibration.match_rows_device(rows["boxes"], rows["box_offsets"], gt[0], gt[1], gt[2], gt[3], iou, k)
+    return rows, torch.where((labels < 0) | (labels > k), torch.full_like(labels, k), labels)
+
+
+def presence_fit(preds, names, records, fitted, iou, box_fusion, device, temperatures, class_prior, variance_scales, pool_weights):
+    """calibration.fit_presence over the fused rows of the fitted images."""
+    from .calibration_report import positions, take_j1
+    dets = [take_j1(p, positions(p, fitted, n)) for p, n in zip(preds, names)]
+    got = presence_labelled(dets, names, records, fitted, iou, box_fusion, device, temperatures, class_prior, variance_scales, pool_weights)
+    if got is None:
+        raise ValueError(f"no detection on the {len(fitted)} fitted images: no fused row to fit a presence table on")
+    rows, labels = got
+    return calibration.fit_presence(rows["log_posterior"], rows["pattern"], labels, len(preds))
+
+
+def pattern_name(P, names):
+    return "+".join(n for d, n in enumerate(names) if P >> d & 1)
 
 
 def labelled_rows(pred, records, fitted_ids, iou, name):
@@ -211,6 +254,24 @@ def main(cmd=None):
         print("pool weights:", ", ".join(f"{m} = {w:.6f}" for m, w in zip(names, fit["weights"])),
               f" NLL per cluster {fit['nll_at_1'] / n:.6f} -> {fit['nll'] / n:.6f} over {n} clusters of >= 2 rows ({fit['excluded']} excluded)"
               f"{'' if fit['converged'] else '  (the gradient criterion was not met)'}{note}")
+    if args.with_presence:
+        names = list(temps)
+        fit = presence_fit(preds, args.predictions, by_id, fitted, args.iou, args.box_fusion, args.device, [temps[n] for n in names],
+                           [c + 1 for c in counts] if args.with_prior else None, [vfit[n]["scale"] for n in names] if args.with_variance else None,
+                           [pool["pool_weights"][n] for n in names] if pool else None)
+        per = {}
+        for P, r in fit["patterns"].items():
+            n = max(r["clusters"], 1)
+            per[pattern_name(P, names)] = {"pattern": P, "clusters": r["clusters"], "excluded": r["excluded"],
+                                           "nll": {"before": r["nll_at_0"] / n, "after": r["nll"] / n}, "rounds": r["rounds"],
+                                           "converged": r["converged"], "at_bound": r["at_bound"]}
+            held = [f"column {j} on the {a} end" for j, a in enumerate(r["at_bound"]) if a]
+            note = f"  (on the search range's bound +-{fit['hi']:g}: {', '.join(held)}: not a fitted value)" if held else ""
+            print(f"presence {pattern_name(P, names)}: ({', '.join(f'{v:+.6f}' for v in fit['table'][P])})  NLL per cluster "
+                  f"{r['nll_at_0'] / n:.6f} -> {r['nll'] / n:.6f} over {r['clusters']} clusters ({r['excluded']} excluded)"
+                  f"{'' if r['converged'] else '  (the gradient criterion was not met)'}{note}")
+        pool = dict(pool, presence={"detectors": names, "columns": len(fit["table"][0]), "table": fit["table"], "hi": fit["hi"],
+                                    "patterns": per, "unassigned": fit["unassigned"], "box_fusion": args.box_fusion, "iou": args.iou})
     if args.with_prior:
         calibration.save(args.out, temps, nll, rows, class_prior=[c + 1 for c in counts], holdout=args.holdout, fitted_image_ids=fitted,
                          at_bound=bound, class_prior_counts=counts, **pool)

@@ -39,6 +39,8 @@ struct ProbenArgs {
     double* out_log_posterior;    // POST only: [Ntot, K+1] the fused rows' normalised log-posterior
     double* out_vars;             // POST only: [Ntot] the fused boxes' variance
     int32_t* out_members;         // POST only: [Ntot] rows in the cluster
+    const double* presence;       // PRES only: [(1 << num_detectors) * (K+1)] log-evidence of each presence pattern (row 0 unused)
+    int32_t* out_pattern;         // PRES only, optional: [Ntot] the fused rows' presence pattern
 };
 
 // Sort rule shared with oracle/proben.py: NaN first, score descending, ties by ORIGINAL index
@@ -75,16 +77,52 @@ __device__ __forceinline__ bool precedes(double sa, int ia, double sb, int ib) {
 // memory than it did; a cluster of one and a passed-through row copy their input log-posterior and variance.  Every element is
 // written once, by the thread that owns the cluster (or the row).  A template parameter: the other instantiations compile to what
 // they were.
+// PRES (pe_proben_fuse_batch_presence, LOGP only, with or without POOL / POST): presence evidence.  Phase 2 stages the row's detector
+// index in gsrc (by sorted position, -1 for a source outside [0, num_detectors): 4 more bytes of LDS per row).  Phase 4 forms the
+// cluster's pattern P = OR of (1 << source) over the members in cluster order and adds presence[P * (K + 1) + j], read from global
+// memory like the prior, to a_j last, inside column(j); a member with a bad source makes every column NaN.  A cluster of ONE row is
+// fused too: a_j = lp_j + presence[P][j] (no weight, no prior: what the pooled and the prior rule give a lone row today), score and
+// class by the same rule over the K + 1 columns, out_log_posterior normalised; box, keep and variance stay the row's own.  A passthrough
+// image is rescored the same way, a thread per row, each row a cluster of one: rows of one detector are never merged there.  Nothing
+// before phase 4 reads the table, so the clusters at a zero table are the clusters at every table.  A template parameter: the other
+// instantiations compile to what they were.
 constexpr int kFuseThreads = 1024;
+
+// PRES, a cluster of one row (phase 4 and the passthrough branch): the score / class rule of phase 4's log-posterior fusion, the same
+// operations in the same order, over L columns a_j = column(j); lq (optional) takes the normalised log-posterior (a_j - top) - log(tot).
+template <typename Column>
+__device__ __forceinline__ void logp_rule(Column column, int L, double* lq, double& out_score, double& out_class) {
+    double top = column(0);
+    for (int j = 1; j < L; ++j) {
+        const double v = column(j);
+        top = (v > top || v != v) ? v : top;          // NaN wins, like np.max
+    }
+    double tot = 0.0;
+    for (int j = 0; j < L; ++j) tot += exp(column(j) - top);
+    double best = exp(column(0) - top) / tot;
+    int bi = 0;
+    bool bnan = best != best;
+    for (int j = 1; j < L; ++j) {
+        const double v = exp(column(j) - top) / tot;
+        if (!bnan && (v != v || v > best)) { best = v; bi = j; bnan = v != v; }
+    }
+    out_score = best;
+    out_class = (double)bi;
+    if (lq) {
+        const double ltot = log(tot);
+        for (int j = 0; j < L; ++j) lq[j] = (column(j) - top) - ltot;
+    }
+}
 
 __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int l) {
     const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, l), hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), l);
     return ((unsigned long long)hi << 32) | lo;
 }
 
-template <bool BITS, bool LOGP, bool POOL, bool POST>
+template <bool BITS, bool LOGP, bool POOL, bool POST, bool PRES>
 __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a) {
     static_assert(LOGP || !POST, "the posterior output belongs to the log-posterior rule");
+    static_assert(LOGP || !PRES, "presence evidence belongs to the log-posterior rule");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int ncl_s;
     const int img = blockIdx.x;
@@ -99,12 +137,27 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
         for (int r = tid; r < n; r += kFuseThreads) {
             const size_t o = (size_t)beg + r;
             for (int e = 0; e < 4; ++e) a.out_boxes[o * 4 + e] = a.boxes[o * 4 + e];
-            a.out_scores[o] = (float)a.scores[o];
-            a.out_classes[o] = (float)a.classes[o];
+            if (PRES) {      // rescored as a cluster of one: a_j = lp_j + presence[1 << source][j]
+                const int k1 = a.K + 1;
+                const int src = a.row_source[o];
+                const bool ok = src >= 0 && src < a.num_detectors;
+                const int pat = ok ? 1 << src : 0;
+                const double* lp = a.probs + o * k1;
+                const double* prow = a.presence + (size_t)pat * k1;
+                double sc, cl;
+                logp_rule([&](int j) { return lp[j] + (ok ? prow[j] : __builtin_nan("")); }, k1, POST ? a.out_log_posterior + o * k1 : nullptr, sc, cl);
+                a.out_scores[o] = (float)sc;
+                a.out_classes[o] = (float)cl;
+                if (a.out_pattern) a.out_pattern[o] = pat;
+            } else {
+                a.out_scores[o] = (float)a.scores[o];
+                a.out_classes[o] = (float)a.classes[o];
+            }
             a.out_keep[o] = r;
-            if ((POOL || POST) && a.out_cluster) a.out_cluster[o] = r;
+            if ((POOL || POST || PRES) && a.out_cluster) a.out_cluster[o] = r;
             if (POST) {
-                for (int j = 0; j <= a.K; ++j) a.out_log_posterior[o * (a.K + 1) + j] = a.probs[o * (a.K + 1) + j];
+                if (!PRES)
+                    for (int j = 0; j <= a.K; ++j) a.out_log_posterior[o * (a.K + 1) + j] = a.probs[o * (a.K + 1) + j];
                 a.out_vars[o] = a.vars[o];
                 a.out_members[o] = 1;
             }
@@ -132,7 +185,8 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
     double* gw = ginv + R;                                    // POOL: the pool weight of the row's detector
     int* ord = reinterpret_cast<int*>(gw + (POOL ? R : 0));   // sorted position -> original row
     int* gcls = ord + R;                                      // class id
-    unsigned short* members = reinterpret_cast<unsigned short*>(gcls + R);   // all clusters' matches, back to back
+    int* gsrc = gcls + R;                                     // PRES: the row's detector index, -1 when outside [0, num_detectors)
+    unsigned short* members = reinterpret_cast<unsigned short*>(gsrc + (PRES ? R : 0));   // all clusters' matches, back to back
     unsigned short* cl_piv = members + R;      // per cluster: pivot position, first member, number of matches
     unsigned short* cl_beg = cl_piv + R;
     unsigned short* cl_cnt = cl_beg + R;
@@ -166,6 +220,10 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
         if (POOL) {
             const int src = a.row_source[beg + r];
             gw[p] = (src >= 0 && src < a.num_detectors) ? a.pool_weights[src] : __builtin_nan("");
+        }
+        if (PRES) {
+            const int src = a.row_source[beg + r];
+            gsrc[p] = (src >= 0 && src < a.num_detectors) ? src : -1;
         }
         if (LOGP) {
             const double* lp = a.probs + (size_t)(beg + r) * (K + 1);
@@ -276,7 +334,7 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
     const int ncl = ncl_s;
     int* rcl = reinterpret_cast<int*>(gx1);      // POOL + out_cluster: sorted position -> output row of its cluster (gx1 is dead now)
     double* gvar = gy1;                          // POST: sorted position -> the row's variance (gy1 is dead now)
-    const bool want_cluster = (POOL || POST) && a.out_cluster;      // block-uniform
+    const bool want_cluster = (POOL || POST || PRES) && a.out_cluster;      // block-uniform
     if (want_cluster)
         for (int p = tid; p < n; p += kFuseThreads) rcl[p] = -1;
     if (POST)
@@ -307,9 +365,24 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
         double out_coord[4];
         const size_t o = (size_t)beg + k;
         double out_var = POST ? gvar[pos] : 0.0;
+        int pat = 0;                                 // PRES: the cluster's presence pattern, its table row (NULL: a member's source is bad)
+        const double* prow = nullptr;
+        if (PRES) {
+            bool ok = true;
+            for (int t = 0; t < m; ++t) {
+                const int src = gsrc[at(t)];
+                ok = ok && src >= 0;
+                pat |= src >= 0 ? 1 << src : 0;
+            }
+            if (ok) prow = a.presence + (size_t)pat * L;
+            if (a.out_pattern) a.out_pattern[o] = pat;
+        }
         if (cnt == 0) {
             for (int c4 = 0; c4 < 4; ++c4) out_coord[c4] = coord(c4, pos);
-            if (POST)
+            if (PRES) {          // a cluster of one is fused: a_j = lp_j + presence[P][j]
+                logp_rule([&](int j) { return glog[(size_t)j * R + pos] + (prow ? prow[j] : __builtin_nan("")); }, L,
+                          POST ? a.out_log_posterior + o * L : nullptr, out_score, out_class);
+            } else if (POST)
                 for (int j = 0; j < L; ++j) a.out_log_posterior[o * L + j] = glog[(size_t)j * R + pos];
         } else {
             // ---------- score fusion ----------
@@ -325,6 +398,7 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
                     const double* col = glog + (size_t)j * R;
                     for (int t = 0; t < m; ++t) acc += POOL ? gw[at(t)] * col[at(t)] : col[at(t)];
                     if (a.log_prior) acc -= (POOL ? wsum - 1.0 : (double)(m - 1)) * a.log_prior[j];
+                    if (PRES) acc += prow ? prow[j] : __builtin_nan("");      // last: the presence evidence of the cluster's pattern
                     return acc;
                 };
                 double top = column(0);
@@ -456,13 +530,20 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
 // K+1 log-posteriors (required), a.score_mode is PE_SCORE_PROBEN_LOGP and is not the caller's to choose.  pool (implies logp):
 // pe_proben_fuse_batch_pooled, a.row_source / a.pool_weights required, 8 more bytes of LDS per row for the staged weight.
 // post (implies logp, pool = the caller gave row_source): pe_proben_fuse_batch_posterior, the three more outputs required.
-int fuse_impl(const char* what, bool logp, bool pool, bool post, ProbenArgs a, int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, void* stream) {
+// pres (implies logp; pool = the caller gave pool_weights, post = the caller gave the three posterior outputs): pe_proben_fuse_batch_presence,
+// a.row_source / a.presence required, num_detectors in [1, PE_PRESENCE_MAX_DETECTORS], 4 more bytes of LDS per row for the staged source.
+int fuse_impl(const char* what, bool logp, bool pool, bool post, bool pres, ProbenArgs a, int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, void* stream) {
     PE_CHECK_ARG(num_images >= 0, "%s: num_images < 0", what);
     if (num_images == 0) return PE_OK;
     PE_CHECK_ARG(a.boxes && a.scores && (a.probs || !logp) && a.vars && a.classes && a.offsets, "%s: null input pointer", what);
     PE_CHECK_ARG(a.out_boxes && a.out_scores && a.out_classes && a.out_keep && a.out_counts, "%s: null output pointer", what);
     PE_CHECK_ARG(!pool || (a.row_source && a.pool_weights), "%s: null input pointer (row_source / pool_weights)", what);
-    PE_CHECK_ARG(!post || (!a.row_source == !a.pool_weights), "%s: row_source and pool_weights go together (both NULL = the unpooled rule)", what);
+    PE_CHECK_ARG(!pres || (a.row_source && a.presence), "%s: null input pointer (row_source / presence)", what);
+    PE_CHECK_ARG(!pres || (!a.out_log_posterior == !a.out_vars && !a.out_vars == !a.out_members),
+                 "%s: out_log_posterior / out_vars / out_members go together (all NULL = a score-only run)", what);
+    PE_CHECK_ARG(!pres || (a.num_detectors >= 1 && a.num_detectors <= PE_PRESENCE_MAX_DETECTORS), "%s: num_detectors %d not in [1,%d]", what,
+                 a.num_detectors, PE_PRESENCE_MAX_DETECTORS);
+    PE_CHECK_ARG(!post || pres || (!a.row_source == !a.pool_weights), "%s: row_source and pool_weights go together (both NULL = the unpooled rule)", what);
     PE_CHECK_ARG(!post || (a.out_log_posterior && a.out_vars && a.out_members),
                  "%s: null output pointer (out_log_posterior / out_vars / out_members)", what);
     PE_CHECK_ARG(!pool || (a.num_detectors >= 1 && a.num_detectors <= PE_POOL_MAX_DETECTORS), "%s: num_detectors %d not in [1,%d]", what,
@@ -478,7 +559,7 @@ int fuse_impl(const char* what, bool logp, bool pool, bool post, ProbenArgs a, i
                  max_rows_per_image);
     const int R = (max_rows_per_image + 1) & ~1;  // keep the int/short/byte carves 8-byte aligned
     const int L = (logp || a.score_mode == PE_SCORE_PROBEN) ? num_classes + 1 : (a.score_mode == PE_SCORE_PROBEN_BINARY ? 2 : 0);
-    const size_t per_row = 8 * (6 + L + 5 + (pool ? 1 : 0)) + 4 + 4 + 4 * 2 + 1;
+    const size_t per_row = 8 * (6 + L + 5 + (pool ? 1 : 0)) + 4 + 4 + (pres ? 4 : 0) + 4 * 2 + 1;
     const size_t lds_seq = (size_t)R * per_row + 16;
     const size_t lds_bits = lds_seq + (size_t)R * ((R + 63) / 64) * 16;        // + the two bit matrices
     constexpr size_t kStatic = 512;                                            // the kernels' static __shared__ scratch (ncl_s, reductions)
@@ -486,7 +567,7 @@ int fuse_impl(const char* what, bool logp, bool pool, bool post, ProbenArgs a, i
     const size_t lds = bits ? lds_bits : lds_seq;
     if (lds + kStatic > 160 * 1024) {
         // a whole image's rows live in LDS (boxes, 1 / variance, class ids, log-odds, cluster tables: 8 (11 + L) + 17 bytes per row,
-        // 8 more for the pooled form's weight);
+        // 8 more for the pooled form's weight, 4 more for the presence form's detector index);
         // capacity at K = 3: 1 195 rows per image (probEn), 1 400 (other score modes) - a detector contributes at most 100
         pe::set_error("%s: %zu bytes of LDS needed (> 160 KiB): max_rows_per_image %d is above the per-image capacity of %zu rows "
                       "for this score mode / class count", what, lds + kStatic, max_rows_per_image,
@@ -495,11 +576,15 @@ int fuse_impl(const char* what, bool logp, bool pool, bool post, ProbenArgs a, i
     }
     a.max_rows = R;
     void (*kernel)(ProbenArgs) =
-        post   ? (pool ? (bits ? proben_fuse_kernel<true, true, true, true> : proben_fuse_kernel<false, true, true, true>)
-                       : (bits ? proben_fuse_kernel<true, true, false, true> : proben_fuse_kernel<false, true, false, true>))
-        : pool ? (bits ? proben_fuse_kernel<true, true, true, false> : proben_fuse_kernel<false, true, true, false>)
-        : logp ? (bits ? proben_fuse_kernel<true, true, false, false> : proben_fuse_kernel<false, true, false, false>)
-               : (bits ? proben_fuse_kernel<true, false, false, false> : proben_fuse_kernel<false, false, false, false>);
+        pres   ? (post ? (pool ? (bits ? proben_fuse_kernel<true, true, true, true, true> : proben_fuse_kernel<false, true, true, true, true>)
+                               : (bits ? proben_fuse_kernel<true, true, false, true, true> : proben_fuse_kernel<false, true, false, true, true>))
+                       : (pool ? (bits ? proben_fuse_kernel<true, true, true, false, true> : proben_fuse_kernel<false, true, true, false, true>)
+                               : (bits ? proben_fuse_kernel<true, true, false, false, true> : proben_fuse_kernel<false, true, false, false, true>)))
+        : post ? (pool ? (bits ? proben_fuse_kernel<true, true, true, true, false> : proben_fuse_kernel<false, true, true, true, false>)
+                       : (bits ? proben_fuse_kernel<true, true, false, true, false> : proben_fuse_kernel<false, true, false, true, false>))
+        : pool ? (bits ? proben_fuse_kernel<true, true, true, false, false> : proben_fuse_kernel<false, true, true, false, false>)
+        : logp ? (bits ? proben_fuse_kernel<true, true, false, false, false> : proben_fuse_kernel<false, true, false, false, false>)
+               : (bits ? proben_fuse_kernel<true, false, false, false, false> : proben_fuse_kernel<false, false, false, false, false>);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
@@ -522,8 +607,8 @@ extern "C" int pe_proben_fuse_batch(const double* boxes, const double* scores, c
                                     int32_t* out_keep, int32_t* out_counts, void* stream) {
     ProbenArgs a{boxes, scores, probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
                  score_mode, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
-    return fuse_impl("pe_proben_fuse_batch", false, false, false, a, num_images, num_classes, max_rows_per_image, stream);
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return fuse_impl("pe_proben_fuse_batch", false, false, false, false, a, num_images, num_classes, max_rows_per_image, stream);
 }
 
 extern "C" int pe_proben_fuse_batch_logp(const double* boxes, const double* scores, const double* log_probs,
@@ -534,8 +619,8 @@ extern "C" int pe_proben_fuse_batch_logp(const double* boxes, const double* scor
                                          float* out_scores, float* out_classes, int32_t* out_keep, int32_t* out_counts, void* stream) {
     ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
                  PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
-    return fuse_impl("pe_proben_fuse_batch_logp", true, false, false, a, num_images, num_classes, max_rows_per_image, stream);
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return fuse_impl("pe_proben_fuse_batch_logp", true, false, false, false, a, num_images, num_classes, max_rows_per_image, stream);
 }
 
 extern "C" int pe_proben_fuse_batch_pooled(const double* boxes, const double* scores, const double* log_probs,
@@ -548,8 +633,8 @@ extern "C" int pe_proben_fuse_batch_pooled(const double* boxes, const double* sc
                                            void* stream) {
     ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
                  PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, row_source, pool_weights, num_detectors, out_cluster, nullptr, nullptr, nullptr};
-    return fuse_impl("pe_proben_fuse_batch_pooled", true, true, false, a, num_images, num_classes, max_rows_per_image, stream);
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, row_source, pool_weights, num_detectors, out_cluster, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return fuse_impl("pe_proben_fuse_batch_pooled", true, true, false, false, a, num_images, num_classes, max_rows_per_image, stream);
 }
 
 extern "C" int pe_proben_fuse_batch_posterior(const double* boxes, const double* scores, const double* log_probs,
@@ -563,7 +648,24 @@ extern "C" int pe_proben_fuse_batch_posterior(const double* boxes, const double*
     ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
                  PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
                  out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, row_source, pool_weights, num_detectors, out_cluster,
-                 out_log_posterior, out_vars, out_members};
-    return fuse_impl("pe_proben_fuse_batch_posterior", true, row_source != nullptr && pool_weights != nullptr, true, a, num_images,
+                 out_log_posterior, out_vars, out_members, nullptr, nullptr};
+    return fuse_impl("pe_proben_fuse_batch_posterior", true, row_source != nullptr && pool_weights != nullptr, true, false, a, num_images,
+                     num_classes, max_rows_per_image, stream);
+}
+
+extern "C" int pe_proben_fuse_batch_presence(const double* boxes, const double* scores, const double* log_probs,
+                                             const double* variances, const int32_t* classes, const int32_t* row_source,
+                                             const int32_t* offsets, const int32_t* row_counts, const int32_t* passthrough,
+                                             int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, int32_t box_mode,
+                                             double iou_thresh, double frame_w, double frame_h, const double* log_prior,
+                                             const double* pool_weights, const double* presence, int32_t num_detectors, double* out_boxes,
+                                             float* out_scores, float* out_classes, int32_t* out_keep, int32_t* out_counts,
+                                             int32_t* out_cluster, double* out_log_posterior, double* out_vars, int32_t* out_members,
+                                             int32_t* out_pattern, void* stream) {
+    ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
+                 PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
+                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, row_source, pool_weights, num_detectors, out_cluster,
+                 out_log_posterior, out_vars, out_members, presence, out_pattern};
+    return fuse_impl("pe_proben_fuse_batch_presence", true, pool_weights != nullptr, out_log_posterior != nullptr, true, a, num_images,
                      num_classes, max_rows_per_image, stream);
 }

@@ -14,6 +14,9 @@ a_j = sum_t w_d(t) log p_t[j] - (W - 1) log prior_j (pe_proben_fuse_batch_pooled
 `with_posterior` ("probEn-log" only, with or without pool weights) keeps what the fusion forms and the plain entry points drop: the
 fused rows' normalised log-posterior over all K + 1 columns, the variance of the fused box under its box rule and the size of the
 cluster (pe_proben_fuse_batch_posterior) - the fused detection as a full prediction, a valid "probEn-log" input itself.
+`presence` ("probEn-log" only, with or without pool weights / with_posterior) adds one row of log-evidence per presence pattern - which
+detectors put a row into the cluster - to the fused columns, last (pe_proben_fuse_batch_presence); clusters of one row and
+passed-through images are fused too, since a silent detector is evidence as well.
 """
 import numpy as np
 import torch
@@ -54,12 +57,15 @@ def pool_weight_tensor(pool_weights, num_detectors, device):
     return torch.tensor(check_pool_weights(pool_weights, num_detectors, "pool_weights"), dtype=torch.float64).to(device)
 
 
-def _check_mode(score_fusion, class_prior, who, pool_weights=None, with_posterior=False):
+def _check_mode(score_fusion, class_prior, who, pool_weights=None, with_posterior=False, presence=None):
     if score_fusion not in SCORE_MODES:
         raise ValueError(f"{who}: unknown score_fusion {score_fusion!r} (one of {', '.join(SCORE_MODES)})")
     if with_posterior and score_fusion != LOGP:
         raise ValueError(f"{who}: with_posterior belongs to score_fusion '{LOGP}' (got {score_fusion!r}): the other score fusions "
                          "form no normalised posterior")
+    if presence is not None and score_fusion != LOGP:
+        raise ValueError(f"{who}: presence belongs to score_fusion '{LOGP}' (got {score_fusion!r}): the other score fusions "
+                         "have no log-evidence to add it to")
     if pool_weights is not None and score_fusion != LOGP:
         raise ValueError(f"{who}: pool_weights belong to score_fusion '{LOGP}' (got {score_fusion!r}): the other score fusions "
                          "have no pooled form")
@@ -70,7 +76,7 @@ def _check_mode(score_fusion, class_prior, who, pool_weights=None, with_posterio
 
 def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="probEn", box_fusion="v-avg",
                max_rows=None, iou_thresh=0.5, frame=(FRAME_W, FRAME_H), row_counts=None, passthrough=None, log_probs=None,
-               class_prior=None, pool_weights=None, row_source=None, with_posterior=False):
+               class_prior=None, pool_weights=None, row_source=None, with_posterior=False, presence=None):
     """Fuse B images in one launch.
 
     score_fusion "probEn-log": log_probs f64 [Ntot,K+1] (calibration.log_posteriors / pack_rows(log_posteriors=True)) replaces
@@ -81,6 +87,10 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
     with_posterior ("probEn-log" only): pe_proben_fuse_batch_posterior; the result then also holds "log_posterior" f64 [Ntot, K+1]
     (the fused rows' normalised log-posterior), "vars" f64 [Ntot] (the fused boxes' variance under the box rule) and "members" i32
     [Ntot] (rows in the cluster), indexed like "scores"; rows nothing was written to hold NaN / NaN / 0.
+    presence ("probEn-log" only; a table [2^D][K+1] or calibration.presence_table's device tensor) with row_source:
+    pe_proben_fuse_batch_presence, with or without pool_weights / with_posterior; the fused columns gain presence[P][j], P the OR of
+    (1 << source) over the cluster's rows, clusters of one row and passthrough images are fused too; the result then also holds
+    "pattern" i32 [Ntot] (the fused rows' P, indexed like "scores"; -1 where nothing was written) and "cluster".
 
     boxes f64 [Ntot,4], scores f64 [Ntot], probs f64 [Ntot,K], variances f64 [Ntot],
     classes i32 [Ntot], offsets i32 [B+1] - all CUDA tensors, rows of each image already
@@ -88,9 +98,13 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
       boxes f64 [Ntot,4], scores f32 [Ntot], classes f32 [Ntot], keep i32 [Ntot], counts i32 [B];
     image b's fused rows are [offsets[b], offsets[b]+counts[b]).
     """
-    _check_mode(score_fusion, class_prior, "fuse_batch", pool_weights, with_posterior)
+    _check_mode(score_fusion, class_prior, "fuse_batch", pool_weights, with_posterior, presence)
     logp = score_fusion == LOGP
     pool = pool_weights is not None
+    pres = presence is not None
+    if pres and (row_source is None or row_source.dim() != 1 or row_source.shape[0] != boxes.shape[0]):
+        raise ValueError(f"fuse_batch: presence needs row_source [Ntot] for the {boxes.shape[0]} rows, got "
+                         f"{None if row_source is None else tuple(row_source.shape)}")
     if pool and (row_source is None or row_source.dim() != 1 or row_source.shape[0] != boxes.shape[0]):
         raise ValueError(f"fuse_batch: pool_weights need row_source [Ntot] for the {boxes.shape[0]} rows, got "
                          f"{None if row_source is None else tuple(row_source.shape)}")
@@ -99,7 +113,7 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
             raise ValueError(f"fuse_batch: score_fusion '{LOGP}' needs log_probs [Ntot, K+1] for the {boxes.shape[0]} rows, got "
                              f"{None if log_probs is None else tuple(log_probs.shape)}")
         probs = log_probs
-    _lib.require_cuda(boxes, scores, probs, variances, classes, offsets, row_source if pool else None)
+    _lib.require_cuda(boxes, scores, probs, variances, classes, offsets, row_source if pool or pres else None)
     if score_fusion == "max" and box_fusion == "argmax":
         raise ValueError("('max','argmax') is the class-aware NMS route: use fusion()/nms_fuse_batch")
     B = offsets.numel() - (0 if row_counts is not None else 1)
@@ -120,7 +134,14 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
     dev = boxes.device
     if pool:
         weights = pool_weight_tensor(pool_weights, len(pool_weights), dev)
+    if pool or pres:
         row_source = row_source.contiguous().to(torch.int32)
+    if pres:
+        from .calibration import presence_detectors, presence_table
+        table = presence_table(presence, None, K + 1, dev)
+        nd = presence_detectors(table)
+        if pool and int(weights.numel()) != nd:
+            raise ValueError(f"fuse_batch: {int(weights.numel())} pool weights beside a presence table over {nd} detectors")
     out = {
         "boxes": torch.empty((ntot, 4), dtype=torch.float64, device=dev),
         "scores": torch.empty((ntot,), dtype=torch.float32, device=dev),
@@ -128,14 +149,18 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
         "keep": torch.empty((ntot,), dtype=torch.int32, device=dev),
         "counts": torch.zeros((max(B, 1),), dtype=torch.int32, device=dev)[:B],
     }
-    name = ("pe_proben_fuse_batch_posterior" if with_posterior else "pe_proben_fuse_batch_pooled" if pool
+    name = ("pe_proben_fuse_batch_presence" if pres else "pe_proben_fuse_batch_posterior" if with_posterior else "pe_proben_fuse_batch_pooled" if pool
             else "pe_proben_fuse_batch_logp" if logp else "pe_proben_fuse_batch")
     head = (_lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(probs), _lib.ptr(variances), _lib.ptr(classes),
-            *([_lib.ptr(row_source) if pool else None] if pool or with_posterior else []), _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows)
+            *([_lib.ptr(row_source) if pool or pres else None] if pool or with_posterior or pres else []), _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows)
     geometry = (BOX_MODES[box_fusion], float(iou_thresh), float(frame[0]), float(frame[1]))
     mode = geometry + (_lib.ptr(log_prior),) if logp else (SCORE_MODES[score_fusion],) + geometry
     tail = ()
-    if pool:
+    if pres:
+        mode += (_lib.ptr(weights) if pool else None, _lib.ptr(table), nd)
+        out["cluster"] = torch.full((ntot,), -2, dtype=torch.int32, device=dev)
+        tail = (_lib.ptr(out["cluster"]),)
+    elif pool:
         mode += (_lib.ptr(weights), int(weights.numel()))
         out["cluster"] = torch.full((ntot,), -2, dtype=torch.int32, device=dev)     # -2: never written (padding, counts == -1)
         tail = (_lib.ptr(out["cluster"]),)
@@ -147,6 +172,11 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
         out["vars"] = torch.full((ntot,), float("nan"), dtype=torch.float64, device=dev)
         out["members"] = torch.zeros((ntot,), dtype=torch.int32, device=dev)
         tail += (_lib.ptr(out["log_posterior"]), _lib.ptr(out["vars"]), _lib.ptr(out["members"]))
+    elif pres:
+        tail += (None, None, None)         # the three posterior outputs NULL together: a score-only run
+    if pres:
+        out["pattern"] = torch.full((ntot,), -1, dtype=torch.int32, device=dev)     # -1: never written (padding, counts == -1)
+        tail += (_lib.ptr(out["pattern"]),)
     st = getattr(_lib.lib(), name)(*head, *mode, _lib.ptr(out["boxes"]), _lib.ptr(out["scores"]), _lib.ptr(out["classes"]),
                                    _lib.ptr(out["keep"]), _lib.ptr(out["counts"]), *tail, _lib.stream())
     _lib.check(st, name)
@@ -327,7 +357,7 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, varian
 
 
 def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=0.5, temperatures=None,
-                    class_prior=None, variance_scales=None, pool_weights=None, with_posterior=False):
+                    class_prior=None, variance_scales=None, pool_weights=None, with_posterior=False, presence=None):
     """Device-to-device stage fusion: `dets` = the result dicts of 2 or 3 detectors run on the SAME batch
     (rcnn.GeneralizedRCNN.forward_batch).  Packs their detections into ProbEn rows (classes <= max_class,
     like the JSON writer demo_FLIR_save_predictions.py:148-155), applies the reference's per-image case
@@ -342,11 +372,17 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     pe_proben_fuse_batch_pooled; the result then also holds "cluster" and "row_source".
     with_posterior ("probEn-log" only): the fusion is pe_proben_fuse_batch_posterior and the result also holds fuse_batch's
     "log_posterior", "vars" and "members".
+    presence ("probEn-log" only; a table [2^D][K+1], D = len(dets), or calibration.presence_table's device tensor): the rows' detector
+    indices come from pe_proben_pack_pooled and the fusion is pe_proben_fuse_batch_presence - images on which one detector fired are
+    rescored row by row, not copied; the result then also holds "pattern", "cluster" and "row_source".
     No host synchronisation.  Returns a dict: boxes f64 [B*S,4], scores f32, classes f32, counts i32 [B],
     offsets i32 [B], stride S = len(dets) * D."""
     # the box heads' candidate-cap bookkeeping travels with the result (no kernel here): check_candidate_overflow() looks
     # at it at the consumer's first host synchronisation
-    _check_mode(score_fusion, class_prior, "fuse_detections", pool_weights, with_posterior)
+    _check_mode(score_fusion, class_prior, "fuse_detections", pool_weights, with_posterior, presence)
+    if presence is not None:
+        from .calibration import presence_table
+        presence = presence_table(presence, len(dets), dets[0]["prob_score"].shape[2] + 1, dets[0]["scores"].device)
     overflow_src = [(d["cand_total"], d["cand_max"]) for d in dets if "cand_total" in d]
     B, D = dets[0]["scores"].shape
     S = len(dets) * D
@@ -355,8 +391,10 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     if logp and temperatures is None:
         temperatures = [1.0] * len(dets)
     ob, os_, op, ov, oc, ooff, ocnt, osingle, *olp = pack_rows(dets, max_class, temperatures, log_posteriors=logp,
-                                                               variance_scales=variance_scales, pool_weights=pool_weights)
-    osrc = olp.pop() if pool_weights is not None else None
+                                                               variance_scales=variance_scales,
+                                                               pool_weights=pool_weights if presence is None or pool_weights is not None
+                                                               else [1.0] * len(dets))      # only their presence matters to pack_rows
+    osrc = olp.pop() if pool_weights is not None or presence is not None else None
     if score_fusion == "max" and box_fusion == "argmax":
         from .layers import nms_batched_raw
         b32 = ob.float().view(B, S, 4)
@@ -372,7 +410,7 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
                 "offsets": ooff, "stride": S, "in_counts": ocnt, "nms_route": True, "cand_overflow_src": overflow_src}
     out = fuse_batch(ob, os_, op, ov, oc, ooff, score_fusion, box_fusion, max_rows=S, iou_thresh=iou_thresh,
                      row_counts=ocnt, passthrough=osingle, log_probs=olp[0] if logp else None, class_prior=class_prior,
-                     pool_weights=pool_weights, row_source=osrc, with_posterior=with_posterior)
+                     pool_weights=pool_weights, row_source=osrc, with_posterior=with_posterior, presence=presence)
     if osrc is not None:
         out["row_source"] = osrc
     out["offsets"], out["stride"], out["in_counts"] = ooff, S, ocnt

@@ -67,7 +67,7 @@ def _info(det, i):
 
 
 def late_fusion(dets, method, device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None,
-                pool_weights=None, with_posterior=False):
+                pool_weights=None, with_posterior=False, presence=None):
     """dets: 2 or 3 J1 dicts over the same images (order = detector order).  Returns per-image
     (boxes float64 [m,4] | None, scores f32, classes f32); None = skipped image (no detector fired).
     Case split of demo_probEn.py:237-267: 0 detectors -> skip, 1 -> passthrough, >= 2 -> fusion of the
@@ -83,8 +83,15 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
     file's position in dets, what pe_proben_pack_pooled writes on the device route.
     with_posterior ("probEn-log" only): every per-image result is a 6-tuple, the three above plus (log_posterior f64 [m, K+1], vars f64
     [m], members i32 [m]) of pe_proben_fuse_batch_posterior; a passed-through image takes its log-posterior from the calibrated file
-    ("log_probs") and its vars from the scaled file, what the device route's passthrough copies."""
-    F._check_mode(method[0], class_prior, "late_fusion", pool_weights, with_posterior)
+    ("log_probs") and its vars from the scaled file, what the device route's passthrough copies.
+    presence (a table [2^D][K+1], D = len(dets), "probEn-log" only): pe_proben_fuse_batch_presence.  Images on which one detector fired
+    are then no longer answered on the host: they go into the batched launch with their passthrough flag set and come back rescored
+    row by row (never clustered), which is what the device route does with the pack kernel's single-source flag - the two routes stay
+    byte-identical."""
+    F._check_mode(method[0], class_prior, "late_fusion", pool_weights, with_posterior, presence)
+    if presence is not None:
+        from . import calibration
+        presence = calibration.check_presence(presence, len(dets), None, "late_fusion: presence")
     if pool_weights is not None:
         from . import calibration
         pool_weights = calibration.check_pool_weights(pool_weights, len(dets), "late_fusion")
@@ -105,13 +112,13 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
         dets = [calibration.calibrate_j1(d, t, n, device, log_probs=logp) for d, t, n in zip(dets, temperatures, names)]
     n_img = len(dets[1]["image"]) if len(dets) > 1 else len(dets[0]["image"])      # the reference loops over det_2's images (:205)
     results = [None] * n_img
-    batch, where = [], []
+    batch, where, single = [], [], []
     for i in range(n_img):
         infos = [_info(d, i) for d in dets]
         live = [x for x in infos if len(x["bbox"]) > 0]
         if len(live) == 0:
             continue
-        if len(live) == 1:
+        if len(live) == 1 and presence is None:
             x = live[0]
             results[i] = (np.array(x["bbox"], dtype=np.float64), torch.tensor(x["score"], dtype=torch.float32),
                           torch.tensor(x["class"], dtype=torch.float32))
@@ -120,15 +127,21 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
                 results[i] += (np.asarray(x["log_prob"], dtype=np.float64).reshape(m, -1),
                                np.asarray(x["vars"], dtype=np.float64).reshape(m), np.ones(m, dtype=np.int32))
             continue
-        batch.append(infos if pool_weights is not None else live)      # pack_infos skips the empty ones; the positions stay
+        batch.append(infos if pool_weights is not None or presence is not None else live)      # pack_infos skips the empty ones; the positions stay
         where.append(i)
+        single.append(int(len(live) == 1))          # presence only: the image's passthrough flag
     if batch:
         if method[0] == "max" and method[1] == "argmax":
             for i, live in zip(where, batch):
                 b, s, c = F.fusion(method, *live)
                 results[i] = (b.double().numpy(), s, c)
         else:
-            if logp and pool_weights is not None:
+            if presence is not None:
+                b, s, p, v, c, offs, lp, src = F.pack_infos(batch, device, with_log_probs=True, with_sources=True)
+                out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior,
+                                   pool_weights=pool_weights, row_source=src, with_posterior=with_posterior, presence=presence,
+                                   passthrough=torch.tensor(single, dtype=torch.int32, device=b.device))
+            elif logp and pool_weights is not None:
                 b, s, p, v, c, offs, lp, src = F.pack_infos(batch, device, with_log_probs=True, with_sources=True)
                 out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior,
                                    pool_weights=pool_weights, row_source=src, with_posterior=with_posterior)
@@ -261,14 +274,62 @@ def fused_clusters(dets, box_fusion="v-avg", device="cuda", temperatures=None, n
             "boxes": out["boxes"][first], "box_offsets": torch.cat([zero, torch.cumsum(cnt, 0)]).to(torch.int32), "images": where}
 
 
+def presence_rows(dets, box_fusion="v-avg", device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None,
+                  pool_weights=None, presence=None):
+    """Every fused row "probEn-log" forms over dets (late_fusion's arguments) under a presence table, for the table's fit and its
+    report: all images on which a detector fired go through ONE pe_proben_fuse_batch_presence launch - images with one live detector
+    with their passthrough flag set, as in late_fusion - with the posterior outputs and out_pattern.  presence None = the zero table:
+    the fused log-posterior is then the `base` of calibration.fit_presence.  Clustering and boxes do not depend on the table.
+    Returns None when no detector fired anywhere, else a dict of device tensors over the C fused rows, image-major: log_posterior f64
+    [C, K+1], pattern i32 [C], boxes f64 [C, 4], box_offsets i32 [B'+1] (the rows of fused image j), and "images": the B' positions of
+    the fused images in dets."""
+    from . import calibration
+    D = len(dets)
+    if variance_scales is not None:
+        variance_scales = calibration.check_variance_scales(variance_scales, D, "presence_rows")
+        dets = [calibration.scale_j1_vars(d, s) for d, s in zip(dets, variance_scales)]
+    temperatures = [1.0] * D if temperatures is None else list(temperatures)
+    if len(temperatures) != D:
+        raise ValueError(f"presence_rows: {len(temperatures)} temperatures for {D} detectors")
+    names = names or [f"prediction file {k + 1}" for k in range(D)]
+    for d, n in zip(dets, names):
+        calibration.require_logits(d, n)
+    dets = [calibration.calibrate_j1(d, t, n, device, log_probs=True) for d, t, n in zip(dets, temperatures, names)]
+    batch, where, single = [], [], []
+    for i in range(len(dets[0]["image"])):
+        infos = [_info(d, i) for d in dets]
+        live = sum(len(x["bbox"]) > 0 for x in infos)
+        if live >= 1:
+            batch.append(infos)
+            where.append(i)
+            single.append(int(live == 1))
+    if not batch:
+        return None
+    b, s, p, v, c, offs, lp, src = F.pack_infos(batch, device, with_log_probs=True, with_sources=True)
+    table = np.zeros((2 ** D, lp.shape[1])) if presence is None else presence
+    out = F.fuse_batch(b, s, p, v, c, offs, F.LOGP, box_fusion, log_probs=lp, class_prior=class_prior, pool_weights=pool_weights,
+                       row_source=src, with_posterior=True, presence=table,
+                       passthrough=torch.tensor(single, dtype=torch.int32, device=b.device))
+    dev = b.device
+    cnt, in_off = out["counts"].long(), offs.long()
+    assert int(cnt.min()) >= 0, "presence_rows: an image over the row bound"       # max_rows is the longest image: cannot happen
+    C = int(cnt.sum())
+    base = torch.cumsum(cnt, 0) - cnt
+    first = torch.repeat_interleave(in_off[:-1] - base, cnt) + torch.arange(C, device=dev)      # fused row c's place in the outputs
+    zero = torch.zeros((1,), dtype=torch.long, device=dev)
+    return {"log_posterior": out["log_posterior"][first], "pattern": out["pattern"][first], "boxes": out["boxes"][first],
+            "box_offsets": torch.cat([zero, torch.cumsum(cnt, 0)]).to(torch.int32), "images": where}
+
+
 def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="", image_hw=None, device="cuda",
                                    img_folder="../../../Datasets/FLIR/val/thermal_8_bit/", temperatures=None, names=None,
-                                   class_prior=None, variance_scales=None, pool_weights=None, fused_out=None):
+                                   class_prior=None, variance_scales=None, pool_weights=None, fused_out=None, presence=None):
     """Same call as the reference (demo_probEn.py:198).  `image_hw`: {image_id: (H, W)} from the dataset
     json (the reference re-reads every thermal JPEG just for its shape); default 512 x 640 (FLIR).
     `img_folder`: the prefix the reference hard-codes into the `file_name` it hands to the evaluator (:200,271).
     `fused_out`: a list; when given ("probEn-log" only) the fusion keeps its posterior and the per-image 6-tuples of late_fusion are
     appended to it, for fused_to_j1 - the evaluator receives what it receives without it.
+    `presence`: late_fusion's presence table ("probEn-log" only).
     What the evaluator receives per image is pinned by tests/golden/p5_cases.json (the reference's function run with a recording
     evaluator): tests/test_pipeline_gpu.py::test_late_fusion_driver_reproduces_the_references_records."""
     evaluator.reset()
@@ -276,7 +337,7 @@ def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="
     start = time.time()
     dets = [det_1, det_2] + ([det_3] if det_3 else [])
     fused = late_fusion(dets, method, device, temperatures, names, class_prior, variance_scales, pool_weights,
-                        with_posterior=fused_out is not None)
+                        with_posterior=fused_out is not None, presence=presence)
     if fused_out is not None:
         fused_out.extend(fused)
     for i, r in enumerate(fused):

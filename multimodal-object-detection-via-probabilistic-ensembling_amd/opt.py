@@ -47,6 +47,11 @@ def config_parser(cmd=None):
                    help="demo_probEn --score_fusion probEn-log: one pooling weight per --detectors entry, 'a,b[,c]' by position or "
                         "'name=a,name=b' by name (a_j = sum_t w_d(t) log p_t[j]: the logarithmic opinion pool); default: the calibration "
                         "file's pool_weights if it has them (fit_temperature --with-pool-weights), else the plain product")
+    p.add_argument("--presence", type=str, default=None, metavar="TEXT",
+                   help="demo_probEn --score_fusion probEn-log (either route): presence evidence, one row of K + 1 numbers per presence "
+                        "pattern, 'thermal_only=a:b:c:d,thermal_only+early_fusion=a:b:c:d' (detector names joined by +, background "
+                        "last; patterns not listed get zeros); default: the calibration file's presence table if it has one "
+                        "(fit_temperature --with-presence), else none")
     p.add_argument("--write_fused", type=str, default=None, metavar="FILE",
                    help="demo_probEn --score_fusion probEn-log (either route): write the fused detections as a prediction file (the "
                         "schema of val_<method>_predictions.json: class_logits = the fused log-posterior, vars = the fused box's "
@@ -54,6 +59,8 @@ def config_parser(cmd=None):
     args = p.parse_args(cmd) if cmd is not None else p.parse_args()
     if args.write_fused is not None and args.score_fusion != "probEn-log":
         p.error(f"--write_fused belongs to --score_fusion probEn-log (got {args.score_fusion}): the other score fusions form no posterior")
+    if args.presence is not None and args.score_fusion != "probEn-log":
+        p.error(f"--presence belongs to --score_fusion probEn-log (got {args.score_fusion})")
     if args.pool_weights is not None and args.score_fusion != "probEn-log":
         p.error(f"--pool_weights belongs to --score_fusion probEn-log (got {args.score_fusion})")
     if args.class_prior is not None:

@@ -23,7 +23,7 @@ class FramePairPipeline:
 
     def __init__(self, models, score_fusion="probEn", box_fusion="v-avg", max_class=2, concurrent=True,
                  staggered=False, stagger_stage=4, fuse=True, temperatures=None, class_prior=None, variance_scales=None,
-                 pool_weights=None, with_posterior=False):
+                 pool_weights=None, with_posterior=False, presence=None):
         self.models = list(models)
         self.fuse = fuse and len(self.models) > 1   # a single detector has nothing to fuse (configs[1])
         self.method = (score_fusion, box_fusion)
@@ -34,7 +34,13 @@ class FramePairPipeline:
             raise ValueError(f"FramePairPipeline: {len(self.temperatures)} temperatures for {len(self.models)} detectors")
         # score_fusion "probEn-log": ProbEn on log_softmax(class_logits / T) with the background column kept (pe_proben_pack_log_posteriors,
         # pe_proben_fuse_batch_logp); T = 1 without temperatures; class_prior = K + 1 probabilities (background last) or None = uniform
-        F._check_mode(score_fusion, class_prior, "FramePairPipeline", pool_weights, with_posterior)
+        F._check_mode(score_fusion, class_prior, "FramePairPipeline", pool_weights, with_posterior, presence)
+        # a table [2^D][K+1] ("probEn-log" only): presence evidence (pe_proben_fuse_batch_presence); validated here, uploaded at the first batch
+        if presence is not None:
+            from .calibration import check_presence
+            presence = check_presence(presence, len(self.models), None, "FramePairPipeline: presence")
+        self.presence = presence
+        self._presence = None
         # "probEn-log" only: the fused rows keep their log-posterior, box variance and cluster size (pe_proben_fuse_batch_posterior)
         self.with_posterior = bool(with_posterior)
         # one w per detector ("probEn-log" only): the pooled rule (pe_proben_pack_pooled, pe_proben_fuse_batch_pooled); None = the product
@@ -144,9 +150,12 @@ class FramePairPipeline:
             self._log_prior = F.log_class_prior(self.class_prior, len(self.class_prior), dets[0]["scores"].device)
         if self.pool_weights is not None and self._pool is None:
             self._pool = F.pool_weight_tensor(self.pool_weights, len(self.pool_weights), dets[0]["scores"].device)
+        if self.presence is not None and self._presence is None:
+            from .calibration import presence_table
+            self._presence = presence_table(self.presence, len(self.models), self.presence.shape[1], dets[0]["scores"].device)
         return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class, temperatures=self.temperatures,
                                  class_prior=self._log_prior, variance_scales=self.variance_scales, pool_weights=self._pool,
-                                 with_posterior=self.with_posterior)
+                                 with_posterior=self.with_posterior, presence=self._presence)
 
 
 class HostFeeder:

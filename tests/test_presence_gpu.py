@@ -1,0 +1,506 @@
+"""Presence evidence for probEn-log on the GPU: pe_proben_fuse_batch_presence against the np.longdouble restatement of
+tests/test_presence_cpu.py, byte for byte against the entry points it extends at a zero table, the file route against the device route,
+pe_bias_nll against its restatement and calibration.fit_presence against the NumPy fit.  The comparator is never the code under test;
+clusters come from oracle.proben.order_desc plus the greedy rule (tests/test_proben_logp_gpu.py::_clusters).  u = 2^-53."""
+import json
+
+import numpy as np
+import pytest
+import torch
+
+from test_presence_cpu import BOX, LD, U, bias_terms, box_bound, np_fit_bias, np_bias_nll, restate, simulate, var_bound
+
+pytestmark = pytest.mark.gpu
+
+POOL = [0.6, 0.5, 0.8, 0.7]
+SEQ_ROWS = {2: 1000, 4: 1000, 63: 250}         # a bound at which the bit matrices no longer fit the LDS: the sequential walk
+BITS_ROWS = 12
+
+
+def _ulp32(x):
+    x = np.abs(np.asarray(x, np.float64))
+    return np.exp2(np.maximum(np.floor(np.log2(np.maximum(x, 2.0 ** -126))), -126.0) - 23.0)
+
+
+def _log_softmax(lg):
+    d = lg - lg.max(1, keepdims=True)
+    return d - np.log(np.exp(d).sum(1, keepdims=True))
+
+
+def _rows(rng, K1, spec):
+    """spec: [(anchor x, anchor y, class, source)]; boxes 60 x 50 jittered by <= 2 px on their anchor (rows of one anchor
+    overlap with IoU > 0.8, anchors 100 px apart never meet).  Scores are the row's own p[class]."""
+    n = len(spec)
+    boxes = np.array([[x, y, x + 60.0, y + 50.0] for x, y, _, _ in spec]) + rng.uniform(-2.0, 2.0, (n, 4))
+    cls = np.array([c for _, _, c, _ in spec], np.int32)
+    lg = rng.normal(0.0, 2.0, (n, K1))
+    lg[np.arange(n), cls] += rng.uniform(1.0, 6.0, n)
+    lp = _log_softmax(lg)
+    return {"boxes": boxes, "classes": cls, "lp": lp, "scores": np.exp(lp[np.arange(n), cls]), "vars": rng.uniform(0.5, 4.0, n),
+            "src": np.array([s for _, _, _, s in spec], np.int32)}
+
+
+_SETS = {}
+
+
+def image_set(K1, D):
+    """The batch of the issue: (0) one row; (1) rows of one detector with the passthrough flag set, two of them overlapping above the gate;
+    (2) rows of every detector: a cluster of three that holds two rows of detector 0, a cluster of two, a lone row of each detector;
+    (3) a row whose NaN coordinate removes it; (4) more rows than any bound used (count -1); (5) a row with source D in a cluster of
+    two, a lone row with source D and a lone row with source -1.  Computed once per (K + 1, D) and left unchanged."""
+    if (K1, D) not in _SETS:
+        rng = np.random.default_rng(100 * K1 + D)
+        K = K1 - 1
+        c = lambda: int(rng.integers(0, K))  # noqa: E731
+        c0, c1 = c(), c()
+        imgs = [_rows(rng, K1, [(10, 10, c(), D - 1)]),
+                _rows(rng, K1, [(10, 10, c0, 1), (10, 10, c0, 1), (210, 10, c(), 1), (410, 10, c(), 1)]),
+                _rows(rng, K1, [(10, 10, c0, 0), (10, 10, c0, 0), (10, 10, c0, 1), (110, 10, c1, D - 1), (110, 10, c1, 0)] +
+                      [(10 + 100 * d, 210, c(), d) for d in range(D)]),
+                _rows(rng, K1, [(10, 10, c0, 0), (10, 10, c0, 1)]),
+                _rows(rng, K1, [(10 + (i % 6) * 100, 10 + (i // 6 % 4) * 100, 0, i % D) for i in range(SEQ_ROWS[K1] + 3)]),
+                _rows(rng, K1, [(10, 10, c0, 0), (10, 10, c0, D), (210, 10, c(), D), (410, 10, c(), -1)])]
+        nan = imgs[3]
+        lo = int(np.argmin(nan["scores"]))
+        nan["boxes"][lo, 0] = np.nan                    # the lower-scored row: its IoU with the pivot is NaN, it leaves without a cluster
+        table = rng.normal(0.0, 1.5, (2 ** D, K1))
+        table[:, K] = 0.0                               # the fit's gauge; row 0 stays random: nothing may read it
+        _SETS[(K1, D)] = (imgs, [0, 1, 0, 0, 0, 0], table)
+    return _SETS[(K1, D)]
+
+
+def _launch(imgs, passthrough, box, max_rows, table, prior=None, pool=None, with_posterior=True, **kw):
+    from proben_amd import fusion as F
+    cat = lambda k, dt: torch.from_numpy(np.ascontiguousarray(np.concatenate([i[k] for i in imgs]).astype(dt))).cuda()  # noqa: E731
+    offs = torch.tensor(np.cumsum([0] + [len(i["scores"]) for i in imgs]), dtype=torch.int32).cuda()
+    out = F.fuse_batch(cat("boxes", np.float64), cat("scores", np.float64), None, cat("vars", np.float64), cat("classes", np.int32), offs,
+                       "probEn-log", box, max_rows=max_rows, log_probs=cat("lp", np.float64), class_prior=prior,
+                       passthrough=None if passthrough is None else torch.tensor(passthrough, dtype=torch.int32).cuda(),
+                       pool_weights=pool, row_source=cat("src", np.int32) if (pool is not None or table is not None or kw.get("src")) else None,
+                       with_posterior=with_posterior, presence=table)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}, offs.cpu().numpy()
+
+
+def _reference(imgs, passthrough, box, table, lprior, pool):
+    """Per image: None (over the bound) or [(pivot, members, restate's dict)] on the reference clustering."""
+    from test_proben_logp_gpu import _clusters
+    ref = []
+    for i, im in enumerate(imgs):
+        if i == 4:
+            ref.append(None)
+            continue
+        if passthrough[i]:
+            cl = [(r, [r]) for r in range(len(im["scores"]))]
+        else:
+            cl = _clusters(im["boxes"], im["scores"], im["classes"].astype(np.float64))
+        ref.append([(piv, mem, restate(im["lp"], im["boxes"], im["scores"], im["vars"], im["src"], mem, box, table, lprior, pool))
+                    for piv, mem in cl])
+    return ref
+
+
+# ---- 1. the fusion against the restatement --------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("box", BOX)
+@pytest.mark.parametrize("D", [2, 3, 4])
+@pytest.mark.parametrize("K1", [2, 4, 63])
+def test_fusion_against_the_restatement(K1, D, box):
+    """Every fused row of pe_proben_fuse_batch_presence against test_presence_cpu.restate on the image's own (reference) clustering: with
+    and without a non-uniform prior, pool weights and the posterior outputs, in both clustering forms (bound 12: bit matrices; bound
+    SEQ_ROWS: the sequential walk; the long image is over both: counts -1).
+      score: float64 relative (sum_{j != best} s_j E_j + K + 1) u plus the float32 exit's half ulp;
+      lq:    |lq_j - exact| <= (D_j + T + 2 |log tot| + |lq_j|) u absolute, A_j carrying the presence addition (restate's docstring);
+      vars:  relative (m + 3) u for v-avg, (3 m + 4) u for s-avg / avg, a copy for argmax and single rows;
+      boxes: (2 m + 1) X u per coordinate, X = sum_t |c_t lambda_t|, a copy for argmax and single rows;
+      classes, keep, counts, members, pattern, cluster: exact.  Rows nothing writes keep their pre-fill."""
+    imgs, passthrough, table = image_set(K1, D)
+    rng = np.random.default_rng(K1 + D)
+    prior = rng.dirichlet(np.full(K1, 2.0)) + 0.01
+    prior = prior / prior.sum()
+    worst = {"score": 0.0, "lq": 0.0, "var": 0.0, "box": 0.0}
+    seen = {"lone": 0, "pass": 0, "m3": 0, "nan": 0, "other": 0}
+    for use_prior in (False, True):
+        for pool in (None, POOL[:D]):
+            lprior = np.log(prior / prior.sum()) if use_prior else None          # what fusion.log_class_prior uploads
+            ref = _reference(imgs, passthrough, box, table, lprior, pool)
+            for post in (False, True):
+                for bound in (BITS_ROWS, SEQ_ROWS[K1]):
+                    out, offs = _launch(imgs, passthrough, box, bound, table, prior.tolist() if use_prior else None, pool, post)
+                    assert ("log_posterior" in out) == post and "pattern" in out and "cluster" in out
+                    written = np.zeros(offs[-1], bool)
+                    for i, (im, cl) in enumerate(zip(imgs, ref)):
+                        o = offs[i]
+                        if cl is None:
+                            assert out["counts"][i] == -1
+                            assert (out["cluster"][o:offs[i + 1]] == -2).all()
+                            continue
+                        assert out["counts"][i] == len(cl), (i, out["counts"][i], len(cl))
+                        np.testing.assert_array_equal(out["keep"][o:o + len(cl)], [p for p, _, _ in cl])
+                        want_cluster = np.full(len(im["scores"]), -1)
+                        for r, (piv, mem, w) in enumerate(cl):
+                            written[o + r] = True
+                            want_cluster[mem] = r
+                            m = len(mem)
+                            seen["pass" if passthrough[i] else "lone" if m == 1 else "m3" if m == 3 else "other"] += 1
+                            seen["nan"] += int(w["nan"])
+                            assert out["pattern"][o + r] == w["pattern"], (i, r, out["pattern"][o + r], w["pattern"])
+                            got_s = out["scores"][o + r]
+                            if w["nan"]:
+                                assert np.isnan(got_s) and out["classes"][o + r] == 0
+                                assert not post or np.isnan(out["log_posterior"][o + r]).all()
+                            else:
+                                want = w["score"]
+                                tol = 0.5 * _ulp32(float(want)) * (1 + 2.0 ** -20) + w["score_bound"] * U * float(want)
+                                err = abs(LD(got_s) - want)
+                                worst["score"] = max(worst["score"], float(err / tol))
+                                assert err <= tol, (i, r, m, got_s, float(want))
+                                assert out["classes"][o + r] == w["cls"], (i, r, out["classes"][o + r], w["cls"])
+                            bb = box_bound(box, m)
+                            X = np.abs(im["boxes"][mem]).max(0) if bb else None       # sum_t |c_t| lambda_t <= max_t |c_t|: the lambdas sum to 1
+                            got_b = out["boxes"][o + r]
+                            if bb == 0:
+                                assert got_b.tobytes() == w["box"].astype(np.float64).tobytes()
+                            else:
+                                eb = np.abs(got_b.astype(LD) - w["box"]).astype(np.float64) / (bb * X * U)
+                                worst["box"] = max(worst["box"], float(eb.max()))
+                                assert (eb <= 1).all(), (i, r, m, eb)
+                            if not post:
+                                continue
+                            assert out["members"][o + r] == m
+                            if not w["nan"]:
+                                e = np.abs(out["log_posterior"][o + r].astype(LD) - w["lq"]).astype(np.float64) / (w["lq_bound"] * U)
+                                worst["lq"] = max(worst["lq"], float(e.max()))
+                                assert (e <= 1).all(), (i, r, m, e)
+                            vb = var_bound(box, m)
+                            got_v = out["vars"][o + r]
+                            if vb == 0:
+                                assert got_v == float(w["var"])
+                            else:
+                                rel = float(abs(LD(got_v) - w["var"]) / w["var"])
+                                worst["var"] = max(worst["var"], rel / (vb * U))
+                                assert rel <= vb * U, (i, r, m, rel / U, vb)
+                        np.testing.assert_array_equal(out["cluster"][o:offs[i + 1]], np.arange(len(im["scores"])) if passthrough[i] else want_cluster)
+                    assert (out["pattern"][~written] == -1).all()
+                    if post:
+                        assert np.isnan(out["log_posterior"][~written]).all() and np.isnan(out["vars"][~written]).all()
+                        assert (out["members"][~written] == 0).all()
+    # the batch holds what the issue lists: lone rows, passthrough rows (two of them overlapping, not merged), a cluster of three, NaN rows,
+    # and a row that left without a cluster
+    assert seen["lone"] and seen["pass"] and seen["m3"] and seen["nan"], seen
+    assert len(_reference(imgs, passthrough, box, table, None, None)[1]) == 4 and (np.asarray([c[2]["pattern"] for c in ref[1]]) == 2).all()
+    assert len(ref[3]) == 1 and len(ref[3][0][1]) == 1
+    print(f"K+1={K1} D={D} {box}: largest error / bound: score {worst['score']:.3f}, lq {worst['lq']:.3f}, variance {worst['var']:.3f}, "
+          f"box {worst['box']:.3f}")
+
+
+# ---- 2. a zero table is the existing kernels on clusters of two or more -----------------------------------------------------------------
+
+@pytest.mark.parametrize("box", ["v-avg", "s-avg", "argmax"])
+@pytest.mark.parametrize("D", [2, 4])
+def test_zero_table_equals_the_existing_entry_points(D, box):
+    """At a zero table every output of a cluster of m >= 2 rows equals pe_proben_fuse_batch_logp, _pooled and _posterior on the same input
+    (np.array_equal: x + 0.0 is x), in both clustering forms; counts, keep, cluster and boxes are equal for EVERY row (the table never
+    touches clustering or boxes), and they are the same at a random table too.  Lone and passthrough rows are normalised, not copied:
+    their class is the argmax of the row's K + 1 log-posteriors and their score float32(exp(max_j lp_j)) within one float32 ulp (the
+    normalisation of an already normalised row moves the float64 value by a few u)."""
+    K1 = 4
+    imgs, passthrough, table = image_set(K1, D)
+    imgs, passthrough = imgs[:4], passthrough[:4]           # sources in range: the pooled entry point would give NaN otherwise
+    zero = np.zeros_like(table)
+    prior = [0.3, 0.2, 0.1, 0.4]
+    for bound in (BITS_ROWS, SEQ_ROWS[K1]):
+        for pool in (None, POOL[:D]):
+            for post in (False, True):
+                new, offs = _launch(imgs, passthrough, box, bound, zero, prior, pool, post)
+                old, _ = _launch(imgs, passthrough, box, bound, None, prior, pool, post, src=True)
+                rnd, _ = _launch(imgs, passthrough, box, bound, table, prior, pool, post)
+                assert np.array_equal(new["counts"], old["counts"]) and np.array_equal(rnd["counts"], old["counts"])
+                live = np.concatenate([np.arange(offs[i], offs[i] + new["counts"][i]) for i in range(len(imgs))])
+                for k in ("keep", "boxes") + (("cluster",) if "cluster" in old else ()):
+                    rows = live if k != "cluster" else slice(None)
+                    assert np.array_equal(new[k][rows], old[k][rows]) and np.array_equal(rnd[k][rows], old[k][rows]), k
+                if post:
+                    assert np.array_equal(new["members"][live], old["members"][live]) and np.array_equal(new["vars"][live], old["vars"][live])
+                    multi = live[old["members"][live] >= 2]
+                else:
+                    m_of, _ = _launch(imgs, passthrough, box, bound, zero, prior, pool, True)
+                    multi = live[m_of["members"][live] >= 2]
+                assert len(multi) >= 2
+                for k in set(old) - {"counts"}:
+                    rows = multi if k != "cluster" else slice(None)
+                    assert np.array_equal(new[k][rows], old[k][rows]), (k, bound, pool, post)
+                assert set(new) - set(old) <= {"pattern", "cluster"}
+                single = np.setdiff1d(live, multi)
+                assert len(single) >= 6
+                lp_all = np.concatenate([i["lp"] for i in imgs])
+                img_of = np.searchsorted(offs, single, side="right") - 1
+                own = lp_all[offs[img_of] + new["keep"][single]]                        # keep = the row itself on both kinds of single rows
+                assert np.array_equal(new["classes"][single], own.argmax(1).astype(np.float32))
+                want = np.exp(own.max(1))
+                assert (np.abs(new["scores"][single].astype(np.float64) - want) <= _ulp32(want)).all()
+
+
+# ---- 3. the file route and the device route ---------------------------------------------------------------------------------------------
+
+def test_late_fusion_and_fuse_detections_agree_byte_for_byte():
+    """late_fusion(presence=...) over prediction dicts and fuse_detections(presence=...) over the same detections give the same bytes,
+    with and without pool weights, on images where both detectors fired, where only one fired (rescored row by row on both routes)
+    and where none fired; without the keyword both routes are what they were."""
+    from test_calibration_gpu import detector_rows
+    from proben_amd import fusion as F
+    from proben_amd.late_fusion import late_fusion
+    src = detector_rows(3)
+    B, Dn = src[0]["scores"].shape
+    dets = [dict(d) for d in src]
+    for k in (0, 1):
+        dets[k]["counts"] = src[k]["counts"].clone()
+    dets[1]["counts"][1] = 0               # image 1: only detector 0
+    dets[0]["counts"][2] = 0               # image 2: only detector 1
+    dets[0]["counts"][3] = 0               # image 3: nobody
+    dets[1]["counts"][3] = 0
+    S = 2 * Dn
+    table = np.array([[9.0, 9.0, 9.0, 9.0], [-0.1, -0.9, 0.2, 0.0], [-1.3, 0.1, 0.3, 0.0], [1.6, 1.5, 1.1, 0.0]])
+    keys = ("boxes", "scores", "classes", "log_posterior", "vars", "members")
+    j1 = []
+    for d in dets:
+        c = d["counts"].cpu().numpy()
+        rec = {k: [] for k in ("image", "boxes", "scores", "classes", "image_id", "class_logits", "probs", "vars")}
+        for b in range(B):
+            keep = [j for j in range(c[b]) if int(d["classes"][b, j]) <= 2]
+            rec["image"].append(f"f{b}.jpeg")
+            rec["image_id"].append(b)
+            for key, s in (("boxes", "boxes"), ("scores", "scores"), ("classes", "classes"), ("class_logits", "class_logits"), ("probs", "prob_score")):
+                rec[key].append([d[s][b, j].tolist() for j in keep])
+            rec["vars"].append([[float(d["vars"][b, j])] for j in keep])
+        j1.append(json.loads(json.dumps(rec)))
+    fired = [[len(r["boxes"][b]) > 0 for r in j1] for b in range(B)]
+    assert fired[1] == [True, False] and fired[2] == [False, True] and fired[3] == [False, False] and sum(all(f) for f in fired) >= 2
+    for tp, pr, pw in (((1.5, 0.8), [0.1, 0.3, 0.2, 0.4], None), (None, None, [0.6, 0.5])):
+        dev = F.fuse_detections(dets, "probEn-log", "v-avg", temperatures=tp, class_prior=pr, pool_weights=pw, with_posterior=True, presence=table)
+        via = late_fusion(j1, ["probEn-log", "v-avg"], temperatures=tp, class_prior=pr, pool_weights=pw, with_posterior=True, presence=table)
+        plain = late_fusion(j1, ["probEn-log", "v-avg"], temperatures=tp, class_prior=pr, pool_weights=pw, with_posterior=True)
+        torch.cuda.synchronize()
+        cnt = dev["counts"].cpu().numpy()
+        host = {k: dev[k].cpu().numpy() for k in keys + ("pattern",)}
+        for b in range(B):
+            if via[b] is None:
+                assert cnt[b] == 0 and fired[b] == [False, False] and plain[b] is None
+                continue
+            sl = slice(b * S, b * S + cnt[b])
+            assert len(via[b]) == 6 and len(via[b][1]) == cnt[b] > 0
+            for k, got in zip(keys, via[b]):
+                got = got.numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
+                assert got.dtype == host[k].dtype and got.tobytes() == host[k][sl].tobytes(), (b, k)
+            if sum(fired[b]) == 1:          # rescored, never merged: one output row per input row, each with its detector's pattern
+                assert (host["pattern"][sl] == (1 if fired[b][0] else 2)).all() and (host["members"][sl] == 1).all()
+                assert len(plain[b][1]) == cnt[b] and np.array_equal(plain[b][0], host["boxes"][sl])
+                a = plain[b][3] + table[1 if fired[b][0] else 2]                  # without the keyword the row's log-posterior is copied
+                a = a - a.max(1, keepdims=True)
+                assert np.allclose(host["log_posterior"][sl], a - np.log(np.exp(a).sum(1, keepdims=True)), rtol=0, atol=1e-12)
+            else:
+                assert set(host["pattern"][sl].tolist()) <= {1, 2, 3}
+    none = F.fuse_detections(dets, "probEn-log", "v-avg")
+    assert "pattern" not in none and "row_source" not in none
+
+
+# ---- 4. pe_bias_nll against the restatement -----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n_c", [1, 64])
+@pytest.mark.parametrize("K1", [2, 4, 16])
+@pytest.mark.parametrize("C", [0, 1, 5, 4 * 1024 + 3])
+def test_bias_nll_against_the_restatement(C, K1, n_c):
+    """NLL and gradient of every candidate against test_presence_cpu.bias_terms summed in np.longdouble.  A label of -1, a label of K + 1
+    and a NaN row (where C allows) are excluded and counted, and the last excluded index is right.  C = 4 * 1024 + 3 makes the workgroup
+    cap bind (1024 workgroups of 4 wavefronts, 3 clusters into a second round).
+    Bound: the per-cluster softmax bound of bias_terms summed over the clusters, plus the accumulation: a value is added up along a
+    chain of at most depth = ceil(C / (4 blocks)) (a lane's clusters) + 3 (the workgroup's waves) + ceil(blocks / 16) (a segment of the
+    second pass) + 15 (the segments) additions, each rounding a partial sum of magnitude <= sum |terms|: depth * sum |terms| u
+    (DESIGN.md sections 16 and 18).  The same input twice gives the same bits."""
+    from proben_amd.calibration import bias_nll
+    rng = np.random.default_rng(C * 100 + K1 + n_c)
+    base = _log_softmax(rng.normal(0.0, 3.0, (C, K1)))
+    labels = rng.integers(0, K1, C).astype(np.int32)
+    bad = []
+    if C >= 5:
+        labels[1], labels[3] = -1, K1
+        base[C - 1, rng.integers(0, K1)] = np.nan
+        bad = [1, 3, C - 1]
+    cand = rng.normal(0.0, 2.0, (n_c, K1))
+    cand[0] = 0.0
+    dev = (torch.from_numpy(base).cuda(), torch.from_numpy(labels).cuda())
+    nll, grad, excluded, last = bias_nll(*dev, cand)
+    nll2, grad2, _, _ = bias_nll(*dev, cand)
+    assert nll.tobytes() == nll2.tobytes() and grad.tobytes() == grad2.tobytes()
+    assert nll.shape == (n_c,) and grad.shape == (n_c, K1)
+    assert excluded == len(bad) and last == (max(bad) if bad else -1)
+    if C == 0:
+        assert not nll.any() and not grad.any()
+        return
+    ok = np.setdiff1d(np.arange(C), bad)
+    blocks = min((C + 3) // 4, 1024)
+    depth = -(-C // (4 * blocks)) + 3 + -(-blocks // 16) + 15
+    worst_n = worst_g = 0.0
+    for c in range(n_c):
+        term, g, nb, gb = bias_terms(base[ok], labels[ok], cand[c])
+        tol_n = (nb.sum() + depth * float(np.abs(term).sum())) * U
+        tol_g = (gb.sum(0) + depth * np.abs(g.astype(np.float64)).sum(0)) * U
+        en = abs(LD(nll[c]) - term.sum())
+        eg = np.abs(grad[c].astype(LD) - g.sum(0)).astype(np.float64)
+        worst_n, worst_g = max(worst_n, float(en / tol_n)), max(worst_g, float((eg / tol_g).max()))
+        assert en <= tol_n and (eg <= tol_g).all(), (c, float(en), tol_n, eg / tol_g)
+    print(f"C={C} K+1={K1} n_c={n_c}: largest error / bound: NLL {worst_n:.3f}, gradient {worst_g:.3f}")
+
+
+# ---- 5. fit_presence ------------------------------------------------------------------------------------------------------------------
+
+def test_fit_presence_against_the_numpy_fit():
+    """3 000 simulated clusters (test_presence_cpu.simulate: K + 1 = 4, two detectors), fitted as a D = 3 call so that patterns 4 .. 7 have no
+    cluster: every populated pattern converges, the empty ones stay zero rows, and the table agrees with the NumPy fit of the same
+    clusters within what the two stop rules allow.
+    Derivation.  Both fits stop at a point whose gradient satisfies |g|_inf <= gtol * C_P on the free coordinates (the device fit's own
+    final gradient is reported; the NumPy fit's is recomputed here).  The NLL is twice differentiable and convex with Hessian
+    H(b) = sum_c diag(s_c) - s_c s_c^T; between the two stopping points g(b1) - g(b2) = Hbar (b1 - b2) with Hbar the Hessian averaged
+    along the segment, so |b1 - b2|_2 <= (|g1|_2 + |g2|_2) / lambda_min(Hbar).  Both points lie within a few 1e-7 of the minimiser, where H
+    varies by a relative 1e-6 at most; lambda_min of the restatement's Hessian AT the NumPy fit, halved, is a safe lower bound for Hbar.
+    The device gradient itself carries its kernel's rounding (test_bias_nll_against_the_restatement: far below gtol * C_P), covered by
+    taking 2 gtol C_P for each gradient norm instead of the measured one.
+    A pattern in which label 0 never occurs has its minimum at b_0 = -infinity: the fit stops at -hi and says so."""
+    from proben_amd.calibration import fit_presence
+    base, pat, lab = simulate(7, 3000)
+    dev = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (base, pat, lab)]
+    gtol = 1e-7
+    fit = fit_presence(*dev, 3, gtol=gtol)
+    table = np.asarray(fit["table"])
+    assert table.shape == (8, 4) and fit["hi"] == 16.0 and fit["unassigned"] == 0
+    worst = 0.0
+    for P in range(1, 8):
+        rec = fit["patterns"][P]
+        sel = pat == P
+        assert rec["clusters"] == int(sel.sum()) and rec["excluded"] == 0
+        if P >= 4:
+            assert rec["clusters"] == 0 and not table[P].any() and rec["rounds"] == 0
+            continue
+        assert rec["clusters"] > 500 and rec["converged"] and rec["at_bound"] == [None] * 3 and rec["nll"] < rec["nll_at_0"]
+        assert max(abs(x) for x in rec["grad"]) <= gtol * rec["clusters"] and table[P, 3] == 0.0
+        b, _, conv = np_fit_bias(base[sel], lab[sel], gtol=gtol)
+        assert conv
+        _, g, H = np_bias_nll(base[sel], lab[sel], b)
+        lam = 0.5 * float(np.linalg.eigvalsh(H[:3, :3]).min())
+        tol = 2 * (2 * gtol * rec["clusters"] * np.sqrt(3.0)) / lam
+        d = float(np.linalg.norm(table[P, :3] - b[:3]))
+        worst = max(worst, d / tol)
+        assert d <= tol, (P, d, tol)
+    print(f"fit_presence against the NumPy fit: largest |b - b_numpy| / bound {worst:.3f}; rows " +
+          " ".join(f"P={P}:({', '.join(f'{v:+.3f}' for v in table[P])})" for P in (1, 2, 3)))
+    # label 0 never occurs in pattern 1
+    lab2 = lab.copy()
+    lab2[(pat == 1) & (lab == 0)] = 3
+    fit2 = fit_presence(dev[0], dev[1], torch.from_numpy(lab2).cuda(), 2, gtol=gtol)
+    rec = fit2["patterns"][1]
+    assert rec["at_bound"][0] == "lo" and rec["at_bound"][1:] == [None, None] and fit2["table"][1][0] == -16.0
+    assert fit2["patterns"][2]["at_bound"] == [None] * 3 and fit2["patterns"][2]["converged"]
+
+
+# ---- 6. the drivers ---------------------------------------------------------------------------------------------------------------------
+
+def test_fit_temperature_demo_and_report_drivers(tmp_path, capsys):
+    """On the synthetic prediction files of the pool-weights driver test (per image four two-row clusters and one row only thermal_only
+    made, which nothing in the ground truth overlaps): fit_temperature --with-presence writes the key - the pattern early_fusion alone
+    has no cluster and keeps a zero row; the lone thermal_only rows are all background, so their row stops on the search bound and says
+    so -, demo_probEn --calibration gives the rows that --presence with the same table typed out gives, and calibration_report prints
+    the per-pattern lines and fuses its "after" rows with the table."""
+    from test_pool_gpu import _dependent_files
+    from proben_amd import calibration as Cal
+    from proben_amd.cli import calibration_report, demo_probEn, fit_temperature
+    root, files, preds, labels = _dependent_files(tmp_path)
+    names = ["thermal_only", "early_fusion"]
+    cal = tmp_path / "cal.json"
+    fit_temperature.main(["--predictions", *files, "--dataset_path", str(root), "--holdout", "0.5", "--out", str(cal),
+                          "--with-pool-weights", "--with-presence"])
+    printed = capsys.readouterr().out
+    with capsys.disabled():          # shown, and kept out of what the next readouterr() returns
+        print(printed)
+    rec = Cal.load(cal)
+    pres = rec["presence"]
+    assert pres["detectors"] == names and pres["columns"] == 4 and pres["hi"] == 16.0 and np.asarray(pres["table"]).shape == (4, 4)
+    assert pres["box_fusion"] == "v-avg" and pres["iou"] == 0.5 and pres["unassigned"] == 0
+    per = pres["patterns"]
+    assert list(per) == ["thermal_only", "early_fusion", "thermal_only+early_fusion"]
+    assert per["early_fusion"]["clusters"] == 0 and pres["table"][2] == [0.0] * 4 and pres["table"][0] == [0.0] * 4
+    assert per["thermal_only"]["clusters"] == 8 and per["thermal_only"]["at_bound"] == ["lo"] * 3 and pres["table"][1] == [-16.0] * 3 + [0.0]
+    both = per["thermal_only+early_fusion"]
+    assert both["clusters"] == 32 and both["converged"] and both["nll"]["after"] < both["nll"]["before"]
+    for name in per:
+        assert f"presence {name}: (" in printed
+    assert "on the search range's bound" in printed
+
+    def demo(tag, extra):
+        out = tmp_path / f"out_{tag}"
+        res = demo_probEn.main(["--dataset_path", str(root), "--prediction_path", str(tmp_path / "pred"), "--detectors", ",".join(names),
+                                "--outfolder", str(out), "--dataset_name", f"flir_presence_{tag}", "--score_fusion", "probEn-log"] + extra)
+        return out, res
+    o_cal, r_cal = demo("cal", ["--calibration", str(cal)])
+    text = ",".join("+".join(n for d, n in enumerate(names) if P >> d & 1) + "=" + ":".join(repr(v) for v in pres["table"][P]) for P in (1, 2, 3))
+    typed = ["--temperatures", ",".join(repr(rec["detectors"][n]) for n in names), "--pool_weights", ",".join(repr(rec["pool_weights"][n]) for n in names)]
+    o_txt, r_txt = demo("typed", typed + ["--presence", text])
+    o_off, r_off = demo("off", typed)
+    assert r_cal["presence"] == r_txt["presence"] == {"detectors": names, "table": pres["table"]} and "presence" not in r_off
+    rows = lambda o: json.load(open(o / "coco_instances_results.json"))  # noqa: E731
+    assert (o_cal / "coco_instances_results.json").read_bytes() == (o_txt / "coco_instances_results.json").read_bytes()
+    assert len(rows(o_cal)) > 0 and [r["score"] for r in rows(o_cal)] != [r["score"] for r in rows(o_off)]
+    # the lone thermal_only rows (x = 85) became background rows (their table row is -16 on every class): the evaluator drops them
+    lone = lambda o: sum(abs(r["bbox"][0] - 85.0) < 1e-9 for r in rows(o))  # noqa: E731
+    assert lone(o_off) == 16 and lone(o_cal) == 0
+
+    capsys.readouterr()
+    base = ["--dataset_path", str(root), "--predictions", *files, "--score_fusion", "probEn-log"]
+    report = calibration_report.main(base + ["--calibration", str(cal)])
+    printed = capsys.readouterr().out
+    with capsys.disabled():
+        print(printed)
+    r = report["presence"]
+    assert "fused NLL per row" in printed and "without the presence table" in printed and r["applied"] and r["table"] == pres["table"]
+    assert r["rows"] == 40 and r["excluded"] == 0 and r["patterns"]["thermal_only"]["rows"] == 8 and r["patterns"]["early_fusion"]["rows"] == 0
+    for name, q in r["patterns"].items():
+        assert f"  presence {name}: " in printed
+    assert f"{r['nll']['before']:.6f} without the presence table, {r['nll']['after']:.6f} with the file's" in printed
+    assert r["patterns"]["thermal_only"]["nll"]["after"] < r["patterns"]["thermal_only"]["nll"]["before"]     # held out: background again
+    stripped = {k: v for k, v in json.load(open(cal)).items() if k != "presence"}
+    json.dump(stripped, open(tmp_path / "cal_plain.json", "w"))
+    plain = calibration_report.main(base + ["--calibration", str(tmp_path / "cal_plain.json")])
+    assert "presence" not in plain and "fused NLL per row" not in capsys.readouterr().out
+    assert plain["fused"]["after"]["brier"] != report["fused"]["after"]["brier"]       # the "after" rows are fused with the table
+    other = calibration_report.main(base[:-1] + ["probEn", "--calibration", str(cal)])
+    assert not other["presence"]["applied"] and "no log-evidence to add it to" in capsys.readouterr().out
+    with pytest.raises(SystemExit):
+        fit_temperature.main(["--predictions", files[0], "--dataset_path", str(root), "--out", str(cal), "--with-presence"])
+
+
+def test_demo_proben_presence_two_stage_and_one_pass(tmp_path):
+    """demo_probEn --score_fusion probEn-log --presence: the two-stage route (late_fusion) and --one-pass (FramePairPipeline) give
+    identical AP tables and rows, --write_fused files included (the fused log-posterior carries the presence term), and they differ
+    from the run without the flag."""
+    from test_stream_gpu import _weights, _write_flir
+    from proben_amd.cli import demo_probEn, save_predictions
+    root = tmp_path / "val"
+    _write_flir(root, 6, 96, 120, (150, 180))
+    names = ["thermal_only", "early_fusion"]
+    paths = [_weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
+    pdir = tmp_path / "pred"
+    for m, p in zip(names, paths):
+        save_predictions.main(["--dataset_path", str(root), "--fusion_method", m, "--model_path", p, "--prediction_path", str(pdir), "--batch", "4"])
+    flags = ["--score_fusion", "probEn-log", "--presence", "thermal_only=-0.4:0.3:-0.2:0,early_fusion=0.5:-0.6:0.1:0,thermal_only+early_fusion=0.9:0.7:1.1:0"]
+    o2, o1, o0 = tmp_path / "o2", tmp_path / "o1", tmp_path / "o0"
+    r2 = demo_probEn.main(["--dataset_path", str(root), "--prediction_path", str(pdir), "--detectors", ",".join(names), "--outfolder", str(o2),
+                           "--dataset_name", "flir_pres2", "--write_fused", str(o2 / "fused.json")] + flags)
+    r1 = demo_probEn.main(["--one-pass", "--dataset_path", str(root), "--detectors", ",".join(names), "--model_paths", ",".join(paths), "--workers", "2",
+                           "--batch", "4", "--outfolder", str(o1), "--dataset_name", "flir_pres1", "--write_fused", str(o1 / "fused.json")] + flags)
+    demo_probEn.main(["--dataset_path", str(root), "--prediction_path", str(pdir), "--detectors", ",".join(names), "--outfolder", str(o0),
+                      "--dataset_name", "flir_pres0"] + flags[:2])
+    assert r2["presence"] == r1["presence"] and r2["presence"]["table"][3] == [0.9, 0.7, 1.1, 0.0]
+    assert (o1 / "FLIR_probEn_eval.json").read_bytes() == (o2 / "FLIR_probEn_eval.json").read_bytes()
+    assert (o1 / "fused.json").read_bytes() == (o2 / "fused.json").read_bytes()
+    a, b, c = (json.load(open(o / "coco_instances_results.json")) for o in (o1, o2, o0))
+    assert len(a) == len(b) > 0
+    assert [(r["image_id"], r["category_id"], r["score"]) for r in a] == [(r["image_id"], r["category_id"], r["score"]) for r in b]
+    assert [r["score"] for r in b] != [r["score"] for r in c]
