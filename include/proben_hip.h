@@ -418,6 +418,42 @@ int pe_bias_nll(const double* base, const int32_t* labels, int32_t num_clusters,
                 int32_t num_candidates, double* workspace, double* out, int32_t* out_flags /* [2] */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Correlated box fusion, box_fusion "c-avg" (csrc/boxcorr.hip).  Not a box_mode of the fusion kernel: a second
+ * launch after a "v-avg" fusion that wrote out_cluster.
+ * pe_box_gls_batch: for every fused row k < counts[b] of image b whose cluster (the input rows with cluster == k) has two or more rows,
+ *   out_boxes[offsets[b] + k] and, when given, out_vars[offsets[b] + k] are OVERWRITTEN with the generalised-least-squares mean of the
+ *   members' boxes and its variance 1 / (1' C^-1 1), C_tu = R_tu sqrt(var_t var_u), R = the members' correlation under `correlation`
+ *   (DEVICE, row-major [num_detectors * num_detectors], symmetric: entry [a][b] between rows of detectors a != b, [d][d] between two rows
+ *   of detector d, in [0, 1); positive semidefinite - the caller's to check).  boxes / variances / row_source / cluster are the
+ *   fusion's inputs and its out_cluster, offsets / row_counts its layout, counts its out_counts.  Nothing else is written: not for an
+ *   image with counts <= 0, not beyond counts[b], not for a cluster of one row.  A member whose source is outside [0, num_detectors)
+ *   makes its cluster's box and variance NaN, and so does a cluster whose R is not positive definite (several rows of one detector
+ *   under an off-diagonal entry the diagonal cannot carry: no distribution has those correlations).  A workgroup per image, rows staged in LDS 1 024 at a time (48 KiB), so the capacity is the
+ *   fusion's: max_rows_per_image in [1, 2048].  num_detectors in [1, PE_BOX_CORR_MAX_DETECTORS].
+ * pe_box_pair_stats: the statistics of the correlation's fit over clusters in CSR form (member_rows [num_members] into the packed rows,
+ *   cluster_offsets [num_clusters + 1], cluster_match [num_clusters] = the cluster's ground-truth box or -1: the cluster adds nothing).
+ *   With z_t = get_deltas(row t, ground truth) / sqrt(var_t) (bbox_reg_weights as pe_variance_stats), out holds 28 eight-byte values:
+ *   int64 N_ab for the 10 detector pairs a <= b in the order 00 01 02 03 11 12 13 22 23 33 (unordered member pairs t < u of one cluster),
+ *   int64 M_d [4] (member rows), then f64 S_ab [10] = sum over those pairs of sum_c z_tc z_uc and f64 Q_d [4] = sum_c z_tc^2.  A member
+ *   with a degenerate box (its own or the ground truth's), a variance that is not finite and > 0 or a source outside [0, num_detectors)
+ *   takes no part and is counted in out_flags ([2]: how many, 1 + the last such member index).  No floating-point atomics; the grid,
+ *   min(ceil(num_clusters / 256), PE_BOX_PAIR_MAX_BLOCKS) workgroups, is a function of num_clusters alone: same input, same bits.
+ *   workspace: f64, 6 * num_members + (num_members + 1) / 2 + 28 * PE_BOX_PAIR_MAX_BLOCKS values.  num_clusters == 0: zeros, no kernel.
+ * Arguments are checked before any device work.
+ * ------------------------------------------------------------------------------------------- */
+#define PE_BOX_CORR_MAX_DETECTORS PE_PRESENCE_MAX_DETECTORS
+#define PE_BOX_PAIR_MAX_BLOCKS 1024
+int pe_box_gls_batch(const double* boxes, const double* variances, const int32_t* row_source, const int32_t* cluster,
+                     const int32_t* offsets, const int32_t* row_counts /* optional */, const int32_t* counts, int32_t num_images,
+                     int32_t max_rows_per_image, const double* correlation, int32_t num_detectors, double* out_boxes /* in/out */,
+                     double* out_vars /* optional, in/out */, void* stream);
+int pe_box_pair_stats(const double* boxes, const double* variances, const int32_t* row_source, int64_t num_rows,
+                      const int32_t* member_rows, int64_t num_members, const int32_t* cluster_offsets, const int32_t* cluster_match,
+                      int32_t num_clusters, const double* gt_boxes, int64_t num_gt, int32_t num_detectors,
+                      const float* bbox_reg_weights_host /* [4] or NULL = 10, 10, 5, 5 */, double* workspace, double* out /* [28] */,
+                      int32_t* out_flags /* [2] */, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused convolution / GEMM: NHWC fp16 activations, [Cout][KH][KW][Cin] fp16 weights, fp32 accumulate
  * on MFMA, epilogue = + bias[Cout] (fp32) + residual + ReLU, fp16 (or fp32) NHWC output.
  * Replaces, per layer, detectron2.layers.Conv2d.forward (layers/wrappers.py:62-98) + FrozenBatchNorm2d

@@ -28,6 +28,9 @@ SIGNATURES = {
     "pe_proben_fuse_batch_posterior": [c_void_p] * 9 + [c_int] * 4 + [c_double] * 3 + [c_void_p] * 2 + [c_int] + [c_void_p] * 9 + [c_void_p],
     "pe_proben_fuse_batch_presence": [c_void_p] * 9 + [c_int] * 4 + [c_double] * 3 + [c_void_p] * 3 + [c_int] + [c_void_p] * 10 + [c_void_p],
     "pe_bias_nll": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "pe_box_gls_batch": [c_void_p] * 7 + [c_int, c_int, c_void_p, c_int] + [c_void_p] * 3,
+    "pe_box_pair_stats": [c_void_p] * 3 + [ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_int64,
+                          c_int] + [c_void_p] * 5,
     "pe_proben_pack_pooled": [c_void_p] * 9 + [c_int] * 6 + [c_void_p] * 11,
     "pe_pool_nll": [c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                     c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],

@@ -32,6 +32,14 @@ the cluster) inside score_fusion "probEn-log", added to the fused columns last; 
   check_presence / presence_table / parse_presence / resolve_presence
   bias_nll / fit_presence                  a table row's NLL and gradient for up to 64 candidates (pe_bias_nll); the per-pattern fit
   save / load                              carry the optional key "presence" {"detectors", "columns", "table", "hi"}
+
+Correlated box fusion (csrc/boxcorr.hip): box_fusion "c-avg", the generalised-least-squares mean of a cluster's boxes under one
+correlation per detector pair of the normalised box errors, and the variance that mean really has.
+  check_box_correlation / box_correlation_tensor / parse_box_correlation / resolve_box_correlation
+  box_pair_stats / fit_box_correlation     the residuals' cross products per detector pair (pe_box_pair_stats); the uncentred estimator
+  shrink_to_psd                            the off-diagonal shrink that makes a fitted matrix positive semidefinite
+  save / load                              carry the optional key "box_correlation" {"detectors", "matrix", "raw", "shrink", "pairs",
+                                           "rows", "excluded", "iou", "box_fusion": "v-avg"}
 """
 import ctypes
 import json
@@ -52,6 +60,8 @@ POOL_NLL_MAX_BLOCKS = 1024   # PE_POOL_NLL_MAX_BLOCKS: 1 + num_detectors partial
 PRESENCE_MAX_DETECTORS = 4   # PE_PRESENCE_MAX_DETECTORS
 BIAS_NLL_MAX_COLUMNS = 16    # PE_BIAS_NLL_MAX_COLUMNS: a lane of pe_bias_nll keeps 1 + (K + 1) accumulators in registers
 BIAS_NLL_MAX_BLOCKS = 1024   # PE_BIAS_NLL_MAX_BLOCKS: 1 + (K + 1) partial values per workgroup and candidate
+BOX_CORR_MAX_DETECTORS = PRESENCE_MAX_DETECTORS      # PE_BOX_CORR_MAX_DETECTORS
+BOX_PAIR_MAX_BLOCKS = 1024   # PE_BOX_PAIR_MAX_BLOCKS: 28 partial values per workgroup
 BBOX_REG_WEIGHTS = (10.0, 10.0, 5.0, 5.0)      # cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS: the units the variance head is trained in
 
 
@@ -255,12 +265,13 @@ def fit_temperature(logits, labels, lo=0.05, hi=20.0, tol=1e-6):
             "rounds": rounds, "rows": int(logits.shape[0]), "at_bound": at}
 
 
-def save(path, detectors, nll=None, rows=None, class_prior=None, pool_weights=None, presence=None, **extra):
+def save(path, detectors, nll=None, rows=None, class_prior=None, pool_weights=None, presence=None, box_correlation=None, **extra):
     """Write the calibration file.  detectors {name: T}; nll {name: {"before": .., "after": ..}}; rows {name: fitted rows};
     class_prior (optional, K + 1 probabilities, background last: the prior of score_fusion "probEn-log") is written normalised -
     without it the file has no such key; pool_weights (optional, {name: w}: the pooling weights of "probEn-log") likewise; presence
     (optional, {"detectors": [names in bit order], "columns": K + 1, "table": [2^D][K + 1], "hi": the fit's search bound or None}: the
-    presence table of "probEn-log") likewise; extra keys
+    presence table of "probEn-log") likewise; box_correlation (optional, {"detectors": [names in matrix order], "matrix": [D][D], and what
+    the fit reports: "raw", "shrink", "pairs", "rows", "excluded", "iou", "box_fusion"}: the correlation of box_fusion "c-avg") likewise; extra keys
     (cli/fit_temperature adds "holdout" and "fitted_image_ids") are kept as given."""
     rec = {"detectors": {k: check_temperature(v, f"temperature of {k}") for k, v in detectors.items()},
            "nll": nll or {}, "rows": rows or {}}
@@ -270,6 +281,8 @@ def save(path, detectors, nll=None, rows=None, class_prior=None, pool_weights=No
         rec["pool_weights"] = _check_pool_table(pool_weights, "pool_weights")
     if presence is not None:
         rec["presence"] = _check_presence_record(presence, "presence")
+    if box_correlation is not None:
+        rec["box_correlation"] = _check_box_correlation_record(box_correlation, "box_correlation")
     rec.update(extra)
     with open(path, "w") as f:
         json.dump(rec, f, indent=1)
@@ -289,6 +302,8 @@ def load(path):
         rec["pool_weights"] = _check_pool_table(rec["pool_weights"], f"{path}: pool_weights")
     if "presence" in rec:
         rec["presence"] = _check_presence_record(rec["presence"], f"{path}: presence")
+    if "box_correlation" in rec:
+        rec["box_correlation"] = _check_box_correlation_record(rec["box_correlation"], f"{path}: box_correlation")
     return rec
 
 
@@ -979,3 +994,236 @@ def fit_presence(base, patterns, labels, num_detectors, hi=16.0, gtol=1e-7, max_
         table[P] = b
         report[P] = rec
     return {"table": table.tolist(), "hi": hi, "unassigned": C - assigned, "patterns": report}
+
+
+# ---- correlated box fusion ("c-avg") --------------------------------------------------------------------------------------------
+
+BOX_PAIRS = [(a, b) for a in range(BOX_CORR_MAX_DETECTORS) for b in range(a, BOX_CORR_MAX_DETECTORS)]      # pe_box_pair_stats' order
+
+
+def box_correlation_min_eig(matrix):
+    """The smallest eigenvalue of the matrix with its diagonal set to 1: the correlation matrix of a cluster that holds one row of
+    every detector."""
+    p = np.array(matrix, dtype=np.float64)
+    np.fill_diagonal(p, 1.0)
+    return float(np.linalg.eigvalsh(p)[0])
+
+
+def check_box_correlation(matrix, num_detectors=None, what="box_correlation"):
+    """The box-error correlation of box_fusion "c-avg" -> float64 ndarray [D, D], 1 <= D <= BOX_CORR_MAX_DETECTORS.  Entry [a][b], a != b:
+    the correlation of the normalised box errors of a row of detector a and a row of detector b in one cluster; entry [d][d]: the same
+    for two DIFFERENT rows of detector d (not 1: a row's correlation with itself is).  Every entry finite, the matrix symmetric,
+    0 <= [d][d] < 1, and the matrix with its diagonal set to 1 - the correlation matrix of a cluster with one row per detector -
+    positive semidefinite (numpy.linalg.eigvalsh, smallest eigenvalue >= -1e-12).  Anything else raises ValueError.
+    A cluster's correlation matrix is R = diag(1 - [d][d]) + G P G'.  It is positive definite for every cluster with at most one row
+    per detector (when the eigenvalue above is > 0); with several rows of one detector it is for every composition only if P itself is
+    positive semidefinite, which a zero diagonal beside a non-zero off-diagonal entry never is (two rows of detector a that share
+    nothing cannot both share much with a row of b).  pe_box_gls_batch answers a cluster whose R is not positive definite with NaN."""
+    if isinstance(matrix, torch.Tensor):
+        matrix = matrix.detach().cpu().numpy()
+    try:
+        p = np.asarray(matrix, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} {matrix!r} is not a matrix of numbers") from None
+    if p.ndim != 2 or p.shape[0] != p.shape[1] or not 1 <= p.shape[0] <= BOX_CORR_MAX_DETECTORS:
+        raise ValueError(f"{what} must be a square matrix over 1 to {BOX_CORR_MAX_DETECTORS} detectors, got shape {p.shape}")
+    if num_detectors is not None and p.shape[0] != int(num_detectors):
+        raise ValueError(f"{what} is over {p.shape[0]} detectors, not {num_detectors}")
+    if not np.all(np.isfinite(p)):
+        r, c = np.argwhere(~np.isfinite(p))[0]
+        raise ValueError(f"{what}: entry {p[r, c]!r} ({r}, {c}) is not finite")
+    if not np.array_equal(p, p.T):
+        r, c = np.argwhere(p != p.T)[0]
+        raise ValueError(f"{what} is not symmetric: entry ({r}, {c}) is {p[r, c]!r}, entry ({c}, {r}) is {p[c, r]!r}")
+    for d in range(p.shape[0]):
+        if not 0.0 <= p[d, d] < 1.0:
+            raise ValueError(f"{what}: diagonal entry {d} is {p[d, d]!r}, not in [0, 1): it is the correlation of two different rows of "
+                             "one detector")
+    low = box_correlation_min_eig(p)
+    if low < -1e-12:
+        raise ValueError(f"{what} is not positive semidefinite with a unit diagonal (smallest eigenvalue {low:.3g}): no joint distribution "
+                         "of one row per detector has these correlations")
+    return np.ascontiguousarray(p)
+
+
+def box_correlation_tensor(matrix, num_detectors, device):
+    """The correlation matrix (check_box_correlation validates) -> the DEVICE f64 [D, D] tensor pe_box_gls_batch takes.  None -> None.
+    A CUDA tensor is taken as the result of an earlier call (FramePairPipeline uploads once, not per batch); num_detectors None takes
+    D from the matrix."""
+    if matrix is None:
+        return None
+    if isinstance(matrix, torch.Tensor) and matrix.is_cuda:
+        D = matrix.shape[0] if matrix.dim() == 2 else -1
+        if matrix.dtype != torch.float64 or matrix.dim() != 2 or matrix.shape[1] != D or not 1 <= D <= BOX_CORR_MAX_DETECTORS \
+                or (num_detectors is not None and D != int(num_detectors)):
+            raise ValueError(f"box-correlation tensor {tuple(matrix.shape)} {matrix.dtype} is not float64 "
+                             f"[{num_detectors or 'D'}, {num_detectors or 'D'}]")
+        return matrix.contiguous()
+    return torch.from_numpy(check_box_correlation(matrix, num_detectors)).to(device)
+
+
+def parse_box_correlation(text, names):
+    """--box_correlation value -> float64 ndarray [D, D], D = len(names).  'name:name=value,...': one entry per detector pair (the same
+    name twice: the diagonal entry of that detector), pairs not listed get 0.  A bare number stands for the off-diagonal entry of two
+    detectors, diagonal 0."""
+    names, flag = list(names), "--box_correlation"
+    D = len(names)
+    if not 1 <= D <= BOX_CORR_MAX_DETECTORS:
+        raise ValueError(f"{flag}: {D} detectors (1 to {BOX_CORR_MAX_DETECTORS})")
+    items = [x.strip() for x in str(text).split(",") if x.strip()]
+    if not items:
+        raise ValueError(f"{flag} {text!r} lists no pair")
+    p = np.zeros((D, D))
+    if len(items) == 1 and "=" not in items[0]:
+        if D != 2:
+            raise ValueError(f"{flag}: a bare number stands for the one pair of two detectors; with {D} ({','.join(names)}) write name:name=value")
+        try:
+            p[0, 1] = p[1, 0] = float(items[0])
+        except ValueError:
+            raise ValueError(f"{flag}: {items[0]!r} is neither a number nor name:name=value") from None
+        return check_box_correlation(p, D, flag)
+    seen = set()
+    for item in items:
+        if "=" not in item or item.split("=", 1)[0].count(":") != 1:
+            raise ValueError(f"{flag}: entry {item!r} is not name:name=value")
+        k, v = item.split("=", 1)
+        pair = [x.strip() for x in k.split(":")]
+        for n in pair:
+            if n not in names:
+                raise ValueError(f"{flag}: unknown detector {n!r} in {item!r} (the detectors are {','.join(names)})")
+        a, b = sorted(names.index(n) for n in pair)
+        if (a, b) in seen:
+            raise ValueError(f"{flag} lists the pair {names[a]}:{names[b]} twice")
+        seen.add((a, b))
+        try:
+            p[a, b] = p[b, a] = float(v)
+        except ValueError:
+            raise ValueError(f"{flag}: entry {item!r} is not name:name=value with a number") from None
+    return check_box_correlation(p, D, flag)
+
+
+def _check_box_correlation_record(rec, what):
+    if not isinstance(rec, dict) or not isinstance(rec.get("detectors"), list) or "matrix" not in rec:
+        raise ValueError(f"{what} is not a box-correlation record (\"detectors\": names in matrix order, \"matrix\")")
+    names = [str(n) for n in rec["detectors"]]
+    if len(set(names)) != len(names):
+        raise ValueError(f"{what}: detectors {names} repeat a name")
+    out = dict(rec)
+    out.update({"detectors": names, "matrix": check_box_correlation(rec["matrix"], len(names), f"{what}: matrix").tolist()})
+    return out
+
+
+def resolve_box_correlation(rec, names, source):
+    """The calibration file's "box_correlation" record -> float64 ndarray [D, D] in the order of `names`.  The file's detectors must be
+    exactly `names` (in any order): a correlation over other detectors is a statement about other errors."""
+    rec = _check_box_correlation_record(rec, f"{source}: box_correlation")
+    names = list(names)
+    if sorted(rec["detectors"]) != sorted(names):
+        raise ValueError(f"{source}: the box correlation is over {','.join(rec['detectors'])}, not {','.join(names)}")
+    src = np.asarray(rec["matrix"], dtype=np.float64)
+    at = [rec["detectors"].index(n) for n in names]
+    return np.ascontiguousarray(src[np.ix_(at, at)])
+
+
+def box_pair_stats(row_boxes, row_vars, row_source, member_rows, cluster_offsets, cluster_match, gt_boxes, num_detectors,
+                   bbox_reg_weights=BBOX_REG_WEIGHTS):
+    """One pe_box_pair_stats call.  Device tensors: the packed rows (row_boxes f64 [N, 4], row_vars f64 [N], row_source i32 [N]), the
+    clusters in CSR form (member_rows i32 [M], cluster_offsets i32 [C+1]), cluster_match i32 [C] (each cluster's ground-truth box in
+    gt_boxes [G, 4], -1: none - the cluster adds nothing).  Returns {"pairs": int ndarray [D, D] (N_ab, symmetric), "rows": [M_d],
+    "S": f64 ndarray [D, D] (symmetric), "Q": [Q_d], "excluded", "last_excluded"}; synchronises."""
+    D = int(num_detectors)
+    if not 1 <= D <= BOX_CORR_MAX_DETECTORS:
+        raise ValueError(f"box_pair_stats: {D} detectors (1 to {BOX_CORR_MAX_DETECTORS})")
+    _lib.require_cuda(row_boxes, row_vars, row_source, member_rows, cluster_offsets, cluster_match, gt_boxes)
+    row_boxes = row_boxes.reshape(-1, 4).contiguous().double()
+    row_vars = row_vars.reshape(-1).contiguous().double()
+    row_source = row_source.reshape(-1).contiguous().to(torch.int32)
+    member_rows = member_rows.reshape(-1).contiguous().to(torch.int32)
+    cluster_offsets = cluster_offsets.reshape(-1).contiguous().to(torch.int32)
+    cluster_match = cluster_match.reshape(-1).contiguous().to(torch.int32)
+    gt_boxes = gt_boxes.reshape(-1, 4).contiguous().double()
+    N, M, C, G = row_boxes.shape[0], member_rows.numel(), cluster_match.numel(), gt_boxes.shape[0]
+    if row_vars.numel() != N or row_source.numel() != N or cluster_offsets.numel() != C + 1:
+        raise ValueError(f"box_pair_stats: {row_vars.numel()} variances and {row_source.numel()} sources for {N} rows, "
+                         f"{cluster_offsets.numel()} offsets for {C} clusters")
+    if C and cluster_offsets[[0, -1]].tolist() != [0, M]:
+        raise ValueError(f"box_pair_stats: cluster_offsets span {cluster_offsets[[0, -1]].tolist()} for {M} member rows")
+    w = [float(x) for x in bbox_reg_weights]
+    if len(w) != 4:
+        raise ValueError(f"box_pair_stats: bbox_reg_weights {bbox_reg_weights!r} is not 4 numbers")
+    nv = 2 * (len(BOX_PAIRS) + BOX_CORR_MAX_DETECTORS)
+    host, bad, last = _statistic("pe_box_pair_stats", nv, 6 * M + (M + 1) // 2 + nv * BOX_PAIR_MAX_BLOCKS, row_boxes.device,
+                                 lambda work, out, flags, stream: _lib.lib().pe_box_pair_stats(
+                                     _lib.ptr(row_boxes) if N else None, _lib.ptr(row_vars) if N else None, _lib.ptr(row_source) if N else None,
+                                     N, _lib.ptr(member_rows) if M else None, M, _lib.ptr(cluster_offsets), _lib.ptr(cluster_match) if C else None,
+                                     C, _lib.ptr(gt_boxes) if G else None, G, D, (ctypes.c_float * 4)(*w), work, out, flags, stream))
+    counts = host[:nv // 2].view(torch.int64).tolist()
+    sums = host[nv // 2:].tolist()
+    pairs, S = np.zeros((D, D), dtype=np.int64), np.zeros((D, D))
+    for i, (a, b) in enumerate(BOX_PAIRS):
+        if b < D:
+            pairs[a, b] = pairs[b, a] = counts[i]
+            S[a, b] = S[b, a] = sums[i]
+    return {"pairs": pairs, "rows": counts[len(BOX_PAIRS):][:D], "S": S, "Q": sums[len(BOX_PAIRS):][:D], "excluded": bad,
+            "last_excluded": last}
+
+
+def shrink_to_psd(raw, tol=1e-9):
+    """raw (symmetric) -> (matrix, factor): every off-diagonal entry times the largest factor in [0, 1] at which check_box_correlation's
+    eigenvalue (box_correlation_min_eig: the matrix with a unit diagonal) is >= -1e-12.  That eigenvalue is concave in the factor and 1
+    at 0, so the factors that work are an interval from 0: bisection to `tol`.  A matrix that passes already is returned as it is,
+    factor 1."""
+    raw = np.asarray(raw, dtype=np.float64)
+    diag = np.diag(np.diag(raw))
+    off = raw - diag
+
+    def ok(f):
+        return box_correlation_min_eig(diag + f * off) >= -1e-12
+    if ok(1.0):
+        return raw.copy(), 1.0
+    lo, hi = 0.0, 1.0
+    while hi - lo > tol:
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if ok(mid) else (lo, mid)
+    return diag + lo * off, lo
+
+
+def box_correlation_estimate(pairs, rows, S, Q):
+    """The uncentred correlation of the normalised residuals from pe_box_pair_stats' sums (host arithmetic):
+    rho_ab = (S_ab / (4 N_ab)) / sqrt((Q_a / (4 M_a)) * (Q_b / (4 M_b))) - the zero-mean assumption of the variance fit, robust to a
+    variance scale that was not fitted.  A pair without member pairs (or a detector without rows) gets 0 and is listed in "empty"; a
+    diagonal entry below 0 (or not below 1) is set to 0 and listed in "clamped"; the off-diagonal entries are then shrunk by shrink_to_psd.
+    Returns {"matrix", "raw", "shrink", "empty": [[a, b]], "clamped": [d], "stderr": [D][D] sqrt((1 + rho^2) / (4 N_ab)) (None
+    without pairs)}."""
+    pairs, S = np.asarray(pairs), np.asarray(S, dtype=np.float64)
+    D = pairs.shape[0]
+    raw, empty, clamped = np.zeros((D, D)), [], []
+    stderr = [[None] * D for _ in range(D)]
+    for a in range(D):
+        for b in range(a, D):
+            n = int(pairs[a, b])
+            if n == 0 or rows[a] == 0 or rows[b] == 0 or not (Q[a] > 0 and Q[b] > 0):
+                empty.append([a, b])
+                continue
+            raw[a, b] = raw[b, a] = (S[a, b] / (4 * n)) / math.sqrt((Q[a] / (4 * rows[a])) * (Q[b] / (4 * rows[b])))
+            stderr[a][b] = stderr[b][a] = math.sqrt((1 + raw[a, b] ** 2) / (4 * n))
+    fixed = raw.copy()
+    for d in range(D):
+        if not 0 <= fixed[d, d] < 1:          # (>= 1 can only come from a handful of pairs: no estimate either)
+            fixed[d, d] = 0.0
+            clamped.append(d)
+    matrix, f = shrink_to_psd(fixed)
+    return {"matrix": matrix.tolist(), "raw": raw.tolist(), "shrink": f, "empty": empty, "clamped": clamped, "stderr": stderr}
+
+
+def fit_box_correlation(row_boxes, row_vars, row_source, member_rows, cluster_offsets, cluster_match, gt_boxes, num_detectors,
+                        bbox_reg_weights=BBOX_REG_WEIGHTS):
+    """The correlation of the detectors' normalised box errors over the clusters a "v-avg" fusion formed (late_fusion.fused_clusters:
+    "row_boxes", "row_vars", "row_source", "member_rows", "cluster_offsets"), each cluster with the ground-truth box its fused box
+    matched (cluster_match: match_rows_device's `match` on the clusters' fused boxes; -1: the cluster adds nothing).  One
+    pe_box_pair_stats call, then box_correlation_estimate on the host.  Returns its dict plus {"pairs" [D][D], "rows" [D], "excluded"}."""
+    st = box_pair_stats(row_boxes, row_vars, row_source, member_rows, cluster_offsets, cluster_match, gt_boxes, num_detectors,
+                        bbox_reg_weights)
+    out = box_correlation_estimate(st["pairs"], st["rows"], st["S"], st["Q"])
+    out.update({"pairs": st["pairs"].tolist(), "rows": list(st["rows"]), "excluded": st["excluded"]})
+    return out

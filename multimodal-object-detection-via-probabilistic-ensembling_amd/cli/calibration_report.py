@@ -33,6 +33,9 @@ columns; under "variance" the Gaussian NLL per matched fused row and the 1-sigma
 the fused variance (calibration.variance_stats), as printed per detector.  The posterior figures go through the statistics the detectors'
 logits go through, which take float32: they are those of the float32 cast of the float64 fused log-posterior (6e-8 relative on a
 log-probability), renormalised - a report's precision, not the fusion's.  Only new keys: everything else is what it is without the flag.
+When the file also has "box_correlation" (fit_temperature --with-box-correlation), --fused-posterior prints the same Gaussian NLL and
+coverage of the fused box variance under --box_fusion v-avg and under c-avg at the file's matrix, side by side, both at the file's
+calibration: c-avg moves boxes and variances only, so the two fusions have the same rows.
 Rows that cannot be binned (a NaN score, a label outside the columns) are counted as "excluded" and printed, never dropped silently.
 
 What the detection-level figures are not.  A detection is "correct" when the ground-truth box it overlaps most, at IoU >= --iou, has
@@ -79,6 +82,9 @@ def parse(argv):
         p.error(f"--iou {args.iou} is not in [0, 1]")
     if not 2 <= len(args.predictions) <= 3:
         p.error(f"--predictions lists {len(args.predictions)} files: late fusion takes 2 or 3")
+    if args.box_fusion == "c-avg":
+        p.error("--box_fusion c-avg: the \"before\" fusion has no matrix to run it with; --fused-posterior with a calibration file that "
+                "carries \"box_correlation\" prints v-avg and c-avg side by side")
     if args.fused_posterior and args.score_fusion != "probEn-log":
         p.error(f"--fused-posterior belongs to --score_fusion probEn-log (got {args.score_fusion}): the other score fusions form no posterior")
     return args
@@ -322,6 +328,16 @@ def main(cmd=None):
     report["fused"] = {"before": fuse(), "after": fuse(temperatures=temps, variance_scales=svals, class_prior=prior,
                                                        pool_weights=pvals if logp else None,
                                                        **({"presence": ptable} if logp and ptable is not None else {}))}
+    ctable = None if "box_correlation" not in rec or not (logp and args.fused_posterior) else \
+        calibration.resolve_box_correlation(rec["box_correlation"], names, args.calibration)
+    if ctable is not None:
+        after = dict(temperatures=temps, variance_scales=svals, class_prior=prior, pool_weights=pvals,
+                     **({"presence": ptable} if ptable is not None else {}))
+        both = {}
+        for rule, extra in (("v-avg", {}), ("c-avg", {"box_correlation": ctable})):
+            both[rule] = fused_report(dets, args.predictions, [args.score_fusion, rule], gt, k, args.bins, args.iou, args.device,
+                                      posterior=True, **after, **extra)["variance"]
+        report["box_correlation"] = dict(both, matrix=ctable.tolist(), detectors=names)
     if pvals is not None:
         report["pool"] = pool_report(dets, args.predictions, by_id, ids, pvals, args.iou, args.box_fusion, args.device, temps,
                                      rec.get("class_prior"), svals)
@@ -334,6 +350,13 @@ def main(cmd=None):
         report["presence"]["applied"] = logp
     print(f"{len(ids)} images ({args.on}) of {len(records)}, {args.bins} bins, IoU >= {args.iou}")
     print(table(report))
+    if ctable is not None:
+        print("fused box variance at the file's calibration, under v-avg and under c-avg at the file's box correlation "
+              f"({', '.join(f'{names[a]}:{names[b]} = {ctable[a, b]:.6g}' for a in range(len(names)) for b in range(a, len(names)))}):")
+        for rule in ("v-avg", "c-avg"):
+            v = report["box_correlation"][rule]
+            print(f"  {rule}: Gaussian NLL per matched fused row {v['nll']:.6f} over {v['rows']} rows ({v['excluded']} excluded), within 1 / 2 "
+                  f"sigma {v['coverage'][0]:.6f} / {v['coverage'][1]:.6f} (a Gaussian: {GAUSSIAN_COVERAGE[0]:.4f} / {GAUSSIAN_COVERAGE[1]:.4f})")
     if pvals is not None:
         r = report["pool"]
         print(f"fused NLL per cluster (probEn-log/{args.box_fusion}, {r['clusters']} clusters of >= 2 rows, {r['excluded']} excluded): "

@@ -35,6 +35,13 @@ listed get zeros.  Detections only one detector made, and images on which one de
 --calibration file that carries "presence" (fit_temperature --with-presence) supplies the table.  With --write_fused the fused
 log-posterior includes the presence term.
 
+--box_fusion c-avg, with --score_fusion probEn-log on either route: the generalised-least-squares mean of a cluster's boxes under
+correlated box errors (pe_box_gls_batch after the fusion).  --box_correlation 0.6 (two detectors: their one pair) or
+thermal_only:early_fusion=0.6,thermal_only:thermal_only=0.2 (one entry per detector pair; the same name twice is the correlation of
+two rows of one detector; pairs not listed get 0); without the flag a --calibration file that carries "box_correlation"
+(fit_temperature --with-box-correlation) supplies the matrix, and a run without either is refused.  With --write_fused the file's vars
+are the variance the correlated mean really has.
+
 --write_fused FILE, with --score_fusion probEn-log on either route: the fused detections leave as a prediction file of the schema the
 detectors' files have (late_fusion.fused_to_j1): class_logits = the fused log-posterior over all K + 1 columns, probs / scores / classes,
 vars = the variance of the fused box under its box rule.  Fused rows whose class is the background column are not detections and are
@@ -69,8 +76,9 @@ def main(cmd=None):
     vscales = _variance_scales(args, names)
     pool = _pool_weights(args, names) if logp else None
     presence = _presence(args, names) if logp else None
+    corr = _box_correlation(args, names) if args.box_fusion == "c-avg" else None
     if args.one_pass:
-        return one_pass(args, names, world, dev, temps, prior, vscales, pool, presence)
+        return one_pass(args, names, world, dev, temps, prior, vscales, pool, presence, corr)
     files = [os.path.join(args.prediction_path, f"val_{n}_predictions.json") for n in names]
     if comm.is_main_process():
         for i, f in enumerate(files):
@@ -99,8 +107,9 @@ def main(cmd=None):
     res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
                                          det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev),
                                          temperatures=None if temps is None else temps["values"], names=files, class_prior=prior,
-                                         variance_scales=vscales, pool_weights=pool, fused_out=fused, presence=presence)
-    _name_options(res, names, temps, prior, vscales, pool, presence)
+                                         variance_scales=vscales, pool_weights=pool, fused_out=fused, presence=presence,
+                                         box_correlation=corr)
+    _name_options(res, names, temps, prior, vscales, pool, presence, corr)
     if fused is not None:
         from ..late_fusion import fused_to_j1
         _write_fused(args.write_fused, [fused_to_j1(dets, fused)], main_rank)
@@ -169,6 +178,23 @@ def _presence(args, names):
     return None
 
 
+def _box_correlation(args, names):
+    """--box_fusion c-avg: --box_correlation, else the calibration file's "box_correlation" (fit_temperature --with-box-correlation); a
+    float64 ndarray [D, D].  Neither: refused - the rule has no default matrix."""
+    from .. import calibration
+    if getattr(args, "box_correlation", None) is not None:
+        return calibration.parse_box_correlation(args.box_correlation, names)
+    rec = calibration.load(args.calibration).get("box_correlation") if args.calibration is not None else None
+    if rec is None:
+        raise ValueError("--box_fusion c-avg needs --box_correlation or a --calibration file that carries \"box_correlation\" "
+                         "(fit_temperature --with-box-correlation)")
+    matrix = calibration.resolve_box_correlation(rec, names, args.calibration)
+    if comm.is_main_process():
+        print(f"box correlation of {args.calibration}:", ", ".join(f"{names[a]}:{names[b]}={matrix[a, b]:.6g}"
+                                                                   for a in range(len(names)) for b in range(a, len(names))))
+    return matrix
+
+
 def _class_prior(args):
     """--class_prior, else the calibration file's "class_prior" (fit_temperature --with-prior), else None (uniform); a list."""
     from .. import calibration
@@ -179,7 +205,7 @@ def _class_prior(args):
     return None
 
 
-def _name_options(res, names, temps, prior, vscales, pool=None, presence=None):
+def _name_options(res, names, temps, prior, vscales, pool=None, presence=None, corr=None):
     """The printed result names the calibration it was made with; a run without any carries none of the keys."""
     if temps is not None:
         res["temperatures"] = dict(zip(names, temps["values"]))
@@ -191,6 +217,8 @@ def _name_options(res, names, temps, prior, vscales, pool=None, presence=None):
         res["pool_weights"] = dict(zip(names, pool))
     if presence is not None:
         res["presence"] = {"detectors": list(names), "table": presence.tolist()}
+    if corr is not None:
+        res["box_correlation"] = {"detectors": list(names), "matrix": corr.tolist()}
 
 
 def _write_fused(path, parts, main_rank):
@@ -230,7 +258,7 @@ def _register(args):
     return cfg
 
 
-def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool=None, presence=None):
+def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool=None, presence=None, corr=None):
     """loader -> FramePairPipeline (one DefaultPredictor model per --detectors entry, cfg as save_predictions.build_cfg) ->
     ProbEn -> evaluation rows on the device (late_fusion.fused_rows_device) -> one all-gather -> FLIREvaluator on rank 0."""
     import argparse
@@ -265,7 +293,7 @@ def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool
         _warn_fitted(temps, [loader.items[i]["id"] for i in loader.mine])
     pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion,
                              temperatures=None if temps is None else temps["values"], class_prior=prior, variance_scales=vscales,
-                             pool_weights=pool, with_posterior=bool(args.write_fused), presence=presence)
+                             pool_weights=pool, with_posterior=bool(args.write_fused), presence=presence, box_correlation=corr)
     fused_parts = []
     j1 = [([], [], []) for _ in names]       # per detector: names, ids, instances
     rows = []
@@ -335,7 +363,7 @@ def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool
         ev.process_rows(all_rows.numpy())
         res = ev.evaluate()
         res["one_pass"] = stats
-        _name_options(res, names, temps, prior, vscales, pool, presence)
+        _name_options(res, names, temps, prior, vscales, pool, presence, corr)
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
         launch.shutdown()

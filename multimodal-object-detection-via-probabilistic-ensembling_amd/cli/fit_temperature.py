@@ -38,6 +38,15 @@ one row and the rows of images on which one detector fired included - is labelle
 (--iou; unmatched = background), and calibration.fit_presence fits each pattern's row to its clusters.  The file gains "presence"
 {"detectors", "columns", "table", "hi", "patterns": per pattern the clusters used / excluded, the NLL per cluster at 0 and at the fit,
 rounds, converged, at_bound, "box_fusion", "iou"}; `demo_probEn --score_fusion probEn-log --calibration FILE` then fuses with the table.
+--with-box-correlation (2 or 3 prediction files) also fits the correlation of the detectors' box errors for --box_fusion c-avg
+(DESIGN.md section 19).  It runs after the variance fit of the same run: the fitted images are fused once with probEn-log at v-avg, at
+the run's temperatures, prior and variance scales (late_fusion.fused_clusters); every cluster takes the ground-truth box its fused box
+matches on the device (--iou; a cluster without one adds nothing); a member row's residual is the variance fit's, divided by the
+square root of its (scaled) variance; calibration.fit_box_correlation forms the uncentred correlation per detector pair from
+pe_box_pair_stats' sums - the entry of a detector with itself is that of two different rows of it in one cluster.  Prints the matrix,
+the pair counts and the standard errors.  The file gains "box_correlation" {"detectors", "matrix", "raw", "shrink", "pairs", "rows",
+"excluded", "stderr", "empty", "clamped", "iou", "box_fusion": "v-avg"};
+`demo_probEn --score_fusion probEn-log --box_fusion c-avg --calibration FILE` then fuses with the matrix.
 """
 import argparse
 import json
@@ -75,10 +84,14 @@ def parse(argv):
                    help="also fit one pooling weight per detector for score_fusion probEn-log and write the pool_* keys")
     p.add_argument("--with-presence", action="store_true",
                    help="also fit the presence table of score_fusion probEn-log (one row per pattern of detectors) and write the presence key")
+    p.add_argument("--with-box-correlation", action="store_true",
+                   help="also fit the correlation of the detectors' box errors for box_fusion c-avg and write the box_correlation key")
     p.add_argument("--box_fusion", default="v-avg", help="--with-pool-weights / --with-presence: box fusion of the fused boxes that are labelled")
     args = p.parse_args(argv)
     if args.with_presence and not 2 <= len(args.predictions) <= 3:
         p.error(f"--with-presence: --predictions lists {len(args.predictions)} files: late fusion takes 2 or 3")
+    if args.with_box_correlation and not 2 <= len(args.predictions) <= 3:
+        p.error(f"--with-box-correlation: --predictions lists {len(args.predictions)} files: late fusion takes 2 or 3")
     if args.with_pool_weights and not 2 <= len(args.predictions) <= 3:
         p.error(f"--with-pool-weights: --predictions lists {len(args.predictions)} files: late fusion takes 2 or 3")
     if not 0.0 < args.holdout <= 1.0:
@@ -177,6 +190,20 @@ def presence_fit(preds, names, records, fitted, iou, box_fusion, device, tempera
     return calibration.fit_presence(rows["log_posterior"], rows["pattern"], labels, len(preds))
 
 
+def box_correlation_fit(preds, names, records, fitted, iou, device, temperatures, class_prior, variance_scales, weights):
+    """calibration.fit_box_correlation over the clusters probEn-log / v-avg forms on the fitted images, each with the ground-truth box
+    its fused box matches (pe_match_ground_truth's match output at `iou`)."""
+    from .calibration_report import ground_truth, positions, take_j1
+    dets = [take_j1(p, positions(p, fitted, n)) for p, n in zip(preds, names)]
+    cl = fused_clusters(dets, "v-avg", device, temperatures, names, class_prior, variance_scales)
+    if cl is None:
+        raise ValueError(f"no image among the {len(fitted)} fitted ones on which two detectors fired: no cluster to fit a box correlation on")
+    gt = ground_truth(records, [fitted[i] for i in cl["images"]], device)
+    _, match, _ = calibration.match_rows_device(cl["boxes"], cl["box_offsets"], gt[0], gt[1], gt[2], gt[3], iou, cl["log_probs"].shape[1] - 1)
+    return calibration.fit_box_correlation(cl["row_boxes"], cl["row_vars"], cl["row_source"], cl["member_rows"], cl["cluster_offsets"],
+                                           match, gt[0], len(preds), weights)
+
+
 def pattern_name(P, names):
     return "+".join(n for d, n in enumerate(names) if P >> d & 1)
 
@@ -272,6 +299,20 @@ def main(cmd=None):
                   f"{'' if r['converged'] else '  (the gradient criterion was not met)'}{note}")
         pool = dict(pool, presence={"detectors": names, "columns": len(fit["table"][0]), "table": fit["table"], "hi": fit["hi"],
                                     "patterns": per, "unassigned": fit["unassigned"], "box_fusion": args.box_fusion, "iou": args.iou})
+    if args.with_box_correlation:
+        names = list(temps)
+        fit = box_correlation_fit(preds, args.predictions, by_id, fitted, args.iou, args.device, [temps[n] for n in names],
+                                  [c + 1 for c in counts] if args.with_prior else None,
+                                  [vfit[n]["scale"] for n in names] if args.with_variance else None, args.bbox_reg_weights)
+        shrunk = "" if fit["shrink"] == 1.0 else f"; off-diagonal entries times {fit['shrink']:.6f} to make it positive semidefinite"
+        print(f"box correlation ({sum(fit['rows'])} member rows, {fit['excluded']} excluded{shrunk}):")
+        for a in range(len(names)):
+            for b in range(a, len(names)):
+                se = fit["stderr"][a][b]
+                note = "  (no pair: set to 0)" if [a, b] in fit["empty"] else "  (not in [0, 1): set to 0)" if a == b and a in fit["clamped"] else ""
+                print(f"  {names[a]}:{names[b]} = {fit['matrix'][a][b]:+.6f}  raw {fit['raw'][a][b]:+.6f}  over {fit['pairs'][a][b]} pairs, "
+                      f"standard error {'-' if se is None else format(se, '.6f')}{note}")
+        pool = dict(pool, box_correlation=dict(fit, detectors=names, iou=args.iou, box_fusion="v-avg"))
     if args.with_prior:
         calibration.save(args.out, temps, nll, rows, class_prior=[c + 1 for c in counts], holdout=args.holdout, fitted_image_ids=fitted,
                          at_bound=bound, class_prior_counts=counts, **pool)

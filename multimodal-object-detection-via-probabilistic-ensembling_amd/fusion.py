@@ -17,6 +17,10 @@ cluster (pe_proben_fuse_batch_posterior) - the fused detection as a full predict
 `presence` ("probEn-log" only, with or without pool weights / with_posterior) adds one row of log-evidence per presence pattern - which
 detectors put a row into the cluster - to the fused columns, last (pe_proben_fuse_batch_presence); clusters of one row and
 passed-through images are fused too, since a silent detector is evidence as well.
+box_fusion "c-avg" ("probEn-log" only, with `box_correlation`, one correlation of the normalised box errors per detector pair) is the
+generalised-least-squares mean of a cluster's boxes under that correlation and the variance the mean really has: the fusion runs at
+"v-avg" and a second launch (pe_box_gls_batch, csrc/boxcorr.hip) overwrites the boxes - and the variances, with_posterior - of the fused
+rows whose cluster has two or more rows.  Scores, classes, clusters and rows of one never read the matrix; a zero matrix is "v-avg".
 """
 import numpy as np
 import torch
@@ -26,6 +30,7 @@ from . import _lib
 SCORE_MODES = {"probEn": 0, "avg": 1, "max": 2, "probEn_binary": 3, "probEn-log": 4}
 LOGP = "probEn-log"
 BOX_MODES = {"v-avg": 0, "s-avg": 1, "avg": 2, "argmax": 3}
+CAVG = "c-avg"      # not a mode of the fusion kernel: "v-avg" there, then pe_box_gls_batch
 FRAME_W, FRAME_H = 640.0, 512.0  # class-band shift hard-coded by the reference (demo_probEn.py:100-103)
 
 
@@ -57,9 +62,17 @@ def pool_weight_tensor(pool_weights, num_detectors, device):
     return torch.tensor(check_pool_weights(pool_weights, num_detectors, "pool_weights"), dtype=torch.float64).to(device)
 
 
-def _check_mode(score_fusion, class_prior, who, pool_weights=None, with_posterior=False, presence=None):
+def _check_mode(score_fusion, class_prior, who, pool_weights=None, with_posterior=False, presence=None, box_fusion=None,
+                box_correlation=None):
     if score_fusion not in SCORE_MODES:
         raise ValueError(f"{who}: unknown score_fusion {score_fusion!r} (one of {', '.join(SCORE_MODES)})")
+    if box_fusion == CAVG and score_fusion != LOGP:
+        raise ValueError(f"{who}: box_fusion '{CAVG}' belongs to score_fusion '{LOGP}' (got {score_fusion!r}): it finds a cluster's rows "
+                         "through the cluster output only that fusion writes")
+    if box_fusion == CAVG and box_correlation is None:
+        raise ValueError(f"{who}: box_fusion '{CAVG}' needs a box_correlation (zeros give 'v-avg')")
+    if box_correlation is not None and box_fusion != CAVG:
+        raise ValueError(f"{who}: box_correlation belongs to box_fusion '{CAVG}' (got {box_fusion!r}): no other box rule reads it")
     if with_posterior and score_fusion != LOGP:
         raise ValueError(f"{who}: with_posterior belongs to score_fusion '{LOGP}' (got {score_fusion!r}): the other score fusions "
                          "form no normalised posterior")
@@ -76,7 +89,7 @@ def _check_mode(score_fusion, class_prior, who, pool_weights=None, with_posterio
 
 def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="probEn", box_fusion="v-avg",
                max_rows=None, iou_thresh=0.5, frame=(FRAME_W, FRAME_H), row_counts=None, passthrough=None, log_probs=None,
-               class_prior=None, pool_weights=None, row_source=None, with_posterior=False, presence=None):
+               class_prior=None, pool_weights=None, row_source=None, with_posterior=False, presence=None, box_correlation=None):
     """Fuse B images in one launch.
 
     score_fusion "probEn-log": log_probs f64 [Ntot,K+1] (calibration.log_posteriors / pack_rows(log_posteriors=True)) replaces
@@ -91,6 +104,11 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
     pe_proben_fuse_batch_presence, with or without pool_weights / with_posterior; the fused columns gain presence[P][j], P the OR of
     (1 << source) over the cluster's rows, clusters of one row and passthrough images are fused too; the result then also holds
     "pattern" i32 [Ntot] (the fused rows' P, indexed like "scores"; -1 where nothing was written) and "cluster".
+    box_fusion "c-avg" ("probEn-log" only) with box_correlation (a matrix [D][D], calibration.check_box_correlation, or
+    calibration.box_correlation_tensor's device tensor) and row_source: the entry point the other arguments select runs at "v-avg"
+    (pe_proben_fuse_batch_pooled with weights of 1.0, which is "probEn-log" bit for bit, when they select none that writes "cluster"),
+    then pe_box_gls_batch overwrites "boxes" - and "vars", with_posterior - of the fused rows whose cluster has two or more rows; a row
+    whose source is outside [0, D) makes its cluster's box and variance NaN.  The result then also holds "cluster".
 
     boxes f64 [Ntot,4], scores f64 [Ntot], probs f64 [Ntot,K], variances f64 [Ntot],
     classes i32 [Ntot], offsets i32 [B+1] - all CUDA tensors, rows of each image already
@@ -98,10 +116,14 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
       boxes f64 [Ntot,4], scores f32 [Ntot], classes f32 [Ntot], keep i32 [Ntot], counts i32 [B];
     image b's fused rows are [offsets[b], offsets[b]+counts[b]).
     """
-    _check_mode(score_fusion, class_prior, "fuse_batch", pool_weights, with_posterior, presence)
+    _check_mode(score_fusion, class_prior, "fuse_batch", pool_weights, with_posterior, presence, box_fusion, box_correlation)
     logp = score_fusion == LOGP
     pool = pool_weights is not None
     pres = presence is not None
+    cavg = box_fusion == CAVG
+    if cavg and (row_source is None or row_source.dim() != 1 or row_source.shape[0] != boxes.shape[0]):
+        raise ValueError(f"fuse_batch: box_fusion '{CAVG}' needs row_source [Ntot] for the {boxes.shape[0]} rows, got "
+                         f"{None if row_source is None else tuple(row_source.shape)}")
     if pres and (row_source is None or row_source.dim() != 1 or row_source.shape[0] != boxes.shape[0]):
         raise ValueError(f"fuse_batch: presence needs row_source [Ntot] for the {boxes.shape[0]} rows, got "
                          f"{None if row_source is None else tuple(row_source.shape)}")
@@ -113,7 +135,7 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
             raise ValueError(f"fuse_batch: score_fusion '{LOGP}' needs log_probs [Ntot, K+1] for the {boxes.shape[0]} rows, got "
                              f"{None if log_probs is None else tuple(log_probs.shape)}")
         probs = log_probs
-    _lib.require_cuda(boxes, scores, probs, variances, classes, offsets, row_source if pool or pres else None)
+    _lib.require_cuda(boxes, scores, probs, variances, classes, offsets, row_source if pool or pres or cavg else None)
     if score_fusion == "max" and box_fusion == "argmax":
         raise ValueError("('max','argmax') is the class-aware NMS route: use fusion()/nms_fuse_batch")
     B = offsets.numel() - (0 if row_counts is not None else 1)
@@ -134,14 +156,23 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
     dev = boxes.device
     if pool:
         weights = pool_weight_tensor(pool_weights, len(pool_weights), dev)
-    if pool or pres:
+    if pool or pres or cavg:
         row_source = row_source.contiguous().to(torch.int32)
+    if cavg:
+        from .calibration import box_correlation_tensor
+        corr = box_correlation_tensor(box_correlation, None, dev)
+        if pool and int(weights.numel()) != corr.shape[0]:
+            raise ValueError(f"fuse_batch: {int(weights.numel())} pool weights beside a box correlation over {corr.shape[0]} detectors")
+        if not (pool or pres or with_posterior):      # no entry point that writes "cluster" is selected: the pooled one at w = 1
+            pool, weights = True, torch.ones((corr.shape[0],), dtype=torch.float64, device=dev)
     if pres:
         from .calibration import presence_detectors, presence_table
         table = presence_table(presence, None, K + 1, dev)
         nd = presence_detectors(table)
         if pool and int(weights.numel()) != nd:
             raise ValueError(f"fuse_batch: {int(weights.numel())} pool weights beside a presence table over {nd} detectors")
+        if cavg and corr.shape[0] != nd:
+            raise ValueError(f"fuse_batch: a box correlation over {corr.shape[0]} detectors beside a presence table over {nd}")
     out = {
         "boxes": torch.empty((ntot, 4), dtype=torch.float64, device=dev),
         "scores": torch.empty((ntot,), dtype=torch.float32, device=dev),
@@ -153,7 +184,7 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
             else "pe_proben_fuse_batch_logp" if logp else "pe_proben_fuse_batch")
     head = (_lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(probs), _lib.ptr(variances), _lib.ptr(classes),
             *([_lib.ptr(row_source) if pool or pres else None] if pool or with_posterior or pres else []), _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows)
-    geometry = (BOX_MODES[box_fusion], float(iou_thresh), float(frame[0]), float(frame[1]))
+    geometry = (BOX_MODES["v-avg" if cavg else box_fusion], float(iou_thresh), float(frame[0]), float(frame[1]))
     mode = geometry + (_lib.ptr(log_prior),) if logp else (SCORE_MODES[score_fusion],) + geometry
     tail = ()
     if pres:
@@ -166,7 +197,9 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
         tail = (_lib.ptr(out["cluster"]),)
     elif with_posterior:
         mode += (None, 0)          # row_source and pool_weights NULL together: the unpooled rule
-        tail = (None,)
+        if cavg:
+            out["cluster"] = torch.full((ntot,), -2, dtype=torch.int32, device=dev)
+        tail = (_lib.ptr(out.get("cluster")),)
     if with_posterior:
         out["log_posterior"] = torch.full((ntot, K + 1), float("nan"), dtype=torch.float64, device=dev)
         out["vars"] = torch.full((ntot,), float("nan"), dtype=torch.float64, device=dev)
@@ -180,6 +213,11 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
     st = getattr(_lib.lib(), name)(*head, *mode, _lib.ptr(out["boxes"]), _lib.ptr(out["scores"]), _lib.ptr(out["classes"]),
                                    _lib.ptr(out["keep"]), _lib.ptr(out["counts"]), *tail, _lib.stream())
     _lib.check(st, name)
+    if cavg:
+        st = _lib.lib().pe_box_gls_batch(_lib.ptr(boxes), _lib.ptr(variances), _lib.ptr(row_source), _lib.ptr(out["cluster"]),
+                                         _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(out["counts"]), B, max_rows, _lib.ptr(corr),
+                                         int(corr.shape[0]), _lib.ptr(out["boxes"]), _lib.ptr(out.get("vars")), _lib.stream())
+        _lib.check(st, "pe_box_gls_batch")
     return out
 
 
@@ -224,7 +262,8 @@ def pack_infos(per_image_infos, device="cuda", with_log_probs=False, with_source
     return out + (cat(src, (0,), np.int32),) if with_sources else out
 
 
-def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=None, variance_scales=None, pool_weights=None):
+def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=None, variance_scales=None, pool_weights=None,
+           box_correlation=None):
     """Drop-in for the reference's ``fusion`` (demo_probEn.py:189-196).
 
     Returns (out_boxes, out_scores, out_class): boxes as a list of float64 ndarrays [4]
@@ -235,11 +274,15 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=Non
     method[0] "probEn-log": the rows' log-posteriors come from their class_logits too (temperatures None = 1 for every info) and
     are fused by pe_proben_fuse_batch_logp, with class_prior (K + 1 probabilities, background last) when given.
     variance_scales (one s per info): the rows' vars are multiplied by s in float64 (one multiply, as pe_proben_pack_calibrated does
-    on the device route); only box rule "v-avg" reads them.
+    on the device route); the box rules "v-avg" and "c-avg" read them.
     pool_weights (one w per info, method[0] "probEn-log" only): the pooled rule of pe_proben_fuse_batch_pooled; a row's detector is
-    its info's position."""
+    its info's position.
+    method[1] "c-avg" (method[0] "probEn-log" only) with box_correlation (one entry per pair of infos): fuse_batch's correlated box rule."""
     infos = [info_1, info_2] + ([info_3] if info_3 else [])
-    _check_mode(method[0], class_prior, "fusion", pool_weights)
+    _check_mode(method[0], class_prior, "fusion", pool_weights, box_fusion=method[1], box_correlation=box_correlation)
+    if box_correlation is not None:
+        from .calibration import check_box_correlation
+        box_correlation = check_box_correlation(box_correlation, len(infos), "fusion: box_correlation")
     if pool_weights is not None:
         from .calibration import check_pool_weights
         pool_weights = check_pool_weights(pool_weights, len(infos), "fusion")
@@ -272,10 +315,10 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=Non
         classes = torch.tensor(sum([list(d["class"]) for d in infos], []), dtype=torch.float32)
         keep = batched_nms(boxes.cuda(), scores.cuda(), classes.cuda(), 0.5).cpu()
         return boxes[keep], scores[keep], classes[keep]
-    if logp and pool_weights is not None:
+    if logp and (pool_weights is not None or box_correlation is not None):
         b, s, p, v, c, offs, lp, src = pack_infos([infos], with_log_probs=True, with_sources=True)
         out = fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior, pool_weights=pool_weights,
-                         row_source=src)
+                         row_source=src, box_correlation=box_correlation)
     elif logp:
         b, s, p, v, c, offs, lp = pack_infos([infos], with_log_probs=True)
         out = fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior)
@@ -357,7 +400,8 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, varian
 
 
 def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=0.5, temperatures=None,
-                    class_prior=None, variance_scales=None, pool_weights=None, with_posterior=False, presence=None):
+                    class_prior=None, variance_scales=None, pool_weights=None, with_posterior=False, presence=None,
+                    box_correlation=None):
     """Device-to-device stage fusion: `dets` = the result dicts of 2 or 3 detectors run on the SAME batch
     (rcnn.GeneralizedRCNN.forward_batch).  Packs their detections into ProbEn rows (classes <= max_class,
     like the JSON writer demo_FLIR_save_predictions.py:148-155), applies the reference's per-image case
@@ -367,7 +411,7 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     score_fusion "probEn-log": pe_proben_pack_log_posteriors + pe_proben_fuse_batch_logp (temperatures None = 1 per detector;
     class_prior: K + 1 probabilities, background last, or the device tensor of log_class_prior).
     variance_scales (one s per detector): the rows' variances are (double)var * s_d (pe_proben_pack_calibrated); they weight the
-    member boxes of box_fusion "v-avg" and nothing else, so every other box rule and the NMS route give the bits they gave.
+    member boxes of box_fusion "v-avg" and "c-avg" and nothing else, so every other box rule and the NMS route give the bits they gave.
     pool_weights (one w per detector or pool_weight_tensor's device tensor, "probEn-log" only): pe_proben_pack_pooled +
     pe_proben_fuse_batch_pooled; the result then also holds "cluster" and "row_source".
     with_posterior ("probEn-log" only): the fusion is pe_proben_fuse_batch_posterior and the result also holds fuse_batch's
@@ -375,11 +419,17 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     presence ("probEn-log" only; a table [2^D][K+1], D = len(dets), or calibration.presence_table's device tensor): the rows' detector
     indices come from pe_proben_pack_pooled and the fusion is pe_proben_fuse_batch_presence - images on which one detector fired are
     rescored row by row, not copied; the result then also holds "pattern", "cluster" and "row_source".
+    box_fusion "c-avg" ("probEn-log" only) with box_correlation (a matrix [D][D], D = len(dets), or calibration.box_correlation_tensor's
+    device tensor): the rows' detector indices come from pe_proben_pack_pooled and fuse_batch's second launch, pe_box_gls_batch,
+    overwrites the boxes (and "vars") of the clusters of two or more rows; the result then also holds "cluster" and "row_source".
     No host synchronisation.  Returns a dict: boxes f64 [B*S,4], scores f32, classes f32, counts i32 [B],
     offsets i32 [B], stride S = len(dets) * D."""
     # the box heads' candidate-cap bookkeeping travels with the result (no kernel here): check_candidate_overflow() looks
     # at it at the consumer's first host synchronisation
-    _check_mode(score_fusion, class_prior, "fuse_detections", pool_weights, with_posterior, presence)
+    _check_mode(score_fusion, class_prior, "fuse_detections", pool_weights, with_posterior, presence, box_fusion, box_correlation)
+    if box_correlation is not None:
+        from .calibration import box_correlation_tensor
+        box_correlation = box_correlation_tensor(box_correlation, len(dets), dets[0]["scores"].device)
     if presence is not None:
         from .calibration import presence_table
         presence = presence_table(presence, len(dets), dets[0]["prob_score"].shape[2] + 1, dets[0]["scores"].device)
@@ -392,9 +442,10 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
         temperatures = [1.0] * len(dets)
     ob, os_, op, ov, oc, ooff, ocnt, osingle, *olp = pack_rows(dets, max_class, temperatures, log_posteriors=logp,
                                                                variance_scales=variance_scales,
-                                                               pool_weights=pool_weights if presence is None or pool_weights is not None
+                                                               pool_weights=pool_weights if (presence is None and box_correlation is None)
+                                                               or pool_weights is not None
                                                                else [1.0] * len(dets))      # only their presence matters to pack_rows
-    osrc = olp.pop() if pool_weights is not None or presence is not None else None
+    osrc = olp.pop() if pool_weights is not None or presence is not None or box_correlation is not None else None
     if score_fusion == "max" and box_fusion == "argmax":
         from .layers import nms_batched_raw
         b32 = ob.float().view(B, S, 4)
@@ -410,7 +461,8 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
                 "offsets": ooff, "stride": S, "in_counts": ocnt, "nms_route": True, "cand_overflow_src": overflow_src}
     out = fuse_batch(ob, os_, op, ov, oc, ooff, score_fusion, box_fusion, max_rows=S, iou_thresh=iou_thresh,
                      row_counts=ocnt, passthrough=osingle, log_probs=olp[0] if logp else None, class_prior=class_prior,
-                     pool_weights=pool_weights, row_source=osrc, with_posterior=with_posterior, presence=presence)
+                     pool_weights=pool_weights, row_source=osrc, with_posterior=with_posterior, presence=presence,
+                     box_correlation=box_correlation)
     if osrc is not None:
         out["row_source"] = osrc
     out["offsets"], out["stride"], out["in_counts"] = ooff, S, ocnt

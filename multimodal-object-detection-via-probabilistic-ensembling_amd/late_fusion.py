@@ -67,7 +67,7 @@ def _info(det, i):
 
 
 def late_fusion(dets, method, device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None,
-                pool_weights=None, with_posterior=False, presence=None):
+                pool_weights=None, with_posterior=False, presence=None, box_correlation=None):
     """dets: 2 or 3 J1 dicts over the same images (order = detector order).  Returns per-image
     (boxes float64 [m,4] | None, scores f32, classes f32); None = skipped image (no detector fired).
     Case split of demo_probEn.py:237-267: 0 detectors -> skip, 1 -> passthrough, >= 2 -> fusion of the
@@ -87,8 +87,14 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
     presence (a table [2^D][K+1], D = len(dets), "probEn-log" only): pe_proben_fuse_batch_presence.  Images on which one detector fired
     are then no longer answered on the host: they go into the batched launch with their passthrough flag set and come back rescored
     row by row (never clustered), which is what the device route does with the pack kernel's single-source flag - the two routes stay
-    byte-identical."""
-    F._check_mode(method[0], class_prior, "late_fusion", pool_weights, with_posterior, presence)
+    byte-identical.
+    method[1] "c-avg" ("probEn-log" only) with box_correlation (a matrix [D][D], D = len(dets); calibration.check_box_correlation):
+    fuse_batch's correlated box rule, a second launch (pe_box_gls_batch) over the fused boxes and, with_posterior, their variances; a
+    row's detector is its file's position in dets."""
+    F._check_mode(method[0], class_prior, "late_fusion", pool_weights, with_posterior, presence, method[1], box_correlation)
+    if box_correlation is not None:
+        from . import calibration
+        box_correlation = calibration.check_box_correlation(box_correlation, len(dets), "late_fusion: box_correlation")
     if presence is not None:
         from . import calibration
         presence = calibration.check_presence(presence, len(dets), None, "late_fusion: presence")
@@ -127,7 +133,7 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
                 results[i] += (np.asarray(x["log_prob"], dtype=np.float64).reshape(m, -1),
                                np.asarray(x["vars"], dtype=np.float64).reshape(m), np.ones(m, dtype=np.int32))
             continue
-        batch.append(infos if pool_weights is not None or presence is not None else live)      # pack_infos skips the empty ones; the positions stay
+        batch.append(infos if pool_weights is not None or presence is not None or box_correlation is not None else live)      # pack_infos skips the empty ones; the positions stay
         where.append(i)
         single.append(int(len(live) == 1))          # presence only: the image's passthrough flag
     if batch:
@@ -140,11 +146,12 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
                 b, s, p, v, c, offs, lp, src = F.pack_infos(batch, device, with_log_probs=True, with_sources=True)
                 out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior,
                                    pool_weights=pool_weights, row_source=src, with_posterior=with_posterior, presence=presence,
-                                   passthrough=torch.tensor(single, dtype=torch.int32, device=b.device))
-            elif logp and pool_weights is not None:
+                                   passthrough=torch.tensor(single, dtype=torch.int32, device=b.device), box_correlation=box_correlation)
+            elif logp and (pool_weights is not None or box_correlation is not None):
                 b, s, p, v, c, offs, lp, src = F.pack_infos(batch, device, with_log_probs=True, with_sources=True)
                 out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior,
-                                   pool_weights=pool_weights, row_source=src, with_posterior=with_posterior)
+                                   pool_weights=pool_weights, row_source=src, with_posterior=with_posterior,
+                                   box_correlation=box_correlation)
             elif logp:
                 b, s, p, v, c, offs, lp = F.pack_infos(batch, device, with_log_probs=True)
                 out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior,
@@ -233,7 +240,8 @@ def fused_clusters(dets, box_fusion="v-avg", device="cuda", temperatures=None, n
     depend on the weights, so the clusters are those of every w.  Returns None when no image has two live detectors, else a dict
     of device tensors: log_probs f64 [N, K+1] and row_source i32 [N] (the packed rows), member_rows i32 [M] / cluster_offsets i32
     [C+1] (cluster c = fused row c, image-major; its rows in packed order), boxes f64 [C, 4] (the fused boxes), box_offsets i32
-    [B'+1] (the clusters of fused image j), and "images": the B' positions of the fused images in dets."""
+    [B'+1] (the clusters of fused image j), and "images": the B' positions of the fused images in dets; "row_boxes" f64 [N, 4] and
+    "row_vars" f64 [N] (the packed rows' boxes and scaled variances: what calibration.fit_box_correlation takes its residuals from)."""
     from . import calibration
     D = len(dets)
     if variance_scales is not None:
@@ -271,7 +279,8 @@ def fused_clusters(dets, box_fusion="v-avg", device="cuda", temperatures=None, n
     first = torch.repeat_interleave(in_off[:-1] - base, cnt) + torch.arange(C, device=dev)      # cluster c's fused row
     return {"log_probs": lp, "row_source": src, "member_rows": rows[order].to(torch.int32),
             "cluster_offsets": torch.cat([zero, torch.cumsum(torch.bincount(gid, minlength=C), 0)]).to(torch.int32),
-            "boxes": out["boxes"][first], "box_offsets": torch.cat([zero, torch.cumsum(cnt, 0)]).to(torch.int32), "images": where}
+            "boxes": out["boxes"][first], "box_offsets": torch.cat([zero, torch.cumsum(cnt, 0)]).to(torch.int32), "images": where,
+            "row_boxes": b, "row_vars": v}
 
 
 def presence_rows(dets, box_fusion="v-avg", device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None,
@@ -323,13 +332,15 @@ def presence_rows(dets, box_fusion="v-avg", device="cuda", temperatures=None, na
 
 def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="", image_hw=None, device="cuda",
                                    img_folder="../../../Datasets/FLIR/val/thermal_8_bit/", temperatures=None, names=None,
-                                   class_prior=None, variance_scales=None, pool_weights=None, fused_out=None, presence=None):
+                                   class_prior=None, variance_scales=None, pool_weights=None, fused_out=None, presence=None,
+                                   box_correlation=None):
     """Same call as the reference (demo_probEn.py:198).  `image_hw`: {image_id: (H, W)} from the dataset
     json (the reference re-reads every thermal JPEG just for its shape); default 512 x 640 (FLIR).
     `img_folder`: the prefix the reference hard-codes into the `file_name` it hands to the evaluator (:200,271).
     `fused_out`: a list; when given ("probEn-log" only) the fusion keeps its posterior and the per-image 6-tuples of late_fusion are
     appended to it, for fused_to_j1 - the evaluator receives what it receives without it.
     `presence`: late_fusion's presence table ("probEn-log" only).
+    `box_correlation`: late_fusion's correlation matrix (method[1] "c-avg", "probEn-log" only).
     What the evaluator receives per image is pinned by tests/golden/p5_cases.json (the reference's function run with a recording
     evaluator): tests/test_pipeline_gpu.py::test_late_fusion_driver_reproduces_the_references_records."""
     evaluator.reset()
@@ -337,7 +348,7 @@ def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="
     start = time.time()
     dets = [det_1, det_2] + ([det_3] if det_3 else [])
     fused = late_fusion(dets, method, device, temperatures, names, class_prior, variance_scales, pool_weights,
-                        with_posterior=fused_out is not None, presence=presence)
+                        with_posterior=fused_out is not None, presence=presence, box_correlation=box_correlation)
     if fused_out is not None:
         fused_out.extend(fused)
     for i, r in enumerate(fused):

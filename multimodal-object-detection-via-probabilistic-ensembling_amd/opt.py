@@ -15,7 +15,9 @@ def config_parser(cmd=None):
     p.add_argument("--score_fusion", type=str, default="probEn", choices=["avg", "max", "probEn", "probEn-log"],
                    help="Which fusion method to use?  probEn-log (not in the reference): ProbEn on log_softmax(class_logits / T) with the "
                         "background column kept - needs prediction files with class_logits")
-    p.add_argument("--box_fusion", type=str, default="v-avg", choices=["avg", "s-avg", "v-avg", "argmax"], help="Which fusion method to use?")
+    p.add_argument("--box_fusion", type=str, default="v-avg", choices=["avg", "s-avg", "v-avg", "argmax", "c-avg"],
+                   help="Which fusion method to use?  c-avg (not in the reference; --score_fusion probEn-log with --box_correlation or a "
+                        "--calibration file that carries one): the generalised-least-squares mean under correlated box errors")
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--batch", type=int, default=16)
     p.add_argument("--world-size", type=int, default=1,
@@ -52,6 +54,11 @@ def config_parser(cmd=None):
                         "pattern, 'thermal_only=a:b:c:d,thermal_only+early_fusion=a:b:c:d' (detector names joined by +, background "
                         "last; patterns not listed get zeros); default: the calibration file's presence table if it has one "
                         "(fit_temperature --with-presence), else none")
+    p.add_argument("--box_correlation", type=str, default=None, metavar="TEXT",
+                   help="demo_probEn --score_fusion probEn-log --box_fusion c-avg (either route): the correlation of the detectors' "
+                        "normalised box errors, 'thermal_only:early_fusion=0.6,thermal_only:thermal_only=0.2' (one entry per detector "
+                        "pair, the same name twice = two rows of one detector; pairs not listed get 0), or a bare number for the one "
+                        "pair of two detectors; default: the calibration file's box_correlation (fit_temperature --with-box-correlation)")
     p.add_argument("--write_fused", type=str, default=None, metavar="FILE",
                    help="demo_probEn --score_fusion probEn-log (either route): write the fused detections as a prediction file (the "
                         "schema of val_<method>_predictions.json: class_logits = the fused log-posterior, vars = the fused box's "
@@ -59,6 +66,10 @@ def config_parser(cmd=None):
     args = p.parse_args(cmd) if cmd is not None else p.parse_args()
     if args.write_fused is not None and args.score_fusion != "probEn-log":
         p.error(f"--write_fused belongs to --score_fusion probEn-log (got {args.score_fusion}): the other score fusions form no posterior")
+    if args.box_fusion == "c-avg" and args.score_fusion != "probEn-log":
+        p.error(f"--box_fusion c-avg belongs to --score_fusion probEn-log (got {args.score_fusion})")
+    if args.box_correlation is not None and args.box_fusion != "c-avg":
+        p.error(f"--box_correlation belongs to --box_fusion c-avg (got {args.box_fusion})")
     if args.presence is not None and args.score_fusion != "probEn-log":
         p.error(f"--presence belongs to --score_fusion probEn-log (got {args.score_fusion})")
     if args.pool_weights is not None and args.score_fusion != "probEn-log":

@@ -23,7 +23,7 @@ class FramePairPipeline:
 
     def __init__(self, models, score_fusion="probEn", box_fusion="v-avg", max_class=2, concurrent=True,
                  staggered=False, stagger_stage=4, fuse=True, temperatures=None, class_prior=None, variance_scales=None,
-                 pool_weights=None, with_posterior=False, presence=None):
+                 pool_weights=None, with_posterior=False, presence=None, box_correlation=None):
         self.models = list(models)
         self.fuse = fuse and len(self.models) > 1   # a single detector has nothing to fuse (configs[1])
         self.method = (score_fusion, box_fusion)
@@ -34,7 +34,14 @@ class FramePairPipeline:
             raise ValueError(f"FramePairPipeline: {len(self.temperatures)} temperatures for {len(self.models)} detectors")
         # score_fusion "probEn-log": ProbEn on log_softmax(class_logits / T) with the background column kept (pe_proben_pack_log_posteriors,
         # pe_proben_fuse_batch_logp); T = 1 without temperatures; class_prior = K + 1 probabilities (background last) or None = uniform
-        F._check_mode(score_fusion, class_prior, "FramePairPipeline", pool_weights, with_posterior, presence)
+        F._check_mode(score_fusion, class_prior, "FramePairPipeline", pool_weights, with_posterior, presence, box_fusion, box_correlation)
+        # a matrix [D][D] (box_fusion "c-avg", "probEn-log" only): the correlation of the detectors' box errors (pe_box_gls_batch);
+        # validated here, uploaded at the first batch
+        if box_correlation is not None:
+            from .calibration import check_box_correlation
+            box_correlation = check_box_correlation(box_correlation, len(self.models), "FramePairPipeline: box_correlation")
+        self.box_correlation = box_correlation
+        self._box_correlation = None
         # a table [2^D][K+1] ("probEn-log" only): presence evidence (pe_proben_fuse_batch_presence); validated here, uploaded at the first batch
         if presence is not None:
             from .calibration import check_presence
@@ -150,12 +157,15 @@ class FramePairPipeline:
             self._log_prior = F.log_class_prior(self.class_prior, len(self.class_prior), dets[0]["scores"].device)
         if self.pool_weights is not None and self._pool is None:
             self._pool = F.pool_weight_tensor(self.pool_weights, len(self.pool_weights), dets[0]["scores"].device)
+        if self.box_correlation is not None and self._box_correlation is None:
+            from .calibration import box_correlation_tensor
+            self._box_correlation = box_correlation_tensor(self.box_correlation, len(self.models), dets[0]["scores"].device)
         if self.presence is not None and self._presence is None:
             from .calibration import presence_table
             self._presence = presence_table(self.presence, len(self.models), self.presence.shape[1], dets[0]["scores"].device)
         return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class, temperatures=self.temperatures,
                                  class_prior=self._log_prior, variance_scales=self.variance_scales, pool_weights=self._pool,
-                                 with_posterior=self.with_posterior, presence=self._presence)
+                                 with_posterior=self.with_posterior, presence=self._presence, box_correlation=self._box_correlation)
 
 
 class HostFeeder:
