@@ -129,7 +129,9 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
                 const _Float16* p = a_base[i] + ((size_t)ih * a.W + iw) * 4;
                 const half4 z4 = {0, 0, 0, 0};
                 const half4 lo = (okr && (unsigned)iw < (unsigned)a.W) ? *reinterpret_cast<const half4*>(p) : z4;
-                const half4 hi = (okr && (unsigned)(iw + 1) < (unsigned)a.W) ? *reinterpret_cast<const half4*>(p + 4) : z4;
+                // the 8th pixel of a row (px + 1 == 7) has zero weights and lies outside the 7-wide window: a select, not 0 * x, keeps
+                // a NaN / Inf there out of this output (finite results are the same bits either way)
+                const half4 hi = (okr && px != 6 && (unsigned)(iw + 1) < (unsigned)a.W) ? *reinterpret_cast<const half4*>(p + 4) : z4;
                 areg[i] = half8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             }
         }

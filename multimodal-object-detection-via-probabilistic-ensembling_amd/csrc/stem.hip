@@ -25,6 +25,7 @@ namespace {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float float16v __attribute__((ext_vector_type(16)));
+typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
 
 constexpr int PH = 5, PW = 16;                       // pooled tile
 constexpr int CR = 2 * PH + 1, CC = 2 * PW + 1;      // conv region 11 x 33
@@ -85,6 +86,7 @@ __global__ __launch_bounds__(THREADS, 2) void stem7x7_pool_kernel(StemArgs a) {
     _Float16* cout_lds = patch + PATCH_HALFS;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l31 = lane & 31, khalf = lane >> 5;
+    const unsigned keep_tap0 = khalf ? 0xffffffffu : 0u;
 
     // weights: A operand fragments, row = output channel
     half8 wf[KSTEPS][2];
@@ -130,7 +132,14 @@ __global__ __launch_bounds__(THREADS, 2) void stem7x7_pool_kernel(StemArgs a) {
             for (int kh = 0; kh < 7; ++kh) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const half8 f = *reinterpret_cast<const half8*>(base + (kh * IC + h * 4) * 4);
+                    half8 f = *reinterpret_cast<const half8*>(base + (kh * IC + h * 4) * 4);
+                    if (h == 0) {   // tap 0 (lanes 0..31, first pixel of the pair) lies outside the 7-wide window: cleared, not 0 * x, so
+                                    // that a NaN / Inf there stays out of this conv pixel (finite results are the same bits either way)
+                        uint4v u = __builtin_bit_cast(uint4v, f);
+                        u[0] &= keep_tap0;
+                        u[1] &= keep_tap0;
+                        f = __builtin_bit_cast(half8, u);
+                    }
                     acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[kh * 2 + h][0], f, acc0, 0, 0, 0);
                     acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[kh * 2 + h][1], f, acc1, 0, 0, 0);
                 }
