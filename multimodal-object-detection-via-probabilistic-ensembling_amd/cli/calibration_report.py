@@ -54,6 +54,7 @@ import torch
 from .. import calibration
 from ..data import load_coco_json
 from ..late_fusion import late_fusion, read_j1
+from ..options import FusionOptions
 from .fit_temperature import detector_name, pattern_name, pool_clusters, presence_labelled
 
 ON = ("heldout", "fitted", "all")
@@ -183,11 +184,12 @@ def variance_report(pred, rows, gt_boxes, s, device):
     return out
 
 
-def fused_report(dets, names, method, gt, k, bins, iou, device, posterior=False, **calibrated):
-    """Reliability of the fused score of late_fusion(dets, method, **calibrated) on the chosen images.  posterior: plus "posterior"
+def fused_report(dets, names, gt, k, bins, iou, device, options):
+    """Reliability of the fused score of late_fusion(dets, options=options) on the chosen images.  options.with_posterior: plus "posterior"
     (NLL per row and top-label reliability of the fused posterior, of its float32 cast: the statistics take float32 logits) and "variance" (the fused boxes' residuals under the fused variance)."""
+    posterior = options.with_posterior
     boxes, conf, cls, offsets, lq, var = [], [], [], [0], [], []
-    for r in late_fusion(dets, method, device, names=names, with_posterior=posterior, **calibrated):
+    for r in late_fusion(dets, [options.score_fusion, options.box_fusion], device, names=names, options=options):
         if r is not None:
             boxes += np.asarray(r[0], dtype=np.float64).reshape(-1, 4).tolist()
             conf += r[1].double().tolist()
@@ -215,16 +217,16 @@ def fused_report(dets, names, method, gt, k, bins, iou, device, posterior=False,
     return out
 
 
-def pool_report(dets, names, records, ids, weights, iou, box_fusion, device, temperatures, class_prior, variance_scales):
-    """NLL per cluster of probEn-log's fused posterior on the chosen images, at w = 1 ("before") and at `weights` ("after")."""
-    from ..fusion import log_class_prior
+def pool_report(dets, names, records, ids, iou, device, cal):
+    """NLL per cluster of probEn-log's fused posterior on the chosen images, at w = 1 ("before") and at cal's pool weights ("after");
+    cal = the file's calibration as a FusionOptions ("probEn-log")."""
     out = {"clusters": 0, "excluded": 0, "nll": {"before": float("nan"), "after": float("nan")}}
-    got = pool_clusters(dets, names, records, ids, iou, box_fusion, device, temperatures, class_prior, variance_scales)
+    got = pool_clusters(dets, names, records, ids, iou, device, cal)
     if got is None:
         return out
     cl, labels = got
-    lp = cl["log_probs"]
-    prior = None if class_prior is None else log_class_prior(class_prior, lp.shape[1], lp.device)
+    lp, weights = cl["log_probs"], cal.pool_weights
+    prior = cal.on(lp.device, lp.shape[1]).log_prior
     nll, _, bad, _ = calibration.pool_nll(lp, cl["row_source"], cl["member_rows"], cl["cluster_offsets"], labels,
                                           [[1.0] * len(weights), weights], prior)
     used = int(labels.numel()) - bad
@@ -234,12 +236,14 @@ def pool_report(dets, names, records, ids, weights, iou, box_fusion, device, tem
     return out
 
 
-def presence_report(dets, names, files, records, ids, table, iou, box_fusion, device, temperatures, class_prior, variance_scales, pool_weights):
-    """NLL per fused row of probEn-log's fused posterior on the chosen images, without the presence table ("before": b = 0) and with it
-    ("after"), per pattern and overall; both from pe_bias_nll over the rows fused at a zero table."""
+def presence_report(dets, names, files, records, ids, iou, device, cal):
+    """NLL per fused row of probEn-log's fused posterior on the chosen images, without cal's presence table ("before": b = 0) and with it
+    ("after"), per pattern and overall; both from pe_bias_nll over the rows fused at a zero table.  cal = the file's calibration as a
+    FusionOptions ("probEn-log")."""
     nan = float("nan")
+    table = cal.presence
     out = {"rows": 0, "excluded": 0, "nll": {"before": nan, "after": nan}, "patterns": {}}
-    got = presence_labelled(dets, files, records, ids, iou, box_fusion, device, temperatures, class_prior, variance_scales, pool_weights)
+    got = presence_labelled(dets, files, records, ids, iou, device, cal.replace(presence=None))
     if got is None:
         return out
     rows, labels = got
@@ -290,7 +294,6 @@ def table(report):
 def main(cmd=None):
     args = parse(list(cmd) if cmd is not None else sys.argv[1:])
     rec = calibration.load(args.calibration)
-    scales = calibration.load_variance(args.calibration)
     records = load_coco_json(os.path.join(args.dataset_path, "FLIR_thermal_RGBT_pairs_val.json"),
                              os.path.join(args.dataset_path, "thermal_8_bit"))
     ids = select_images([r["image_id"] for r in records], rec.get("fitted_image_ids", []), args.on, args.calibration)
@@ -298,8 +301,11 @@ def main(cmd=None):
     names = [detector_name(p) for p in args.predictions]
     if len(set(names)) != len(names):
         raise ValueError(f"two prediction files for one detector ({', '.join(names)})")
-    temps = calibration.resolve(rec["detectors"], names, args.calibration)
-    svals = None if scales is None else calibration.resolve_variance_scales(scales, names, args.calibration)
+    # the file as demo_probEn would fuse with it: `after` at the report's own fusion, `cal` at probEn-log (everything the file carries)
+    after = FusionOptions.from_args(args, names, who="calibration_report", say=None).replace(with_posterior=args.fused_posterior)
+    cal = FusionOptions.from_args(argparse.Namespace(score_fusion="probEn-log", box_fusion=args.box_fusion, calibration=args.calibration),
+                                  names, who="calibration_report", say=None)
+    temps, svals, pvals, ptable = cal.temperatures, cal.variance_scales, cal.pool_weights, cal.presence
     gt = ground_truth(by_id, ids, args.device)
     report = {"images": ids, "on": args.on, "bins": args.bins, "iou": args.iou, "method": [args.score_fusion, args.box_fusion],
               "detectors": {}, "variance": {}}
@@ -318,34 +324,22 @@ def main(cmd=None):
     if len(k1) != 1:
         raise ValueError(f"the prediction files have {sorted(k1)} class columns: they cannot be fused")
     k = k1.pop() - 1
-    method = [args.score_fusion, args.box_fusion]
-    logp = args.score_fusion == "probEn-log"
-    prior = rec.get("class_prior") if logp else None
-    pvals = None if "pool_weights" not in rec else calibration.resolve_pool_weights(rec["pool_weights"], names, args.calibration)
-    ptable = None if "presence" not in rec else calibration.resolve_presence(rec["presence"], names, args.calibration)
-    fuse = lambda **kw: fused_report(dets, args.predictions, method, gt, k, args.bins, args.iou, args.device,
-                                     posterior=args.fused_posterior, **kw)
-    report["fused"] = {"before": fuse(), "after": fuse(temperatures=temps, variance_scales=svals, class_prior=prior,
-                                                       pool_weights=pvals if logp else None,
-                                                       **({"presence": ptable} if logp and ptable is not None else {}))}
+    logp = after.logp
+    fuse = lambda options: fused_report(dets, args.predictions, gt, k, args.bins, args.iou, args.device, options)  # noqa: E731
+    report["fused"] = {"before": fuse(FusionOptions(args.score_fusion, args.box_fusion, with_posterior=args.fused_posterior,
+                                                    num_detectors=len(names), who="calibration_report")), "after": fuse(after)}
     ctable = None if "box_correlation" not in rec or not (logp and args.fused_posterior) else \
         calibration.resolve_box_correlation(rec["box_correlation"], names, args.calibration)
     if ctable is not None:
-        after = dict(temperatures=temps, variance_scales=svals, class_prior=prior, pool_weights=pvals,
-                     **({"presence": ptable} if ptable is not None else {}))
-        both = {}
-        for rule, extra in (("v-avg", {}), ("c-avg", {"box_correlation": ctable})):
-            both[rule] = fused_report(dets, args.predictions, [args.score_fusion, rule], gt, k, args.bins, args.iou, args.device,
-                                      posterior=True, **after, **extra)["variance"]
-        report["box_correlation"] = dict(both, matrix=ctable.tolist(), detectors=names)
+        report["box_correlation"] = {"v-avg": fuse(after.replace(box_fusion="v-avg"))["variance"],
+                                     "c-avg": fuse(after.replace(box_fusion="c-avg", box_correlation=ctable))["variance"],
+                                     "matrix": ctable.tolist(), "detectors": names}
     if pvals is not None:
-        report["pool"] = pool_report(dets, args.predictions, by_id, ids, pvals, args.iou, args.box_fusion, args.device, temps,
-                                     rec.get("class_prior"), svals)
+        report["pool"] = pool_report(dets, args.predictions, by_id, ids, args.iou, args.device, cal)
         report["pool"]["weights"] = dict(zip(names, pvals))
         report["pool"]["applied"] = logp
     if ptable is not None:
-        report["presence"] = presence_report(dets, names, args.predictions, by_id, ids, ptable, args.iou, args.box_fusion, args.device, temps,
-                                             rec.get("class_prior"), svals, pvals)
+        report["presence"] = presence_report(dets, names, args.predictions, by_id, ids, args.iou, args.device, cal)
         report["presence"]["table"] = ptable.tolist()
         report["presence"]["applied"] = logp
     print(f"{len(ids)} images ({args.on}) of {len(records)}, {args.bins} bins, IoU >= {args.iou}")

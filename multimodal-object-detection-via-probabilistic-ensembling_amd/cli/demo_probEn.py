@@ -57,6 +57,7 @@ from ..data import DatasetCatalog, register_coco_instances
 from ..evaluation import FLIREvaluator
 from ..late_fusion import apply_late_fusion_and_evaluate, read_j1, shard_j1
 from ..opt import config_parser
+from ..options import FusionOptions
 
 
 def main(cmd=None):
@@ -68,17 +69,9 @@ def main(cmd=None):
     rank, world, dev = launch.init_distributed(args.device, expect_world=args.world_size)
     names = [n for n in args.detectors.split(",") if n]
     assert 2 <= len(names) <= 3, "--detectors takes 2 or 3 names"
-    temps = _temperatures(args, names)
-    logp = args.score_fusion == "probEn-log"
-    prior = _class_prior(args) if logp else None
-    if logp and temps is None:
-        temps = {"values": [1.0] * len(names), "fitted": set()}
-    vscales = _variance_scales(args, names)
-    pool = _pool_weights(args, names) if logp else None
-    presence = _presence(args, names) if logp else None
-    corr = _box_correlation(args, names) if args.box_fusion == "c-avg" else None
+    opts = FusionOptions.from_args(args, names, say=print if comm.is_main_process() else None)
     if args.one_pass:
-        return one_pass(args, names, world, dev, temps, prior, vscales, pool, presence, corr)
+        return one_pass(args, names, world, dev, opts)
     files = [os.path.join(args.prediction_path, f"val_{n}_predictions.json") for n in names]
     if comm.is_main_process():
         for i, f in enumerate(files):
@@ -100,16 +93,12 @@ def main(cmd=None):
     main_rank = comm.is_main_process()
     ev = FLIREvaluator(args.dataset_name, cfg, world > 1 or comm.is_distributed(), output_dir=args.outfolder if main_rank else None, save_eval=main_rank,
                        out_eval_path=os.path.join(args.outfolder, "FLIR_probEn_eval.json"))
-    if temps is not None:
-        _warn_fitted(temps, [i for d in dets for i in d["image_id"]])
+    _warn_fitted(opts, [i for d in dets for i in d["image_id"]])
     fused = [] if args.write_fused else None
-    # every option is None unless it was asked for, and None is the callee's default
     res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
-                                         det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev),
-                                         temperatures=None if temps is None else temps["values"], names=files, class_prior=prior,
-                                         variance_scales=vscales, pool_weights=pool, fused_out=fused, presence=presence,
-                                         box_correlation=corr)
-    _name_options(res, names, temps, prior, vscales, pool, presence, corr)
+                                         det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev), names=files,
+                                         fused_out=fused, options=opts)
+    res.update(opts.named(names))
     if fused is not None:
         from ..late_fusion import fused_to_j1
         _write_fused(args.write_fused, [fused_to_j1(dets, fused)], main_rank)
@@ -118,107 +107,6 @@ def main(cmd=None):
     if comm.is_distributed():
         launch.shutdown()
     return res
-
-
-def _temperatures(args, names):
-    """--temperatures / --calibration -> {"values": [T per --detectors entry], "fitted": image ids the file was fitted on} or None."""
-    from .. import calibration
-    if args.temperatures is not None:
-        return {"values": calibration.parse_temperatures(args.temperatures, names), "fitted": set()}
-    if args.calibration is not None:
-        rec = calibration.load(args.calibration)
-        return {"values": calibration.resolve(rec["detectors"], names, args.calibration), "fitted": set(rec.get("fitted_image_ids", []))}
-    return None
-
-
-def _variance_scales(args, names):
-    """--variance_scales, else the calibration file's "variance_scales" (fit_temperature --with-variance), else None; a list."""
-    from .. import calibration
-    if getattr(args, "variance_scales", None) is not None:
-        return calibration.parse_variance_scales(args.variance_scales, names)
-    if args.calibration is not None:
-        table = calibration.load_variance(args.calibration)
-        if table is not None:
-            vals = calibration.resolve_variance_scales(table, names, args.calibration)
-            if comm.is_main_process():
-                print(f"variance scales of {args.calibration}:", ", ".join(f"{n}={v:.6g}" for n, v in zip(names, vals)))
-            return vals
-    return None
-
-
-def _pool_weights(args, names):
-    """--pool_weights, else the calibration file's "pool_weights" (fit_temperature --with-pool-weights), else None; a list."""
-    from .. import calibration
-    if getattr(args, "pool_weights", None) is not None:
-        return calibration.parse_pool_weights(args.pool_weights, names)
-    if args.calibration is not None:
-        table = calibration.load(args.calibration).get("pool_weights")
-        if table is not None:
-            vals = calibration.resolve_pool_weights(table, names, args.calibration)
-            if comm.is_main_process():
-                print(f"pool weights of {args.calibration}:", ", ".join(f"{n}={v:.6g}" for n, v in zip(names, vals)))
-            return vals
-    return None
-
-
-def _presence(args, names):
-    """--presence, else the calibration file's "presence" (fit_temperature --with-presence), else None; a float64 ndarray [2^D, K+1]."""
-    from .. import calibration
-    if getattr(args, "presence", None) is not None:
-        return calibration.parse_presence(args.presence, names)
-    if args.calibration is not None:
-        rec = calibration.load(args.calibration).get("presence")
-        if rec is not None:
-            table = calibration.resolve_presence(rec, names, args.calibration)
-            if comm.is_main_process():
-                print(f"presence table of {args.calibration}:", ", ".join(
-                    "+".join(n for d, n in enumerate(names) if p >> d & 1) + "=" + ":".join(f"{v:.6g}" for v in table[p])
-                    for p in range(1, len(table))))
-            return table
-    return None
-
-
-def _box_correlation(args, names):
-    """--box_fusion c-avg: --box_correlation, else the calibration file's "box_correlation" (fit_temperature --with-box-correlation); a
-    float64 ndarray [D, D].  Neither: refused - the rule has no default matrix."""
-    from .. import calibration
-    if getattr(args, "box_correlation", None) is not None:
-        return calibration.parse_box_correlation(args.box_correlation, names)
-    rec = calibration.load(args.calibration).get("box_correlation") if args.calibration is not None else None
-    if rec is None:
-        raise ValueError("--box_fusion c-avg needs --box_correlation or a --calibration file that carries \"box_correlation\" "
-                         "(fit_temperature --with-box-correlation)")
-    matrix = calibration.resolve_box_correlation(rec, names, args.calibration)
-    if comm.is_main_process():
-        print(f"box correlation of {args.calibration}:", ", ".join(f"{names[a]}:{names[b]}={matrix[a, b]:.6g}"
-                                                                   for a in range(len(names)) for b in range(a, len(names))))
-    return matrix
-
-
-def _class_prior(args):
-    """--class_prior, else the calibration file's "class_prior" (fit_temperature --with-prior), else None (uniform); a list."""
-    from .. import calibration
-    if args.class_prior is not None:
-        return calibration.parse_class_prior(args.class_prior).tolist()
-    if args.calibration is not None:
-        return calibration.load(args.calibration).get("class_prior")
-    return None
-
-
-def _name_options(res, names, temps, prior, vscales, pool=None, presence=None, corr=None):
-    """The printed result names the calibration it was made with; a run without any carries none of the keys."""
-    if temps is not None:
-        res["temperatures"] = dict(zip(names, temps["values"]))
-    if prior is not None:
-        res["class_prior"] = prior
-    if vscales is not None:
-        res["variance_scales"] = dict(zip(names, vscales))
-    if pool is not None:
-        res["pool_weights"] = dict(zip(names, pool))
-    if presence is not None:
-        res["presence"] = {"detectors": list(names), "table": presence.tolist()}
-    if corr is not None:
-        res["box_correlation"] = {"detectors": list(names), "matrix": corr.tolist()}
 
 
 def _write_fused(path, parts, main_rank):
@@ -238,9 +126,9 @@ def _write_fused(path, parts, main_rank):
           f"{sum(d for _, d in parts)} background rows dropped")
 
 
-def _warn_fitted(temps, image_ids):
+def _warn_fitted(opts, image_ids):
     """The calibration file records the images its temperatures were fitted on: say so when the evaluation includes them."""
-    seen = temps["fitted"] & set(image_ids)
+    seen = opts.fitted & set(image_ids)
     if seen and comm.is_main_process():
         print(f"warning: {len(seen)} of the evaluated images were used to fit the temperatures (the calibration file's holdout split): "
               "the result is optimistic on them")
@@ -258,8 +146,8 @@ def _register(args):
     return cfg
 
 
-def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool=None, presence=None, corr=None):
-    """loader -> FramePairPipeline (one DefaultPredictor model per --detectors entry, cfg as save_predictions.build_cfg) ->
+def one_pass(args, names, world, dev, opts):
+    """`opts`: the run's FusionOptions (FusionOptions.from_args).  loader -> FramePairPipeline (one DefaultPredictor model per --detectors entry, cfg as save_predictions.build_cfg) ->
     ProbEn -> evaluation rows on the device (late_fusion.fused_rows_device) -> one all-gather -> FLIREvaluator on rank 0."""
     import argparse
     import time
@@ -289,11 +177,8 @@ def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool
         preds.append(DefaultPredictor(c))
     need_rgb = any(p.input_format in ("BGRT", "BGRTTT") for p in preds)
     loader = FlirPairLoader(args.dataset_path, args.batch, need_rgb=need_rgb, workers=workers)
-    if temps is not None:
-        _warn_fitted(temps, [loader.items[i]["id"] for i in loader.mine])
-    pipe = FramePairPipeline([p.model for p in preds], args.score_fusion, args.box_fusion,
-                             temperatures=None if temps is None else temps["values"], class_prior=prior, variance_scales=vscales,
-                             pool_weights=pool, with_posterior=bool(args.write_fused), presence=presence, box_correlation=corr)
+    _warn_fitted(opts, [loader.items[i]["id"] for i in loader.mine])
+    pipe = FramePairPipeline([p.model for p in preds], options=opts)
     fused_parts = []
     j1 = [([], [], []) for _ in names]       # per detector: names, ids, instances
     rows = []
@@ -363,7 +248,7 @@ def one_pass(args, names, world, dev, temps=None, prior=None, vscales=None, pool
         ev.process_rows(all_rows.numpy())
         res = ev.evaluate()
         res["one_pass"] = stats
-        _name_options(res, names, temps, prior, vscales, pool, presence, corr)
+        res.update(opts.named(names))
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
         launch.shutdown()

@@ -59,6 +59,7 @@ import torch
 from .. import calibration
 from ..data import load_coco_json
 from ..late_fusion import fused_clusters, presence_rows, read_j1
+from ..options import FusionOptions
 
 
 def detector_name(path):
@@ -134,13 +135,14 @@ def variance_fit(pred, records, fitted_ids, iou, name, weights, device):
     return calibration.fit_variance_scale(db[hit], match[hit], gb, t(var, torch.float64, (-1,))[hit], weights)
 
 
-def pool_clusters(dets, names, records, ids, iou, box_fusion, device, temperatures=None, class_prior=None, variance_scales=None):
+def pool_clusters(dets, names, records, ids, iou, device, cal):
     """The labelled clusters of the pooling-weight fit (and of calibration_report's fused NLL): dets = the prediction dicts sliced to
-    the images `ids`, in that order.  late_fusion.fused_clusters fuses them once at w = 1; every fused box is matched to the ground
-    truth of its image on the device (pe_match_ground_truth at `iou`): an unmatched cluster is background, and so is a class the
-    head has no column for.  Returns (clusters, labels i32 [C] on the device), or None when no image has two live detectors."""
+    the images `ids`, in that order; cal = the FusionOptions ("probEn-log") whose temperatures, prior, variance scales and box fusion
+    form them.  late_fusion.fused_clusters fuses them once at w = 1; every fused box is matched to the ground truth of its image on
+    the device (pe_match_ground_truth at `iou`): an unmatched cluster is background, and so is a class the head has no column for.
+    Returns (clusters, labels i32 [C] on the device), or None when no image has two live detectors."""
     from .calibration_report import ground_truth
-    cl = fused_clusters(dets, box_fusion, device, temperatures, names, class_prior, variance_scales)
+    cl = fused_clusters(dets, device=device, names=names, options=cal)
     if cl is None:
         return None
     k = cl["log_probs"].shape[1] - 1
@@ -149,28 +151,27 @@ def pool_clusters(dets, names, records, ids, iou, box_fusion, device, temperatur
     return cl, torch.where((labels < 0) | (labels > k), torch.full_like(labels, k), labels)
 
 
-def pool_fit(preds, names, records, fitted, iou, box_fusion, device, temperatures, class_prior, variance_scales):
+def pool_fit(preds, names, records, fitted, iou, device, cal):
     """calibration.fit_pool_weights over the clusters of the fitted images."""
     from .calibration_report import positions, take_j1
-    from ..fusion import log_class_prior
     dets = [take_j1(p, positions(p, fitted, n)) for p, n in zip(preds, names)]
-    got = pool_clusters(dets, names, records, fitted, iou, box_fusion, device, temperatures, class_prior, variance_scales)
+    got = pool_clusters(dets, names, records, fitted, iou, device, cal)
     if got is None:
         raise ValueError(f"no image among the {len(fitted)} fitted ones on which two detectors fired: no cluster to fit pooling weights on")
     cl, labels = got
     lp = cl["log_probs"]
-    prior = None if class_prior is None else log_class_prior(class_prior, lp.shape[1], lp.device)
-    return calibration.fit_pool_weights(lp, cl["row_source"], cl["member_rows"], cl["cluster_offsets"], labels, len(preds), prior)
+    return calibration.fit_pool_weights(lp, cl["row_source"], cl["member_rows"], cl["cluster_offsets"], labels, len(preds),
+                                        cal.on(lp.device, lp.shape[1]).log_prior)
 
 
-def presence_labelled(dets, names, records, ids, iou, box_fusion, device, temperatures=None, class_prior=None, variance_scales=None,
-                      pool_weights=None, presence=None):
+def presence_labelled(dets, names, records, ids, iou, device, cal):
     """The labelled fused rows of the presence fit (and of calibration_report's per-pattern NLL): dets = the prediction dicts sliced to
-    the images `ids`, in that order.  late_fusion.presence_rows fuses them once (a zero table unless `presence` is given); every fused
-    box is matched to the ground truth of its image on the device: an unmatched row is background, and so is a class the head has no
-    column for.  Returns (rows, labels i32 [C] on the device), or None when no detector fired."""
+    the images `ids`, in that order; cal = the FusionOptions ("probEn-log") they are fused with.  late_fusion.presence_rows fuses them
+    once (a zero table unless cal has one); every fused box is matched to the ground truth of its image on the device: an unmatched row
+    is background, and so is a class the head has no column for.  Returns (rows, labels i32 [C] on the device), or None when no
+    detector fired."""
     from .calibration_report import ground_truth
-    rows = presence_rows(dets, box_fusion, device, temperatures, names, class_prior, variance_scales, pool_weights, presence)
+    rows = presence_rows(dets, device=device, names=names, options=cal)
     if rows is None:
         return None
     k = rows["log_posterior"].shape[1] - 1
@@ -179,23 +180,23 @@ def presence_labelled(dets, names, records, ids, iou, box_fusion, device, temper
     return rows, torch.where((labels < 0) | (labels > k), torch.full_like(labels, k), labels)
 
 
-def presence_fit(preds, names, records, fitted, iou, box_fusion, device, temperatures, class_prior, variance_scales, pool_weights):
+def presence_fit(preds, names, records, fitted, iou, device, cal):
     """calibration.fit_presence over the fused rows of the fitted images."""
     from .calibration_report import positions, take_j1
     dets = [take_j1(p, positions(p, fitted, n)) for p, n in zip(preds, names)]
-    got = presence_labelled(dets, names, records, fitted, iou, box_fusion, device, temperatures, class_prior, variance_scales, pool_weights)
+    got = presence_labelled(dets, names, records, fitted, iou, device, cal)
     if got is None:
         raise ValueError(f"no detection on the {len(fitted)} fitted images: no fused row to fit a presence table on")
     rows, labels = got
     return calibration.fit_presence(rows["log_posterior"], rows["pattern"], labels, len(preds))
 
 
-def box_correlation_fit(preds, names, records, fitted, iou, device, temperatures, class_prior, variance_scales, weights):
+def box_correlation_fit(preds, names, records, fitted, iou, device, cal, weights):
     """calibration.fit_box_correlation over the clusters probEn-log / v-avg forms on the fitted images, each with the ground-truth box
     its fused box matches (pe_match_ground_truth's match output at `iou`)."""
     from .calibration_report import ground_truth, positions, take_j1
     dets = [take_j1(p, positions(p, fitted, n)) for p, n in zip(preds, names)]
-    cl = fused_clusters(dets, "v-avg", device, temperatures, names, class_prior, variance_scales)
+    cl = fused_clusters(dets, device=device, names=names, options=cal)
     if cl is None:
         raise ValueError(f"no image among the {len(fitted)} fitted ones on which two detectors fired: no cluster to fit a box correlation on")
     gt = ground_truth(records, [fitted[i] for i in cl["images"]], device)
@@ -268,10 +269,13 @@ def main(cmd=None):
                   f"({v['excluded']} excluded), within 1 / 2 sigma {v['coverage_before'][0]:.4f} / {v['coverage_before'][1]:.4f} -> "
                   f"{v['coverage_after'][0]:.4f} / {v['coverage_after'][1]:.4f} (a Gaussian: 0.6827 / 0.9545)")
     pool = {}
+    names = list(temps)
+    if args.with_pool_weights or args.with_presence or args.with_box_correlation:
+        # the calibration fitted so far, as the later fits fuse with it (the box-correlation fit at v-avg, the others at --box_fusion)
+        cal = FusionOptions("probEn-log", "v-avg", [temps[n] for n in names], [c + 1 for c in counts] if args.with_prior else None,
+                            [vfit[n]["scale"] for n in names] if args.with_variance else None, num_detectors=len(names), who="fit_temperature")
     if args.with_pool_weights:
-        names = list(temps)
-        fit = pool_fit(preds, args.predictions, by_id, fitted, args.iou, args.box_fusion, args.device, [temps[n] for n in names],
-                       [c + 1 for c in counts] if args.with_prior else None, [vfit[n]["scale"] for n in names] if args.with_variance else None)
+        fit = pool_fit(preds, args.predictions, by_id, fitted, args.iou, args.device, cal.replace(box_fusion=args.box_fusion))
         n = fit["clusters"]
         pool = {"pool_weights": dict(zip(names, fit["weights"])), "pool_nll": {"before": fit["nll_at_1"] / n, "after": fit["nll"] / n},
                 "pool_clusters": n, "pool_excluded": fit["excluded"], "pool_at_bound": dict(zip(names, fit["at_bound"])),
@@ -282,10 +286,8 @@ def main(cmd=None):
               f" NLL per cluster {fit['nll_at_1'] / n:.6f} -> {fit['nll'] / n:.6f} over {n} clusters of >= 2 rows ({fit['excluded']} excluded)"
               f"{'' if fit['converged'] else '  (the gradient criterion was not met)'}{note}")
     if args.with_presence:
-        names = list(temps)
-        fit = presence_fit(preds, args.predictions, by_id, fitted, args.iou, args.box_fusion, args.device, [temps[n] for n in names],
-                           [c + 1 for c in counts] if args.with_prior else None, [vfit[n]["scale"] for n in names] if args.with_variance else None,
-                           [pool["pool_weights"][n] for n in names] if pool else None)
+        fit = presence_fit(preds, args.predictions, by_id, fitted, args.iou, args.device,
+                           cal.replace(box_fusion=args.box_fusion, pool_weights=[pool["pool_weights"][n] for n in names] if pool else None))
         per = {}
         for P, r in fit["patterns"].items():
             n = max(r["clusters"], 1)
@@ -300,10 +302,7 @@ def main(cmd=None):
         pool = dict(pool, presence={"detectors": names, "columns": len(fit["table"][0]), "table": fit["table"], "hi": fit["hi"],
                                     "patterns": per, "unassigned": fit["unassigned"], "box_fusion": args.box_fusion, "iou": args.iou})
     if args.with_box_correlation:
-        names = list(temps)
-        fit = box_correlation_fit(preds, args.predictions, by_id, fitted, args.iou, args.device, [temps[n] for n in names],
-                                  [c + 1 for c in counts] if args.with_prior else None,
-                                  [vfit[n]["scale"] for n in names] if args.with_variance else None, args.bbox_reg_weights)
+        fit = box_correlation_fit(preds, args.predictions, by_id, fitted, args.iou, args.device, cal, args.bbox_reg_weights)
         shrunk = "" if fit["shrink"] == 1.0 else f"; off-diagonal entries times {fit['shrink']:.6f} to make it positive semidefinite"
         print(f"box correlation ({sum(fit['rows'])} member rows, {fit['excluded']} excluded{shrunk}):")
         for a in range(len(names)):

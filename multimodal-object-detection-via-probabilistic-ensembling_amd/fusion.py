@@ -26,40 +26,14 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import options as O
+from .options import log_class_prior, pool_weight_tensor  # noqa: F401  (their callers know them by this module)
 
 SCORE_MODES = {"probEn": 0, "avg": 1, "max": 2, "probEn_binary": 3, "probEn-log": 4}
 LOGP = "probEn-log"
 BOX_MODES = {"v-avg": 0, "s-avg": 1, "avg": 2, "argmax": 3}
 CAVG = "c-avg"      # not a mode of the fusion kernel: "v-avg" there, then pe_box_gls_batch
 FRAME_W, FRAME_H = 640.0, 512.0  # class-band shift hard-coded by the reference (demo_probEn.py:100-103)
-
-
-def log_class_prior(class_prior, num_columns, device):
-    """class_prior (K + 1 probabilities, background last; calibration.check_class_prior validates and normalises) -> the DEVICE
-    f64 [K + 1] log-prior pe_proben_fuse_batch_logp takes.  None -> None (uniform).  A CUDA tensor is taken as the result of an
-    earlier call (FramePairPipeline uploads once, not per batch)."""
-    if class_prior is None:
-        return None
-    if isinstance(class_prior, torch.Tensor) and class_prior.is_cuda:
-        if class_prior.dtype != torch.float64 or tuple(class_prior.shape) != (num_columns,):
-            raise ValueError(f"log-prior tensor {tuple(class_prior.shape)} {class_prior.dtype} is not float64 [{num_columns}]")
-        return class_prior.contiguous()
-    from .calibration import check_class_prior
-    return torch.from_numpy(np.log(check_class_prior(class_prior, num_columns))).to(device)
-
-
-def pool_weight_tensor(pool_weights, num_detectors, device):
-    """pool_weights (one exponent per detector; calibration.check_pool_weights validates: finite, >= 0, not all 0) -> the DEVICE f64
-    [num_detectors] tensor pe_proben_fuse_batch_pooled takes.  None -> None.  A CUDA tensor is taken as the result of an earlier call
-    (FramePairPipeline uploads once, not per batch)."""
-    if pool_weights is None:
-        return None
-    if isinstance(pool_weights, torch.Tensor) and pool_weights.is_cuda:
-        if pool_weights.dtype != torch.float64 or tuple(pool_weights.shape) != (num_detectors,):
-            raise ValueError(f"pool-weight tensor {tuple(pool_weights.shape)} {pool_weights.dtype} is not float64 [{num_detectors}]")
-        return pool_weights.contiguous()
-    from .calibration import check_pool_weights
-    return torch.tensor(check_pool_weights(pool_weights, num_detectors, "pool_weights"), dtype=torch.float64).to(device)
 
 
 def _check_mode(score_fusion, class_prior, who, pool_weights=None, with_posterior=False, presence=None, box_fusion=None,
@@ -89,60 +63,51 @@ def _check_mode(score_fusion, class_prior, who, pool_weights=None, with_posterio
 
 def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="probEn", box_fusion="v-avg",
                max_rows=None, iou_thresh=0.5, frame=(FRAME_W, FRAME_H), row_counts=None, passthrough=None, log_probs=None,
-               class_prior=None, pool_weights=None, row_source=None, with_posterior=False, presence=None, box_correlation=None):
+               class_prior=None, pool_weights=None, row_source=None, with_posterior=False, presence=None, box_correlation=None,
+               options=None):
     """Fuse B images in one launch.
-
-    score_fusion "probEn-log": log_probs f64 [Ntot,K+1] (calibration.log_posteriors / pack_rows(log_posteriors=True)) replaces
-    probs (ignored, may be None); class_prior: K + 1 probabilities, background last, or None = uniform.
-    pool_weights ("probEn-log" only; one w_d per detector or pool_weight_tensor's device tensor) with row_source i32 [Ntot] (each
-    row's detector index): pe_proben_fuse_batch_pooled; the result then also holds "cluster" i32 [Ntot], the output row of the
-    cluster each input row ended in (-1: it left the pool without one; -2 where nothing was written: counts == -1, padding).
-    with_posterior ("probEn-log" only): pe_proben_fuse_batch_posterior; the result then also holds "log_posterior" f64 [Ntot, K+1]
-    (the fused rows' normalised log-posterior), "vars" f64 [Ntot] (the fused boxes' variance under the box rule) and "members" i32
-    [Ntot] (rows in the cluster), indexed like "scores"; rows nothing was written to hold NaN / NaN / 0.
-    presence ("probEn-log" only; a table [2^D][K+1] or calibration.presence_table's device tensor) with row_source:
-    pe_proben_fuse_batch_presence, with or without pool_weights / with_posterior; the fused columns gain presence[P][j], P the OR of
-    (1 << source) over the cluster's rows, clusters of one row and passthrough images are fused too; the result then also holds
-    "pattern" i32 [Ntot] (the fused rows' P, indexed like "scores"; -1 where nothing was written) and "cluster".
-    box_fusion "c-avg" ("probEn-log" only) with box_correlation (a matrix [D][D], calibration.check_box_correlation, or
-    calibration.box_correlation_tensor's device tensor) and row_source: the entry point the other arguments select runs at "v-avg"
-    (pe_proben_fuse_batch_pooled with weights of 1.0, which is "probEn-log" bit for bit, when they select none that writes "cluster"),
-    then pe_box_gls_batch overwrites "boxes" - and "vars", with_posterior - of the fused rows whose cluster has two or more rows; a row
-    whose source is outside [0, D) makes its cluster's box and variance NaN.  The result then also holds "cluster".
 
     boxes f64 [Ntot,4], scores f64 [Ntot], probs f64 [Ntot,K], variances f64 [Ntot],
     classes i32 [Ntot], offsets i32 [B+1] - all CUDA tensors, rows of each image already
     concatenated in detector order.  Returns a dict of device tensors:
       boxes f64 [Ntot,4], scores f32 [Ntot], classes f32 [Ntot], keep i32 [Ntot], counts i32 [B];
     image b's fused rows are [offsets[b], offsets[b]+counts[b]).
-    """
-    _check_mode(score_fusion, class_prior, "fuse_batch", pool_weights, with_posterior, presence, box_fusion, box_correlation)
-    logp = score_fusion == LOGP
-    pool = pool_weights is not None
-    pres = presence is not None
-    cavg = box_fusion == CAVG
-    if cavg and (row_source is None or row_source.dim() != 1 or row_source.shape[0] != boxes.shape[0]):
-        raise ValueError(f"fuse_batch: box_fusion '{CAVG}' needs row_source [Ntot] for the {boxes.shape[0]} rows, got "
-                         f"{None if row_source is None else tuple(row_source.shape)}")
-    if pres and (row_source is None or row_source.dim() != 1 or row_source.shape[0] != boxes.shape[0]):
-        raise ValueError(f"fuse_batch: presence needs row_source [Ntot] for the {boxes.shape[0]} rows, got "
-                         f"{None if row_source is None else tuple(row_source.shape)}")
-    if pool and (row_source is None or row_source.dim() != 1 or row_source.shape[0] != boxes.shape[0]):
-        raise ValueError(f"fuse_batch: pool_weights need row_source [Ntot] for the {boxes.shape[0]} rows, got "
+
+    The option keywords, or `options` (an options.FusionOptions, which documents them and the outputs they add; not both), select the
+    entry point.  score_fusion "probEn-log": log_probs f64 [Ntot,K+1] (calibration.log_posteriors / pack_rows(log_posteriors=True))
+    replaces probs (ignored, may be None).  pool_weights, presence and box_fusion "c-avg" need row_source i32 [Ntot], each row's
+    detector index.  Temperatures and variance scales are in the rows already: they are not read here.
+
+      entry point                      when                                  row_source, pool_weights, D   cluster  posterior  pattern
+      pe_proben_fuse_batch             any other score_fusion                -                             -        -          -
+      pe_proben_fuse_batch_logp        "probEn-log", nothing below           -                             -        -          -
+      pe_proben_fuse_batch_pooled      pool_weights, or "c-avg" alone        given (c-avg alone: w = 1.0)  yes      -          -
+      pe_proben_fuse_batch_posterior   with_posterior                        given, or NULL / NULL / 0     c-avg    yes        -
+      pe_proben_fuse_batch_presence    presence                              row_source, weights or NULL   yes      or NULL    yes
+    (first match from the bottom).  "c-avg" runs the chosen entry point at "v-avg" - the pooled one at weights of 1.0, which is
+    "probEn-log" bit for bit, when nothing else selects one that writes "cluster" - and then pe_box_gls_batch."""
+    opts = O.FusionOptions.of(options, "fuse_batch", None, score_fusion, box_fusion, class_prior=class_prior, pool_weights=pool_weights,
+                              with_posterior=with_posterior, presence=presence, box_correlation=box_correlation)
+    logp, cavg, post = opts.logp, opts.cavg, opts.with_posterior
+    pool, pres = opts.pool_weights is not None, opts.presence is not None
+    ntot = boxes.shape[0]
+    if opts.needs_row_source and (row_source is None or row_source.dim() != 1 or row_source.shape[0] != ntot):
+        what = f"box_fusion '{CAVG}' needs" if cavg else "presence needs" if pres else "pool_weights need"
+        raise ValueError(f"fuse_batch: {what} row_source [Ntot] for the {ntot} rows, got "
                          f"{None if row_source is None else tuple(row_source.shape)}")
     if logp:
-        if log_probs is None or log_probs.dim() != 2 or log_probs.shape[1] < 2 or log_probs.shape[0] != boxes.shape[0]:
-            raise ValueError(f"fuse_batch: score_fusion '{LOGP}' needs log_probs [Ntot, K+1] for the {boxes.shape[0]} rows, got "
+        if log_probs is None or log_probs.dim() != 2 or log_probs.shape[1] < 2 or log_probs.shape[0] != ntot:
+            raise ValueError(f"fuse_batch: score_fusion '{LOGP}' needs log_probs [Ntot, K+1] for the {ntot} rows, got "
                              f"{None if log_probs is None else tuple(log_probs.shape)}")
         probs = log_probs
-    _lib.require_cuda(boxes, scores, probs, variances, classes, offsets, row_source if pool or pres or cavg else None)
-    if score_fusion == "max" and box_fusion == "argmax":
+    _lib.require_cuda(boxes, scores, probs, variances, classes, offsets, row_source if opts.needs_row_source else None)
+    if opts.score_fusion == "max" and opts.box_fusion == "argmax":
         raise ValueError("('max','argmax') is the class-aware NMS route: use fusion()/nms_fuse_batch")
     B = offsets.numel() - (0 if row_counts is not None else 1)
-    ntot = boxes.shape[0]
     K = probs.shape[1] if probs is not None and probs.dim() == 2 else 1
     K -= 1 if logp else 0
-    log_prior = log_class_prior(class_prior, K + 1, boxes.device) if logp else None
+    dev = boxes.device
+    log_prior, weights, table, corr = opts.on(dev, K + 1) if logp else (None,) * 4
     boxes = boxes.contiguous().double()
     scores = scores.contiguous().double()
     probs = probs.contiguous().double() if probs is not None else None
@@ -153,26 +118,16 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
         assert row_counts is None, "max_rows must be given with row_counts (avoids a host sync)"
         max_rows = int((offsets[1:] - offsets[:-1]).max().item()) if B > 0 else 1
     max_rows = max(int(max_rows), 1)
-    dev = boxes.device
-    if pool:
-        weights = pool_weight_tensor(pool_weights, len(pool_weights), dev)
-    if pool or pres or cavg:
+    if opts.needs_row_source:
         row_source = row_source.contiguous().to(torch.int32)
-    if cavg:
-        from .calibration import box_correlation_tensor
-        corr = box_correlation_tensor(box_correlation, None, dev)
-        if pool and int(weights.numel()) != corr.shape[0]:
-            raise ValueError(f"fuse_batch: {int(weights.numel())} pool weights beside a box correlation over {corr.shape[0]} detectors")
-        if not (pool or pres or with_posterior):      # no entry point that writes "cluster" is selected: the pooled one at w = 1
-            pool, weights = True, torch.ones((corr.shape[0],), dtype=torch.float64, device=dev)
-    if pres:
-        from .calibration import presence_detectors, presence_table
-        table = presence_table(presence, None, K + 1, dev)
-        nd = presence_detectors(table)
-        if pool and int(weights.numel()) != nd:
-            raise ValueError(f"fuse_batch: {int(weights.numel())} pool weights beside a presence table over {nd} detectors")
-        if cavg and corr.shape[0] != nd:
-            raise ValueError(f"fuse_batch: a box correlation over {corr.shape[0]} detectors beside a presence table over {nd}")
+    if cavg and not (pool or pres or post):     # no entry point that writes "cluster" is selected: the pooled one at w = 1
+        pool, weights = True, torch.ones((corr.shape[0],), dtype=torch.float64, device=dev)
+    entry = "_presence" if pres else "_posterior" if post else "_pooled" if pool else "_logp" if logp else ""
+    wide = entry in ("_pooled", "_posterior", "_presence")      # the entry points with row_source, pool_weights, num_detectors, out_cluster
+    detectors = opts.num_detectors if pres else int(weights.numel()) if pool else 0
+
+    def new(shape, dtype, fill):
+        return torch.full(shape, fill, dtype=dtype, device=dev)
     out = {
         "boxes": torch.empty((ntot, 4), dtype=torch.float64, device=dev),
         "scores": torch.empty((ntot,), dtype=torch.float32, device=dev),
@@ -180,43 +135,36 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
         "keep": torch.empty((ntot,), dtype=torch.int32, device=dev),
         "counts": torch.zeros((max(B, 1),), dtype=torch.int32, device=dev)[:B],
     }
-    name = ("pe_proben_fuse_batch_presence" if pres else "pe_proben_fuse_batch_posterior" if with_posterior else "pe_proben_fuse_batch_pooled" if pool
-            else "pe_proben_fuse_batch_logp" if logp else "pe_proben_fuse_batch")
-    head = (_lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(probs), _lib.ptr(variances), _lib.ptr(classes),
-            *([_lib.ptr(row_source) if pool or pres else None] if pool or with_posterior or pres else []), _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(passthrough), B, K, max_rows)
-    geometry = (BOX_MODES["v-avg" if cavg else box_fusion], float(iou_thresh), float(frame[0]), float(frame[1]))
-    mode = geometry + (_lib.ptr(log_prior),) if logp else (SCORE_MODES[score_fusion],) + geometry
-    tail = ()
-    if pres:
-        mode += (_lib.ptr(weights) if pool else None, _lib.ptr(table), nd)
-        out["cluster"] = torch.full((ntot,), -2, dtype=torch.int32, device=dev)
-        tail = (_lib.ptr(out["cluster"]),)
-    elif pool:
-        mode += (_lib.ptr(weights), int(weights.numel()))
-        out["cluster"] = torch.full((ntot,), -2, dtype=torch.int32, device=dev)     # -2: never written (padding, counts == -1)
-        tail = (_lib.ptr(out["cluster"]),)
-    elif with_posterior:
-        mode += (None, 0)          # row_source and pool_weights NULL together: the unpooled rule
-        if cavg:
-            out["cluster"] = torch.full((ntot,), -2, dtype=torch.int32, device=dev)
-        tail = (_lib.ptr(out.get("cluster")),)
-    if with_posterior:
-        out["log_posterior"] = torch.full((ntot, K + 1), float("nan"), dtype=torch.float64, device=dev)
-        out["vars"] = torch.full((ntot,), float("nan"), dtype=torch.float64, device=dev)
+    # outputs only some entry points write, pre-filled with what "nothing was written here" reads as (padding, counts == -1)
+    if pres or pool or cavg:
+        out["cluster"] = new((ntot,), torch.int32, -2)
+    if post:
+        out["log_posterior"] = new((ntot, K + 1), torch.float64, float("nan"))
+        out["vars"] = new((ntot,), torch.float64, float("nan"))
         out["members"] = torch.zeros((ntot,), dtype=torch.int32, device=dev)
-        tail += (_lib.ptr(out["log_posterior"]), _lib.ptr(out["vars"]), _lib.ptr(out["members"]))
-    elif pres:
-        tail += (None, None, None)         # the three posterior outputs NULL together: a score-only run
     if pres:
-        out["pattern"] = torch.full((ntot,), -1, dtype=torch.int32, device=dev)     # -1: never written (padding, counts == -1)
-        tail += (_lib.ptr(out["pattern"]),)
-    st = getattr(_lib.lib(), name)(*head, *mode, _lib.ptr(out["boxes"]), _lib.ptr(out["scores"]), _lib.ptr(out["classes"]),
-                                   _lib.ptr(out["keep"]), _lib.ptr(out["counts"]), *tail, _lib.stream())
-    _lib.check(st, name)
+        out["pattern"] = new((ntot,), torch.int32, -1)
+    P = _lib.ptr
+    name = "pe_proben_fuse_batch" + entry
+    args = [P(boxes), P(scores), P(probs), P(variances), P(classes)]
+    args += [P(row_source) if pool or pres else None] if wide else []
+    args += [P(offsets), P(row_counts), P(passthrough), B, K, max_rows]
+    args += [] if logp else [SCORE_MODES[opts.score_fusion]]
+    args += [BOX_MODES["v-avg" if cavg else opts.box_fusion], float(iou_thresh), float(frame[0]), float(frame[1])]
+    args += [P(log_prior)] if logp else []
+    args += [P(weights) if pool else None] if wide else []      # NULL with row_source NULL: the unpooled rule
+    args += [P(table)] if entry == "_presence" else []
+    args += [detectors] if wide else []
+    args += [P(out["boxes"]), P(out["scores"]), P(out["classes"]), P(out["keep"]), P(out["counts"])]
+    args += [P(out.get("cluster"))] if wide else []
+    # the three posterior outputs are NULL together on a score-only presence run
+    args += [P(out.get("log_posterior")), P(out.get("vars")), P(out.get("members"))] if entry in ("_posterior", "_presence") else []
+    args += [P(out["pattern"])] if entry == "_presence" else []
+    _lib.check(getattr(_lib.lib(), name)(*args, _lib.stream()), name)
     if cavg:
-        st = _lib.lib().pe_box_gls_batch(_lib.ptr(boxes), _lib.ptr(variances), _lib.ptr(row_source), _lib.ptr(out["cluster"]),
-                                         _lib.ptr(offsets), _lib.ptr(row_counts), _lib.ptr(out["counts"]), B, max_rows, _lib.ptr(corr),
-                                         int(corr.shape[0]), _lib.ptr(out["boxes"]), _lib.ptr(out.get("vars")), _lib.stream())
+        st = _lib.lib().pe_box_gls_batch(P(boxes), P(variances), P(row_source), P(out["cluster"]), P(offsets), P(row_counts),
+                                         P(out["counts"]), B, max_rows, P(corr), int(corr.shape[0]), P(out["boxes"]), P(out.get("vars")),
+                                         _lib.stream())
         _lib.check(st, "pe_box_gls_batch")
     return out
 
@@ -263,42 +211,25 @@ def pack_infos(per_image_infos, device="cuda", with_log_probs=False, with_source
 
 
 def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=None, variance_scales=None, pool_weights=None,
-           box_correlation=None):
+           box_correlation=None, options=None):
     """Drop-in for the reference's ``fusion`` (demo_probEn.py:189-196).
 
     Returns (out_boxes, out_scores, out_class): boxes as a list of float64 ndarrays [4]
     (or a float32 Tensor [n,4] on the ('max','argmax') route), scores / classes as float32
     CPU tensors - the reference's return types.
-    temperatures (one T per info): the rows' prob / score are rebuilt from their class_logits as softmax(logits / T)
-    (calibration.calibrate_rows); an info without logits is refused.
-    method[0] "probEn-log": the rows' log-posteriors come from their class_logits too (temperatures None = 1 for every info) and
-    are fused by pe_proben_fuse_batch_logp, with class_prior (K + 1 probabilities, background last) when given.
-    variance_scales (one s per info): the rows' vars are multiplied by s in float64 (one multiply, as pe_proben_pack_calibrated does
-    on the device route); the box rules "v-avg" and "c-avg" read them.
-    pool_weights (one w per info, method[0] "probEn-log" only): the pooled rule of pe_proben_fuse_batch_pooled; a row's detector is
-    its info's position.
-    method[1] "c-avg" (method[0] "probEn-log" only) with box_correlation (one entry per pair of infos): fuse_batch's correlated box rule."""
+    The option keywords, or `options` (options.FusionOptions, which documents them; not both), one value per info: the rows' prob /
+    score are rebuilt from their class_logits as softmax(logits / T) (calibration.calibrate_rows; an info without logits is refused),
+    their vars multiplied by s in float64, and a row's detector is its info's position."""
     infos = [info_1, info_2] + ([info_3] if info_3 else [])
-    _check_mode(method[0], class_prior, "fusion", pool_weights, box_fusion=method[1], box_correlation=box_correlation)
-    if box_correlation is not None:
-        from .calibration import check_box_correlation
-        box_correlation = check_box_correlation(box_correlation, len(infos), "fusion: box_correlation")
-    if pool_weights is not None:
-        from .calibration import check_pool_weights
-        pool_weights = check_pool_weights(pool_weights, len(infos), "fusion")
-    if variance_scales is not None:
-        from .calibration import check_variance_scales
-        variance_scales = check_variance_scales(variance_scales, len(infos), "fusion")
-        infos = [dict(d, vars=(np.asarray(d["vars"], dtype=np.float64) * s).tolist()) for d, s in zip(infos, variance_scales)]
-    logp = method[0] == LOGP
-    if logp and temperatures is None:
-        temperatures = [1.0] * len(infos)
-    if temperatures is not None:
+    opts = O.FusionOptions.of(options, "fusion", len(infos), method[0], method[1], temperatures=temperatures, class_prior=class_prior,
+                              variance_scales=variance_scales, pool_weights=pool_weights, box_correlation=box_correlation)
+    if opts.variance_scales is not None:
+        infos = [dict(d, vars=(np.asarray(d["vars"], dtype=np.float64) * s).tolist()) for d, s in zip(infos, opts.variance_scales)]
+    logp = opts.logp
+    if opts.temperatures is not None:
         from . import calibration
-        if len(temperatures) != len(infos):
-            raise ValueError(f"fusion: {len(temperatures)} temperatures for {len(infos)} detectors")
         cal = []
-        for k, (d, T) in enumerate(zip(infos, temperatures)):
+        for k, (d, T) in enumerate(zip(infos, opts.temperatures)):
             lg = d.get("class_logits")
             if lg is None or len(lg) != len(d["bbox"]) or any(len(r) < 2 for r in lg):
                 raise ValueError(f"fusion: info_{k + 1} ({d.get('img_name', '?')}) carries no class_logits: temperature calibration "
@@ -315,16 +246,9 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=Non
         classes = torch.tensor(sum([list(d["class"]) for d in infos], []), dtype=torch.float32)
         keep = batched_nms(boxes.cuda(), scores.cuda(), classes.cuda(), 0.5).cpu()
         return boxes[keep], scores[keep], classes[keep]
-    if logp and (pool_weights is not None or box_correlation is not None):
-        b, s, p, v, c, offs, lp, src = pack_infos([infos], with_log_probs=True, with_sources=True)
-        out = fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior, pool_weights=pool_weights,
-                         row_source=src, box_correlation=box_correlation)
-    elif logp:
-        b, s, p, v, c, offs, lp = pack_infos([infos], with_log_probs=True)
-        out = fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior)
-    else:
-        b, s, p, v, c, offs = pack_infos([infos])
-        out = fuse_batch(b, s, p, v, c, offs, method[0], method[1])
+    b, s, p, v, c, offs, *rest = pack_infos([infos], with_log_probs=logp, with_sources=opts.needs_row_source)
+    out = fuse_batch(b, s, p, v, c, offs, log_probs=rest[0] if logp else None, row_source=rest[-1] if opts.needs_row_source else None,
+                     options=opts)
     m = int(out["counts"][0].item())
     if m < 0:
         raise RuntimeError("fusion: too many rows for one image")
@@ -332,7 +256,8 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=Non
     return [boxes[i] for i in range(m)], out["scores"][:m].cpu(), out["classes"][:m].cpu()
 
 
-def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, variance_scales=None, pool_weights=None):
+def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, variance_scales=None, pool_weights=None, with_sources=False,
+              options=None):
     """The detectors' padded outputs -> ProbEn input rows on the device (pe_proben_pack_detections; with temperatures
     pe_proben_pack_logits: probabilities and scores from class_logits as softmax(logits / T_d) in float64).
     Returns (boxes f64 [B*S,4], scores f64, probs f64 [B*S,K], vars f64, classes i32, offsets i32 [B], counts i32 [B],
@@ -340,18 +265,19 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, varian
     same eight plus the rows' log-posteriors f64 [B*S,K+1] as a ninth.
     variance_scales (one s per detector): pe_proben_pack_calibrated, whichever of the three routes the other arguments select, with
     vars = (double)var * s_d; None calls the three entry points above as before.
-    pool_weights (one w per detector; only their presence and count matter here): pe_proben_pack_pooled, the same route with each
-    written row's detector index i32 [B*S] appended as the LAST element of the result."""
+    with_sources (or pool_weights, one w per detector, of which only the presence and the count matter here): pe_proben_pack_pooled,
+    the same route with each written row's detector index i32 [B*S] appended as the LAST element of the result.
+    options (an options.FusionOptions, instead of the keywords): its temperatures and variance scales, log-posteriors on
+    "probEn-log", sources where its fusion needs row_source."""
     import ctypes
     nd = len(dets)
-    if pool_weights is not None and not (isinstance(pool_weights, torch.Tensor) and pool_weights.is_cuda):
-        from .calibration import check_pool_weights
-        check_pool_weights(pool_weights, nd, "pack_rows")
-    elif pool_weights is not None and pool_weights.numel() != nd:
-        raise ValueError(f"pack_rows: {pool_weights.numel()} pool weights for {nd} detectors")
-    if variance_scales is not None:
-        from .calibration import check_variance_scales
-        variance_scales = check_variance_scales(variance_scales, nd, "pack_rows")
+    if options is not None:
+        temperatures, variance_scales = options.temperatures, options.variance_scales
+        log_posteriors, with_sources = options.logp, options.needs_row_source
+    else:
+        temperatures = O.checked("temperatures", temperatures, nd, "fuse_detections")   # (the caller these messages have always named)
+        variance_scales = O.checked("variance_scales", variance_scales, nd, "pack_rows")
+        with_sources = with_sources or O.checked("pool_weights", pool_weights, nd, "pack_rows") is not None
     B, D = dets[0]["scores"].shape
     K = dets[0]["prob_score"].shape[2]
     dev = dets[0]["scores"].device
@@ -369,9 +295,7 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, varian
     osingle = torch.empty((B,), dtype=torch.int32, device=dev)
     if log_posteriors and temperatures is None:
         raise ValueError("pack_rows: log_posteriors needs temperatures (1.0 per detector for the uncalibrated logits)")
-    if temperatures is not None:       # (worded for fuse_detections, the caller these messages have always named)
-        if len(temperatures) != nd:
-            raise ValueError(f"fuse_detections: {len(temperatures)} temperatures for {nd} detectors")
+    if temperatures is not None:
         for d in dets:
             if d["class_logits"].shape != (B, D, K + 1) or d["class_logits"].dtype != torch.float32:
                 raise ValueError(f"fuse_detections: class_logits {tuple(d['class_logits'].shape)} is not float32 [{B}, {D}, {K + 1}]")
@@ -381,7 +305,7 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, varian
     scores, probs, lg = (None, None, arr("class_logits")) if logits else (arr("scores"), arr("prob_score"), None)
     dims = (nd, B, D, K, max_class, S)
     head, tail = [_lib.ptr(t) for t in (ob, os_, op)], [_lib.ptr(t) for t in (ov, oc, ooff, ocnt, osingle)]
-    osrc = torch.empty((B * S,), dtype=torch.int32, device=dev) if pool_weights is not None else None
+    osrc = torch.empty((B * S,), dtype=torch.int32, device=dev) if with_sources else None
     if variance_scales is not None or osrc is not None:
         name = "pe_proben_pack_pooled" if osrc is not None else "pe_proben_pack_calibrated"
         args = (arr("boxes"), scores, arr("classes"), probs, lg, arr("vars"), arr("counts"), temps,
@@ -401,52 +325,30 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, varian
 
 def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=0.5, temperatures=None,
                     class_prior=None, variance_scales=None, pool_weights=None, with_posterior=False, presence=None,
-                    box_correlation=None):
+                    box_correlation=None, options=None):
     """Device-to-device stage fusion: `dets` = the result dicts of 2 or 3 detectors run on the SAME batch
     (rcnn.GeneralizedRCNN.forward_batch).  Packs their detections into ProbEn rows (classes <= max_class,
     like the JSON writer demo_FLIR_save_predictions.py:148-155), applies the reference's per-image case
     split (0 detectors -> nothing, 1 -> passthrough, >= 2 -> fusion; demo_probEn.py:237-267) and fuses.
-    temperatures (one T per detector): the rows' probabilities and scores come from the detectors' class_logits as
-    softmax(logits / T) in float64 (pe_proben_pack_logits) instead of the float32 prob_score / scores.
-    score_fusion "probEn-log": pe_proben_pack_log_posteriors + pe_proben_fuse_batch_logp (temperatures None = 1 per detector;
-    class_prior: K + 1 probabilities, background last, or the device tensor of log_class_prior).
-    variance_scales (one s per detector): the rows' variances are (double)var * s_d (pe_proben_pack_calibrated); they weight the
-    member boxes of box_fusion "v-avg" and "c-avg" and nothing else, so every other box rule and the NMS route give the bits they gave.
-    pool_weights (one w per detector or pool_weight_tensor's device tensor, "probEn-log" only): pe_proben_pack_pooled +
-    pe_proben_fuse_batch_pooled; the result then also holds "cluster" and "row_source".
-    with_posterior ("probEn-log" only): the fusion is pe_proben_fuse_batch_posterior and the result also holds fuse_batch's
-    "log_posterior", "vars" and "members".
-    presence ("probEn-log" only; a table [2^D][K+1], D = len(dets), or calibration.presence_table's device tensor): the rows' detector
-    indices come from pe_proben_pack_pooled and the fusion is pe_proben_fuse_batch_presence - images on which one detector fired are
-    rescored row by row, not copied; the result then also holds "pattern", "cluster" and "row_source".
-    box_fusion "c-avg" ("probEn-log" only) with box_correlation (a matrix [D][D], D = len(dets), or calibration.box_correlation_tensor's
-    device tensor): the rows' detector indices come from pe_proben_pack_pooled and fuse_batch's second launch, pe_box_gls_batch,
-    overwrites the boxes (and "vars") of the clusters of two or more rows; the result then also holds "cluster" and "row_source".
+    The option keywords, or `options` (options.FusionOptions, which documents them and the outputs they add; not both), one value per
+    detector: with temperatures the rows come from the detectors' class_logits (pe_proben_pack_logits, pe_proben_pack_log_posteriors
+    on "probEn-log") instead of the float32 prob_score / scores, with variance_scales through pe_proben_pack_calibrated; where the
+    fusion needs each row's detector (pool_weights, presence, box_fusion "c-avg") pe_proben_pack_pooled writes it and the result
+    also holds it as "row_source".  With presence, images on which one detector fired are rescored row by row, not copied.
     No host synchronisation.  Returns a dict: boxes f64 [B*S,4], scores f32, classes f32, counts i32 [B],
     offsets i32 [B], stride S = len(dets) * D."""
+    opts = O.FusionOptions.of(options, "fuse_detections", len(dets), score_fusion, box_fusion, temperatures=temperatures,
+                              class_prior=class_prior, variance_scales=variance_scales, pool_weights=pool_weights,
+                              with_posterior=with_posterior, presence=presence, box_correlation=box_correlation)
     # the box heads' candidate-cap bookkeeping travels with the result (no kernel here): check_candidate_overflow() looks
     # at it at the consumer's first host synchronisation
-    _check_mode(score_fusion, class_prior, "fuse_detections", pool_weights, with_posterior, presence, box_fusion, box_correlation)
-    if box_correlation is not None:
-        from .calibration import box_correlation_tensor
-        box_correlation = box_correlation_tensor(box_correlation, len(dets), dets[0]["scores"].device)
-    if presence is not None:
-        from .calibration import presence_table
-        presence = presence_table(presence, len(dets), dets[0]["prob_score"].shape[2] + 1, dets[0]["scores"].device)
     overflow_src = [(d["cand_total"], d["cand_max"]) for d in dets if "cand_total" in d]
     B, D = dets[0]["scores"].shape
     S = len(dets) * D
     dev = dets[0]["scores"].device
-    logp = score_fusion == LOGP
-    if logp and temperatures is None:
-        temperatures = [1.0] * len(dets)
-    ob, os_, op, ov, oc, ooff, ocnt, osingle, *olp = pack_rows(dets, max_class, temperatures, log_posteriors=logp,
-                                                               variance_scales=variance_scales,
-                                                               pool_weights=pool_weights if (presence is None and box_correlation is None)
-                                                               or pool_weights is not None
-                                                               else [1.0] * len(dets))      # only their presence matters to pack_rows
-    osrc = olp.pop() if pool_weights is not None or presence is not None or box_correlation is not None else None
-    if score_fusion == "max" and box_fusion == "argmax":
+    ob, os_, op, ov, oc, ooff, ocnt, osingle, *olp = pack_rows(dets, max_class, options=opts)
+    osrc = olp.pop() if opts.needs_row_source else None
+    if opts.score_fusion == "max" and opts.box_fusion == "argmax":
         from .layers import nms_batched_raw
         b32 = ob.float().view(B, S, 4)
         keep, kcnt = nms_batched_raw(b32, os_.float().view(B, S), oc.view(B, S), ocnt, None, iou_thresh, 0, S)
@@ -459,10 +361,8 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
         g = (torch.arange(B, device=dev).view(B, 1) * S + keep.clamp(0, S - 1).long()).view(-1)
         return {"boxes": ob[g], "scores": os_.float()[g], "classes": oc.float()[g], "counts": kcnt, "keep": keep,
                 "offsets": ooff, "stride": S, "in_counts": ocnt, "nms_route": True, "cand_overflow_src": overflow_src}
-    out = fuse_batch(ob, os_, op, ov, oc, ooff, score_fusion, box_fusion, max_rows=S, iou_thresh=iou_thresh,
-                     row_counts=ocnt, passthrough=osingle, log_probs=olp[0] if logp else None, class_prior=class_prior,
-                     pool_weights=pool_weights, row_source=osrc, with_posterior=with_posterior, presence=presence,
-                     box_correlation=box_correlation)
+    out = fuse_batch(ob, os_, op, ov, oc, ooff, max_rows=S, iou_thresh=iou_thresh, row_counts=ocnt, passthrough=osingle,
+                     log_probs=olp[0] if opts.logp else None, row_source=osrc, options=opts)
     if osrc is not None:
         out["row_source"] = osrc
     out["offsets"], out["stride"], out["in_counts"] = ooff, S, ocnt

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import fusion as F
+from . import options as O
 from .structures import Boxes, Instances
 
 J1_KEYS = ["image", "boxes", "scores", "classes", "image_id", "class_logits", "probs", "vars"]
@@ -66,56 +67,42 @@ def _info(det, i):
     return d
 
 
+def _calibrated(dets, opts, names, device):
+    """The prediction dicts as the fusion reads them: vars times the variance scales (calibration.scale_j1_vars: float64, the single
+    multiply of the device route's pe_proben_pack_calibrated), probs / scores - and, "probEn-log", log_probs - rebuilt from the
+    class_logits at the temperatures (calibration.calibrate_j1).  `names` (the files) word the refusal of a file without logits: every
+    file is checked before the first launch."""
+    from . import calibration
+    if opts.variance_scales is not None:
+        dets = [calibration.scale_j1_vars(d, s) for d, s in zip(dets, opts.variance_scales)]
+    if opts.temperatures is not None:
+        names = names or [f"prediction file {k + 1}" for k in range(len(dets))]
+        for d, n in zip(dets, names):
+            calibration.require_logits(d, n)
+        dets = [calibration.calibrate_j1(d, t, n, device, log_probs=opts.logp) for d, t, n in zip(dets, opts.temperatures, names)]
+    return dets
+
+
 def late_fusion(dets, method, device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None,
-                pool_weights=None, with_posterior=False, presence=None, box_correlation=None):
+                pool_weights=None, with_posterior=False, presence=None, box_correlation=None, options=None):
     """dets: 2 or 3 J1 dicts over the same images (order = detector order).  Returns per-image
     (boxes float64 [m,4] | None, scores f32, classes f32); None = skipped image (no detector fired).
     Case split of demo_probEn.py:237-267: 0 detectors -> skip, 1 -> passthrough, >= 2 -> fusion of the
     non-empty lists in order.  All images needing fusion go through ONE batched launch.
-    temperatures (one T per detector): every file's probs / scores are rebuilt from its class_logits as softmax(logits / T) before
-    the case split (calibration.calibrate_j1), so passed-through rows carry the calibrated score like the device route's;
-    `names` (the files) word the refusal of a file without logits.
-    method[0] "probEn-log": the files' log-posteriors log_softmax(class_logits / T) (temperatures None = 1 per file) go through
-    pe_proben_fuse_batch_logp, with class_prior (K + 1 probabilities, background last) when given.
-    variance_scales (one s per detector): every file's vars are multiplied by s in float64 (calibration.scale_j1_vars), the single
-    multiply of the device route's pe_proben_pack_calibrated, so both routes fuse identical variances.
-    pool_weights (one w per detector, "probEn-log" only): the pooled rule of pe_proben_fuse_batch_pooled; a row's detector is its
-    file's position in dets, what pe_proben_pack_pooled writes on the device route.
-    with_posterior ("probEn-log" only): every per-image result is a 6-tuple, the three above plus (log_posterior f64 [m, K+1], vars f64
-    [m], members i32 [m]) of pe_proben_fuse_batch_posterior; a passed-through image takes its log-posterior from the calibrated file
-    ("log_probs") and its vars from the scaled file, what the device route's passthrough copies.
-    presence (a table [2^D][K+1], D = len(dets), "probEn-log" only): pe_proben_fuse_batch_presence.  Images on which one detector fired
-    are then no longer answered on the host: they go into the batched launch with their passthrough flag set and come back rescored
-    row by row (never clustered), which is what the device route does with the pack kernel's single-source flag - the two routes stay
-    byte-identical.
-    method[1] "c-avg" ("probEn-log" only) with box_correlation (a matrix [D][D], D = len(dets); calibration.check_box_correlation):
-    fuse_batch's correlated box rule, a second launch (pe_box_gls_batch) over the fused boxes and, with_posterior, their variances; a
-    row's detector is its file's position in dets."""
-    F._check_mode(method[0], class_prior, "late_fusion", pool_weights, with_posterior, presence, method[1], box_correlation)
-    if box_correlation is not None:
-        from . import calibration
-        box_correlation = calibration.check_box_correlation(box_correlation, len(dets), "late_fusion: box_correlation")
-    if presence is not None:
-        from . import calibration
-        presence = calibration.check_presence(presence, len(dets), None, "late_fusion: presence")
-    if pool_weights is not None:
-        from . import calibration
-        pool_weights = calibration.check_pool_weights(pool_weights, len(dets), "late_fusion")
-    if variance_scales is not None:
-        from . import calibration
-        variance_scales = calibration.check_variance_scales(variance_scales, len(dets), "late_fusion")
-        dets = [calibration.scale_j1_vars(d, s) for d, s in zip(dets, variance_scales)]
-    logp = method[0] == F.LOGP
-    if logp and temperatures is None:
-        temperatures = [1.0] * len(dets)
-    if temperatures is not None:
-        from . import calibration
-        if len(temperatures) != len(dets):
-            raise ValueError(f"late_fusion: {len(temperatures)} temperatures for {len(dets)} detectors")
-        names = names or [f"prediction file {k + 1}" for k in range(len(dets))]
-        for d, n in zip(dets, names):          # every file is checked before the first launch
-            calibration.require_logits(d, n)
-        dets = [calibration.calibrate_j1(d, t, n, device, log_probs=logp) for d, t, n in zip(dets, temperatures, names)]
+    The option keywords, or `options` (options.FusionOptions, which documents them; not both), one value per file; a row's detector is
+    its file's position in dets, what pe_proben_pack_pooled writes on the device route.  Temperatures and variance scales are applied
+    to the files before the case split (_calibrated), so passed-through rows carry the calibrated score like the device route's.
+    with_posterior: every per-image result is a 6-tuple, the three above plus (log_posterior f64 [m, K+1], vars f64 [m], members i32
+    [m]); a passed-through image takes its log-posterior from the calibrated file ("log_probs") and its vars from the scaled file, what
+    the device route's passthrough copies.
+    presence: images on which one detector fired are no longer answered on the host: they go into the batched launch with their
+    passthrough flag set and come back rescored row by row (never clustered), which is what the device route does with the pack
+    kernel's single-source flag - the two routes stay byte-identical."""
+    opts = O.FusionOptions.of(options, "late_fusion", len(dets), method[0], method[1], temperatures=temperatures, class_prior=class_prior,
+                              variance_scales=variance_scales, pool_weights=pool_weights, with_posterior=with_posterior,
+                              presence=presence, box_correlation=box_correlation)
+    dets = _calibrated(dets, opts, names, device)
+    with_posterior, presence, logp = opts.with_posterior, opts.presence, opts.logp
     n_img = len(dets[1]["image"]) if len(dets) > 1 else len(dets[0]["image"])      # the reference loops over det_2's images (:205)
     results = [None] * n_img
     batch, where, single = [], [], []
@@ -133,7 +120,7 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
                 results[i] += (np.asarray(x["log_prob"], dtype=np.float64).reshape(m, -1),
                                np.asarray(x["vars"], dtype=np.float64).reshape(m), np.ones(m, dtype=np.int32))
             continue
-        batch.append(infos if pool_weights is not None or presence is not None or box_correlation is not None else live)      # pack_infos skips the empty ones; the positions stay
+        batch.append(infos if opts.needs_row_source else live)      # pack_infos skips the empty ones; the positions stay
         where.append(i)
         single.append(int(len(live) == 1))          # presence only: the image's passthrough flag
     if batch:
@@ -142,23 +129,10 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
                 b, s, c = F.fusion(method, *live)
                 results[i] = (b.double().numpy(), s, c)
         else:
-            if presence is not None:
-                b, s, p, v, c, offs, lp, src = F.pack_infos(batch, device, with_log_probs=True, with_sources=True)
-                out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior,
-                                   pool_weights=pool_weights, row_source=src, with_posterior=with_posterior, presence=presence,
-                                   passthrough=torch.tensor(single, dtype=torch.int32, device=b.device), box_correlation=box_correlation)
-            elif logp and (pool_weights is not None or box_correlation is not None):
-                b, s, p, v, c, offs, lp, src = F.pack_infos(batch, device, with_log_probs=True, with_sources=True)
-                out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior,
-                                   pool_weights=pool_weights, row_source=src, with_posterior=with_posterior,
-                                   box_correlation=box_correlation)
-            elif logp:
-                b, s, p, v, c, offs, lp = F.pack_infos(batch, device, with_log_probs=True)
-                out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1], log_probs=lp, class_prior=class_prior,
-                                   with_posterior=with_posterior)
-            else:
-                b, s, p, v, c, offs = F.pack_infos(batch, device)
-                out = F.fuse_batch(b, s, p, v, c, offs, method[0], method[1])
+            b, s, p, v, c, offs, *rest = F.pack_infos(batch, device, with_log_probs=logp, with_sources=opts.needs_row_source)
+            out = F.fuse_batch(b, s, p, v, c, offs, log_probs=rest[0] if logp else None,
+                               row_source=rest[-1] if opts.needs_row_source else None, options=opts,
+                               passthrough=torch.tensor(single, dtype=torch.int32, device=b.device) if presence is not None else None)
             cnt = out["counts"].cpu().numpy()
             ob, os_, oc = out["boxes"].cpu().numpy(), out["scores"].cpu(), out["classes"].cpu()
             oh = offs.cpu().numpy()
@@ -233,7 +207,8 @@ def fused_device_to_j1(fused, file_names, image_ids):
     return out, dropped
 
 
-def fused_clusters(dets, box_fusion="v-avg", device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None):
+def fused_clusters(dets, box_fusion="v-avg", device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None,
+                   options=None):
     """The clusters "probEn-log" forms over dets (late_fusion's arguments), for the pooling-weight fit and its report: the images
     where two or more detectors fired go through ONE pe_proben_fuse_batch_pooled launch at w = 1 - which is probEn-log bit for bit -
     with out_cluster, and the clusters come back in CSR form, built with torch on the device.  Clustering and the fused boxes do not
@@ -242,18 +217,11 @@ def fused_clusters(dets, box_fusion="v-avg", device="cuda", temperatures=None, n
     [C+1] (cluster c = fused row c, image-major; its rows in packed order), boxes f64 [C, 4] (the fused boxes), box_offsets i32
     [B'+1] (the clusters of fused image j), and "images": the B' positions of the fused images in dets; "row_boxes" f64 [N, 4] and
     "row_vars" f64 [N] (the packed rows' boxes and scaled variances: what calibration.fit_box_correlation takes its residuals from)."""
-    from . import calibration
     D = len(dets)
-    if variance_scales is not None:
-        variance_scales = calibration.check_variance_scales(variance_scales, D, "fused_clusters")
-        dets = [calibration.scale_j1_vars(d, s) for d, s in zip(dets, variance_scales)]
-    temperatures = [1.0] * D if temperatures is None else list(temperatures)
-    if len(temperatures) != D:
-        raise ValueError(f"fused_clusters: {len(temperatures)} temperatures for {D} detectors")
-    names = names or [f"prediction file {k + 1}" for k in range(D)]
-    for d, n in zip(dets, names):
-        calibration.require_logits(d, n)
-    dets = [calibration.calibrate_j1(d, t, n, device, log_probs=True) for d, t, n in zip(dets, temperatures, names)]
+    opts = O.FusionOptions.of(options, "fused_clusters", D, F.LOGP, box_fusion, temperatures=temperatures, class_prior=class_prior,
+                              variance_scales=variance_scales)
+    opts = opts.replace(pool_weights=[1.0] * D, with_posterior=False, presence=None)       # w = 1, for "cluster"
+    dets = _calibrated(dets, opts, names, device)
     batch, where = [], []
     for i in range(len(dets[0]["image"])):
         infos = [_info(d, i) for d in dets]
@@ -263,8 +231,7 @@ def fused_clusters(dets, box_fusion="v-avg", device="cuda", temperatures=None, n
     if not batch:
         return None
     b, s, p, v, c, offs, lp, src = F.pack_infos(batch, device, with_log_probs=True, with_sources=True)
-    out = F.fuse_batch(b, s, p, v, c, offs, F.LOGP, box_fusion, log_probs=lp, class_prior=class_prior, pool_weights=[1.0] * D,
-                       row_source=src)
+    out = F.fuse_batch(b, s, p, v, c, offs, log_probs=lp, row_source=src, options=opts)
     dev = b.device
     cnt, in_off = out["counts"].long(), offs.long()
     assert int(cnt.min()) >= 0, "fused_clusters: an image over the row bound"       # max_rows is the longest image: cannot happen
@@ -284,7 +251,7 @@ def fused_clusters(dets, box_fusion="v-avg", device="cuda", temperatures=None, n
 
 
 def presence_rows(dets, box_fusion="v-avg", device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None,
-                  pool_weights=None, presence=None):
+                  pool_weights=None, presence=None, options=None):
     """Every fused row "probEn-log" forms over dets (late_fusion's arguments) under a presence table, for the table's fit and its
     report: all images on which a detector fired go through ONE pe_proben_fuse_batch_presence launch - images with one live detector
     with their passthrough flag set, as in late_fusion - with the posterior outputs and out_pattern.  presence None = the zero table:
@@ -292,18 +259,9 @@ def presence_rows(dets, box_fusion="v-avg", device="cuda", temperatures=None, na
     Returns None when no detector fired anywhere, else a dict of device tensors over the C fused rows, image-major: log_posterior f64
     [C, K+1], pattern i32 [C], boxes f64 [C, 4], box_offsets i32 [B'+1] (the rows of fused image j), and "images": the B' positions of
     the fused images in dets."""
-    from . import calibration
-    D = len(dets)
-    if variance_scales is not None:
-        variance_scales = calibration.check_variance_scales(variance_scales, D, "presence_rows")
-        dets = [calibration.scale_j1_vars(d, s) for d, s in zip(dets, variance_scales)]
-    temperatures = [1.0] * D if temperatures is None else list(temperatures)
-    if len(temperatures) != D:
-        raise ValueError(f"presence_rows: {len(temperatures)} temperatures for {D} detectors")
-    names = names or [f"prediction file {k + 1}" for k in range(D)]
-    for d, n in zip(dets, names):
-        calibration.require_logits(d, n)
-    dets = [calibration.calibrate_j1(d, t, n, device, log_probs=True) for d, t, n in zip(dets, temperatures, names)]
+    opts = O.FusionOptions.of(options, "presence_rows", len(dets), F.LOGP, box_fusion, temperatures=temperatures, class_prior=class_prior,
+                              variance_scales=variance_scales, pool_weights=pool_weights, presence=presence)
+    dets = _calibrated(dets, opts, names, device)
     batch, where, single = [], [], []
     for i in range(len(dets[0]["image"])):
         infos = [_info(d, i) for d in dets]
@@ -315,9 +273,8 @@ def presence_rows(dets, box_fusion="v-avg", device="cuda", temperatures=None, na
     if not batch:
         return None
     b, s, p, v, c, offs, lp, src = F.pack_infos(batch, device, with_log_probs=True, with_sources=True)
-    table = np.zeros((2 ** D, lp.shape[1])) if presence is None else presence
-    out = F.fuse_batch(b, s, p, v, c, offs, F.LOGP, box_fusion, log_probs=lp, class_prior=class_prior, pool_weights=pool_weights,
-                       row_source=src, with_posterior=True, presence=table,
+    table = np.zeros((2 ** len(dets), lp.shape[1])) if opts.presence is None else opts.presence
+    out = F.fuse_batch(b, s, p, v, c, offs, log_probs=lp, row_source=src, options=opts.replace(with_posterior=True, presence=table),
                        passthrough=torch.tensor(single, dtype=torch.int32, device=b.device))
     dev = b.device
     cnt, in_off = out["counts"].long(), offs.long()
@@ -333,22 +290,26 @@ def presence_rows(dets, box_fusion="v-avg", device="cuda", temperatures=None, na
 def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="", image_hw=None, device="cuda",
                                    img_folder="../../../Datasets/FLIR/val/thermal_8_bit/", temperatures=None, names=None,
                                    class_prior=None, variance_scales=None, pool_weights=None, fused_out=None, presence=None,
-                                   box_correlation=None):
+                                   box_correlation=None, options=None):
     """Same call as the reference (demo_probEn.py:198).  `image_hw`: {image_id: (H, W)} from the dataset
     json (the reference re-reads every thermal JPEG just for its shape); default 512 x 640 (FLIR).
     `img_folder`: the prefix the reference hard-codes into the `file_name` it hands to the evaluator (:200,271).
     `fused_out`: a list; when given ("probEn-log" only) the fusion keeps its posterior and the per-image 6-tuples of late_fusion are
     appended to it, for fused_to_j1 - the evaluator receives what it receives without it.
-    `presence`: late_fusion's presence table ("probEn-log" only).
-    `box_correlation`: late_fusion's correlation matrix (method[1] "c-avg", "probEn-log" only).
+    The option keywords, or `options` (options.FusionOptions; not both), are late_fusion's; with `options`, fused_out needs one
+    built with_posterior.
     What the evaluator receives per image is pinned by tests/golden/p5_cases.json (the reference's function run with a recording
     evaluator): tests/test_pipeline_gpu.py::test_late_fusion_driver_reproduces_the_references_records."""
+    dets = [det_1, det_2] + ([det_3] if det_3 else [])
+    opts = O.FusionOptions.of(options, "late_fusion", len(dets), method[0], method[1], temperatures=temperatures, class_prior=class_prior,
+                              variance_scales=variance_scales, pool_weights=pool_weights,
+                              with_posterior=fused_out is not None and options is None, presence=presence, box_correlation=box_correlation)
+    if fused_out is not None and not opts.with_posterior:
+        raise ValueError("apply_late_fusion_and_evaluate: fused_out needs options built with_posterior")
     evaluator.reset()
     print("Method: ", method)
     start = time.time()
-    dets = [det_1, det_2] + ([det_3] if det_3 else [])
-    fused = late_fusion(dets, method, device, temperatures, names, class_prior, variance_scales, pool_weights,
-                        with_posterior=fused_out is not None, presence=presence, box_correlation=box_correlation)
+    fused = late_fusion(dets, method, device, names=names, options=opts)
     if fused_out is not None:
         fused_out.extend(fused)
     for i, r in enumerate(fused):

@@ -10,6 +10,7 @@ import torch
 
 from . import fusion as F
 from . import layers as L
+from . import options as O
 
 
 class FramePairPipeline:
@@ -23,48 +24,16 @@ class FramePairPipeline:
 
     def __init__(self, models, score_fusion="probEn", box_fusion="v-avg", max_class=2, concurrent=True,
                  staggered=False, stagger_stage=4, fuse=True, temperatures=None, class_prior=None, variance_scales=None,
-                 pool_weights=None, with_posterior=False, presence=None, box_correlation=None):
+                 pool_weights=None, with_posterior=False, presence=None, box_correlation=None, options=None):
         self.models = list(models)
         self.fuse = fuse and len(self.models) > 1   # a single detector has nothing to fuse (configs[1])
-        self.method = (score_fusion, box_fusion)
         self.max_class = max_class
-        # one T per detector: ProbEn's rows are softmax(class_logits / T) (pe_proben_pack_logits); None = the detectors' own prob_score
-        self.temperatures = None if temperatures is None else [float(t) for t in temperatures]
-        if self.temperatures is not None and len(self.temperatures) != len(self.models):
-            raise ValueError(f"FramePairPipeline: {len(self.temperatures)} temperatures for {len(self.models)} detectors")
-        # score_fusion "probEn-log": ProbEn on log_softmax(class_logits / T) with the background column kept (pe_proben_pack_log_posteriors,
-        # pe_proben_fuse_batch_logp); T = 1 without temperatures; class_prior = K + 1 probabilities (background last) or None = uniform
-        F._check_mode(score_fusion, class_prior, "FramePairPipeline", pool_weights, with_posterior, presence, box_fusion, box_correlation)
-        # a matrix [D][D] (box_fusion "c-avg", "probEn-log" only): the correlation of the detectors' box errors (pe_box_gls_batch);
-        # validated here, uploaded at the first batch
-        if box_correlation is not None:
-            from .calibration import check_box_correlation
-            box_correlation = check_box_correlation(box_correlation, len(self.models), "FramePairPipeline: box_correlation")
-        self.box_correlation = box_correlation
-        self._box_correlation = None
-        # a table [2^D][K+1] ("probEn-log" only): presence evidence (pe_proben_fuse_batch_presence); validated here, uploaded at the first batch
-        if presence is not None:
-            from .calibration import check_presence
-            presence = check_presence(presence, len(self.models), None, "FramePairPipeline: presence")
-        self.presence = presence
-        self._presence = None
-        # "probEn-log" only: the fused rows keep their log-posterior, box variance and cluster size (pe_proben_fuse_batch_posterior)
-        self.with_posterior = bool(with_posterior)
-        # one w per detector ("probEn-log" only): the pooled rule (pe_proben_pack_pooled, pe_proben_fuse_batch_pooled); None = the product
-        from .calibration import check_pool_weights
-        self.pool_weights = check_pool_weights(pool_weights, len(self.models), "FramePairPipeline")
-        self._pool = None           # the weights on the device, uploaded at the first batch
-        self.logp = score_fusion == F.LOGP
-        if self.logp and self.temperatures is None:
-            self.temperatures = [1.0] * len(self.models)
-        if class_prior is not None:
-            from .calibration import check_class_prior
-            class_prior = check_class_prior(class_prior)
-        self.class_prior = class_prior
-        self._log_prior = None      # its log on the device, uploaded at the first batch
-        # one s per detector: the rows' variances are (double)var * s (pe_proben_pack_calibrated); None = the box heads' own
-        from .calibration import check_variance_scales
-        self.variance_scales = check_variance_scales(variance_scales, len(self.models), "FramePairPipeline")
+        # the fusion and its calibration (the keywords, or an options.FusionOptions, which documents them): validated here, uploaded at
+        # the first batch and kept by the object
+        self.options = O.FusionOptions.of(options, "FramePairPipeline", len(self.models), score_fusion, box_fusion, temperatures=temperatures,
+                                          class_prior=class_prior, variance_scales=variance_scales, pool_weights=pool_weights,
+                                          with_posterior=with_posterior, presence=presence, box_correlation=box_correlation)
+        self.method = (self.options.score_fusion, self.options.box_fusion)
         self.concurrent = concurrent and len(self.models) > 1
         self.staggered = staggered and self.concurrent and len(self.models) == 2
         self.stagger_stage = stagger_stage
@@ -152,20 +121,11 @@ class FramePairPipeline:
         return dets, fused
 
     def _fuse(self, dets):
-        # every option is None unless it was asked for (a class prior exists with "probEn-log" only), and None is fuse_detections' default
-        if self.class_prior is not None and self._log_prior is None:
-            self._log_prior = F.log_class_prior(self.class_prior, len(self.class_prior), dets[0]["scores"].device)
-        if self.pool_weights is not None and self._pool is None:
-            self._pool = F.pool_weight_tensor(self.pool_weights, len(self.pool_weights), dets[0]["scores"].device)
-        if self.box_correlation is not None and self._box_correlation is None:
-            from .calibration import box_correlation_tensor
-            self._box_correlation = box_correlation_tensor(self.box_correlation, len(self.models), dets[0]["scores"].device)
-        if self.presence is not None and self._presence is None:
-            from .calibration import presence_table
-            self._presence = presence_table(self.presence, len(self.models), self.presence.shape[1], dets[0]["scores"].device)
-        return F.fuse_detections(dets, self.method[0], self.method[1], max_class=self.max_class, temperatures=self.temperatures,
-                                 class_prior=self._log_prior, variance_scales=self.variance_scales, pool_weights=self._pool,
-                                 with_posterior=self.with_posterior, presence=self._presence, box_correlation=self._box_correlation)
+        return F.fuse_detections(dets, max_class=self.max_class, options=self.options)
+
+    temperatures = property(lambda self: self.options.temperatures)
+    class_prior = property(lambda self: self.options.class_prior)
+    logp = property(lambda self: self.options.logp)
 
 
 class HostFeeder:
