@@ -530,6 +530,18 @@ int pe_bneck64_pack(const void* w2, const void* w3, const void* wsc, const void*
 int pe_bneck64_f16(const void* t1, const void* shortcut_src, const void* packed, const float* bias2, const float* bias3,
                    const float* bias_sc, const float* bias1n, void* out, void* t1_next, int32_t N, int32_t H, int32_t W,
                    int32_t has_shortcut_conv, int32_t has_next, void* stream);
+/* The last convolution of an identity BottleneckBlock and the first of the NEXT block in ONE launch (res3:
+ * modeling/backbone/resnet.py:205-221 - `out = self.conv3(out)`, `out += shortcut`, `relu_` - followed by the next block's
+ * `out = self.conv1(x)`, `relu_` of the same rows):
+ *     out = relu(conv3(t2) + bias3 + residual);  t1_next = relu(conv1_next(out) + bias1_next)
+ * t2 [N,H,W,Cin] fp16 is the block's 3x3 output, residual [N,H,W,Cout] fp16 its input; w3 [Cout][Cin], w1_next [Cnext][Cout]
+ * fp16 and the fp32 biases in the layouts pe_conv2d_nhwc_f16 takes (BN folded).  out [N,H,W,Cout] and t1_next [N,H,W,Cnext]
+ * fp16 are both written, with the bits of the two pe_conv2d_nhwc_f16 launches it replaces; the re-read of `out` by the next
+ * conv1 never touches HBM.  One instantiation: Cin = 128, Cout = 512, Cnext = 128.  Any N, H, W; tensors < 2 GiB; out and
+ * t1_next must not overlap t2, residual or each other. */
+int pe_conv1x1_pair_f16(const void* t2, const void* w3, const float* bias3, const void* residual, const void* w1_next,
+                        const float* bias1_next, void* out, void* t1_next, int32_t N, int32_t H, int32_t W, int32_t Cin,
+                        int32_t Cout, int32_t Cnext, void* stream);
 int pe_conv_wd_pack_head(const void* head_weight, void* packed, int32_t rows, int32_t C, void* stream);
 int pe_conv3x3_wd_rpn_head_f16(const void* input, const void* packed_weight, const float* bias, const void* packed_head,
                                const float* head_bias16, float* head_out, int32_t N, int32_t H, int32_t W, int32_t Cin,

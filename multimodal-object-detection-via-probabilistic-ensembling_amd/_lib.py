@@ -46,6 +46,7 @@ SIGNATURES = {
     "pe_bneck64_packed_bytes": [c_int] * 2,
     "pe_bneck64_pack": [c_void_p] * 6,
     "pe_bneck64_f16": [c_void_p] * 9 + [c_int] * 5 + [c_void_p],
+    "pe_conv1x1_pair_f16": [c_void_p] * 8 + [c_int] * 6 + [c_void_p],
     "pe_conv_wd_pack_head": [c_void_p] * 2 + [c_int] * 2 + [c_void_p],
     "pe_conv3x3_wd_rpn_head_f16": [c_void_p] * 6 + [c_int] * 4 + [c_void_p],
     "pe_preprocess_pack": [c_void_p] + [c_int] * 11 + [c_void_p] * 4,

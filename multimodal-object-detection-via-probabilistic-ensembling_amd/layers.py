@@ -335,6 +335,36 @@ def bneck64(t1, shortcut_src, packed, bias2, bias3, bias_sc=None, bias1n=None, o
     return out, (t1_next if has_next else None)
 
 
+def conv1x1_pair_supported(cin, cout, cnext, pixels):
+    """True where conv1x1_pair takes a conv3 (cin -> cout) + next conv1 (cout -> cnext) pair: channel counts and the 2 GiB limit only."""
+    return (cin, cout, cnext) == (128, 512, 128) and pixels * cout * 2 < 2 ** 31
+
+
+def conv1x1_pair(t2, w3, b3, residual, w1n, b1n, out=None, t1_next=None):
+    """out = relu(conv3(t2) + b3 + residual) of an identity bottleneck block and t1_next = relu(conv1_next(out) + b1n) of the block
+    behind it, in one launch (csrc/conv1x1_pair.hip; the bits of the two conv2d_nhwc launches).  t2 [N,H,W,128], residual
+    [N,H,W,512] fp16; w3 [512,1,1,128], w1n [128,1,1,512] fp16.  Returns (out [N,H,W,512], t1_next [N,H,W,128])."""
+    _lib.require_cuda(t2, w3, b3, residual, w1n, b1n)
+    N, H, W, Cin = t2.shape
+    Cout, Cnext = w3.shape[0], w1n.shape[0]
+    assert t2.dtype == torch.float16 and residual.dtype == torch.float16 and tuple(residual.shape) == (N, H, W, Cout)
+    assert w3.numel() == Cout * Cin and w1n.numel() == Cnext * Cout and b3.numel() == Cout and b1n.numel() == Cnext
+    if out is None:
+        out = torch.empty((N, H, W, Cout), dtype=torch.float16, device=t2.device)
+    if t1_next is None:
+        t1_next = torch.empty((N, H, W, Cnext), dtype=torch.float16, device=t2.device)
+    st = _lib.lib().pe_conv1x1_pair_f16(_lib.ptr(t2), _lib.ptr(w3), _lib.ptr(b3), _lib.ptr(residual), _lib.ptr(w1n), _lib.ptr(b1n),
+                                        _lib.ptr(out), _lib.ptr(t1_next), N, H, W, Cin, Cout, Cnext, _lib.stream())
+    _lib.check(st, "pe_conv1x1_pair_f16")
+    if PROFILE is not None:
+        M = N * H * W
+        PROFILE.append({"variant": "conv1x1_pair_kernel", "shape": f"N{N} {H}x{W} {Cin}->{Cout}+id->{Cnext} f320",
+                        "flops": 2.0 * M * Cout * (Cin + Cnext),
+                        "bytes": float(M * 2 * (Cin + 2 * Cout + Cnext) + (w3.numel() + w1n.numel()) * 2),
+                        "replay": (lambda: conv1x1_pair(t2, w3, b3, residual, w1n, b1n, out=out, t1_next=t1_next))})
+    return out, t1_next
+
+
 def conv_wd_pack_head(weight2d):
     """[rows <= 16, 256] fp16 head weight (objectness + anchor deltas) -> the fragment-ordered 16 KiB block of the fused RPN head."""
     _lib.require_cuda(weight2d)

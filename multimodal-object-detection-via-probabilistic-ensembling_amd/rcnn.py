@@ -81,6 +81,7 @@ class GeneralizedRCNN:
         self.training = False
         self.use_wd = True   # weights-direct 3x3 kernel where the geometry allows (A/B switch)
         self.fuse_tails = True   # conv2 + conv3 of a bottleneck in one launch where conv2 is 256 wide (A/B switch)
+        self.fuse_pairs = True   # conv3 + shortcut of a 128 -> 512 block with the next block's conv1 in one launch: res3 (A/B switch)
         self.fuse_res2 = True    # res2 as the fused 64-wide bottleneck chain of csrc/bneck64.hip (A/B switch)
 
     def eval(self):
@@ -131,11 +132,22 @@ class GeneralizedRCNN:
                 if hook is not None:
                     hook(si + 2)
                 continue
+            t1 = None   # this block's conv1 output where the previous block's conv3 launch has already produced it
             for bi in range(nb):
                 p = f"{bu}.res{si + 2}.{bi}"
                 stride = 2 if (bi == 0 and si > 0) else 1
                 sc = self._conv(x, p + ".shortcut", kernel=1, stride=stride) if (p + ".shortcut") in self.w.convs else x
-                o = self._conv(x, p + ".conv1", kernel=1, stride=stride, relu=True)
+                o = t1 if t1 is not None else self._conv(x, p + ".conv1", kernel=1, stride=stride, relu=True)
+                t1 = None
+                pn = f"{bu}.res{si + 2}.{bi + 1}"
+                if self.fuse_pairs and bi + 1 < nb and (pn + ".shortcut") not in self.w.convs:
+                    # conv3 + shortcut + ReLU and the next block's (stride 1) conv1 + ReLU in one launch where the channel counts are
+                    # res3's: the block output is not read back from HBM.  Decided by the layers and the 2 GiB limit of 32-bit offsets, as for the tails.
+                    (w3, b3), (w1n, b1n) = self.w.convs[p + ".conv3"], self.w.convs[pn + ".conv1"]
+                    if L.conv1x1_pair_supported(w3.shape[-1], w3.shape[0], w1n.shape[0], o.shape[0] * o.shape[1] * o.shape[2]):
+                        o = self._conv(o, p + ".conv2", kernel=3, relu=True)
+                        x, t1 = L.conv1x1_pair(o, w3, b3, sc, w1n, b1n)
+                        continue
                 tail = self.w.tails.get(p) if self.use_wd and self.fuse_tails else None
                 if tail is not None and L.conv_wd_supported(3, 1, o.shape[1], o.shape[2], o.shape[3], 256) \
                         and o.shape[0] * o.shape[1] * o.shape[2] * self.w.convs[p + ".conv3"][0].shape[0] * 2 < 2 ** 31:
