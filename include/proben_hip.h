@@ -491,6 +491,10 @@ int pe_conv2d_nhwc_f16(const void* input, const void* weight, const float* bias,
  * output with row stride out_stride (0 = Cout).
  * ------------------------------------------------------------------------------------------- */
 int pe_conv_wd_supported(int32_t kernel, int32_t stride, int32_t H, int32_t W, int32_t Cin, int32_t Cout);
+/* ... and the batch: 1 where pe_conv3x3_wd_f16 (tail_cout 0), pe_conv3x3_wd_rpn_head_f16 (Cout 256, tail_cout 0) or
+ * pe_bottleneck_tail_wd_f16 (Cout 256) takes the launch - the geometry rule above, input and tail output < 2 GiB.  The entry
+ * points make their size checks through it; a caller that wants to fall back to pe_conv2d_nhwc_f16 asks it first. */
+int pe_conv_wd_launch_supported(int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t tail_cout);
 /* Two kernel generations stand behind pe_conv3x3_wd_f16, pe_conv3x3_wd_rpn_head_f16 and pe_bottleneck_tail_wd_f16: two waves per SIMD,
  * one tile per workgroup (csrc/conv_wd.h), and one wave per SIMD with 256 accumulators in the AGPRs and PERSISTENT workgroups
  * (csrc/conv_wd9.h: the pure 3x3 and the fused RPN head at image widths 64 / 128 / 256 from 128 tiles of 256 pixels on - the same
@@ -526,6 +530,7 @@ int pe_bottleneck_tail_wd_f16(const void* input, const void* packed_weight3x3, c
  * pe_bneck64_pack: w2 [64][3][3][64], w3 [256][64], wsc [256][64] or NULL, w1n [64][256] or NULL (fp16, the layouts
  * pe_conv2d_nhwc_f16 takes) -> one fragment-ordered stream of pe_bneck64_packed_bytes(wsc != NULL, w1n != NULL) bytes. */
 size_t pe_bneck64_packed_bytes(int32_t has_shortcut_conv, int32_t has_next);
+int pe_bneck64_supported(int32_t N, int32_t H, int32_t W);   /* 1 where pe_bneck64_f16 takes the size (its own check) */
 int pe_bneck64_pack(const void* w2, const void* w3, const void* wsc, const void* w1n, void* packed, void* stream);
 int pe_bneck64_f16(const void* t1, const void* shortcut_src, const void* packed, const float* bias2, const float* bias3,
                    const float* bias_sc, const float* bias1n, void* out, void* t1_next, int32_t N, int32_t H, int32_t W,
@@ -538,7 +543,9 @@ int pe_bneck64_f16(const void* t1, const void* shortcut_src, const void* packed,
  * fp16 and the fp32 biases in the layouts pe_conv2d_nhwc_f16 takes (BN folded).  out [N,H,W,Cout] and t1_next [N,H,W,Cnext]
  * fp16 are both written, with the bits of the two pe_conv2d_nhwc_f16 launches it replaces; the re-read of `out` by the next
  * conv1 never touches HBM.  One instantiation: Cin = 128, Cout = 512, Cnext = 128.  Any N, H, W; tensors < 2 GiB; out and
- * t1_next must not overlap t2, residual or each other. */
+ * t1_next must not overlap t2, residual or each other.  pe_conv1x1_pair_supported: 1 where the launch takes these channel
+ * counts and N * H * W = pixels (the check pe_conv1x1_pair_f16 itself makes). */
+int pe_conv1x1_pair_supported(int32_t Cin, int32_t Cout, int32_t Cnext, int64_t pixels);
 int pe_conv1x1_pair_f16(const void* t2, const void* w3, const float* bias3, const void* residual, const void* w1_next,
                         const float* bias1_next, void* out, void* t1_next, int32_t N, int32_t H, int32_t W, int32_t Cin,
                         int32_t Cout, int32_t Cnext, void* stream);

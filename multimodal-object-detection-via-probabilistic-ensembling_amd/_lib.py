@@ -39,6 +39,8 @@ SIGNATURES = {
     "pe_proben_fuse_batch": [c_void_p] * 8 + [c_int] * 5 + [c_double] * 3 + [c_void_p] * 5 + [c_void_p],
     "pe_conv2d_nhwc_f16": [c_void_p] * 5 + [c_int] * 14 + [c_void_p],
     "pe_conv_wd_supported": [c_int] * 6,
+    "pe_conv_wd_launch_supported": [c_int] * 6,
+    "pe_bneck64_supported": [c_int] * 3,
     "pe_conv_wd_pack_weights": [c_void_p] * 2 + [c_int] * 3 + [c_void_p],
     "pe_conv3x3_wd_f16": [c_void_p] * 4 + [c_int] * 7 + [c_void_p],
     "pe_conv_wd_pack_tail": [c_void_p] * 2 + [c_int] * 2 + [c_void_p],
@@ -46,6 +48,7 @@ SIGNATURES = {
     "pe_bneck64_packed_bytes": [c_int] * 2,
     "pe_bneck64_pack": [c_void_p] * 6,
     "pe_bneck64_f16": [c_void_p] * 9 + [c_int] * 5 + [c_void_p],
+    "pe_conv1x1_pair_supported": [c_int] * 3 + [ctypes.c_int64],
     "pe_conv1x1_pair_f16": [c_void_p] * 8 + [c_int] * 6 + [c_void_p],
     "pe_conv_wd_pack_head": [c_void_p] * 2 + [c_int] * 2 + [c_void_p],
     "pe_conv3x3_wd_rpn_head_f16": [c_void_p] * 6 + [c_int] * 4 + [c_void_p],
@@ -73,11 +76,11 @@ SIGNATURES = {
     "pe_boxhead_finalize": [c_void_p] + [c_int] * 7 + [c_void_p] * 18,
 }
 _RESTYPE = {"pe_last_error": ctypes.c_char_p, "pe_nms_scratch_bytes": ctypes.c_size_t, "pe_rpn_scratch_bytes": ctypes.c_size_t,
-             "pe_bneck64_packed_bytes": ctypes.c_size_t}
+             "pe_bneck64_packed_bytes": ctypes.c_size_t, "pe_test_conv_variant": ctypes.c_char_p}
 
 
 # exported for tests/ and scripts/ only (csrc/test_hooks.h) - not in include/proben_hip.h
-TEST_HOOKS = {"pe_test_set_conv_policy": [c_int, c_int], "pe_test_set_wd9_mode": [c_int], "pe_test_wd9_takes": [c_int] * 5, "pe_test_wd9_head_takes": [c_int] * 3, "pe_test_set_wd9_wgs": [c_int, c_int], "pe_test_set_ring_wgs": [c_int], "pe_test_set_roi_fast": [c_int], "pe_test_set_nms_presorted": [c_int]}
+TEST_HOOKS = {"pe_test_set_conv_policy": [c_int, c_int], "pe_test_get_conv_policy": [], "pe_test_conv_variant": [c_int] * 10 + [ctypes.c_int64], "pe_test_set_wd9_mode": [c_int], "pe_test_wd9_takes": [c_int] * 5, "pe_test_wd9_head_takes": [c_int] * 3, "pe_test_set_wd9_wgs": [c_int, c_int], "pe_test_set_ring_wgs": [c_int], "pe_test_set_roi_fast": [c_int], "pe_test_set_nms_presorted": [c_int]}
 
 
 class HipLibraryError(RuntimeError):
@@ -114,7 +117,7 @@ def test_hooks():
             getattr(L, name).argtypes, getattr(L, name).restype = args, ctypes.c_int
     for name, args in TEST_HOOKS.items():
         fn = getattr(L, name)
-        fn.argtypes, fn.restype = args, ctypes.c_int
+        fn.argtypes, fn.restype = args, _RESTYPE.get(name, ctypes.c_int)
     return L
 
 

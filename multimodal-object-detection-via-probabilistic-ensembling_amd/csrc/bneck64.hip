@@ -383,6 +383,10 @@ extern "C" int pe_bneck64_pack(const void* w2, const void* w3, const void* wsc, 
     return PE_OK;
 }
 
+extern "C" int pe_bneck64_supported(int32_t N, int32_t H, int32_t W) {
+    return N > 0 && H > 0 && W > 0 && (long long)N * H * W * 512 < (1ll << 31);      // the 256-channel tensors stay below 2 GiB
+}
+
 extern "C" int pe_bneck64_f16(const void* t1, const void* shortcut_src, const void* packed, const float* bias2, const float* bias3,
                               const float* bias_sc, const float* bias1n, void* out, void* t1_next, int32_t N, int32_t H, int32_t W,
                               int32_t has_shortcut_conv, int32_t has_next, void* stream) {
@@ -390,8 +394,7 @@ extern "C" int pe_bneck64_f16(const void* t1, const void* shortcut_src, const vo
     PE_CHECK_ARG(!has_shortcut_conv || bias_sc, "pe_bneck64_f16: shortcut convolution needs its bias");
     PE_CHECK_ARG(!has_next || (bias1n && t1_next), "pe_bneck64_f16: next conv1 needs its bias and output");
     PE_CHECK_ARG(N > 0 && H > 0 && W > 0, "pe_bneck64_f16: bad dims");
-    const long long M = (long long)N * H * W;
-    PE_CHECK_ARG(M * 512 < (1ll << 31), "pe_bneck64_f16: tensors larger than 2 GiB (32-bit buffer offsets)");
+    PE_CHECK_ARG(pe_bneck64_supported(N, H, W), "pe_bneck64_f16: tensors larger than 2 GiB (32-bit buffer offsets)");
     B64Args a{};
     a.t1 = (const _Float16*)t1; a.res = (const _Float16*)shortcut_src; a.wpk = (const _Float16*)packed;
     a.b2 = bias2; a.b3 = bias3; a.bsc = bias_sc; a.b1n = bias1n; a.out = (_Float16*)out; a.t1n = (_Float16*)t1_next;

@@ -332,15 +332,19 @@ int pair_cu_count() {
 
 }  // namespace
 
+extern "C" int pe_conv1x1_pair_supported(int32_t Cin, int32_t Cout, int32_t Cnext, int64_t pixels) {
+    return Cin == PR_K1 && Cout == PR_CY && Cnext == PR_C2 && pixels * PR_CY * 2 < (1ll << 31);
+}
+
 extern "C" int pe_conv1x1_pair_f16(const void* t2, const void* w3, const float* b3, const void* residual, const void* w1_next,
                                    const float* b1_next, void* out, void* t1_next, int32_t N, int32_t H, int32_t W, int32_t Cin,
                                    int32_t Cout, int32_t Cnext, void* stream) {
     PE_CHECK_ARG(t2 && w3 && b3 && residual && w1_next && b1_next && out && t1_next, "pe_conv1x1_pair_f16: null pointer");
     PE_CHECK_ARG(N > 0 && H > 0 && W > 0, "pe_conv1x1_pair_f16: bad dims");
-    PE_CHECK_ARG(Cin == PR_K1 && Cout == PR_CY && Cnext == PR_C2, "pe_conv1x1_pair_f16: channels must be 128 -> 512 -> 128 (got %d -> %d -> %d)",
-                 Cin, Cout, Cnext);
     const long long M = (long long)N * H * W;
-    PE_CHECK_ARG(M * PR_CY * 2 < (1ll << 31), "pe_conv1x1_pair_f16: tensors larger than 2 GiB (32-bit buffer offsets)");
+    PE_CHECK_ARG(pe_conv1x1_pair_supported(Cin, Cout, Cnext, M),
+                 "pe_conv1x1_pair_f16: channels must be 128 -> 512 -> 128 (got %d -> %d -> %d) and no tensor larger than 2 GiB (32-bit buffer offsets; "
+                 "got %lld pixels)", Cin, Cout, Cnext, M);
     // the next tile's inputs are fetched while this tile's outputs are stored: neither output may overlap an input tensor or the other output
     {
         const uintptr_t t2_b = (uintptr_t)M * PR_K1 * 2, y_b = (uintptr_t)M * PR_CY * 2, t1_b = (uintptr_t)M * PR_C2 * 2;

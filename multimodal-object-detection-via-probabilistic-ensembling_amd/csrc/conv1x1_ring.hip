@@ -29,6 +29,7 @@
 #include <atomic>
 
 #include "conv_common.h"
+#include "conv_route.h"
 
 namespace {
 
@@ -448,11 +449,8 @@ std::atomic<int> g_ring_wgs{256};
 std::atomic<int> g_ring_abl{0};
 #endif
 
-// true when the ring kernel can take the launch (the caller has checked: 1x1, stride 1, no residual, fp16 output)
-bool conv1x1_ring_eligible(int M, int K, int Cout, int cout_store, int out_stride, long long in_pixels) {
-    return Cout % RG_BN == 0 && cout_store == Cout && K % 64 == 0 && in_pixels * K * 2 < (1ll << 31) &&
-           (long long)Cout * K * 2 < (1ll << 31) && (long long)M * out_stride * 2 < (1ll << 31);
-}
+// which launches come here is csrc/conv_route.h's rule (whole RG_BN-channel tiles, K % 64 == 0, every tensor below 2 GiB)
+static_assert(route::RING_BN == RG_BN, "conv_route.h sends launches here by this kernel's channel tile");
 
 int conv1x1_ring_launch(const void* in, const void* wgt, const float* bias, const void* res, int res_mode, int resH, int resW, void* out, int N,
                         int H, int W, int Ho, int Wo, int stride, int M, int K, int Cout, int out_stride, int relu, hipStream_t st) {

@@ -18,6 +18,7 @@
 #include <atomic>
 
 #include "conv_common.h"
+#include "conv_route.h"
 
 namespace {
 
@@ -465,7 +466,6 @@ int launch2(const Conv2Args& a0, hipStream_t st) {
 }  // namespace
 
 namespace pe {
-bool conv1x1_ring_eligible(int M, int K, int Cout, int cout_store, int out_stride, long long in_pixels);
 int conv1x1_ring_launch(const void* in, const void* wgt, const float* bias, const void* res, int res_mode, int resH, int resW, void* out, int N,
                         int H, int W, int Ho, int Wo, int stride, int M, int K, int Cout, int out_stride, int relu, hipStream_t st);
 std::atomic<int> g_conv_tile256{329};  // bit 0: 256-row tiles for big 3x3 launches, bit 1: for big 1x1 launches, bit 2: two-stage 1x1 pipeline,
@@ -473,7 +473,12 @@ std::atomic<int> g_conv_tile256{329};  // bit 0: 256-row tiles for big 3x3 launc
                                       // bit 5 / 6: the persistent loader / consumer 1x1 kernel for res4 conv1 / for every eligible residual-free launch,
                                       // bit 8: ... for the residual layers as well
 std::atomic<int> g_conv3x3_reuse{1};  // 0: the generic per-tap 3x3 kernel instead of the kw-reuse one (A/B measurements)
-// called from pe_conv2d_nhwc_f16 (conv_igemm.hip) for the 1x1 / 3x3 cases
+
+static route::Kernel conv_route(const route::ConvShape& s) {
+    return route::choose(s, g_conv_tile256.load(std::memory_order_relaxed), g_conv3x3_reuse.load(std::memory_order_relaxed));
+}
+
+// called from pe_conv2d_nhwc_f16 (conv_igemm.hip) for the 1x1 / 3x3 cases; which kernel takes the launch is csrc/conv_route.h's rule
 int conv2_dispatch(const void* in, const void* wgt, const float* bias, const void* res, void* out, int N, int H, int W,
                    int Cin, int Cout, int Ho, int Wo, int K, int M, int mode3x3, int stride, int relu, int res_mode,
                    int resH, int resW, int out_f32, int cout_store, int out_stride, hipStream_t st) {
@@ -482,39 +487,29 @@ int conv2_dispatch(const void* in, const void* wgt, const float* bias, const voi
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.stride = stride; a.M = M; a.K = K;
     a.relu = relu; a.res_mode = res_mode; a.resH = resH; a.resW = resW; a.out_f32 = out_f32;
     a.cout_store = cout_store; a.out_stride = out_stride;
-    const int policy = g_conv_tile256.load(std::memory_order_relaxed);
-    const bool narrow = Cout <= 64;
-    // persistent loader / consumer 1x1 kernel (csrc/conv1x1_ring.hip; bit-identical results): policy bit 5 = the long-K, 256-output
-    // layers (res4 conv1), bit 6 = every eligible launch (residual-free, fp16 out, bias, Cout % 256 == 0; K >= 512 at stride 1, the
-    // stride-2 shortcut convolutions from K = 256).  Chosen by channel counts and stride only, never by the batch.
-    if ((policy & 96) && !mode3x3 && (stride == 1 || stride == 2) && !out_f32 && bias && conv1x1_ring_eligible(M, K, Cout, cout_store, out_stride, (long long)N * H * W)) {
-        bool take;
-        if (!(policy & 64)) take = stride == 1 && !res_mode && K >= 1024 && Cout == 256;
-        else if (res_mode) take = stride == 1 && K >= 128 && (policy & 256) && (long long)M * Cout * 2 < (1ll << 31);      // bit 8: the residual layers too (conv3 of res3 / res5, FPN laterals)
-        else take = K >= (stride == 1 ? 512 : 256);
-        if (take) return conv1x1_ring_launch(in, wgt, bias, res, res_mode, resH, resW, out, N, H, W, Ho, Wo, stride, M, K, Cout, out_stride, relu, st);
+    switch (conv_route({M, K, Cout, mode3x3, stride, res_mode, out_f32, bias != nullptr, cout_store, out_stride, (long long)N * H * W})) {
+        case route::RING:
+            return conv1x1_ring_launch(in, wgt, bias, res, res_mode, resH, resW, out, N, H, W, Ho, Wo, stride, M, K, Cout, out_stride, relu, st);
+        case route::BIG_3X3: return launch_big<MODE_3X3>(a, st);
+        case route::BIG_1X1: return launch_big<MODE_1X1>(a, st);
+        case route::RB_128_64: return launch3x3r<128, 64>(a, st);
+        case route::RB_256_128: return launch3x3r<256, 128>(a, st);
+        case route::RB_128_128: return launch3x3r<128, 128>(a, st);
+        case route::IGEMM2_128_64_3X3: return launch2<128, 64, MODE_3X3>(a, st);
+        case route::IGEMM2_128_128_3X3: return launch2<128, 128, MODE_3X3>(a, st);
+        case route::IGEMM2_128_64_1X1: return launch2<128, 64, MODE_1X1>(a, st);
+        case route::IGEMM2_256_128_1X1_2STAGE: return launch2<256, 128, MODE_1X1, 2>(a, st);
+        case route::IGEMM2_128_128_1X1_2STAGE: return launch2<128, 128, MODE_1X1, 2>(a, st);
+        case route::IGEMM2_256_128_1X1: return launch2<256, 128, MODE_1X1>(a, st);
+        case route::IGEMM2_128_128_1X1: return launch2<128, 128, MODE_1X1>(a, st);
+        case route::STEM: break;      // pe_conv2d_nhwc_f16 launches the stem itself
     }
-    // 256 x 256 two-stage kernel: fp16 output, whole 256-channel tiles, a grid that fills the 256 CUs
-    // (measured r01: +24 % on the K = 12544 FC GEMM, neutral-to-negative on the convolutions -> long-K GEMMs only;
-    //  policy bit 4 forces it everywhere it applies, for A/B runs)
-    if ((policy & 8) && !out_f32 && Cout % 256 == 0 && cout_store == Cout &&
-        (long long)pe::ceil_div(M, 256) * (Cout / 256) >= 224 && ((policy & 16) || (!mode3x3 && K >= 4096)))
-        return mode3x3 ? launch_big<MODE_3X3>(a, st) : launch_big<MODE_1X1>(a, st);
-    if (mode3x3 && g_conv3x3_reuse.load(std::memory_order_relaxed)) {
-        if (narrow) return launch3x3r<128, 64>(a, st);
-        // 256-row tiles (8 waves) halve the weight-tile traffic per flop; keep 128 when the grid would not fill the chip
-        const bool big = (policy & 1) && (long long)pe::ceil_div(M, 256) * pe::ceil_div(Cout, 128) >= 512;
-        return big ? launch3x3r<256, 128>(a, st) : launch3x3r<128, 128>(a, st);
-    }
-    if (mode3x3) return narrow ? launch2<128, 64, MODE_3X3>(a, st) : launch2<128, 128, MODE_3X3>(a, st);
-    if (narrow) return launch2<128, 64, MODE_1X1>(a, st);
-    const bool big1 = (policy & 2) && (long long)pe::ceil_div(M, 256) * pe::ceil_div(Cout, 128) >= 512;
-    if (policy & 4) return big1 ? launch2<256, 128, MODE_1X1, 2>(a, st) : launch2<128, 128, MODE_1X1, 2>(a, st);
-    return big1 ? launch2<256, 128, MODE_1X1>(a, st) : launch2<128, 128, MODE_1X1>(a, st);
+    pe::set_error("pe_conv2d_nhwc_f16: no kernel for this launch");
+    return PE_ERR_UNSUPPORTED;
 }
 }  // namespace pe
 
-// Measurement / test hook - deliberately NOT part of include/proben_hip.h (csrc/test_hooks.h): selects among kernels that all
+// Measurement / test hooks - deliberately NOT part of include/proben_hip.h (csrc/test_hooks.h).  The policy selects among kernels that all
 // compute the same convolution, so that tests can cover every variant and scripts/ablate_conv.py can A/B them.
 extern "C" int pe_test_set_conv_policy(int tile_bits, int reuse3x3) {
     pe::g_conv_tile256 = tile_bits;
@@ -522,3 +517,12 @@ extern "C" int pe_test_set_conv_policy(int tile_bits, int reuse3x3) {
     return PE_OK;
 }
 
+extern "C" int pe_test_get_conv_policy() { return pe::g_conv_tile256.load(std::memory_order_relaxed); }
+
+// arguments as pe_conv2d_nhwc_f16 takes them (kernel 1 | 3 | 7; cout_store / out_stride 0 = Cout; in_pixels 0 = M)
+extern "C" const char* pe_test_conv_variant(int M, int K, int Cout, int kernel, int stride, int res_mode, int out_f32, int has_bias,
+                                            int cout_store, int out_stride, long long in_pixels) {
+    if (kernel == 7) return pe::route::name(pe::route::STEM);
+    return pe::route::name(pe::conv_route({M, K, Cout, kernel == 3, stride, res_mode, out_f32, has_bias, cout_store > 0 ? cout_store : Cout,
+                                           out_stride > 0 ? out_stride : Cout, in_pixels > 0 ? in_pixels : M}));
+}

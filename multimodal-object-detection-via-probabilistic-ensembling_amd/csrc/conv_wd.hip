@@ -20,6 +20,11 @@ extern "C" int pe_conv_wd_supported(int32_t kernel, int32_t stride, int32_t H, i
     return wd::wd3x3_geometry(W, 128, &seg, &nseg) ? 1 : 0;
 }
 
+extern "C" int pe_conv_wd_launch_supported(int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t tail_cout) {
+    const long long M = (long long)N * H * W;
+    return N > 0 && pe_conv_wd_supported(3, 1, H, W, Cin, Cout) && M * Cin * 2 < (1ll << 31) && M * tail_cout * 2 < (1ll << 31);
+}
+
 extern "C" int pe_conv_wd_pack_weights(const void* weight, void* packed, int32_t Cout, int32_t Cin, int32_t kernel,
                                        void* stream) {
     PE_CHECK_ARG(weight && packed, "pe_conv_wd_pack_weights: null pointer");
@@ -44,7 +49,7 @@ extern "C" int pe_conv3x3_wd_f16(const void* input, const void* packed_weight, c
         return PE_ERR_UNSUPPORTED;
     }
     const long long M = (long long)N * H * W;
-    PE_CHECK_ARG(M * Cin * 2 < (1ll << 31), "pe_conv3x3_wd_f16: input larger than 2 GiB (32-bit buffer offsets)");
+    PE_CHECK_ARG(pe_conv_wd_launch_supported(N, H, W, Cin, Cout, 0), "pe_conv3x3_wd_f16: input larger than 2 GiB (32-bit buffer offsets)");
     const int os = out_stride > 0 ? out_stride : Cout;
     PE_CHECK_ARG(os % 8 == 0, "pe_conv3x3_wd_f16: out_stride must be a multiple of 8");
     pe::ConvWdArgs a{};
@@ -81,7 +86,7 @@ extern "C" int pe_conv3x3_wd_rpn_head_f16(const void* input, const void* packed_
         return PE_ERR_UNSUPPORTED;
     }
     const long long M = (long long)N * H * W;
-    PE_CHECK_ARG(M * Cin * 2 < (1ll << 31), "pe_conv3x3_wd_rpn_head_f16: input larger than 2 GiB (32-bit buffer offsets)");
+    PE_CHECK_ARG(pe_conv_wd_launch_supported(N, H, W, Cin, 256, 0), "pe_conv3x3_wd_rpn_head_f16: input larger than 2 GiB (32-bit buffer offsets)");
     pe::ConvWdArgs a{};
     a.in = (const _Float16*)input; a.wpk = (const _Float16*)packed_weight; a.bias = bias; a.out = nullptr;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = 256; a.M = (int)M; a.relu = 1; a.out_stride = 256;
@@ -116,7 +121,7 @@ extern "C" int pe_bottleneck_tail_wd_f16(const void* input, const void* packed_w
         return PE_ERR_UNSUPPORTED;
     }
     const long long M = (long long)N * H * W;
-    PE_CHECK_ARG(M * tail_cout * 2 < (1ll << 31) && M * Cin * 2 < (1ll << 31), "pe_bottleneck_tail_wd_f16: tensors larger than 2 GiB (32-bit buffer offsets)");
+    PE_CHECK_ARG(pe_conv_wd_launch_supported(N, H, W, Cin, 256, tail_cout), "pe_bottleneck_tail_wd_f16: tensors larger than 2 GiB (32-bit buffer offsets)");
     pe::ConvWdArgs a{};
     a.in = (const _Float16*)input; a.wpk = (const _Float16*)packed_weight3x3; a.bias = bias3x3; a.out = nullptr;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = 256; a.M = (int)M; a.relu = 1; a.out_stride = 256;

@@ -13,6 +13,13 @@ extern "C" {
  *                               256: ... and for the stride-1 layers WITH a residual (both modes) from K = 128
  *   reuse3x3 (default 1): 1 = kw-reuse 3x3 kernel, 0 = generic per-tap 3x3 kernel */
 int pe_test_set_conv_policy(int tile_bits, int reuse3x3);
+/* the tile_bits in force */
+int pe_test_get_conv_policy(void);
+/* Name of the kernel (as rocprofv3 prints it) that pe_conv2d_nhwc_f16 launches for these arguments under the policy in force: the answer
+ * of csrc/conv_route.h's choose(), the function the dispatch itself switches over.  M = N * Ho * Wo output pixels, K = Cin (ignored
+ * for kernel 3 and 7), kernel 1 | 3 | 7; cout_store / out_stride 0 = Cout, in_pixels (N * H * W) 0 = M.  Touches no device. */
+const char* pe_test_conv_variant(int M, int K, int Cout, int kernel, int stride, int res_mode, int out_f32, int has_bias, int cout_store,
+                                 int out_stride, long long in_pixels);
 /* Which generation of the weights-direct kernels takes a launch.  Bit mask (default 1 | 8; a negative mode restores the default;
  * bit 2 was round 4's fused tail on this structure, now scripts/lab/conv_wd9_tail.h):
  *   1 = pure 3x3: conv_wd9.h for launches of >= 128 tiles of 256 pixels (same bits as conv_wd.h)   2 = ... whenever the geometry allows

@@ -12,6 +12,12 @@ _scratch = {}
 PROFILE = None  # bench.py's roofline leg sets this to a list and gets one record per conv launch
 
 
+def _record(variant, shape, flops, nbytes, replay):
+    """One PROFILE record per conv launch: kernel name as rocprofv3 prints it, shape (bench.py keys its labels on substrings of it),
+    algorithmic flops and bytes, and a closure that issues the same launch again."""
+    PROFILE.append({"variant": variant, "shape": shape, "flops": flops, "bytes": float(nbytes), "replay": replay})
+
+
 def _get_scratch(nbytes, device):
     key = (device.index, torch.cuda.current_stream().cuda_stream)
     buf = _scratch.get(key)
@@ -214,22 +220,26 @@ def conv2d_nhwc(x, weight, bias, *, kernel, stride=1, relu=False, residual=None,
         variant = conv_variant_name(N * Ho * Wo, Cout, kernel, Cin if kernel == 1 else 0, stride=stride, residual_mode=residual_mode,
                                     out_f32=out_f32, has_bias=bias is not None, cout_store=cout_store, out_stride=out_stride, in_pixels=N * H * W)
         cin_real = 3 if kernel == 7 else Cin
-        shape = f"N{N} {H}x{W} Cin{Cin} Cout{Cout} k{kernel} s{stride} res{residual_mode} f32{int(out_f32)}"
         M = N * Ho * Wo
-        in_elems = M * Cin if kernel == 1 else N * H * W * (3 if kernel == 7 else Cin)   # a strided 1x1 reads only its samples
+        in_elems = M * Cin if kernel == 1 else N * H * W * cin_real   # a strided 1x1 reads only its samples
         nbytes = (in_elems * 2 + weight.numel() * 2 + M * (cout_store or Cout) * (4 if out_f32 else 2)
                   + (M * Cout * 2 if residual_mode == 1 else (residual.numel() * 2 if residual_mode == 2 else 0)))
-        PROFILE.append({"variant": variant, "shape": shape, "flops": 2.0 * N * Ho * Wo * Cout * kernel * kernel * cin_real,
-                        "bytes": float(nbytes),
-                        "replay": (lambda: conv2d_nhwc(x, weight, bias, kernel=kernel, stride=stride, relu=relu, residual=residual,
-                                                       residual_mode=residual_mode, out=out, out_f32=out_f32,
-                                                       cout_store=cout_store, out_stride=out_stride, cout=cout))})
+        _record(variant, f"N{N} {H}x{W} Cin{Cin} Cout{Cout} k{kernel} s{stride} res{residual_mode} f32{int(out_f32)}",
+                2.0 * M * Cout * kernel * kernel * cin_real, nbytes,
+                lambda: conv2d_nhwc(x, weight, bias, kernel=kernel, stride=stride, relu=relu, residual=residual, residual_mode=residual_mode,
+                                    out=out, out_f32=out_f32, cout_store=cout_store, out_stride=out_stride, cout=cout))
     return out
 
 
 def conv_wd_supported(kernel, stride, H, W, Cin, Cout):
     """True when the weights-direct kernel (csrc/conv_wd.h) takes this geometry."""
     return bool(_lib.lib().pe_conv_wd_supported(int(kernel), int(stride), int(H), int(W), int(Cin), int(Cout)))
+
+
+def conv_wd_takes(x, cout, tail_cout=0):
+    """True when conv3x3_wd (cout 256: conv3x3_wd_rpn_head / bottleneck_tail_wd) takes x: conv_wd_supported's geometry and the 2 GiB limits."""
+    N, H, W, Cin = x.shape
+    return bool(_lib.lib().pe_conv_wd_launch_supported(N, H, W, Cin, int(cout), int(tail_cout)))
 
 
 def conv_wd_pack(weight):
@@ -256,10 +266,9 @@ def conv3x3_wd(x, packed, bias, cout, *, relu=False, out=None, out_stride=0):
     if PROFILE is not None:
         M = N * H * W
         wd9 = _lib.test_hooks().pe_test_wd9_takes(N, H, W, Cin, cout)      # which kernel generation took the launch (same bits either way)
-        PROFILE.append({"variant": "conv3x3_wd9_kernel<8, 4, 5, 0>" if wd9 else "conv3x3_wd_kernel<1, 4, 4, 4, 0, 0>",
-                        "shape": f"N{N} {H}x{W} Cin{Cin} Cout{cout} k3 s1 res0 f320",
-                        "flops": 2.0 * M * cout * 9 * Cin, "bytes": float(M * Cin * 2 + cout * 9 * Cin * 2 + M * cout * 2),
-                        "replay": (lambda: conv3x3_wd(x, packed, bias, cout, relu=relu, out=out, out_stride=out_stride))})
+        _record("conv3x3_wd9_kernel<8, 4, 5, 0>" if wd9 else "conv3x3_wd_kernel<1, 4, 4, 4, 0, 0>", f"N{N} {H}x{W} Cin{Cin} Cout{cout} k3 s1 res0 f320",
+                2.0 * M * cout * 9 * Cin, M * Cin * 2 + cout * 9 * Cin * 2 + M * cout * 2,
+                lambda: conv3x3_wd(x, packed, bias, cout, relu=relu, out=out, out_stride=out_stride))
     return out
 
 
@@ -287,11 +296,10 @@ def bottleneck_tail_wd(x, packed3x3, bias3x3, packed_tail, tail_bias, residual, 
     _lib.check(st, "pe_bottleneck_tail_wd_f16")
     if PROFILE is not None:
         M = N * H * W
-        PROFILE.append({"variant": "conv3x3_wd_kernel<1, 4, 4, 4, 0, 2>",
-                        "shape": f"N{N} {H}x{W} Cin{Cin} Cout256->{tail_cout} k3+k1 s1 res{int(residual is not None)} f320",
-                        "flops": 2.0 * M * 256 * 9 * Cin + 2.0 * M * tail_cout * 256,
-                        "bytes": float(M * Cin * 2 + 256 * 9 * Cin * 2 + tail_cout * 256 * 2 + M * tail_cout * 2 * (2 if residual is not None else 1)),
-                        "replay": (lambda: bottleneck_tail_wd(x, packed3x3, bias3x3, packed_tail, tail_bias, residual, tail_cout, out=out))})
+        _record("conv3x3_wd_kernel<1, 4, 4, 4, 0, 2>", f"N{N} {H}x{W} Cin{Cin} Cout256->{tail_cout} k3+k1 s1 res{int(residual is not None)} f320",
+                2.0 * M * 256 * 9 * Cin + 2.0 * M * tail_cout * 256,
+                M * Cin * 2 + 256 * 9 * Cin * 2 + tail_cout * 256 * 2 + M * tail_cout * 2 * (2 if residual is not None else 1),
+                lambda: bottleneck_tail_wd(x, packed3x3, bias3x3, packed_tail, tail_bias, residual, tail_cout, out=out))
     return out
 
 
@@ -306,6 +314,11 @@ def bneck64_pack(w2, w3, wsc=None, w1n=None):
     packed = torch.empty(nbytes // 2, dtype=torch.float16, device=w2.device)
     _lib.check(_lib.lib().pe_bneck64_pack(_lib.ptr(w2), _lib.ptr(w3), _lib.ptr(wsc), _lib.ptr(w1n), _lib.ptr(packed), _lib.stream()), "pe_bneck64_pack")
     return packed
+
+
+def bneck64_supported(N, H, W):
+    """True where bneck64 takes a stage of this size (tensors below 2 GiB)."""
+    return bool(_lib.lib().pe_bneck64_supported(int(N), int(H), int(W)))
 
 
 def bneck64(t1, shortcut_src, packed, bias2, bias3, bias_sc=None, bias1n=None, out=None, t1_next=None):
@@ -328,16 +341,16 @@ def bneck64(t1, shortcut_src, packed, bias2, bias3, bias_sc=None, bias1n=None, o
     _lib.check(st, "pe_bneck64_f16")
     if PROFILE is not None:
         M = N * H * W
-        PROFILE.append({"variant": f"bneck64_kernel<{int(has_sc)}, {int(has_next)}>", "shape": f"N{N} {H}x{W} 64->64->256{'+sc' if has_sc else '+id'}{'->64' if has_next else ''} f320",
-                        "flops": 2.0 * M * 64 * (576 + 256 + (64 if has_sc else 0) + (256 if has_next else 0)),
-                        "bytes": float(M * 2 * (64 + (64 if has_sc else 256) + 256 + (64 if has_next else 0)) + packed.numel() * 2),
-                        "replay": (lambda: bneck64(t1, shortcut_src, packed, bias2, bias3, bias_sc, bias1n, out=out, t1_next=t1_next))})
+        _record(f"bneck64_kernel<{int(has_sc)}, {int(has_next)}>", f"N{N} {H}x{W} 64->64->256{'+sc' if has_sc else '+id'}{'->64' if has_next else ''} f320",
+                2.0 * M * 64 * (576 + 256 + (64 if has_sc else 0) + (256 if has_next else 0)),
+                M * 2 * (64 + (64 if has_sc else 256) + 256 + (64 if has_next else 0)) + packed.numel() * 2,
+                lambda: bneck64(t1, shortcut_src, packed, bias2, bias3, bias_sc, bias1n, out=out, t1_next=t1_next))
     return out, (t1_next if has_next else None)
 
 
 def conv1x1_pair_supported(cin, cout, cnext, pixels):
     """True where conv1x1_pair takes a conv3 (cin -> cout) + next conv1 (cout -> cnext) pair: channel counts and the 2 GiB limit only."""
-    return (cin, cout, cnext) == (128, 512, 128) and pixels * cout * 2 < 2 ** 31
+    return bool(_lib.lib().pe_conv1x1_pair_supported(int(cin), int(cout), int(cnext), int(pixels)))
 
 
 def conv1x1_pair(t2, w3, b3, residual, w1n, b1n, out=None, t1_next=None):
@@ -358,10 +371,9 @@ def conv1x1_pair(t2, w3, b3, residual, w1n, b1n, out=None, t1_next=None):
     _lib.check(st, "pe_conv1x1_pair_f16")
     if PROFILE is not None:
         M = N * H * W
-        PROFILE.append({"variant": "conv1x1_pair_kernel", "shape": f"N{N} {H}x{W} {Cin}->{Cout}+id->{Cnext} f320",
-                        "flops": 2.0 * M * Cout * (Cin + Cnext),
-                        "bytes": float(M * 2 * (Cin + 2 * Cout + Cnext) + (w3.numel() + w1n.numel()) * 2),
-                        "replay": (lambda: conv1x1_pair(t2, w3, b3, residual, w1n, b1n, out=out, t1_next=t1_next))})
+        _record("conv1x1_pair_kernel", f"N{N} {H}x{W} {Cin}->{Cout}+id->{Cnext} f320", 2.0 * M * Cout * (Cin + Cnext),
+                M * 2 * (Cin + 2 * Cout + Cnext) + (w3.numel() + w1n.numel()) * 2,
+                lambda: conv1x1_pair(t2, w3, b3, residual, w1n, b1n, out=out, t1_next=t1_next))
     return out, t1_next
 
 
@@ -388,10 +400,9 @@ def conv3x3_wd_rpn_head(x, packed, bias, packed_head, head_bias16, out=None):
     if PROFILE is not None:
         M = N * H * W
         wd9 = _lib.test_hooks().pe_test_wd9_head_takes(N, H, W)
-        PROFILE.append({"variant": "conv3x3_wd9_kernel<8, 4, 9, 1>" if wd9 else "conv3x3_wd_kernel<1, 4, 4, 4, 0, 1>",
-                        "shape": f"N{N} {H}x{W} Cin{Cin} Cout256+head k3 s1 res0 f321",
-                        "flops": 2.0 * M * 256 * 9 * Cin + 2.0 * M * 15 * 256, "bytes": float(M * Cin * 2 + 256 * 9 * Cin * 2 + M * 15 * 4),
-                        "replay": (lambda: conv3x3_wd_rpn_head(x, packed, bias, packed_head, head_bias16, out=out))})
+        _record("conv3x3_wd9_kernel<8, 4, 9, 1>" if wd9 else "conv3x3_wd_kernel<1, 4, 4, 4, 0, 1>", f"N{N} {H}x{W} Cin{Cin} Cout256+head k3 s1 res0 f321",
+                2.0 * M * 256 * 9 * Cin + 2.0 * M * 15 * 256, M * Cin * 2 + 256 * 9 * Cin * 2 + M * 15 * 4,
+                lambda: conv3x3_wd_rpn_head(x, packed, bias, packed_head, head_bias16, out=out))
     return out
 
 
@@ -399,24 +410,10 @@ DEFAULT_CONV_POLICY = 329   # tile_bits of csrc/test_hooks.h pe_test_set_conv_po
 
 
 def conv_variant_name(M, Cout, kernel, K=0, *, stride=1, residual_mode=0, out_f32=False, has_bias=True, cout_store=0, out_stride=0, in_pixels=None):
-    """Name of the kernel pe_conv2d_nhwc_f16 dispatches to under the DEFAULT policy (mirrors conv2_dispatch in
-    csrc/conv_igemm2.hip; matches the rocprofv3 kernel names)."""
-    bn = 64 if Cout <= 64 else 128
-    if kernel == 7:
-        return "conv_igemm_kernel<128, 64, 2>"          # 7x7 stem, register-staged kernel
-    if kernel == 1:
-        ring = (stride in (1, 2) and not out_f32 and has_bias and Cout % 256 == 0
-                and (K >= (512 if stride == 1 else 256) if residual_mode == 0 else (stride == 1 and K >= 128 and M * Cout * 2 < 2 ** 31))
-                and (cout_store or Cout) == Cout and (in_pixels or M) * K * 2 < 2 ** 31 and Cout * K * 2 < 2 ** 31 and M * (out_stride or Cout) * 2 < 2 ** 31)
-        if ring:
-            return "conv1x1_ring_kernel"                # persistent loader / consumer kernel (csrc/conv1x1_ring.hip)
-        if K >= 4096 and Cout % 256 == 0 and ((M + 255) // 256) * (Cout // 256) >= 224:
-            return "conv_big_kernel<0>"                 # 256x256 two-stage kernel (long-K GEMM)
-        return f"conv_igemm2_kernel<128, {bn}, 0, 1>"   # LDS-DMA 1x1 / GEMM
-    if bn == 64:
-        return "conv3x3rb_kernel<128, 64>"
-    big = ((M + 255) // 256) * ((Cout + 127) // 128) >= 512
-    return f"conv3x3rb_kernel<{256 if big else 128}, 128>"  # kw-reuse 3x3, double-buffered weight tile
+    """Name of the kernel pe_conv2d_nhwc_f16 launches for these arguments under the policy in force, as rocprofv3 prints it: the
+    library's own answer (csrc/conv_route.h, through pe_test_conv_variant), not a restatement of its rule."""
+    return _lib.test_hooks().pe_test_conv_variant(int(M), int(K), int(Cout), int(kernel), int(stride), int(residual_mode), int(out_f32),
+                                                  int(has_bias), int(cout_store), int(out_stride), int(in_pixels or 0)).decode()
 
 
 def linear_f16(x, weight, bias, *, relu=False, out_f32=False, cout_store=0, out_stride=0):

@@ -21,7 +21,7 @@ from . import _lib
 from . import layers as L
 from .data import PairFrames
 from .structures import Boxes, Instances
-from .weights import STAGE_BLOCKS, PackedDetector
+from .weights import PackedDetector
 
 SCALE_CLAMP = math.log(1000.0 / 16)
 
@@ -100,68 +100,71 @@ class GeneralizedRCNN:
         return self
 
     # ------------------------------------------------------------------ stages
-    def _conv(self, x, name, **kw):
-        w, b = self.w.convs[name]
-        if kw.get("kernel") == 3 and name in self.w.wd and self.use_wd and kw.get("residual") is None and x.numel() * 2 < 2 ** 31 \
-                and L.conv_wd_supported(3, 1, x.shape[1], x.shape[2], x.shape[3], w.shape[0]):
-            return L.conv3x3_wd(x, self.w.wd[name], b, w.shape[0], relu=kw.get("relu", False), out=kw.get("out"),
-                                out_stride=kw.get("out_stride", 0))
+    def _conv(self, x, conv, wd=None, **kw):
+        """conv2d_nhwc of a (weight, bias) entry; a 3x3 with a fragment-ordered copy `wd` runs on the weights-direct kernel where that takes x."""
+        w, b = conv
+        if wd is not None and self.use_wd and kw.get("residual") is None and L.conv_wd_takes(x, w.shape[0]):
+            return L.conv3x3_wd(x, wd, b, w.shape[0], relu=kw.get("relu", False), out=kw.get("out"), out_stride=kw.get("out_stride", 0))
         return L.conv2d_nhwc(x, w, b, **kw)
 
+    def _named(self, x, name, **kw):
+        return self._conv(x, self.w.convs[name], self.w.wd.get(name), **kw)
+
     def _bottom_up(self, x, prefix):
-        bu = prefix + ".bottom_up"
-        if (bu + ".stem.fused") in self.w.convs and x.shape[1] % 4 == 0 and x.shape[2] % 4 == 0:
-            x = L.stem_conv_pool(x, *self.w.convs[bu + ".stem.fused"])  # conv + ReLU + pool in one pass over HBM
+        """Stem, then every stage (weights.Stage) as its 64-wide chain or block by block.  Which routes a block CAN take was settled when
+        the weights were packed; the A/B switches and the launch's size decide here."""
+        fused = self.w.convs.get(prefix + ".bottom_up.stem.fused")
+        if fused is not None and x.shape[1] % 4 == 0 and x.shape[2] % 4 == 0:
+            x = L.stem_conv_pool(x, *fused)  # conv + ReLU + pool in one pass over HBM
         else:
-            x = self._conv(x, bu + ".stem.conv1", kernel=7, stride=2, relu=True)
+            x = self._named(x, prefix + ".bottom_up.stem.conv1", kernel=7, stride=2, relu=True)
             x = L.maxpool3x3s2_nhwc(x)
         outs = []
-        for si, nb in enumerate(STAGE_BLOCKS[self.depth]):
-            chain = self.w.chains64.get(f"{bu}.res{si + 2}") if self.fuse_res2 else None
-            if chain is not None and si == 0 and len(chain) == nb and x.shape[0] * x.shape[1] * x.shape[2] * 512 < 2 ** 31:
-                # res2 in 1 + nb launches: conv1 of the first block, then per block 3x3 -> conv3 (+ shortcut) -> the next block's conv1;
-                # neither the 64-channel intermediates' round trips, nor the shortcut convolution's output, nor a re-read of a block
-                # output by the following conv1 go through HBM
-                t1 = self._conv(x, f"{bu}.res2.0.conv1", kernel=1, relu=True)
-                src = x
-                for blk in chain:
-                    src, t1 = L.bneck64(t1, src, blk["packed"], blk["b2"], blk["b3"], blk["bsc"], blk["b1n"])
-                x = src
-                outs.append(x)
-                hook = getattr(self, "stage_hook", None)
-                if hook is not None:
-                    hook(si + 2)
-                continue
-            t1 = None   # this block's conv1 output where the previous block's conv3 launch has already produced it
-            for bi in range(nb):
-                p = f"{bu}.res{si + 2}.{bi}"
-                stride = 2 if (bi == 0 and si > 0) else 1
-                sc = self._conv(x, p + ".shortcut", kernel=1, stride=stride) if (p + ".shortcut") in self.w.convs else x
-                o = t1 if t1 is not None else self._conv(x, p + ".conv1", kernel=1, stride=stride, relu=True)
-                t1 = None
-                pn = f"{bu}.res{si + 2}.{bi + 1}"
-                if self.fuse_pairs and bi + 1 < nb and (pn + ".shortcut") not in self.w.convs:
-                    # conv3 + shortcut + ReLU and the next block's (stride 1) conv1 + ReLU in one launch where the channel counts are
-                    # res3's: the block output is not read back from HBM.  Decided by the layers and the 2 GiB limit of 32-bit offsets, as for the tails.
-                    (w3, b3), (w1n, b1n) = self.w.convs[p + ".conv3"], self.w.convs[pn + ".conv1"]
-                    if L.conv1x1_pair_supported(w3.shape[-1], w3.shape[0], w1n.shape[0], o.shape[0] * o.shape[1] * o.shape[2]):
-                        o = self._conv(o, p + ".conv2", kernel=3, relu=True)
-                        x, t1 = L.conv1x1_pair(o, w3, b3, sc, w1n, b1n)
-                        continue
-                tail = self.w.tails.get(p) if self.use_wd and self.fuse_tails else None
-                if tail is not None and L.conv_wd_supported(3, 1, o.shape[1], o.shape[2], o.shape[3], 256) \
-                        and o.shape[0] * o.shape[1] * o.shape[2] * self.w.convs[p + ".conv3"][0].shape[0] * 2 < 2 ** 31:
-                    # conv2 + ReLU + conv3 + shortcut + ReLU in one launch: the 256-channel intermediate stays on the chip
-                    x = L.bottleneck_tail_wd(o, self.w.wd[p + ".conv2"], self.w.convs[p + ".conv2"][1], tail[0], tail[1], sc,
-                                             self.w.convs[p + ".conv3"][0].shape[0])
-                    continue
-                o = self._conv(o, p + ".conv2", kernel=3, relu=True)
-                x = self._conv(o, p + ".conv3", kernel=1, relu=True, residual=sc, residual_mode=1)
+        for si, stage in enumerate(self.w.stages[prefix]):
+            if self.fuse_res2 and stage.chain64 is not None and L.bneck64_supported(*x.shape[:3]):
+                x = self._chain64(x, stage)
+            else:
+                t1 = None   # a block's conv1 output where the previous block's pair launch has already produced it
+                for blk in stage.blocks:
+                    x, t1 = self._block(x, blk, t1)
             outs.append(x)
             hook = getattr(self, "stage_hook", None)
             if hook is not None:
                 hook(si + 2)  # pipeline.py staggers the second detector's stream behind this point
         return outs  # res2..res5
+
+    def _chain64(self, x, stage):
+        """res2 in 1 + nb launches: conv1 of the first block, then per block 3x3 -> conv3 (+ shortcut) -> the next block's conv1; neither the
+        64-channel intermediates, nor the shortcut convolution's output, nor a re-read of a block output by the next conv1 go through HBM."""
+        t1 = self._conv(x, stage.blocks[0].conv1, kernel=1, relu=True)
+        for c in stage.chain64:
+            x, t1 = L.bneck64(t1, x, c["packed"], c["b2"], c["b3"], c["bsc"], c["b1n"])
+        return x
+
+    def _block(self, x, blk, t1):
+        """The first route of pair > tail > plain that takes the block -> (its output, the NEXT block's conv1 output | None)."""
+        sc = self._conv(x, blk.shortcut, kernel=1, stride=blk.stride) if blk.shortcut is not None else x
+        o = t1 if t1 is not None else self._conv(x, blk.conv1, kernel=1, stride=blk.stride, relu=True)
+        w3 = blk.conv3[0]
+        if self.fuse_pairs and blk.pair is not None \
+                and L.conv1x1_pair_supported(w3.shape[-1], w3.shape[0], blk.pair[0].shape[0], o.shape[0] * o.shape[1] * o.shape[2]):
+            return self._pair(o, sc, blk)
+        if self.use_wd and self.fuse_tails and blk.tail is not None and L.conv_wd_takes(o, 256, blk.tail[2]):
+            return self._tail(o, sc, blk), None
+        return self._plain(o, sc, blk), None
+
+    def _pair(self, o, sc, blk):
+        """conv2, then conv3 + shortcut + ReLU and the next block's conv1 + ReLU in one launch (res3): the output is not read back from HBM."""
+        o = self._conv(o, blk.conv2, blk.wd, kernel=3, relu=True)
+        return L.conv1x1_pair(o, *blk.conv3, sc, *blk.pair)
+
+    def _tail(self, o, sc, blk):
+        """conv2 + ReLU + conv3 + shortcut + ReLU in one launch (res4): the 256-channel intermediate stays on the chip."""
+        return L.bottleneck_tail_wd(o, blk.wd, blk.conv2[1], blk.tail[0], blk.tail[1], sc, blk.tail[2])
+
+    def _plain(self, o, sc, blk):
+        o = self._conv(o, blk.conv2, blk.wd, kernel=3, relu=True)
+        return self._conv(o, blk.conv3, kernel=1, relu=True, residual=sc, residual_mode=1)
 
     def _fpn(self, x, prefix="backbone", outs=None, ch_off=0, ch_total=256):
         """Returns [p2,p3,p4,p5,p6].  With `outs` given (middle fusion) the 3x3 output convs write their
@@ -172,25 +175,35 @@ class GeneralizedRCNN:
         for i in (5, 4, 3, 2):
             c = res[i - 2]
             if prev is None:
-                prev = self._conv(c, f"{prefix}.fpn_lateral{i}", kernel=1)
+                prev = self._named(c, f"{prefix}.fpn_lateral{i}", kernel=1)
             else:
-                prev = self._conv(c, f"{prefix}.fpn_lateral{i}", kernel=1, residual=prev, residual_mode=2)
+                prev = self._named(c, f"{prefix}.fpn_lateral{i}", kernel=1, residual=prev, residual_mode=2)
             if outs is None:
-                feats[i - 2] = self._conv(prev, f"{prefix}.fpn_output{i}", kernel=3)
+                feats[i - 2] = self._named(prev, f"{prefix}.fpn_output{i}", kernel=3)
             else:
                 view = outs[i - 2].view(-1)[ch_off:]
-                self._conv(prev, f"{prefix}.fpn_output{i}", kernel=3, out=view, out_stride=ch_total)
+                self._named(prev, f"{prefix}.fpn_output{i}", kernel=3, out=view, out_stride=ch_total)
                 feats[i - 2] = outs[i - 2]
         if outs is None:
             feats[4] = L.subsample2_nhwc(feats[3])
         return feats
 
+    def _input_plan(self, sizes):
+        """For resized images of `sizes`: per NHWC4 batch to fill, the keywords ch0 / nch / mean / std of its pack launch; the padded (H, W)."""
+        cfg = self.cfg
+        C, d = cfg.in_channels, cfg.size_divisibility
+        mean = list(cfg.pixel_mean)
+        std = list(cfg.pixel_std) + [cfg.pixel_std[-1]] * (C - len(cfg.pixel_std))
+        assert len(mean) == C, f"PIXEL_MEAN needs {C} entries for INPUT.FORMAT {cfg.input_format}"
+        # BGRTTT: the thermal half divides by PIXEL_STD[:3] (meta_arch/rcnn.py:63-66)
+        groups = [dict(ch0=c0, nch=n, mean=mean[c0:c0 + n], std=std[:n]) for c0, n in ([(0, min(C, 4))] if C <= 4 else [(0, 3), (3, 3)])]
+        return groups, tuple((max(s[i] for s in sizes) + d - 1) // d * d for i in (0, 1))
+
     def _preprocess(self, images, resize_to=None):
         """images: list of device tensors.  CHW float32 (reference contract, already resized) or HWC uint8 /
         float32 raw frames (then `resize_to` = (h, w) applies ResizeShortestEdge's target on the GPU).
         Returns NHWC4 fp16 batch(es) and [(h, w)] of the resized, unpadded images."""
-        cfg = self.cfg
-        C = cfg.in_channels
+        C = self.cfg.in_channels
         if isinstance(images, PairFrames):
             return self._preprocess_pair(images, resize_to)
         if isinstance(images, torch.Tensor):  # one [N,H,W,C] (or [N,C,H,W] f32) batch of equally sized frames
@@ -201,54 +214,31 @@ class GeneralizedRCNN:
             kinds.append(2 if chw else (0 if im.dtype == torch.uint8 else 1))
             h, w = (im.shape[1], im.shape[2]) if chw else (im.shape[0], im.shape[1])
             sizes.append(tuple(resize_to) if (resize_to is not None and not chw) else (h, w))
-        d = cfg.size_divisibility
-        Hp = (max(s[0] for s in sizes) + d - 1) // d * d
-        Wp = (max(s[1] for s in sizes) + d - 1) // d * d
-        mean = list(cfg.pixel_mean)
-        std = list(cfg.pixel_std) + [cfg.pixel_std[-1]] * (C - len(cfg.pixel_std))
-        assert len(mean) == C, f"PIXEL_MEAN needs {C} entries for INPUT.FORMAT {cfg.input_format}"
-        N = len(images)
-        groups = [(0, min(C, 4))] if C <= 4 else [(0, 3), (3, 3)]
-        batches = []
-        for ch0, nch in groups:
-            x = torch.empty((N, Hp, Wp, 4), dtype=torch.float16, device=self.device)
-            sd0 = 0 if ch0 == 3 else ch0    # BGRTTT: the thermal half divides by PIXEL_STD[:3] (meta_arch/rcnn.py:63-66)
+        groups, (Hp, Wp) = self._input_plan(sizes)
+        batches = [torch.empty((len(images), Hp, Wp, 4), dtype=torch.float16, device=self.device) for _ in groups]
+        for g, x in zip(groups, batches):
             for i, im in enumerate(images):
                 if kinds[i] == 0 and C == 3 and tuple(sizes[i]) != tuple(im.shape[:2]):
                     # 3-channel uint8 + resize: the reference goes through Pillow (transform.py:92-97) - exact restatement
-                    L.preprocess_pack_pil_u8(im.contiguous(), x[i], ch0=ch0, nch=nch, flip_rgb=False, dst_hw=sizes[i],
-                                             mean=mean[ch0:ch0 + nch], std=std[sd0:sd0 + nch])
-                    continue
-                L.preprocess_pack(im.contiguous(), x[i], src_kind=kinds[i], ch0=ch0, nch=nch, flip_rgb=False,
-                                  dst_hw=sizes[i], mean=mean[ch0:ch0 + nch], std=std[sd0:sd0 + nch])
-            batches.append(x)
+                    L.preprocess_pack_pil_u8(im.contiguous(), x[i], flip_rgb=False, dst_hw=sizes[i], **g)
+                else:
+                    L.preprocess_pack(im.contiguous(), x[i], src_kind=kinds[i], flip_rgb=False, dst_hw=sizes[i], **g)
         return batches, sizes
 
     def _preprocess_batch(self, images, resize_to):
-        cfg = self.cfg
-        C = cfg.in_channels
+        C = self.cfg.in_channels
         N = images.shape[0]
         chw = images.dtype == torch.float32 and images.shape[1] == C and images.shape[3] != C
         kind = 2 if chw else (0 if images.dtype == torch.uint8 else 1)
         h, w = (images.shape[2], images.shape[3]) if chw else (images.shape[1], images.shape[2])
         size = tuple(resize_to) if (resize_to is not None and not chw) else (h, w)
-        d = cfg.size_divisibility
-        Hp, Wp = (size[0] + d - 1) // d * d, (size[1] + d - 1) // d * d
-        mean = list(cfg.pixel_mean)
-        std = list(cfg.pixel_std) + [cfg.pixel_std[-1]] * (C - len(cfg.pixel_std))
-        assert len(mean) == C, f"PIXEL_MEAN needs {C} entries for INPUT.FORMAT {cfg.input_format}"
-        batches = []
-        for ch0, nch in ([(0, min(C, 4))] if C <= 4 else [(0, 3), (3, 3)]):
-            x = torch.empty((N, Hp, Wp, 4), dtype=torch.float16, device=self.device)
-            sd0 = 0 if ch0 == 3 else ch0    # BGRTTT: thermal half uses PIXEL_STD[:3] (meta_arch/rcnn.py:63-66)
+        groups, (Hp, Wp) = self._input_plan([size])
+        batches = [torch.empty((N, Hp, Wp, 4), dtype=torch.float16, device=self.device) for _ in groups]
+        for g, x in zip(groups, batches):
             if kind == 0 and C == 3 and tuple(size) != (h, w):   # Pillow-exact resize (see _preprocess)
-                L.preprocess_pack_pil_u8(images.contiguous(), x, ch0=ch0, nch=nch, flip_rgb=False, dst_hw=size,
-                                         mean=mean[ch0:ch0 + nch], std=std[sd0:sd0 + nch])
-                batches.append(x)
-                continue
-            L.preprocess_pack_batch(images.contiguous(), x, src_kind=kind, ch0=ch0, nch=nch, flip_rgb=False, dst_hw=size,
-                                    mean=mean[ch0:ch0 + nch], std=std[sd0:sd0 + nch])
-            batches.append(x)
+                L.preprocess_pack_pil_u8(images.contiguous(), x, flip_rgb=False, dst_hw=size, **g)
+            else:
+                L.preprocess_pack_batch(images.contiguous(), x, src_kind=kind, flip_rgb=False, dst_hw=size, **g)
         return batches, [size] * N
 
     def _preprocess_pair(self, pair, resize_to):
@@ -262,21 +252,13 @@ class GeneralizedRCNN:
                              f"{cfg.input_format} sees the RGB frame at its own size - give it the RGB batch itself")
         if pair.rgb is None:
             raise ValueError(f"INPUT.FORMAT {cfg.input_format} needs the RGB batch of the frame pairs")
-        C = cfg.in_channels
         N, h, w = pair.thermal.shape[:3]
         size = tuple(resize_to) if resize_to is not None else (h, w)
-        d = cfg.size_divisibility
-        Hp, Wp = (size[0] + d - 1) // d * d, (size[1] + d - 1) // d * d
-        mean = list(cfg.pixel_mean)
-        std = list(cfg.pixel_std) + [cfg.pixel_std[-1]] * (C - len(cfg.pixel_std))
-        assert len(mean) == C, f"PIXEL_MEAN needs {C} entries for INPUT.FORMAT {cfg.input_format}"
-        batches = []
-        for ch0, nch in ([(0, 4)] if C == 4 else [(0, 3), (3, 3)]):
-            x = torch.empty((N, Hp, Wp, 4), dtype=torch.float16, device=self.device)
-            sd0 = 0 if ch0 == 3 else ch0    # BGRTTT: thermal half uses PIXEL_STD[:3] (meta_arch/rcnn.py:63-66)
-            L.fusion_input_pack(pair.thermal.contiguous(), pair.rgb.contiguous() if ch0 < 3 else None, x, ch0=ch0, nch=nch,
-                                dst_hw=size, mean=mean[ch0:ch0 + nch], std=std[sd0:sd0 + nch], pad_multiple=d)
-            batches.append(x)
+        groups, (Hp, Wp) = self._input_plan([size])
+        batches = [torch.empty((N, Hp, Wp, 4), dtype=torch.float16, device=self.device) for _ in groups]
+        for g, x in zip(groups, batches):
+            L.fusion_input_pack(pair.thermal.contiguous(), pair.rgb.contiguous() if g["ch0"] < 3 else None, x, dst_hw=size,
+                                pad_multiple=cfg.size_divisibility, **g)
         return batches, [size] * N
 
     def _rpn(self, feats, sizes_dev, N, heads=None):
@@ -288,13 +270,12 @@ class GeneralizedRCNN:
             heads = []
             fused = self.w.rpn_head_fused if self.use_wd else None
             for f in feats:
-                if fused is not None and f.numel() * 2 < 2 ** 31 and L.conv_wd_supported(3, 1, f.shape[1], f.shape[2], f.shape[3], 256):
+                if fused is not None and L.conv_wd_takes(f, 256):
                     # StandardRPNHead in one launch: the 256-channel ReLU'd map never goes to HBM
                     heads.append(L.conv3x3_wd_rpn_head(f, self.w.wd["rpn.conv"], self.w.convs["rpn.conv"][1], fused[0], fused[1]))
                     continue
-                t = self._conv(f, "rpn.conv", kernel=3, relu=True)
-                w, b = self.w.convs["rpn.head"]
-                heads.append(L.conv2d_nhwc(t, w, b, kernel=1, out_f32=True, cout=15, cout_store=15, out_stride=16))
+                t = self._named(f, "rpn.conv", kernel=3, relu=True)
+                heads.append(L.conv2d_nhwc(t, *self.w.convs["rpn.head"], kernel=1, out_f32=True, cout=15, cout_store=15, out_stride=16))
         feats = heads
         for f in feats:
             hw += [f.shape[1], f.shape[2]]

@@ -10,6 +10,8 @@ tensors the HIP kernels consume:
   * fc1 columns permuted from (c, ph, pw) to the ROIAlign kernel's (ph, pw, c) order;
   * cls_score (K+1) + bbox_pred (4K) + var_pred (1) fused into one [5K+2, 1024] predictor.
 """
+from dataclasses import dataclass
+
 import torch
 
 BN_EPS = 1e-5
@@ -73,6 +75,27 @@ def pack_stem_fused(w):
     return p.half()
 
 
+@dataclass
+class Block:
+    """One BottleneckBlock as GeneralizedRCNN._bottom_up reads it: conv1 .. shortcut are its (weight, bias) entries of PackedDetector.convs
+    (shortcut None = identity); the rest is filled by _pack_wd on a GPU and stays None where its kernel's rule fails."""
+    name: str
+    stride: int
+    conv1: tuple
+    conv2: tuple
+    conv3: tuple
+    shortcut: tuple = None
+    wd: torch.Tensor = None   # fragment-ordered copy of conv2's weight for the weights-direct kernel (csrc/conv_wd.h)
+    tail: tuple = None        # (packed conv3, bias, cout) of the fused conv2 + conv3 launch
+    pair: tuple = None        # the next block's conv1 where conv3 + shortcut + that conv1 go in one launch (csrc/conv1x1_pair.hip)
+
+
+@dataclass
+class Stage:
+    blocks: list
+    chain64: list = None      # per block the weight stream and biases of csrc/bneck64.hip, where the whole stage runs on it
+
+
 class PackedDetector:
     """Device-resident packed weights of one detector."""
 
@@ -86,11 +109,10 @@ class PackedDetector:
         ncls = sd["roi_heads.box_predictor.cls_score.weight"].shape[0] - 1
         self.num_classes = num_classes if num_classes is not None else ncls
         assert self.num_classes == ncls, (self.num_classes, ncls)
-        self.convs = {}
-        self.wd = {}   # name -> fragment-ordered copy of a 3x3 weight for the weights-direct kernel (csrc/conv_wd.h)
-        self.tails = {}            # block -> packed conv3 of a fused bottleneck tail      } filled by _pack_wd on a GPU; a host-packed
-        self.chains64 = {}         # stage -> fused 64-wide chain (res2)                  } object keeps them empty, so rcnn raises its
-        self.rpn_head_fused = None  # packed 15-row RPN head for the fused launch         } 'no CPU fallback' error, not AttributeError
+        self.convs = {}    # name -> (weight, bias): the stem, FPN and RPN are launched from here; the blocks' entries are also in `stages`
+        self.stages = {}   # backbone prefix -> [Stage of res2, .. res5]
+        self.wd = {}       # name -> fragment-ordered copy of a 3x3 weight for the weights-direct kernel (csrc/conv_wd.h)   } filled by
+        self.rpn_head_fused = None  # packed 15-row RPN head for the fused launch                                          } _pack_wd
         self._pack_backbone(sd, "backbone")
         if self.has_backbone_2:
             self._pack_backbone(sd, "backbone_2")
@@ -131,48 +153,42 @@ class PackedDetector:
         for name, (w, b) in self.convs.items():
             if w.dim() == 4 and w.shape[1] == 3 and w.shape[2] == 3 and w.shape[3] % 64 == 0 and w.shape[0] % 256 == 0 and b is not None:
                 self.wd[name] = L.conv_wd_pack(w)
-        # fused bottleneck tails (conv2 3x3 + ReLU + conv3 1x1 + shortcut + ReLU in one launch) where conv2 is 256 wide (res4)
-        self.tails = {}
-        for name in list(self.wd):
-            if name.endswith(".conv2") and self.convs[name][0].shape[0] == 256:
-                w3, b3 = self.convs[name[:-1] + "3"]
-                if w3.shape[3] == 256 and w3.shape[0] % 256 == 0:
-                    self.tails[name[: -len(".conv2")]] = (L.conv_wd_pack_tail(w3.reshape(w3.shape[0], 256).contiguous()), b3)
-        # 64-wide stride-1 stages (res2): every block from its 3x3 on, fused with the next block's conv1 (csrc/bneck64.hip)
-        self.chains64 = {}
-        for name in self.convs:
-            if not name.endswith(".0.conv2") or tuple(self.convs[name][0].shape) != (64, 3, 3, 64):
-                continue
-            stage = name[: -len(".0.conv2")]
-            blocks, bi = [], 0
-            while f"{stage}.{bi}.conv2" in self.convs:
-                blocks.append(f"{stage}.{bi}")
-                bi += 1
-            ok = all(tuple(self.convs[b + ".conv2"][0].shape) == (64, 3, 3, 64) and tuple(self.convs[b + ".conv3"][0].shape) == (256, 1, 1, 64) and
-                     tuple(self.convs[b + ".conv1"][0].shape)[:3] == (64, 1, 1) for b in blocks)
-            ok = ok and all(self.convs[b + k][1] is not None for b in blocks for k in (".conv1", ".conv2", ".conv3"))
-            ok = ok and all(tuple(self.convs[b + ".conv1"][0].shape) == (64, 1, 1, 256) for b in blocks[1:])
-            ok = ok and all((b + ".shortcut") not in self.convs for b in blocks[1:])
-            sc0 = self.convs.get(blocks[0] + ".shortcut")
-            ok = ok and sc0 is not None and tuple(sc0[0].shape) == (256, 1, 1, 64) and sc0[1] is not None
-            if not ok:
-                continue
-            chain = []
-            for i, b in enumerate(blocks):
-                nxt = self.convs[blocks[i + 1] + ".conv1"] if i + 1 < len(blocks) else None
-                sc = sc0 if i == 0 else None
-                packed = L.bneck64_pack(self.convs[b + ".conv2"][0], self.convs[b + ".conv3"][0].reshape(256, 64),
-                                        sc[0].reshape(256, 64) if sc else None, nxt[0].reshape(64, 256) if nxt else None)
-                chain.append({"packed": packed, "b2": self.convs[b + ".conv2"][1], "b3": self.convs[b + ".conv3"][1],
-                              "bsc": sc[1] if sc else None, "b1n": nxt[1] if nxt else None})
-            self.chains64[stage] = chain
+        for stage in (s for stages in self.stages.values() for s in stages):
+            for blk, nxt in zip(stage.blocks, stage.blocks[1:] + [None]):
+                blk.wd = self.wd.get(blk.name + ".conv2")
+                w3, b3 = blk.conv3
+                # fused bottleneck tail (conv2 3x3 + ReLU + conv3 1x1 + shortcut + ReLU in one launch) where conv2 is 256 wide (res4)
+                if blk.wd is not None and blk.conv2[0].shape[0] == 256 and w3.shape[3] == 256 and w3.shape[0] % 256 == 0:
+                    blk.tail = (L.conv_wd_pack_tail(w3.reshape(w3.shape[0], 256).contiguous()), b3, w3.shape[0])
+                # conv3 + shortcut + ReLU and the next (identity: stride 1) block's conv1 + ReLU in one launch where the channels are res3's
+                if nxt is not None and nxt.shortcut is None and L.conv1x1_pair_supported(w3.shape[3], w3.shape[0], nxt.conv1[0].shape[0], 1):
+                    blk.pair = nxt.conv1
+            stage.chain64 = self._pack_chain64(stage.blocks)
         # fused StandardRPNHead (3x3 + ReLU + 1x1 in one launch) when the RPN is 256 wide
-        self.rpn_head_fused = None
         hw, hb = self.convs["rpn.head"]
         if "rpn.conv" in self.wd and self.convs["rpn.conv"][0].shape[0] == 256 and hw.shape[0] <= 16:
             b16 = torch.zeros(16, dtype=torch.float32, device=self.device)
             b16[: hb.shape[0]] = hb
             self.rpn_head_fused = (L.conv_wd_pack_head(hw.reshape(hw.shape[0], -1).contiguous()), b16)
+
+    @staticmethod
+    def _pack_chain64(blocks):
+        """A 64-wide stride-1 stage (res2) on csrc/bneck64.hip: every block from its 3x3 on, fused with the next block's conv1 -> one
+        dict of layers.bneck64's weight arguments per block, or None where the stage is not of that form."""
+        from . import layers as L
+        shape = lambda conv: tuple(conv[0].shape)
+        ok = all(b.stride == 1 and shape(b.conv2) == (64, 3, 3, 64) and shape(b.conv3) == (256, 1, 1, 64) and shape(b.conv1)[:3] == (64, 1, 1)
+                 and all(c[1] is not None for c in (b.conv1, b.conv2, b.conv3)) for b in blocks)
+        ok = ok and all(shape(b.conv1) == (64, 1, 1, 256) and b.shortcut is None for b in blocks[1:])
+        sc0 = blocks[0].shortcut
+        if not (ok and sc0 is not None and shape(sc0) == (256, 1, 1, 64) and sc0[1] is not None):
+            return None
+        chain = []
+        for b, nxt in zip(blocks, blocks[1:] + [None]):
+            sc, n1 = b.shortcut, nxt.conv1 if nxt else None
+            packed = L.bneck64_pack(b.conv2[0], b.conv3[0].reshape(256, 64), sc[0].reshape(256, 64) if sc else None, n1[0].reshape(64, 256) if n1 else None)
+            chain.append({"packed": packed, "b2": b.conv2[1], "b3": b.conv3[1], "bsc": sc[1] if sc else None, "b1n": n1[1] if n1 else None})
+        return chain
 
     def _pack_backbone(self, sd, prefix):
         dev = self.device
@@ -181,13 +197,18 @@ class PackedDetector:
         self.convs[bu + ".stem.conv1"] = (_pack_stem(w).to(dev), b.to(dev))
         if w.shape[0] == 64 and w.shape[1] <= 4:  # every reference config (STEM_OUT_CHANNELS 64)
             self.convs[bu + ".stem.fused"] = (pack_stem_fused(w).to(dev), b.to(dev))
+        self.stages[prefix] = stages = []
         for si, nb in enumerate(STAGE_BLOCKS[self.depth]):
+            blocks = []
             for bi in range(nb):
+                name = f"{bu}.res{si + 2}.{bi}"
                 for c in ("conv1", "conv2", "conv3", "shortcut"):
-                    name = f"{bu}.res{si + 2}.{bi}.{c}"
-                    if name + ".weight" in sd:
-                        w, b = _fold(sd, name)
-                        self.convs[name] = (_pack_conv(w).to(dev), b.to(dev))
+                    if f"{name}.{c}.weight" in sd:
+                        w, b = _fold(sd, f"{name}.{c}")
+                        self.convs[f"{name}.{c}"] = (_pack_conv(w).to(dev), b.to(dev))
+                blocks.append(Block(name, 2 if (bi == 0 and si > 0) else 1,
+                                    *(self.convs.get(f"{name}.{c}") for c in ("conv1", "conv2", "conv3", "shortcut"))))
+            stages.append(Stage(blocks))
         for i in (2, 3, 4, 5):
             for kind in ("fpn_lateral", "fpn_output"):
                 name = f"{prefix}.{kind}{i}"
