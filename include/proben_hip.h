@@ -617,6 +617,10 @@ int pe_stem_conv7x7_maxpool_f16(const void* x, const void* w_packed, const float
  *   suppressed by - the neighbouring class exactly as torchvision's trick does.
  *   out_keep [B,max_out] input-row indices in score-descending order (ties: lower index first),
  *   out_counts [B].  scratch: pe_nms_scratch_bytes(B, n_max) bytes of device memory.
+ *   Non-finite inputs (csrc/nms.hip and oracle/nms.py state the rule in full): NaN scores come first, whatever their sign or
+ *   payload, ties by index, then +Inf down to -Inf.  A row with a NaN coordinate has a NaN IoU with everything: it is kept and
+ *   suppresses nothing.  Mode 0's max is a NaN-propagating maximum over the rows that take part: with a NaN or +Inf
+ *   coordinate among them every shifted box is NaN and every row is kept.  Rows masked out or beyond counts never take part.
  * ------------------------------------------------------------------------------------------- */
 #define PE_NMS_TRICK 0
 #define PE_NMS_CLASS 1

@@ -33,6 +33,7 @@ int ensure_dynamic_lds(const void* kernel, size_t bytes, const char* what) {
     if (have >= bytes) return PE_OK;
     const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) {
+        (void)hipGetLastError();   // reported here: the next HIP user of the thread (torch's allocator) must not find it again
         set_error("%s: %zu bytes of dynamic LDS refused on device %d: %s", what, bytes, dev, hipGetErrorString(e));
         return PE_ERR_HIP;
     }

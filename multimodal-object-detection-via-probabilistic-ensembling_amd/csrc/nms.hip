@@ -6,7 +6,14 @@
 // and nms_1 (demo/FLIR/demo_probEn.py:64).  float32 IoU = inter / (a + b - inter), suppress on IoU > thr,
 // no "+1"; PE_NMS_TRICK adds idx * (max_coord + 1) to the coordinates first (torchvision's
 // "coordinate trick"), PE_NMS_CLASS compares class ids instead (== one nms per class, "vanilla").
-// Order rule: score descending, ties by input index ascending (stable descending sort).
+// Order rule: score descending, ties by input index ascending (stable descending sort).  Non-finite scores follow torch's
+// stable descending sort: every NaN first, whatever its sign or payload, ties by index; then +Inf down to -Inf; -0 and +0 tie.
+// Non-finite boxes (the same rule as oracle/nms.py and the docstrings of layers.nms / layers.batched_nms): the IoU is plain
+// float32 arithmetic, so a row with a NaN coordinate has a NaN area, a NaN IoU with everything, and neither suppresses nor is
+// suppressed; the finite rows around it are not affected.  PE_NMS_TRICK's max_coord is a NaN-propagating maximum over the
+// rows that take part, like torchvision's boxes.max(): one NaN coordinate makes every offset NaN (0 * NaN too), a +Inf maximum
+// makes them NaN or Inf, every box turns NaN and every row survives.  Rows that do not take part (valid == 0, beyond
+// counts[b]) never enter the maximum.  A plain nms has no trick: layers.nms runs PE_NMS_CLASS without class ids.
 //
 // Suppression only ever happens inside a class (mode 1 by definition; mode 0 because boxes of different classes are moved
 // max_coord + 1 apart and cannot intersect), so the work is organised per class:
@@ -25,12 +32,17 @@ namespace {
 constexpr int kSortThreads = 1024;
 __device__ int g_presorted_path = 1;     // test hook (pe_test_set_nms_presorted): 0 = always run the sorting network
 
+// Smaller key = better.  Every NaN gets the best key (0; +Inf is 0x007FFFFF), so NaNs come first and tie by index; the worst
+// key is -Inf's 0xFF800000, so no live row's 64-bit key is the dead rows' ~0.
 __device__ __forceinline__ unsigned ordered_desc(float s) {
+    if (s != s) return 0u;
     s += 0.0f;  // -0 -> +0
     unsigned u = __float_as_uint(s);
     u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;  // ascending order for floats
     return ~u;                                  // descending
 }
+
+__device__ __forceinline__ float nan_max(float x, float y) { return (x != x || y != y) ? NAN : fmaxf(x, y); }
 
 struct NmsArgs {
     const float* boxes;    // [B, n_max, 4]
@@ -71,18 +83,20 @@ __global__ __launch_bounds__(kSortThreads) void nms_sort_kernel(NmsArgs a) {
     // the per-class organisation is legal for mode 0: boxes + idx * (max + 1) keeps classes apart only while every coordinate
     // is >= 0 (a box with coordinates below -1 reaches into the previous class's band and torchvision's trick lets the two
     // suppress each other).  Such an image ("generic") is handled as ONE segment with all pairs compared on the shifted boxes.
+    // The maximum propagates NaN like torchvision's boxes.max() (fmaxf alone would drop it); the minimum only takes the decision
+    // below, and with a NaN maximum every shifted box is NaN on either route.
     float mx = -INFINITY, mn = INFINITY;
     for (int i = tid; i < n; i += kSortThreads) {
         if (a.valid && !a.valid[(size_t)b * a.n_max + i]) continue;
         const float lo = fminf(fminf(bx[i * 4], bx[i * 4 + 1]), fminf(bx[i * 4 + 2], bx[i * 4 + 3]));
-        const float hi = fmaxf(fmaxf(bx[i * 4], bx[i * 4 + 1]), fmaxf(bx[i * 4 + 2], bx[i * 4 + 3]));
-        mx = fmaxf(mx, hi); mn = fminf(mn, lo);
+        const float hi = nan_max(nan_max(bx[i * 4], bx[i * 4 + 1]), nan_max(bx[i * 4 + 2], bx[i * 4 + 3]));
+        mx = nan_max(mx, hi); mn = fminf(mn, lo);
     }
-    for (int o = 32; o > 0; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o)); mn = fminf(mn, __shfl_xor(mn, o)); }
+    for (int o = 32; o > 0; o >>= 1) { mx = nan_max(mx, __shfl_xor(mx, o)); mn = fminf(mn, __shfl_xor(mn, o)); }
     if ((tid & 63) == 0) { red[tid >> 6] = mx; red_mn[tid >> 6] = mn; }
     __syncthreads();
     mx = red[0]; mn = red_mn[0];
-    for (int w = 1; w < kSortThreads / 64; ++w) { mx = fmaxf(mx, red[w]); mn = fminf(mn, red_mn[w]); }
+    for (int w = 1; w < kSortThreads / 64; ++w) { mx = nan_max(mx, red[w]); mn = fminf(mn, red_mn[w]); }
     const bool generic = a.mode == 0 && a.idxs && mn < 0.f;
     // pass 2: keys
     int local_cnt = 0;
@@ -463,7 +477,10 @@ extern "C" int pe_nms_batched(const float* boxes, const float* scores, const int
     PE_CHECK_LAUNCH("pe_nms_batched(mask)");
     const size_t lists = (((((size_t)n_max * 2 + 15) & ~(size_t)15) + (size_t)a.n_pad / 8 + 15) & ~(size_t)15);   // kept lists + flags
     size_t lds2 = std::max((size_t)a.n_pad * 8, lists + 16);
-    a.merge = lists + (size_t)n_max * 8 + 512 <= 160 * 1024;       // + the survivors' keys (at most one per row)
+    // + the survivors' keys (at most one per row).  The request below asks for lds2 + 512 and the runtime counts the kernel's static
+    // LDS on top of what is asked for: asking for all 160 KiB (n_max = 16128 under the earlier bound of one 512) is refused,
+    // so the bound leaves both free.  n_pad = 16384: merge by rank up to 16076 rows, sorting network from 16077.
+    a.merge = lists + (size_t)n_max * 8 + 512 + 512 <= 160 * 1024;
     if (a.merge) lds2 = std::max(lds2, lists + (size_t)n_max * 8);
     PE_ENSURE_LDS(nms_scan_order_kernel, lds2 + 512, "pe_nms_batched(scan + order)");   // + the kernel's static LDS (~132 B)
     hipLaunchKernelGGL(nms_scan_order_kernel, dim3(B), dim3(kScanThreads), lds2, st, a);

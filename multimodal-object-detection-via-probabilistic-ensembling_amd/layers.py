@@ -55,7 +55,11 @@ def batched_nms(boxes, scores, idxs, iou_threshold):
     idxs [N] -> int64 keep indices sorted by score descending.  torchvision's dispatch rule is kept:
     coordinate trick up to 20000 box elements on a GPU, one NMS per class beyond that.  Arbitrary boxes are fine: with
     negative coordinates the trick's class bands can overlap and the kernel then compares all pairs like torchvision
-    (csrc/nms.hip, "generic" images)."""
+    (csrc/nms.hip, "generic" images).
+    Non-finite inputs (one rule with csrc/nms.hip and oracle/nms.py): NaN scores come first, whatever their sign or payload,
+    ties by index, then +Inf down to -Inf.  The trick's max_coord propagates NaN like boxes.max(): with one NaN or +Inf
+    coordinate among the boxes every shifted box is NaN and every row is kept.  In the per-class form a row with a NaN
+    coordinate has a NaN IoU with everything: it is kept and suppresses nothing, the finite rows are not affected."""
     assert boxes.shape[-1] == 4
     _lib.require_cuda(boxes, scores, idxs)
     n = boxes.shape[0]
@@ -71,8 +75,20 @@ def batched_nms(boxes, scores, idxs, iou_threshold):
 
 
 def nms(boxes, scores, iou_threshold):
-    """torchvision.ops.nms equivalent (re-exported by layers/nms.py:6)."""
-    return batched_nms(boxes, scores, torch.zeros(len(scores), dtype=torch.int32, device=boxes.device), iou_threshold)
+    """torchvision.ops.nms equivalent (re-exported by layers/nms.py:6): boxes [N,4], scores [N] -> int64 keep indices sorted
+    by score descending.  No coordinate trick is involved (PE_NMS_CLASS without class ids), so a non-finite coordinate stays
+    in its own row: a row with a NaN coordinate has a NaN IoU with everything, is kept and suppresses nothing, +-Inf go
+    through the float32 IoU like any number, and the finite rows suppress each other as usual.  NaN scores come first,
+    whatever their sign or payload, ties by index, then +Inf down to -Inf (one rule with csrc/nms.hip and oracle/nms.py)."""
+    assert boxes.shape[-1] == 4
+    _lib.require_cuda(boxes, scores)
+    n = boxes.shape[0]
+    if n == 0:
+        return torch.empty((0,), dtype=torch.int64, device=boxes.device)
+    b = boxes.detach().float().contiguous().view(1, n, 4)
+    s = scores.detach().float().contiguous().view(1, n)
+    keep, cnt = nms_batched_raw(b, s, None, None, None, iou_threshold, 1, n)
+    return keep[0, : int(cnt.item())].to(torch.int64)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -23,14 +23,28 @@ file to reproduce their keep lists index for index (the HIP kernel likewise, tes
 code: the coordinate-trick / per-class dispatch thresholds of batched_nms (torchvision's, restated) and the order of exactly tied
 scores (the fixtures are tie-free).
 Tie rule: score descending, then index ascending (stable descending sort).
+Non-finite inputs (tests/nms_cases.py, tests/test_nms_edges_cpu.py / _gpu.py; csrc/nms.hip and layers.nms / batched_nms state
+the same rule):
+  scores:  torch's stable descending sort - every NaN first, whatever its sign or payload, ties by index; then +Inf down to
+           -Inf; -0.0 and +0.0 tie.
+  boxes:   nms has no coordinate trick: a row with a NaN coordinate has a NaN area, so its IoU with anything is NaN and it
+           neither suppresses nor is suppressed; +-Inf go through the same float32 arithmetic as any other number; the finite
+           rows suppress each other as usual.  The trick's max_coord is a NaN-propagating maximum over the rows that take part:
+           one NaN coordinate makes every offset NaN (0 * NaN too), a +Inf maximum makes them NaN (class 0) or Inf, and in both
+           cases every box turns NaN and every row survives.  Rows that do not take part (masked out, beyond the count) never
+           enter the maximum.
 """
 import numpy as np
 
 
 def order_desc_stable(scores):
-    scores = np.asarray(scores)
-    # stable descending == stable ascending on negated keys (NaN-free inputs)
-    return np.argsort(-scores.astype(np.float64), kind="stable")
+    """Indices of torch.sort(scores, descending=True, stable=True): NaNs (any sign, any payload) first in index order, then
+    the rest by value descending, ties (-0.0 == +0.0 included) in index order."""
+    s = np.asarray(scores).astype(np.float64).reshape(-1)
+    nan = np.isnan(s)
+    rest = np.nonzero(~nan)[0]
+    # stable descending == stable ascending on negated keys
+    return np.concatenate([np.nonzero(nan)[0], rest[np.argsort(-s[rest], kind="stable")]]).astype(np.int64)
 
 
 def nms_f32(boxes, scores, thr):
