@@ -78,7 +78,7 @@ def check_temperature(t, what="temperature"):
 
 
 def _statistic(who, nv, work_values, dev, launch):
-    """The device side of the four statistic calls (csrc/reduce2.h): allocate [nv result slots | the two int32 flags in one f64 slot]
+    """The device side of the six statistic calls (csrc/reduce2.h): allocate [nv result slots | the two int32 flags in one f64 slot]
     as one buffer and a workspace of work_values f64, run launch(work, out, flags, stream) -> status, download once.
     Returns (the nv result slots on the host, excluded items, the last excluded index or -1)."""
     res = torch.empty((nv + 1,), dtype=torch.float64, device=dev)
@@ -605,6 +605,55 @@ def reliability_scores(conf, correct, bins=15):
         _lib.ptr(conf) if M else None, _lib.ptr(correct) if M else None, M, B, work, cnt, sums, flags, stream))
 
 
+# ---- the fitter of the pooling weights and of the presence rows -------------------------------------------------------------------
+
+def _projected_newton(evaluate, x0, lo, hi, gtol, used, max_rounds):
+    """x in [lo, hi]^D that minimises a convex objective known only through evaluate(candidates [n, D]) -> (f [n], gradient [n, D]),
+    from x0, by a projected Newton iteration with a line search.  Per round one evaluate gives the gradient at x and at x + h e_d (the
+    Hessian's columns by forward differences, h = 1e-4, symmetrised), the ridged Newton system is solved over the coordinates that are
+    not held at a bound (a coordinate is held at lo / hi when the gradient pushes it outwards), and a second evaluate tries the 40 step
+    lengths 2, 1, 1/2, ... along the clipped direction; the step with the lowest f is taken if it is lower than the current one.  A
+    direction that is not a descent direction (a nearly singular Hessian) is replaced by the scaled negative gradient.
+    Stops when max_d |pg_d| <= gtol * used (pg_d = the gradient entry, 0 for a held coordinate), when no step length lowers f (float64
+    resolution reached), or after max_rounds; one more evaluate at the final point.
+    Returns (x, f, gradient, rounds, converged: the gradient criterion was met, at_bound [D]: "lo" / "hi" where f still falls beyond that
+    end of [lo, hi], else None)."""
+    D, h = len(x0), 1e-4
+    x, rounds, converged = x0, 0, False
+    while rounds < max_rounds:
+        rounds += 1
+        fs, gs = evaluate(np.vstack([x] + [x + h * np.eye(D)[d] for d in range(D)]))
+        f, g = float(fs[0]), gs[0]
+        held = ((x <= lo) & (g > 0)) | ((x >= hi) & (g < 0))
+        pg = np.where(held, 0.0, g)
+        if np.max(np.abs(pg)) <= gtol * used:
+            converged = True
+            break
+        H = (gs[1:] - g[None, :]) / h
+        H = 0.5 * (H + H.T)
+        free = ~held
+        p = np.zeros(D)
+        try:
+            Hf = H[np.ix_(free, free)] + 1e-10 * max(np.trace(H), 1.0) * np.eye(int(free.sum()))
+            p[free] = -np.linalg.solve(Hf, g[free])
+        except np.linalg.LinAlgError:
+            p[free] = -g[free]
+        if not (np.all(np.isfinite(p)) and p @ g < 0):
+            p = np.where(free, -g, 0.0) / max(np.max(np.abs(np.diag(H))), 1e-300)
+        steps = 2.0 ** (1 - np.arange(40))
+        trial = np.clip(x[None, :] + steps[:, None] * p[None, :], lo, hi)
+        ft, _ = evaluate(trial)
+        ft = np.where(np.isfinite(ft), ft, np.inf)
+        i = int(np.argmin(ft))
+        if not ft[i] < f:
+            break
+        x = trial[i]
+    fs, gs = evaluate(x[None, :])
+    g = gs[0]
+    at = ["lo" if (x[d] <= lo and g[d] > 0) else "hi" if (x[d] >= hi and g[d] < 0) else None for d in range(D)]
+    return x, float(fs[0]), g, rounds, converged, at
+
+
 # ---- pooling weights -----------------------------------------------------------------------------------------------------------
 
 def check_pool_weight(w, what="pool weight"):
@@ -710,49 +759,15 @@ def fit_pool_weights(log_probs, row_source, member_rows, cluster_offsets, labels
         raise ValueError(f"fit_pool_weights: hi {hi} <= 1 (the start of the search)")
     C = int(labels.numel())
     args = (log_probs, row_source, member_rows, cluster_offsets, labels)
-    h = 1e-4
-    w = np.ones(D)
-    f1, _, bad, _ = pool_nll(*args, [w], log_prior)
+    f1, _, bad, _ = pool_nll(*args, [np.ones(D)], log_prior)
     used = C - bad
     if used <= 0:
         raise ValueError(f"fit_pool_weights: no usable cluster ({bad} of {C} excluded: fewer than 2 rows, a label or a row source "
                          "out of range)")
     if not math.isfinite(f1[0]):
         raise ValueError("fit_pool_weights: the NLL at w = 1 is not finite (non-finite log-posteriors?)")
-    rounds, converged = 0, False
-    f, g = float(f1[0]), None
-    while rounds < max_rounds:
-        rounds += 1
-        cand = np.vstack([w] + [w + h * np.eye(D)[d] for d in range(D)])
-        fs, gs, _, _ = pool_nll(*args, cand, log_prior)
-        f, g = float(fs[0]), gs[0]
-        held = ((w <= 0) & (g > 0)) | ((w >= hi) & (g < 0))
-        pg = np.where(held, 0.0, g)
-        if np.max(np.abs(pg)) <= gtol * used:
-            converged = True
-            break
-        H = (gs[1:] - g[None, :]) / h
-        H = 0.5 * (H + H.T)
-        free = ~held
-        p = np.zeros(D)
-        try:
-            Hf = H[np.ix_(free, free)] + 1e-10 * max(np.trace(H), 1.0) * np.eye(int(free.sum()))
-            p[free] = -np.linalg.solve(Hf, g[free])
-        except np.linalg.LinAlgError:
-            p[free] = -g[free]
-        if not (np.all(np.isfinite(p)) and p @ g < 0):
-            p = np.where(free, -g, 0.0) / max(np.max(np.abs(np.diag(H))), 1e-300)
-        steps = 2.0 ** (1 - np.arange(40))
-        trial = np.clip(w[None, :] + steps[:, None] * p[None, :], 0.0, hi)
-        ft, _, _, _ = pool_nll(*args, trial, log_prior)
-        ft = np.where(np.isfinite(ft), ft, np.inf)
-        i = int(np.argmin(ft))
-        if not ft[i] < f:
-            break
-        w, f = trial[i], float(ft[i])
-    fs, gs, _, _ = pool_nll(*args, [w], log_prior)
-    f, g = float(fs[0]), gs[0]
-    at = ["lo" if (w[d] <= 0 and g[d] > 0) else "hi" if (w[d] >= hi and g[d] < 0) else None for d in range(D)]
+    w, f, g, rounds, converged, at = _projected_newton(lambda cand: pool_nll(*args, cand, log_prior)[:2], np.ones(D), 0.0, hi, gtol, used,
+                                                       max_rounds)
     return {"weights": [float(x) for x in w], "nll": f, "nll_at_1": float(f1[0]), "grad": [float(x) for x in g], "clusters": used,
             "excluded": bad, "rounds": rounds, "converged": converged, "at_bound": at}
 
@@ -905,10 +920,9 @@ def bias_nll(base, labels, candidates):
 
 
 def _fit_bias(base, labels, hi, gtol, max_rounds):
-    """One row of the table: b in [-hi, hi]^K x {0} that minimises bias_nll, by fit_pool_weights' projected Newton scheme."""
+    """One row of the table: b in [-hi, hi]^K x {0} that minimises bias_nll, by _projected_newton over b[:K]."""
     C, k1 = base.shape
     K = k1 - 1
-    h = 1e-4
     b = np.zeros(k1)
     f0, _, bad, _ = bias_nll(base, labels, [b])
     used = C - bad
@@ -918,43 +932,13 @@ def _fit_bias(base, labels, hi, gtol, max_rounds):
         return b, rec
     if not math.isfinite(f0[0]):
         raise ValueError("fit_presence: the NLL at a zero row is not finite")
-    eye = np.eye(k1)[:K]
-    rounds, converged, f = 0, False, float(f0[0])
-    while rounds < max_rounds:
-        rounds += 1
-        fs, gs, _, _ = bias_nll(base, labels, np.vstack([b] + [b + h * eye[d] for d in range(K)]))
-        f, g = float(fs[0]), gs[0, :K]
-        x = b[:K]
-        held = ((x <= -hi) & (g > 0)) | ((x >= hi) & (g < 0))
-        pg = np.where(held, 0.0, g)
-        if np.max(np.abs(pg)) <= gtol * used:
-            converged = True
-            break
-        H = (gs[1:, :K] - g[None, :]) / h
-        H = 0.5 * (H + H.T)
-        free = ~held
-        p = np.zeros(K)
-        try:
-            Hf = H[np.ix_(free, free)] + 1e-10 * max(np.trace(H), 1.0) * np.eye(int(free.sum()))
-            p[free] = -np.linalg.solve(Hf, g[free])
-        except np.linalg.LinAlgError:
-            p[free] = -g[free]
-        if not (np.all(np.isfinite(p)) and p @ g < 0):
-            p = np.where(free, -g, 0.0) / max(np.max(np.abs(np.diag(H))), 1e-300)
-        steps = 2.0 ** (1 - np.arange(40))
-        trial = np.zeros((40, k1))
-        trial[:, :K] = np.clip(x[None, :] + steps[:, None] * p[None, :], -hi, hi)
-        ft, _, _, _ = bias_nll(base, labels, trial)
-        ft = np.where(np.isfinite(ft), ft, np.inf)
-        i = int(np.argmin(ft))
-        if not ft[i] < f:
-            break
-        b, f = trial[i], float(ft[i])
-    fs, gs, _, _ = bias_nll(base, labels, [b])
-    g = gs[0, :K]
-    rec.update({"nll": float(fs[0]), "rounds": rounds, "converged": converged, "grad": [float(v) for v in g],
-                "at_bound": ["lo" if (b[d] <= -hi and g[d] > 0) else "hi" if (b[d] >= hi and g[d] < 0) else None for d in range(K)]})
-    return b, rec
+
+    def evaluate(cand):          # the background column is pinned at 0
+        fs, gs, _, _ = bias_nll(base, labels, np.hstack([cand, np.zeros((len(cand), 1))]))
+        return fs, gs[:, :K]
+    x, f, g, rounds, converged, at = _projected_newton(evaluate, np.zeros(K), -hi, hi, gtol, used, max_rounds)
+    rec.update({"nll": f, "rounds": rounds, "converged": converged, "grad": [float(v) for v in g], "at_bound": at})
+    return np.append(x, 0.0), rec
 
 
 def fit_presence(base, patterns, labels, num_detectors, hi=16.0, gtol=1e-7, max_rounds=60):

@@ -26,6 +26,7 @@
 // stride-halving tree in LDS; pe::launch_finish (csrc/reduce2.h) adds the workgroups' partials in its stated order.
 #include "common.h"
 #include "reduce2.h"
+#include "box_residual.h"
 
 namespace {
 
@@ -229,29 +230,14 @@ __global__ __launch_bounds__(kPairThreads) void box_residual_kernel(PairArgs a) 
         bool ok = row >= 0 && row < a.N;
         double v = 0.0;
         int d = -1;
-        double sw = 0, sh = 0, tw = 0, th = 0;
-        const double* s = a.boxes + (size_t)(ok ? row : 0) * 4;
-        const double* t = a.gt + (size_t)g * 4;
         if (ok) {
             v = a.vars[row];
             d = a.source[row];
             ok = v > 0.0 && v < __builtin_huge_val() && d >= 0 && d < a.D;
         }
-        if (ok) {
-            sw = s[2] - s[0]; sh = s[3] - s[1];
-            tw = t[2] - t[0]; th = t[3] - t[1];
-            ok = sw > 0.0 && sh > 0.0 && tw > 0.0 && th > 0.0;
-        }
-        if (ok) {
-            // Box2BoxTransform.get_deltas(detection, ground truth), the expressions of pe_variance_stats
-            const double scx = s[0] + 0.5 * sw, scy = s[1] + 0.5 * sh;
-            const double tcx = t[0] + 0.5 * tw, tcy = t[1] + 0.5 * th;
+        if (ok && pe::box_residual(a.boxes + (size_t)row * 4, a.gt + (size_t)g * 4, a.w, z)) {      // pe_variance_stats' residual
             sd = sqrt(v);
             vv = v;
-            z[0] = a.w[0] * (tcx - scx) / sw;
-            z[1] = a.w[1] * (tcy - scy) / sh;
-            z[2] = a.w[2] * log(tw / sw);
-            z[3] = a.w[3] * log(th / sh);
             out_src = d;
         } else {
             pe::flag_excluded(a.flags, i);
@@ -305,24 +291,14 @@ __global__ __launch_bounds__(kPairThreads) void box_pair_kernel(PairArgs a) {
     // the sums, then the counts through the same LDS array: a stride-halving tree, the same pairs whatever the data
 #pragma unroll
     for (int v = 0; v < kHalf; ++v) x[threadIdx.x][v] = S[v];
-    for (int s = kPairThreads >> 1; s > 0; s >>= 1) {
-        __syncthreads();
-        if ((int)threadIdx.x < s)
-            for (int v = 0; v < kHalf; ++v) x[threadIdx.x][v] += x[threadIdx.x + s][v];
-    }
-    __syncthreads();
+    pe::block_tree(x, kPairThreads);
     if (threadIdx.x == 0)
         for (int v = 0; v < kHalf; ++v) a.partial[(size_t)blockIdx.x * 2 * kHalf + kHalf + v] = x[0][v];
     __syncthreads();
     long long (*xi)[kHalf] = reinterpret_cast<long long (*)[kHalf]>(x);
 #pragma unroll
     for (int v = 0; v < kHalf; ++v) xi[threadIdx.x][v] = Nc[v];
-    for (int s = kPairThreads >> 1; s > 0; s >>= 1) {
-        __syncthreads();
-        if ((int)threadIdx.x < s)
-            for (int v = 0; v < kHalf; ++v) xi[threadIdx.x][v] += xi[threadIdx.x + s][v];
-    }
-    __syncthreads();
+    pe::block_tree(xi, kPairThreads);
     if (threadIdx.x == 0)
         for (int v = 0; v < kHalf; ++v) a.partial[(size_t)blockIdx.x * 2 * kHalf + v] = __longlong_as_double(xi[0][v]);
 }
@@ -365,14 +341,8 @@ extern "C" int pe_box_pair_stats(const double* boxes, const double* variances, c
                  what);
     PE_CHECK_ARG(num_clusters == 0 || (boxes && variances && row_source && (gt_boxes || num_gt == 0)),
                  "%s: null pointer (boxes / variances / row_source / gt_boxes)", what);
-    static const float kDefaultWeights[4] = {10.f, 10.f, 5.f, 5.f};
-    const float* w = bbox_reg_weights_host ? bbox_reg_weights_host : kDefaultWeights;
     PairArgs a{};
-    for (int c = 0; c < 4; ++c) {
-        PE_CHECK_ARG(w[c] == w[c] && w[c] > 0.f && w[c] < __builtin_huge_valf(), "%s: bbox_reg_weights[%d] %g is not finite and > 0", what, c,
-                     (double)w[c]);
-        a.w[c] = (double)w[c];
-    }
+    if (int rc = pe::bbox_reg_weights(bbox_reg_weights_host, a.w, what)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = pe::zero_flags(out_flags, st, what)) return rc;
     if (num_clusters == 0) {        // nothing to add up: zeros, no launch

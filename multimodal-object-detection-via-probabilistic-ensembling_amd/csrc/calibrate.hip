@@ -5,8 +5,8 @@
 // The row arithmetic is csrc/softmax_row.h, shared with the pack kernel (csrc/pack.hip: pe_proben_pack_logits,
 // pe_proben_pack_log_posteriors), so a row gets the same bits from either.  Built with -ffp-contract=off like the other ProbEn code.
 #include "common.h"
-#include "reduce2.h"
 #include "softmax_row.h"
+#include "sweep.h"
 
 namespace {
 
@@ -31,60 +31,47 @@ __global__ __launch_bounds__(256) void calibrated_softmax_kernel(const float* lo
     }
 }
 
-constexpr int kNllThreads = 256, kNllWaves = kNllThreads / 64;
-
-struct NllArgs {
+// the model of pe::sweep (csrc/sweep.h): an item is a row, a candidate a temperature, the sums are the NLL and d NLL / d(log T).  The 64
+// lanes read the same logits (one cache line, broadcast).  The candidates stay in the kernel arguments: the workspace is all partials.
+struct NllModel {
+    static constexpr int kMaxValues = 2;
+    using Shared = pe::NoShared;
+    struct Lane { double T; };
     const float* logits;
     const int32_t* labels;
-    long long M;
-    int k1, n_t;
+    long long items;     // = M
+    int k1, nc;
     double T[64];
-    double* partial;     // [blocks, n_t, 2], added up by pe::launch_finish (csrc/reduce2.h)
+    double* partial;     // [blocks, nc, 2], added up by pe::launch_finish (csrc/reduce2.h)
     int32_t* flags;      // pe::flag_excluded: rows with a label outside [0, K]
-};
 
-// Lane = candidate temperature, wavefront = row: the 64 lanes read the same logits (one cache line, broadcast) and each keeps its own
-// two sums.  Wave w of block g takes rows g * kNllWaves + w, + gridDim.x * kNllWaves, ...: a fixed order for a fixed (M, grid).
-__global__ __launch_bounds__(kNllThreads) void temperature_nll_kernel(NllArgs a) {
-    __shared__ double part[kNllWaves][64][2];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const double T = a.T[lane < a.n_t ? lane : 0];
-    double nll = 0.0, dnll = 0.0;
-    const long long step = (long long)gridDim.x * kNllWaves;
-    for (long long r = (long long)blockIdx.x * kNllWaves + w; r < a.M; r += step) {
-        const int y = a.labels[r];
-        if (y < 0 || y >= a.k1) {
-            if (lane == 0) pe::flag_excluded(a.flags, r);
-            continue;
-        }
-        const float* row = a.logits + r * a.k1;
+    __host__ __device__ __forceinline__ int values() const { return 2; }
+    __device__ __forceinline__ void setup(Shared&) const {}
+    __device__ __forceinline__ void load(Lane& L, int c, Shared&) const { L.T = T[c]; }
+    __device__ __forceinline__ bool item(const Lane& L, double (&acc)[kMaxValues], long long r, Shared&) const {
+        const int y = labels[r];
+        if (y < 0 || y >= k1) return false;
+        const float* row = logits + r * k1;
         double m = pe::kNegInf;
-        for (int k = 0; k < a.k1; ++k) {
-            const double z = (double)row[k] / T;
+        for (int k = 0; k < k1; ++k) {
+            const double z = (double)row[k] / L.T;
             m = (z > m || z != z) ? z : m;
         }
         double s = 0.0, sz = 0.0;
-        for (int k = 0; k < a.k1; ++k) {
-            const double z = (double)row[k] / T;
+        for (int k = 0; k < k1; ++k) {
+            const double z = (double)row[k] / L.T;
             const double e = exp(z - m);
             s += e;
             sz += e * (z - m);
         }
-        const double zy = (double)row[y] / T - m;
-        nll += log(s) - zy;           // -log softmax(z)[y]
-        dnll += zy - sz / s;          // d/d(log T): z_y - sum_k p_k z_k (the shift by m cancels)
+        const double zy = (double)row[y] / L.T - m;
+        acc[0] += log(s) - zy;           // -log softmax(z)[y]
+        acc[1] += zy - sz / s;           // d/d(log T): z_y - sum_k p_k z_k (the shift by m cancels)
+        return true;
     }
-    part[w][lane][0] = nll;
-    part[w][lane][1] = dnll;
-    __syncthreads();
-    if (threadIdx.x < a.n_t) {
-        double s0 = part[0][lane][0], s1 = part[0][lane][1];
-        for (int v = 1; v < kNllWaves; ++v) { s0 += part[v][lane][0]; s1 += part[v][lane][1]; }
-        double* o = a.partial + ((size_t)blockIdx.x * a.n_t + lane) * 2;
-        o[0] = s0;
-        o[1] = s1;
-    }
-}
+};
+
+__global__ __launch_bounds__(pe::kSweepThreads) void temperature_nll_kernel(NllModel m) { pe::sweep(m); }
 
 int flat_softmax_impl(const char* what, const float* logits, int64_t num_rows, int32_t num_columns, double temperature, double* out,
                       bool logp, void* stream) {
@@ -131,15 +118,9 @@ extern "C" int pe_temperature_nll(const float* logits, const int32_t* labels, in
     PE_CHECK_ARG(num_columns >= 2, "pe_temperature_nll: num_columns %d (K + 1) < 2", num_columns);
     PE_CHECK_ARG(workspace && out && out_flags, "pe_temperature_nll: null pointer (workspace / out / out_flags)");
     PE_CHECK_ARG(num_rows == 0 || (logits && labels), "pe_temperature_nll: null pointer (logits / labels)");
-    NllArgs a{};
-    a.logits = logits; a.labels = labels; a.M = num_rows; a.k1 = num_columns; a.n_t = num_temperatures;
-    for (int t = 0; t < num_temperatures; ++t) a.T[t] = temperatures_host[t];
-    a.partial = workspace; a.flags = out_flags;
-    // the grid is a function of num_rows alone: same input, same partition, same bits
-    const int blocks = (int)std::max<long long>(1, std::min<long long>((num_rows + kNllWaves - 1) / kNllWaves,
-                                                                        PE_TEMPERATURE_NLL_MAX_BLOCKS));
-    if (int st = pe::zero_flags(out_flags, (hipStream_t)stream, "pe_temperature_nll")) return st;
-    hipLaunchKernelGGL(temperature_nll_kernel, dim3(blocks), dim3(kNllThreads), 0, (hipStream_t)stream, a);
-    PE_CHECK_LAUNCH("pe_temperature_nll");
-    return pe::launch_finish(workspace, blocks, 2 * num_temperatures, 0, nullptr, out, (hipStream_t)stream, "pe_temperature_nll");
+    NllModel m{};
+    m.logits = logits; m.labels = labels; m.items = num_rows; m.k1 = num_columns; m.nc = num_temperatures;
+    for (int t = 0; t < num_temperatures; ++t) m.T[t] = temperatures_host[t];
+    m.partial = workspace; m.flags = out_flags;
+    return pe::launch_sweep(temperature_nll_kernel, m, PE_TEMPERATURE_NLL_MAX_BLOCKS, out, (hipStream_t)stream, "pe_temperature_nll");
 }

@@ -1,5 +1,7 @@
-// The second pass and the exclusion flags of the device-side calibration statistics (pe_temperature_nll, pe_pool_nll,
-// pe_reliability_logits / _scores; pe_variance_stats takes the flags only).  DESIGN.md section 16.
+// The second pass, the exclusion flags and the workgroup tree of the six device-side calibration statistics: pe_temperature_nll,
+// pe_pool_nll and pe_bias_nll (through csrc/sweep.h), pe_reliability_logits / _scores and pe_box_pair_stats take the second pass and the
+// flags, pe_variance_stats the flags only; pe_variance_stats and pe_box_pair_stats add a workgroup's threads with block_tree.
+// DESIGN.md sections 16 and 23.
 //
 // A first-pass kernel leaves nv eight-byte values per workgroup, partial[(size_t)k * nv + v] for workgroup k: the leading n_int of them
 // int64 counts, the rest doubles.  No floating-point atomics anywhere, and the first-pass grid is a function of the item count alone,
@@ -30,6 +32,17 @@ inline int zero_flags(int32_t* flags, hipStream_t stream, const char* what) {
         return PE_ERR_HIP;
     }
     return PE_OK;
+}
+
+// x[0 .. n - 1] of NV values each -> x[0], stride-halving tree: level by level, the same pairs whatever the data.  n is a power of two
+// and the workgroup's size; the caller fills x before and lets thread 0 read x[0] after (no barrier follows the last level).
+template <typename T, int NV>
+__device__ __forceinline__ void block_tree(T (*x)[NV], int n) {
+    for (int s = n >> 1; s > 0; s >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < s)
+            for (int v = 0; v < NV; ++v) x[threadIdx.x][v] += x[threadIdx.x + s][v];
+    }
 }
 
 #ifndef PE_REDUCE2_FLAGS_ONLY

@@ -14,6 +14,7 @@
 #include "common.h"
 #define PE_REDUCE2_FLAGS_ONLY          // the flags, not the finish kernel: see the note at variance_stats_finish_kernel
 #include "reduce2.h"
+#include "box_residual.h"
 
 namespace {
 
@@ -87,15 +88,6 @@ struct StatArgs {
     int32_t* flags;       // pe::flag_excluded (csrc/reduce2.h): excluded rows
 };
 
-// x[0..255] of the five values -> x[0], stride-halving tree: level by level, the same pairs whatever the data
-__device__ __forceinline__ void block_tree(double (*x)[kStatValues], int n) {
-    for (int s = n >> 1; s > 0; s >>= 1) {
-        __syncthreads();
-        if ((int)threadIdx.x < s)
-            for (int v = 0; v < kStatValues; ++v) x[threadIdx.x][v] += x[threadIdx.x + s][v];
-    }
-}
-
 __global__ __launch_bounds__(kStatThreads) void variance_stats_kernel(StatArgs a) {
     __shared__ double x[kStatThreads][kStatValues];
     double n = 0.0, sq = 0.0, sl = 0.0, c1 = 0.0, c2 = 0.0;
@@ -104,26 +96,12 @@ __global__ __launch_bounds__(kStatThreads) void variance_stats_kernel(StatArgs a
         const int m = a.match[r];
         const double v = a.var[r];
         bool ok = m >= 0 && m < a.G && v > 0.0 && v < __builtin_huge_val();       // NaN fails v > 0; an index beyond the table is never read
-        double sw = 0, sh = 0, tw = 0, th = 0;
-        const double* s = a.det + r * 4;
-        const double* t = a.gt + (size_t)(ok ? m : 0) * 4;
-        if (ok) {
-            sw = s[2] - s[0]; sh = s[3] - s[1];
-            tw = t[2] - t[0]; th = t[3] - t[1];
-            ok = sw > 0.0 && sh > 0.0 && tw > 0.0 && th > 0.0;
-        }
+        double res[4];
+        if (ok) ok = pe::box_residual(a.det + r * 4, a.gt + (size_t)m * 4, a.w, res);
         if (!ok) {
             pe::flag_excluded(a.flags, r);
             continue;
         }
-        // Box2BoxTransform.get_deltas(detection, ground truth): w[:2] * (tc - sc) / swh, w[2:] * log(twh / swh)
-        const double scx = s[0] + 0.5 * sw, scy = s[1] + 0.5 * sh;
-        const double tcx = t[0] + 0.5 * tw, tcy = t[1] + 0.5 * th;
-        double res[4];
-        res[0] = a.w[0] * (tcx - scx) / sw;
-        res[1] = a.w[1] * (tcy - scy) / sh;
-        res[2] = a.w[2] * log(tw / sw);
-        res[3] = a.w[3] * log(th / sh);
         const double sv = a.s * v, sv4 = 4.0 * sv;
         double q = 0.0;
         for (int c = 0; c < 4; ++c) {
@@ -137,7 +115,7 @@ __global__ __launch_bounds__(kStatThreads) void variance_stats_kernel(StatArgs a
         sl += log(v);
     }
     x[threadIdx.x][0] = n; x[threadIdx.x][1] = sq; x[threadIdx.x][2] = sl; x[threadIdx.x][3] = c1; x[threadIdx.x][4] = c2;
-    block_tree(x, kStatThreads);
+    pe::block_tree(x, kStatThreads);
     if (threadIdx.x == 0)
         for (int v = 0; v < kStatValues; ++v) a.partial[(size_t)blockIdx.x * kStatValues + v] = x[0][v];
 }
@@ -149,7 +127,7 @@ __global__ __launch_bounds__(PE_VARIANCE_STATS_MAX_BLOCKS) void variance_stats_f
     __shared__ double x[PE_VARIANCE_STATS_MAX_BLOCKS][kStatValues];
     for (int v = 0; v < kStatValues; ++v)
         x[threadIdx.x][v] = (int)threadIdx.x < blocks ? partial[(size_t)threadIdx.x * kStatValues + v] : 0.0;
-    block_tree(x, PE_VARIANCE_STATS_MAX_BLOCKS);
+    pe::block_tree(x, PE_VARIANCE_STATS_MAX_BLOCKS);
     if (threadIdx.x == 0)
         for (int v = 0; v < kStatValues; ++v) out[v] = x[0][v];
 }
@@ -183,14 +161,8 @@ extern "C" int pe_variance_stats(const double* det_boxes, const int32_t* match, 
     PE_CHECK_ARG(workspace && out && out_flags, "pe_variance_stats: null pointer (workspace / out / out_flags)");
     PE_CHECK_ARG(num_rows == 0 || (det_boxes && match && variances && (gt_boxes || num_gt == 0)),
                  "pe_variance_stats: null pointer (det_boxes / match / gt_boxes / variances)");
-    static const float kDefaultWeights[4] = {10.f, 10.f, 5.f, 5.f};
-    const float* w = bbox_reg_weights_host ? bbox_reg_weights_host : kDefaultWeights;
     StatArgs a{};
-    for (int c = 0; c < 4; ++c) {
-        PE_CHECK_ARG(w[c] == w[c] && w[c] > 0.f && w[c] < __builtin_huge_valf(), "pe_variance_stats: bbox_reg_weights[%d] %g is not finite and > 0",
-                     c, (double)w[c]);
-        a.w[c] = (double)w[c];
-    }
+    if (int rc = pe::bbox_reg_weights(bbox_reg_weights_host, a.w, "pe_variance_stats")) return rc;
     a.det = det_boxes; a.match = match; a.gt = gt_boxes; a.var = variances; a.M = num_rows; a.G = num_gt; a.s = scale;
     a.partial = workspace; a.flags = out_flags;
     // the grid is a function of num_rows alone: same input, same partition, same bits

@@ -1,24 +1,27 @@
-"""Generate tests/golden/stat_sums_parent.npz: what the four device-side calibration statistics returned for a set of small cases,
-recorded on the GPU at the commit BEFORE their second passes became one kernel (DESIGN.md names it).
-tests/test_stat_sums_golden_gpu.py holds the same calls to these bits.
+"""Generate tests/golden/stat_sums_parent.npz and stat_sums_parent2.npz: what the device-side calibration statistics returned for a
+set of small cases, recorded on the GPU at an earlier commit.  The first file (temperature, pool, reliability, variance) is from the
+commit BEFORE their second passes became one kernel; the second (bias, boxpair) from the commit before the first passes and the
+fitters were unified (DESIGN.md names both).  tests/test_stat_sums_golden_gpu.py holds the same calls to these bits.
 
-    python tests/golden/gen_stat_sums.py [--out FILE]        on the GPU, at that commit
-    python tests/golden/gen_stat_sums.py --check-inputs      anywhere: the coverage condition below on the host alone
+    python tests/golden/gen_stat_sums.py FILE.npz [--out PATH]     on the GPU, at that file's commit
+    python tests/golden/gen_stat_sums.py --check-inputs            anywhere: the coverage condition below on the host alone
 
-Only the public Python surface is used (calibration.temperature_nll, pool_nll, reliability, reliability_scores, variance_stats) and
-the file holds OUTPUTS ONLY: per case `<name>_f64` (every returned float64, in order) and `<name>_i64` (every returned integer, the
+Only the public Python surface is used (calibration.temperature_nll, pool_nll, reliability, reliability_scores, variance_stats,
+bias_nll, box_pair_stats) and a file holds OUTPUTS ONLY: per case `<name>_f64` (every returned float64, in order) and `<name>_i64` (every returned integer, the
 two flag values last).  The inputs are closed-form integer formulas (multipliers modulo the prime 8191, scaled) that the test
 rebuilds by importing this file: no random generator is involved.
 
 Cases, by what the shared second pass sees:
   workgroups   1, 5 (one per segment, 11 segments empty), 17 (two per segment, the last used segment short), 1024 at the cap with
                one more unit of work behind it: 3 / 20 / 68 / 4100 rows or clusters at 4 a workgroup (temperature, pool),
-               200 / 1280 / 4352 / 262400 rows at 256 a workgroup (reliability, variance)
+               (and bias), 200 / 1280 / 4352 / 262400 rows at 256 a workgroup (reliability, variance; boxpair: clusters of 1 to 3
+               member rows)
   values       temperature n_t = 1, 32, 64 (2, 64, 128 values a workgroup); pool (candidates, detectors) = (1, 1), (64, 8) (2, 576),
                with and without log_prior; reliability bins = 1, 15, 64 (4, 60, 256), both sources, with and without `classes`,
-               K + 1 = 4 and 65
+               K + 1 = 4 and 65; bias (candidates, K + 1) = (1, 2), (40, 4), (64, 16); boxpair detectors = 1, 2, 4
   excluded     every case has excluded items and the last index is one of them (3 items: the last only), so both flag values are
-               non-trivial; a variance case holds each of its exclusion causes once.  temperature_nll raises on an excluded row, so
+               non-trivial; a variance or boxpair case holds each of its exclusion causes once (a boxpair item is a member row; a
+               cluster without a ground-truth box adds nothing and is no exclusion).  temperature_nll raises on an excluded row, so
                a temperature case is two calls: the clean labels give the sums, the labels with bad rows give the message, whose two
                numbers are the flags.
 
@@ -50,12 +53,16 @@ RELIABILITY = [("own", 200, 1, 4), ("own", 1280, 15, 65), ("own", 4352, 64, 4), 
                ("scores", 200, 15, 0), ("scores", 1280, 64, 0), ("scores", 4352, 1, 0), ("scores", 262400, 15, 0),
                ("scores", 262400, 1, 0)]
 VARIANCE = [(200, 1.0), (1280, 1.0), (4352, 0.75), (262400, 0.75)]                                           # (M, scale)
+BIAS = [(C, nc, k1) for C in (3, 20, 68, 4100) for nc, k1 in ((1, 2), (40, 4), (64, 16))]                      # (C, candidates, K + 1)
+BOXPAIR = [(200, 1), (1280, 2), (4352, 4), (262400, 1), (262400, 4)]                                          # (C, detectors)
 CASES = ([("temperature", c) for c in TEMPERATURE] + [("pool", c) for c in POOL] + [("reliability", c) for c in RELIABILITY] +
          [("variance", c) for c in VARIANCE])
+CASES2 = [("bias", c) for c in BIAS] + [("boxpair", c) for c in BOXPAIR]
+FILES = {"stat_sums_parent.npz": CASES, "stat_sums_parent2.npz": CASES2}          # a file per commit of record
 
 
 def case_name(family, c):
-    return family[0] + "_" + "_".join(str(int(x) if isinstance(x, bool) else x).replace(".", "p") for x in c)
+    return {"boxpair": "bp"}.get(family, family[0]) + "_" + "_".join(str(int(x) if isinstance(x, bool) else x).replace(".", "p") for x in c)
 
 
 def frac(i, a=1, c=0):
@@ -146,6 +153,54 @@ def variance_input(M):
 VARIANCE_EXCLUDED = (10, 20, 30, 40, 50, 60, 70)          # and M - 1
 
 
+def bias_input(C, nc, k1):
+    """base f64 [C, k1], labels i32 [C], candidates f64 [nc, k1].  Excluded: the last cluster (label k1), and with room a label of -1
+    and a NaN base entry."""
+    r, k = np.arange(C, dtype=np.int64)[:, None], np.arange(k1, dtype=np.int64)[None]
+    base = -(0.05 + 6.0 * frac(r * 389 + k * 1277 + r * k * 31, 1, 5))
+    labels = ((np.arange(C) * 3 + 1) % k1).astype(np.int32)
+    ex = planted(C)
+    labels[ex[-1]] = k1
+    if len(ex) == 3:
+        labels[ex[0]] = -1
+        base[ex[1], 1] = np.nan
+    cand = ((np.arange(nc)[:, None] * 5 + np.arange(k1)[None] * 3) % 16) / 8.0 - 1.0
+    return base, labels, cand
+
+
+BOXPAIR_GT = 38           # as VARIANCE_GT: the last box is degenerate and only the planted cluster matches it
+BOXPAIR_EXCLUDED = (10, 20, 30, 40, 50, 60, 72, 80, 90)          # member rows; and the last
+BOXPAIR_NO_MATCH = (100, 101)                                    # clusters without a ground-truth box: -1, beyond the table
+
+
+def boxpair_input(C, D):
+    """row_boxes f64 [N, 4], row_vars f64 [N], row_source i32 [N], member_rows i32 [N], cluster_offsets i32 [C + 1], cluster_match i32
+    [C], gt f64 [38, 4]: cluster c has 1 + c mod 3 member rows.  Excluded, one member row each: a member_rows entry of -1 / N, a
+    variance of 0 / NaN / inf, a degenerate row box, a degenerate ground-truth box (member 72 is cluster 36, of one row), a source of
+    D / -1; and the last member row (a variance of -1)."""
+    c = np.arange(C, dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(1 + c % 3)]).astype(np.int32)
+    N = int(offs[-1])
+    i = np.arange(N, dtype=np.int64)
+    cl = np.repeat(c, 1 + c % 3)
+
+    def boxes(j, a):
+        x1, y1 = 500.0 * frac(j, 613 + a, 1), 400.0 * frac(j, 1277 + a, 2)
+        return np.stack([x1, y1, x1 + 20.0 + 100.0 * frac(j, 71 + a, 3), y1 + 20.0 + 80.0 * frac(j, 97 + a, 4)], 1)
+    rb, gt = boxes(i, 0), boxes(np.arange(BOXPAIR_GT, dtype=np.int64), 100)
+    gt[-1, 2] = gt[-1, 0]
+    var = 0.001 + 2.0 * frac(i, 389, 7)
+    src = ((i * 3 + cl) % D).astype(np.int32)
+    mem = i.astype(np.int32)
+    match = (c % (BOXPAIR_GT - 1)).astype(np.int32)
+    match[BOXPAIR_NO_MATCH[0]], match[BOXPAIR_NO_MATCH[1]], match[36] = -1, BOXPAIR_GT, BOXPAIR_GT - 1
+    mem[10], mem[20] = -1, N
+    var[30], var[40], var[50], var[N - 1] = 0.0, np.nan, np.inf, -1.0
+    rb[60, 2] = rb[60, 0] - 1.0
+    src[80], src[90] = D, -1
+    return rb, var, src, mem, offs, match, gt
+
+
 def run_case(family, c):
     """The case on the GPU through the public calls -> (float64 array, int64 array)."""
     import torch
@@ -179,6 +234,15 @@ def run_case(family, c):
         f = [x for b in out["bins"] for x in (b["conf_sum"], b["brier_sum"])] + [out["ece"], out["mce"], out["brier"]]
         i = [x for b in out["bins"] for x in (b["count"], b["correct"])] + [out["rows"], out["excluded"], out["last_excluded"]]
         return np.asarray(f, np.float64), np.asarray(i, np.int64)
+    if family == "bias":
+        base, labels, cand = bias_input(*c)
+        nll, grad, bad, last = C.bias_nll(dev(base), dev(labels), cand)
+        return np.concatenate([nll, grad.reshape(-1)]), np.asarray([bad, last], np.int64)
+    if family == "boxpair":
+        rb, var, src, mem, offs, match, gt = boxpair_input(*c)
+        s = C.box_pair_stats(dev(rb), dev(var), dev(src), dev(mem), dev(offs), dev(match), dev(gt), c[1])
+        return (np.concatenate([np.asarray(s["Q"], np.float64), s["S"].reshape(-1)]),
+                np.concatenate([np.asarray(s["rows"], np.int64), s["pairs"].reshape(-1), [s["excluded"], s["last_excluded"]]]).astype(np.int64))
     M, scale = c
     det, match, gt, var = variance_input(M)
     s = C.variance_stats(dev(det), dev(match), dev(gt), dev(var), scale)
@@ -190,11 +254,18 @@ def items_and_excluded(family, c, i64):
     """(items of the case, excluded items it reported, the last excluded index it reported)."""
     if family == "temperature":
         return c[0], int(i64[0]), int(i64[1])
-    if family == "pool":
+    if family in ("pool", "bias"):
         return c[0], int(i64[0]), int(i64[1])
     if family == "reliability":
         return c[1], int(i64[-2]), int(i64[-1])
+    if family == "boxpair":          # an item is a member row: clusters c = 3 q + r hold 1 + r of them
+        return sum(len(range(r, c[0], 3)) * (1 + r) for r in range(3)), int(i64[-2]), int(i64[-1])
     return c[0], int(i64[3]), int(i64[4])
+
+
+def first_pass_units(family, c):
+    """(what the first pass's grid is sized from, units a workgroup): rows or clusters."""
+    return (c[1] if family == "reliability" else c[0]), (4 if family in ("temperature", "pool", "bias") else 256)
 
 
 # ---- the coverage condition: the host's terms of one sum per family, added in ascending order and in the kernels' order ------------
@@ -223,9 +294,10 @@ def _tree(x):
 
 
 def two_pass_sum(family, terms):
-    """`terms` (one per item, 0.0 for an excluded one) in the order the family's kernels add them."""
+    """`terms` (one per item, 0.0 for an excluded one; boxpair: [clusters, 3], a cluster's member rows in order, 0.0 where it has
+    fewer) in the order the family's kernels add them."""
     n = len(terms)
-    if family in ("temperature", "pool"):          # wavefront = item, 4 wavefronts a workgroup
+    if family in ("temperature", "pool", "bias"):          # wavefront = item, 4 wavefronts a workgroup
         blocks = max(1, min(-(-n // 4), 1024))
         waves = _seq(_padded(terms, 4 * blocks).reshape(-1, 4 * blocks), 0)
         return _segments(_seq(waves.reshape(blocks, 4), 1))
@@ -233,6 +305,9 @@ def two_pass_sum(family, terms):
     if family == "reliability":                    # wavefront = groups of 64 rows, one bin
         x = _padded(terms, 256 * blocks).reshape(-1, 4 * blocks, 64).transpose(1, 0, 2).reshape(4 * blocks, -1)
         return _segments(_seq(_seq(x, 1).reshape(blocks, 4), 1))
+    if family == "boxpair":                        # thread = cluster mod the grid, its clusters' member rows in order; a tree, then segments
+        x = np.concatenate([terms, np.zeros(((-n) % (256 * blocks), 3))]).reshape(-1, 256 * blocks, 3).transpose(1, 0, 2)
+        return _segments(_tree(_seq(x.reshape(256 * blocks, -1), 1).reshape(blocks, 256)))
     threads = _seq(_padded(terms, 256 * blocks).reshape(-1, 256 * blocks), 0)          # variance: thread = row mod the grid, trees
     return _tree(_padded(_tree(threads.reshape(blocks, 256)), 1024)[None])[0]
 
@@ -259,30 +334,51 @@ def host_terms(family, c):
             return None
         conf, _ = reliability_input(*c[:2], c[3])
         return np.where((conf >= 0) & (conf <= 1), conf, 0.0)
-    det, match, gt, var = variance_input(c[0])
-    ok = np.ones(c[0], bool)
-    ok[list(VARIANCE_EXCLUDED) + [c[0] - 1]] = False
+    if family == "bias":
+        if c[1:] != (1, 2):
+            return None
+        base, labels, cand = bias_input(*c)
+        ok = (labels >= 0) & (labels < 2) & np.isfinite(base).all(1)
+        a = np.where(ok[:, None], base, 0.0) + cand[0][None]
+        top = a.max(1)
+        e = np.exp(a - top[:, None])
+        return np.where(ok, np.log(e[:, 0] + e[:, 1]) - (a[np.arange(len(a)), np.clip(labels, 0, 1)] - top), 0.0)
+    if family == "boxpair":
+        if c[1] != 1:
+            return None
+        det, var, _, _, offs, cmatch, gt = boxpair_input(*c)
+        match = np.repeat(cmatch, np.diff(offs))
+        ok = (match >= 0) & (match < BOXPAIR_GT)
+        ok[list(BOXPAIR_EXCLUDED) + [len(det) - 1]] = False
+    else:
+        det, match, gt, var = variance_input(c[0])
+        ok = np.ones(c[0], bool)
+        ok[list(VARIANCE_EXCLUDED) + [c[0] - 1]] = False
     t = gt[np.where(ok, match, 0)]
     sw, sh, tw, th = det[:, 2] - det[:, 0], det[:, 3] - det[:, 1], t[:, 2] - t[:, 0], t[:, 3] - t[:, 1]
     with np.errstate(all="ignore"):
         res = np.stack([10.0 * ((t[:, 0] + 0.5 * tw) - (det[:, 0] + 0.5 * sw)) / sw, 10.0 * ((t[:, 1] + 0.5 * th) - (det[:, 1] + 0.5 * sh)) / sh,
                         5.0 * np.log(tw / sw), 5.0 * np.log(th / sh)], 1)
-        q = _seq(res * res / var[:, None], 1)
-    return np.where(ok, q, 0.0)
+        q = np.where(ok, _seq(res * res / var[:, None], 1), 0.0)
+    if family == "boxpair":          # Q_0 of one detector: [clusters, 3]
+        out = np.zeros((c[0], 3))
+        out[np.repeat(np.arange(c[0]), np.diff(offs)), np.arange(len(q)) - np.repeat(offs[:-1], np.diff(offs))] = q
+        return out
+    return q
 
 
 def check_inputs():
     """Host only: per family, the cases whose terms add up differently in ascending order and in the kernels' order."""
     told = {}
-    for family, c in CASES:
+    for family, c in CASES + CASES2:
         t = host_terms(family, c)
         if t is None:
             continue
         assert np.isfinite(t).all(), (family, c)
-        asc, dev = float(_seq(t)), float(two_pass_sum(family, t))
+        asc, dev = float(_seq(t.reshape(-1))), float(two_pass_sum(family, t))
         told.setdefault(family, []).append(asc != dev)
         print(f"{case_name(family, c):28s} ascending {asc!r:24s} two-pass order {dev!r:24s} {'differ' if asc != dev else 'equal'}")
-    assert set(told) == {"temperature", "pool", "reliability", "variance"} and all(any(v) for v in told.values()), told
+    assert set(told) == {f for f, _ in CASES + CASES2} and all(any(v) for v in told.values()), told
     return told
 
 
@@ -291,9 +387,12 @@ def main():
         check_inputs()
         return
     import proben_amd  # noqa: F401
-    path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(HERE, "stat_sums_parent.npz")
+    which = [a for a in sys.argv[1:] if a in FILES]
+    assert len(which) == 1, f"name the file to record: one of {sorted(FILES)}"
+    cases = FILES[which[0]]
+    path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(HERE, which[0])
     z, told = {}, {}
-    for family, c in CASES:
+    for family, c in cases:
         name = case_name(family, c)
         f64, i64 = run_case(family, c)
         items, bad, last = items_and_excluded(family, c, i64)
@@ -304,12 +403,12 @@ def main():
         if t is not None:
             # the host's terms in the kernels' order give the device's bits, so a difference from ascending order is the order's alone
             assert float(two_pass_sum(family, t)) == float(f64[0]), (name, float(two_pass_sum(family, t)), float(f64[0]))
-            told.setdefault(family, []).append(float(_seq(t)) != float(f64[0]))
-            print(f"{name:28s} device {float(f64[0])!r:24s} host ascending {float(_seq(t))!r:24s} host two-pass order "
+            told.setdefault(family, []).append(float(_seq(t.reshape(-1))) != float(f64[0]))
+            print(f"{name:28s} device {float(f64[0])!r:24s} host ascending {float(_seq(t.reshape(-1)))!r:24s} host two-pass order "
                   f"{float(two_pass_sum(family, t))!r}", flush=True)
-    assert set(told) == {"temperature", "pool", "reliability", "variance"} and all(any(v) for v in told.values()), told
+    assert set(told) == {f for f, _ in cases} and all(any(v) for v in told.values()), told
     np.savez_compressed(path, **z)
-    print("wrote", path, os.path.getsize(path), "bytes,", len(CASES), "cases")
+    print("wrote", path, os.path.getsize(path), "bytes,", len(cases), "cases")
 
 
 if __name__ == "__main__":
