@@ -18,15 +18,11 @@ SIGNATURES = {
     "pe_proben_pack_logits": [c_void_p] * 6 + [c_int] * 6 + [c_void_p] * 9,
     "pe_proben_pack_log_posteriors": [c_void_p] * 6 + [c_int] * 6 + [c_void_p] * 10,
     "pe_log_softmax": [c_void_p, ctypes.c_int64, c_int, c_double, c_void_p, c_void_p],
-    "pe_proben_fuse_batch_logp": [c_void_p] * 8 + [c_int] * 4 + [c_double] * 3 + [c_void_p] * 6 + [c_void_p],
     "pe_calibrated_softmax": [c_void_p, ctypes.c_int64, c_int, c_double, c_void_p, c_void_p],
     "pe_temperature_nll": [c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "pe_match_ground_truth": [c_void_p] * 6 + [c_int, c_double, c_int] + [c_void_p] * 4,
     "pe_variance_stats": [c_void_p] * 4 + [ctypes.c_int64, ctypes.c_int64, c_void_p, c_double] + [c_void_p] * 4,
     "pe_proben_pack_calibrated": [c_void_p] * 9 + [c_int] * 6 + [c_void_p] * 10,
-    "pe_proben_fuse_batch_pooled": [c_void_p] * 9 + [c_int] * 4 + [c_double] * 3 + [c_void_p] * 2 + [c_int] + [c_void_p] * 6 + [c_void_p],
-    "pe_proben_fuse_batch_posterior": [c_void_p] * 9 + [c_int] * 4 + [c_double] * 3 + [c_void_p] * 2 + [c_int] + [c_void_p] * 9 + [c_void_p],
-    "pe_proben_fuse_batch_presence": [c_void_p] * 9 + [c_int] * 4 + [c_double] * 3 + [c_void_p] * 3 + [c_int] + [c_void_p] * 10 + [c_void_p],
     "pe_bias_nll": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "pe_box_gls_batch": [c_void_p] * 7 + [c_int, c_int, c_void_p, c_int] + [c_void_p] * 3,
     "pe_box_pair_stats": [c_void_p] * 3 + [ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_int64,
@@ -36,7 +32,6 @@ SIGNATURES = {
                     c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "pe_reliability_logits": [c_void_p] * 3 + [ctypes.c_int64, c_int, c_double, c_int] + [c_void_p] * 5,
     "pe_reliability_scores": [c_void_p] * 2 + [ctypes.c_int64, c_int] + [c_void_p] * 5,
-    "pe_proben_fuse_batch": [c_void_p] * 8 + [c_int] * 5 + [c_double] * 3 + [c_void_p] * 5 + [c_void_p],
     "pe_conv2d_nhwc_f16": [c_void_p] * 5 + [c_int] * 14 + [c_void_p],
     "pe_conv_wd_supported": [c_int] * 6,
     "pe_conv_wd_launch_supported": [c_int] * 6,
@@ -75,6 +70,21 @@ SIGNATURES = {
                          c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "pe_boxhead_finalize": [c_void_p] + [c_int] * 7 + [c_void_p] * 18,
 }
+
+# The fusion's five entry points share one parameter order; each leaves out the fields it does not have.  (field, ctype, the entry
+# points that carry it, by the suffix of "pe_proben_fuse_batch"): SIGNATURES and fusion.fuse_batch's argument lists both come from here.
+_EVERY = ("", "_logp", "_pooled", "_posterior", "_presence")
+_LOGP, _WIDE = _EVERY[1:], _EVERY[2:]
+FUSE_FIELDS = (
+    [(f, c_void_p, _EVERY) for f in ("boxes", "scores", "probs", "vars", "classes")] + [("row_source", c_void_p, _WIDE)] +
+    [(f, c_void_p, _EVERY) for f in ("offsets", "row_counts", "passthrough")] + [(f, c_int, _EVERY) for f in ("B", "K", "max_rows")] +
+    [("score_mode", c_int, ("",)), ("box_mode", c_int, _EVERY)] + [(f, c_double, _EVERY) for f in ("thr", "fw", "fh")] +
+    [("log_prior", c_void_p, _LOGP), ("pool_weights", c_void_p, _WIDE), ("presence", c_void_p, ("_presence",)), ("num_detectors", c_int, _WIDE)] +
+    [(f, c_void_p, _EVERY) for f in ("out_boxes", "out_scores", "out_classes", "out_keep", "out_counts")] + [("out_cluster", c_void_p, _WIDE)] +
+    [(f, c_void_p, _WIDE[1:]) for f in ("out_log_posterior", "out_vars", "out_members")] + [("out_pattern", c_void_p, ("_presence",)), ("stream", c_void_p, _EVERY)])
+# entry point -> the fields it takes, in its parameter order; its argtypes are the same selection of the ctypes
+FUSE_ORDER = {"pe_proben_fuse_batch" + e: [f for f, _, entries in FUSE_FIELDS if e in entries] for e in _EVERY}
+SIGNATURES.update({"pe_proben_fuse_batch" + e: [t for _, t, entries in FUSE_FIELDS if e in entries] for e in _EVERY})
 _RESTYPE = {"pe_last_error": ctypes.c_char_p, "pe_nms_scratch_bytes": ctypes.c_size_t, "pe_rpn_scratch_bytes": ctypes.c_size_t,
              "pe_bneck64_packed_bytes": ctypes.c_size_t, "pe_test_conv_variant": ctypes.c_char_p}
 

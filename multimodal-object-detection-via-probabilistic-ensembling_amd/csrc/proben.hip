@@ -15,33 +15,69 @@
 
 namespace {
 
+// First what every entry point passes, in the order the five C signatures share (a wrapper lists exactly these, max_rows as 0: it is
+// fuse_impl's to set); then, defaulted to "absent", what only some pass: a wrapper assigns those it has by name.
 struct ProbenArgs {
-    const double* boxes;
-    const double* scores;
-    const double* probs;
-    const double* vars;
-    const int32_t* classes;
-    const int32_t* offsets;
-    const int32_t* row_counts;
-    const int32_t* passthrough;
-    int32_t B, K, max_rows, score_mode, box_mode;
-    double thr, fw, fh;
-    double* out_boxes;
-    float* out_scores;
-    float* out_classes;
-    int32_t* out_keep;
-    int32_t* out_counts;
-    const double* log_prior;   // LOGP only: optional [K+1] log class prior (NULL = uniform)
-    const int32_t* row_source;    // POOL only: [Ntot] detector index of each row
-    const double* pool_weights;   // POOL only: [num_detectors] fusion exponents
-    int32_t num_detectors;        // POOL only
-    int32_t* out_cluster;         // POOL / POST, optional: [Ntot] output row of the cluster each input row ended in
-    double* out_log_posterior;    // POST only: [Ntot, K+1] the fused rows' normalised log-posterior
-    double* out_vars;             // POST only: [Ntot] the fused boxes' variance
-    int32_t* out_members;         // POST only: [Ntot] rows in the cluster
-    const double* presence;       // PRES only: [(1 << num_detectors) * (K+1)] log-evidence of each presence pattern (row 0 unused)
-    int32_t* out_pattern;         // PRES only, optional: [Ntot] the fused rows' presence pattern
+    const double *boxes = nullptr, *scores = nullptr, *probs = nullptr, *vars = nullptr;
+    const int32_t *classes = nullptr, *offsets = nullptr, *row_counts = nullptr, *passthrough = nullptr;
+    int32_t B = 0, K = 0, max_rows = 0, score_mode = 0, box_mode = 0;
+    double thr = 0.0, fw = 0.0, fh = 0.0;
+    double* out_boxes = nullptr;
+    float *out_scores = nullptr, *out_classes = nullptr;
+    int32_t *out_keep = nullptr, *out_counts = nullptr;
+    const double* log_prior = nullptr;      // LOGP only: optional [K+1] log class prior (NULL = uniform)
+    const int32_t* row_source = nullptr;    // POOL only: [Ntot] detector index of each row
+    const double* pool_weights = nullptr;   // POOL only: [num_detectors] fusion exponents
+    int32_t num_detectors = 0;              // POOL only
+    int32_t* out_cluster = nullptr;         // POOL / POST, optional: [Ntot] output row of the cluster each input row ended in
+    double* out_log_posterior = nullptr;    // POST only: [Ntot, K+1] the fused rows' normalised log-posterior
+    double* out_vars = nullptr;             // POST only: [Ntot] the fused boxes' variance
+    int32_t* out_members = nullptr;         // POST only: [Ntot] rows in the cluster
+    const double* presence = nullptr;       // PRES only: [(1 << num_detectors) * (K+1)] log-evidence of each presence pattern (row 0 unused)
+    int32_t* out_pattern = nullptr;         // PRES only, optional: [Ntot] the fused rows' presence pattern
 };
+
+// The dynamic LDS of one image, stated once: every array in order, for max_rows R (even, so that every array starts 8-byte aligned), L
+// log-probability columns and the mode's optional arrays.  The kernel walks it with typed pointers into its LDS (LdsPointers), fuse_impl
+// with byte counts (LdsBytes) for the size of either clustering form and the capacity it prints: the same statement gives both.  All
+// arrays are indexed by SORTED position unless noted.
+struct LdsPointers {
+    template <typename T> using at = T*;
+    unsigned char* next;
+    template <typename T> __device__ T* take(size_t count) { T* p = reinterpret_cast<T*>(next); next = reinterpret_cast<unsigned char*>(p + count); return p; }
+};
+struct LdsBytes {
+    template <typename T> using at = size_t;
+    size_t next;
+    template <typename T> size_t take(size_t count) { const size_t p = next; next += count * sizeof(T); return p; }
+};
+template <typename Cursor>
+struct FuseLayout {
+    template <typename T> using at = typename Cursor::template at<T>;
+    at<unsigned long long> mbits, kbits;          // BITS: match [R][W] (then the clusters' member bits) and kill [R][W], W = 64-row words
+    at<double> gx1, gy1, gx2, gy2, gar, gsc;      // [R]: class-band shifted corners, legacy "+1" area, score
+    at<double> glog, gob, ginv, gw;               // [L][R] log-probabilities, [4][R] original coordinates, [R] 1 / variance, POOL: [R] weight
+    at<int> ord, gcls, gsrc;                      // [R]: sorted position -> original row, class id, PRES: detector index (-1 = bad)
+    at<unsigned short> members, cl_piv, cl_beg, cl_cnt;   // [R]: all clusters' matches back to back; per cluster pivot, first member, matches
+    at<unsigned char> alive;                      // [R], sequential form only (the bit-matrix form leaves it unused)
+    __host__ __device__ FuseLayout(Cursor c, int R, int L, bool pool, bool pres, bool bits) {
+        const size_t matrix = bits ? (size_t)R * ((R + 63) >> 6) : 0;
+        mbits = c.template take<unsigned long long>(matrix); kbits = c.template take<unsigned long long>(matrix);
+        gx1 = c.template take<double>(R); gy1 = c.template take<double>(R); gx2 = c.template take<double>(R); gy2 = c.template take<double>(R);
+        gar = c.template take<double>(R); gsc = c.template take<double>(R); glog = c.template take<double>((size_t)L * R);
+        gob = c.template take<double>(4 * (size_t)R); ginv = c.template take<double>(R); gw = c.template take<double>(pool ? R : 0);
+        ord = c.template take<int>(R); gcls = c.template take<int>(R); gsrc = c.template take<int>(pres ? R : 0);
+        members = c.template take<unsigned short>(R); cl_piv = c.template take<unsigned short>(R);
+        cl_beg = c.template take<unsigned short>(R); cl_cnt = c.template take<unsigned short>(R);
+        alive = c.template take<unsigned char>(R);
+    }
+};
+// The bytes of dynamic LDS at max_rows R (the last array and 16 bytes of slack), and what one more row costs in the sequential form
+// (which is linear in R).
+inline size_t fuse_lds_bytes(int R, int L, bool pool, bool pres, bool bits) { return FuseLayout<LdsBytes>(LdsBytes{0}, R, L, pool, pres, bits).alive + R + 16; }
+inline size_t fuse_row_bytes(int L, bool pool, bool pres) { return (fuse_lds_bytes(2, L, pool, pres, false) - fuse_lds_bytes(0, L, pool, pres, false)) / 2; }
+constexpr size_t kFuseLdsLimit = 160 * 1024;
+constexpr size_t kFuseLdsStatic = 512;          // the kernels' static __shared__ scratch (ncl_s, reductions)
 
 // Sort rule shared with oracle/proben.py: NaN first, score descending, ties by ORIGINAL index
 // descending (== reversed stable ascending argsort, the reference's `argsort()[::-1]`).
@@ -88,26 +124,49 @@ __device__ __forceinline__ bool precedes(double sa, int ia, double sb, int ib) {
 // instantiations compile to what they were.
 constexpr int kFuseThreads = 1024;
 
-// PRES, a cluster of one row (phase 4 and the passthrough branch): the score / class rule of phase 4's log-posterior fusion, the same
-// operations in the same order, over L columns a_j = column(j); lq (optional) takes the normalised log-posterior (a_j - top) - log(tot).
+// np.max / np.argmax over value(0 .. n - 1): the first maximum in order; a NaN wins and ends the scan (so the first NaN).
+struct FirstMax { int index; double value; };
+template <typename Value>
+__device__ __forceinline__ FirstMax first_max(Value value, int n) {
+    FirstMax best{0, value(0)};
+    bool bnan = best.value != best.value;
+    for (int i = 1; i < n; ++i) {
+        const double v = value(i);
+        if (!bnan && (v != v || v > best.value)) { best.value = v; best.index = i; bnan = v != v; }
+    }
+    return best;
+}
+
+// The pair test every discrete decision of the clustering hangs on: IoU of a pivot and a candidate from the class-band shifted corners
+// with the legacy "+1" widths and areas; match = IoU > thr joins the pivot's cluster, kill = !(IoU <= thr) leaves the pool (matched or NaN).
+struct RowGeometry { double x1, y1, x2, y2, area; };
+struct PairTest { bool match, kill; };
+__device__ __forceinline__ PairTest pair_test(const RowGeometry& p, const RowGeometry& q, double thr) {
+    const double w = fmax(0.0, fmin(p.x2, q.x2) - fmax(p.x1, q.x1) + 1.0);
+    const double h = fmax(0.0, fmin(p.y2, q.y2) - fmax(p.y1, q.y1) + 1.0);
+    const double inter = w * h;
+    const double ovr = inter / (p.area + q.area - inter);
+    return {ovr > thr, !(ovr <= thr)};
+}
+
+// A row's detector index where it is valid, else -1: what poisons the row's cluster in the pooled and the presence rule.
+__device__ __forceinline__ int checked_source(int src, int num_detectors) { return (src >= 0 && src < num_detectors) ? src : -1; }
+
+// The score / class rule of the log-posterior fusion over L columns a_j = column(j): NaN-wins maximum, max-subtracted sum, first maximum
+// / first NaN of the normalised columns; lq (optional) takes the normalised log-posterior (a_j - top) - log(tot).  Phase 4 calls it for
+// a cluster, the presence rule also for its clusters of one row (phase 4 and the passthrough branch).  In the presence kernels phase 4
+// runs its own copy, so the rule is written twice: there a third inlined call made the pooled + posterior + presence instantiation 2 to
+// 5 % slower (profiles/fuse_refactor.txt section 4).  The copy computes the same values by the same sums, subtractions and divisions
+// in the same order; its maximum loop keeps the LAST NaN of the columns where first_max keeps the first, which only the payload of a
+// NaN result could show (the kernel's own NaNs all carry one payload).
 template <typename Column>
 __device__ __forceinline__ void logp_rule(Column column, int L, double* lq, double& out_score, double& out_class) {
-    double top = column(0);
-    for (int j = 1; j < L; ++j) {
-        const double v = column(j);
-        top = (v > top || v != v) ? v : top;          // NaN wins, like np.max
-    }
+    const double top = first_max(column, L).value;          // NaN wins, like np.max
     double tot = 0.0;
     for (int j = 0; j < L; ++j) tot += exp(column(j) - top);
-    double best = exp(column(0) - top) / tot;
-    int bi = 0;
-    bool bnan = best != best;
-    for (int j = 1; j < L; ++j) {
-        const double v = exp(column(j) - top) / tot;
-        if (!bnan && (v != v || v > best)) { best = v; bi = j; bnan = v != v; }
-    }
-    out_score = best;
-    out_class = (double)bi;
+    const FirstMax best = first_max([&](int j) { return exp(column(j) - top) / tot; }, L);
+    out_score = best.value;
+    out_class = (double)best.index;
     if (lq) {
         const double ltot = log(tot);
         for (int j = 0; j < L; ++j) lq[j] = (column(j) - top) - ltot;
@@ -139,8 +198,8 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
             for (int e = 0; e < 4; ++e) a.out_boxes[o * 4 + e] = a.boxes[o * 4 + e];
             if (PRES) {      // rescored as a cluster of one: a_j = lp_j + presence[1 << source][j]
                 const int k1 = a.K + 1;
-                const int src = a.row_source[o];
-                const bool ok = src >= 0 && src < a.num_detectors;
+                const int src = checked_source(a.row_source[o], a.num_detectors);
+                const bool ok = src >= 0;
                 const int pat = ok ? 1 << src : 0;
                 const double* lp = a.probs + o * k1;
                 const double* prow = a.presence + (size_t)pat * k1;
@@ -170,27 +229,14 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
     const int W = (R + 63) >> 6;   // 64-row words per matrix line
     // columns of log-probabilities kept per row (0 when the score mode does not need them)
     const int L = (LOGP || a.score_mode == PE_SCORE_PROBEN) ? K + 1 : (a.score_mode == PE_SCORE_PROBEN_BINARY ? 2 : 0);
-    // ---- LDS carve (all arrays indexed by SORTED position unless noted) ----
-    unsigned long long* mbits = reinterpret_cast<unsigned long long*>(smem);      // BITS: match [R][W], then the clusters' member bits
-    unsigned long long* kbits = mbits + (BITS ? (size_t)R * W : 0);               // BITS: kill [R][W]
-    double* gx1 = reinterpret_cast<double*>(kbits + (BITS ? (size_t)R * W : 0));
-    double* gy1 = gx1 + R;
-    double* gx2 = gy1 + R;
-    double* gy2 = gx2 + R;
-    double* gar = gy2 + R;
-    double* gsc = gar + R;   // score
-    double* glog = gsc + R;  // [L][R]
-    double* gob = glog + (size_t)L * R;                       // [4][R] original coordinates
-    double* ginv = gob + 4 * (size_t)R;                       // 1 / variance (v-avg only)
-    double* gw = ginv + R;                                    // POOL: the pool weight of the row's detector
-    int* ord = reinterpret_cast<int*>(gw + (POOL ? R : 0));   // sorted position -> original row
-    int* gcls = ord + R;                                      // class id
-    int* gsrc = gcls + R;                                     // PRES: the row's detector index, -1 when outside [0, num_detectors)
-    unsigned short* members = reinterpret_cast<unsigned short*>(gsrc + (PRES ? R : 0));   // all clusters' matches, back to back
-    unsigned short* cl_piv = members + R;      // per cluster: pivot position, first member, number of matches
-    unsigned short* cl_beg = cl_piv + R;
-    unsigned short* cl_cnt = cl_beg + R;
-    unsigned char* alive = reinterpret_cast<unsigned char*>(cl_cnt + R);       // sequential form only
+    const FuseLayout<LdsPointers> lay(LdsPointers{smem}, R, L, POOL, PRES, BITS);
+    unsigned long long *mbits = lay.mbits, *kbits = lay.kbits;
+    double *gx1 = lay.gx1, *gy1 = lay.gy1, *gx2 = lay.gx2, *gy2 = lay.gy2, *gar = lay.gar, *gsc = lay.gsc, *glog = lay.glog, *gob = lay.gob;
+    double *ginv = lay.ginv, *gw = lay.gw;
+    int *ord = lay.ord, *gcls = lay.gcls, *gsrc = lay.gsrc;
+    unsigned short *members = lay.members, *cl_piv = lay.cl_piv, *cl_beg = lay.cl_beg, *cl_cnt = lay.cl_cnt;
+    unsigned char* alive = lay.alive;
+    auto geometry = [&](int p) { return RowGeometry{gx1[p], gy1[p], gx2[p], gy2[p], gar[p]}; };
 
     // ---- 1. rank sort by score (scores staged through gar, indexed by ORIGINAL row) ----
     for (int r = tid; r < n; r += kFuseThreads) gar[r] = a.scores[beg + r];
@@ -218,13 +264,10 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
         gcls[p] = a.classes[beg + r];
         if (a.box_mode == PE_BOX_VAVG) ginv[p] = 1.0 / a.vars[beg + r];
         if (POOL) {
-            const int src = a.row_source[beg + r];
-            gw[p] = (src >= 0 && src < a.num_detectors) ? a.pool_weights[src] : __builtin_nan("");
+            const int src = checked_source(a.row_source[beg + r], a.num_detectors);
+            gw[p] = src >= 0 ? a.pool_weights[src] : __builtin_nan("");
         }
-        if (PRES) {
-            const int src = a.row_source[beg + r];
-            gsrc[p] = (src >= 0 && src < a.num_detectors) ? src : -1;
-        }
+        if (PRES) gsrc[p] = checked_source(a.row_source[beg + r], a.num_detectors);
         if (LOGP) {
             const double* lp = a.probs + (size_t)(beg + r) * (K + 1);
             for (int j = 0; j <= K; ++j) glog[(size_t)j * R + p] = lp[j];
@@ -254,18 +297,10 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
             unsigned long long m = 0, kl = 0;
             if (c >= (p >> 6)) {
                 const int q = c * 64 + lane;
-                bool match = false, kill = false;
-                if (q > p && q < n) {
-                    const double px1 = gx1[p], py1 = gy1[p], px2 = gx2[p], py2 = gy2[p], par = gar[p];
-                    const double w = fmax(0.0, fmin(px2, gx2[q]) - fmax(px1, gx1[q]) + 1.0);
-                    const double h = fmax(0.0, fmin(py2, gy2[q]) - fmax(py1, gy1[q]) + 1.0);
-                    const double inter = w * h;
-                    const double ovr = inter / (par + gar[q] - inter);
-                    match = ovr > a.thr;
-                    kill = !(ovr <= a.thr);      // matched or NaN: leaves the pool
-                }
-                m = __ballot(match);
-                kl = __ballot(kill);
+                PairTest t{false, false};
+                if (q > p && q < n) t = pair_test(geometry(p), geometry(q), a.thr);
+                m = __ballot(t.match);
+                kl = __ballot(t.kill);
             }
             if (lane == 0) { mbits[(size_t)p * W + c] = m; kbits[(size_t)p * W + c] = kl; }
         }
@@ -305,18 +340,15 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
         int ncl = 0, cursor = 0;
         for (int pos = 0; pos < n; ++pos) {
             if (!alive[pos]) continue;  // wave-uniform (LDS broadcast)
-            const double px1 = gx1[pos], py1 = gy1[pos], px2 = gx2[pos], py2 = gy2[pos], par = gar[pos];
+            const RowGeometry pivot = geometry(pos);
             int cnt = 0;
             for (int base = pos + 1; base < n; base += 64) {
                 const int q = base + lane;
                 bool match = false;
                 if (q < n && alive[q]) {
-                    const double w = fmax(0.0, fmin(px2, gx2[q]) - fmax(px1, gx1[q]) + 1.0);
-                    const double h = fmax(0.0, fmin(py2, gy2[q]) - fmax(py1, gy1[q]) + 1.0);
-                    const double inter = w * h;
-                    const double ovr = inter / (par + gar[q] - inter);
-                    match = ovr > a.thr;
-                    if (!(ovr <= a.thr)) alive[q] = 0;  // matched or NaN: leaves the pool
+                    const PairTest t = pair_test(pivot, geometry(q), a.thr);
+                    match = t.match;
+                    if (t.kill) alive[q] = 0;
                 }
                 const unsigned long long mask = __ballot(match);
                 if (match) members[cursor + cnt + __popcll(mask & pe::lanemask_lt())] = (unsigned short)q;
@@ -389,7 +421,7 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
             if (LOGP) {
                 // a_j = sum over the members (cluster order) of log p_j, less (m - 1) log prior_j; s = softmax(a) with the maximum
                 // subtracted first, so the largest term is exp(0) and nothing under- or overflows before the division.  np.max /
-                // np.argmax over the K+1 entries INCLUDING background, NaN wins, first index - the rule of PE_SCORE_PROBEN below.
+                // np.argmax over the K+1 entries INCLUDING background, NaN wins, first index - logp_rule() above.
                 // POOL: a_j = sum of w log p_j, less (W - 1) log prior_j, W = the members' weights summed in the same order
                 double wsum = 0.0;
                 if (POOL) for (int t = 0; t < m; ++t) wsum += gw[at(t)];
@@ -401,25 +433,29 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
                     if (PRES) acc += prow ? prow[j] : __builtin_nan("");      // last: the presence evidence of the cluster's pattern
                     return acc;
                 };
-                double top = column(0);
-                for (int j = 1; j < L; ++j) {
-                    const double v = column(j);
-                    top = (v > top || v != v) ? v : top;          // NaN wins, like np.max
-                }
-                double tot = 0.0;
-                for (int j = 0; j < L; ++j) tot += exp(column(j) - top);
-                double best = exp(column(0) - top) / tot;
-                int bi = 0;
-                bool bnan = best != best;
-                for (int j = 1; j < L; ++j) {
-                    const double v = exp(column(j) - top) / tot;
-                    if (!bnan && (v != v || v > best)) { best = v; bi = j; bnan = v != v; }
-                }
-                out_score = best;
-                out_class = (double)bi;
-                if (POST) {
-                    const double ltot = log(tot);
-                    for (int j = 0; j < L; ++j) a.out_log_posterior[o * L + j] = (column(j) - top) - ltot;
+                if (!PRES) {
+                    logp_rule(column, L, POST ? a.out_log_posterior + o * L : nullptr, out_score, out_class);
+                } else {        // the presence kernels' copy of the rule: see logp_rule
+                    double top = column(0);
+                    for (int j = 1; j < L; ++j) {
+                        const double v = column(j);
+                        top = (v > top || v != v) ? v : top;          // NaN wins, like np.max
+                    }
+                    double tot = 0.0;
+                    for (int j = 0; j < L; ++j) tot += exp(column(j) - top);
+                    double best = exp(column(0) - top) / tot;
+                    int bi = 0;
+                    bool bnan = best != best;
+                    for (int j = 1; j < L; ++j) {
+                        const double v = exp(column(j) - top) / tot;
+                        if (!bnan && (v != v || v > best)) { best = v; bi = j; bnan = v != v; }
+                    }
+                    out_score = best;
+                    out_class = (double)bi;
+                    if (POST) {
+                        const double ltot = log(tot);
+                        for (int j = 0; j < L; ++j) a.out_log_posterior[o * L + j] = (column(j) - top) - ltot;
+                    }
                 }
             } else if (L > 0) {
                 auto column = [&](int j) {       // exp of the cluster's summed log-probability of column j
@@ -431,16 +467,10 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
                 double tot = 0.0;
                 for (int j = 0; j < L; ++j) tot += column(j);
                 if (a.score_mode == PE_SCORE_PROBEN) {
-                    // np.max / np.argmax over the K+1 entries INCLUDING background; NaN wins, first NaN index
-                    double best = column(0) / tot;
-                    int bi = 0;
-                    bool bnan = best != best;
-                    for (int j = 1; j < L; ++j) {
-                        const double v = column(j) / tot;
-                        if (!bnan && (v != v || v > best)) { best = v; bi = j; bnan = v != v; }
-                    }
-                    out_score = best;
-                    out_class = (double)bi;
+                    // np.max / np.argmax over the K+1 entries INCLUDING background
+                    const FirstMax best = first_max([&](int j) { return column(j) / tot; }, L);
+                    out_score = best.value;
+                    out_class = (double)best.index;
                 } else {
                     out_score = column(0) / tot;
                 }
@@ -498,14 +528,7 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
                     for (int t = 0; t < m; ++t) out_var += (lam * lam) * gvar[at(t)];
                 }
             } else {  // argmax: box of the first maximal score in cluster order
-                int bp = at(0);
-                double best = gsc[bp];
-                bool bnan = best != best;
-                for (int t = 1; t < m; ++t) {
-                    const int p = at(t);
-                    const double v = gsc[p];
-                    if (!bnan && (v != v || v > best)) { best = v; bp = p; bnan = v != v; }
-                }
+                const int bp = at(first_max([&](int t) { return gsc[at(t)]; }, m).index);
                 for (int c4 = 0; c4 < 4; ++c4) out_coord[c4] = coord(c4, bp);
                 if (POST) out_var = gvar[bp];
             }
@@ -526,13 +549,24 @@ __global__ __launch_bounds__(kFuseThreads) void proben_fuse_kernel(ProbenArgs a)
     if (tid == 0) a.out_counts[img] = ncl;
 }
 
+// The 18 instantiations, stated once: the plain rule and "probEn-log" with each of its eight option sets, each in the sequential [0] and
+// the bit-matrix [1] form.  fuse_impl's index: logp ? 1 + pool + 2 post + 4 pres : 0.
+using FuseKernel = void (*)(ProbenArgs);
+template <bool LOGP, bool POOL, bool POST, bool PRES>
+constexpr FuseKernel kFuseForms[2] = {proben_fuse_kernel<false, LOGP, POOL, POST, PRES>, proben_fuse_kernel<true, LOGP, POOL, POST, PRES>};
+constexpr const FuseKernel* kFuseKernels[9] = {
+    kFuseForms<false, false, false, false>,
+    kFuseForms<true, false, false, false>, kFuseForms<true, true, false, false>, kFuseForms<true, false, true, false>, kFuseForms<true, true, true, false>,
+    kFuseForms<true, false, false, true>, kFuseForms<true, true, false, true>, kFuseForms<true, false, true, true>, kFuseForms<true, true, true, true>};
+
 // pe_proben_fuse_batch / pe_proben_fuse_batch_logp: the argument checks, LDS sizing, clustering form, launch.  logp: a.probs holds the
 // K+1 log-posteriors (required), a.score_mode is PE_SCORE_PROBEN_LOGP and is not the caller's to choose.  pool (implies logp):
 // pe_proben_fuse_batch_pooled, a.row_source / a.pool_weights required, 8 more bytes of LDS per row for the staged weight.
 // post (implies logp, pool = the caller gave row_source): pe_proben_fuse_batch_posterior, the three more outputs required.
 // pres (implies logp; pool = the caller gave pool_weights, post = the caller gave the three posterior outputs): pe_proben_fuse_batch_presence,
 // a.row_source / a.presence required, num_detectors in [1, PE_PRESENCE_MAX_DETECTORS], 4 more bytes of LDS per row for the staged source.
-int fuse_impl(const char* what, bool logp, bool pool, bool post, bool pres, ProbenArgs a, int32_t num_images, int32_t num_classes, int32_t max_rows_per_image, void* stream) {
+int fuse_impl(const char* what, bool logp, bool pool, bool post, bool pres, ProbenArgs a, int32_t max_rows_per_image, void* stream) {
+    const int32_t num_images = a.B, num_classes = a.K;
     PE_CHECK_ARG(num_images >= 0, "%s: num_images < 0", what);
     if (num_images == 0) return PE_OK;
     PE_CHECK_ARG(a.boxes && a.scores && (a.probs || !logp) && a.vars && a.classes && a.offsets, "%s: null input pointer", what);
@@ -559,32 +593,22 @@ int fuse_impl(const char* what, bool logp, bool pool, bool post, bool pres, Prob
                  max_rows_per_image);
     const int R = (max_rows_per_image + 1) & ~1;  // keep the int/short/byte carves 8-byte aligned
     const int L = (logp || a.score_mode == PE_SCORE_PROBEN) ? num_classes + 1 : (a.score_mode == PE_SCORE_PROBEN_BINARY ? 2 : 0);
-    const size_t per_row = 8 * (6 + L + 5 + (pool ? 1 : 0)) + 4 + 4 + (pres ? 4 : 0) + 4 * 2 + 1;
-    const size_t lds_seq = (size_t)R * per_row + 16;
-    const size_t lds_bits = lds_seq + (size_t)R * ((R + 63) / 64) * 16;        // + the two bit matrices
-    constexpr size_t kStatic = 512;                                            // the kernels' static __shared__ scratch (ncl_s, reductions)
-    const bool bits = lds_bits + kStatic <= 160 * 1024;
+    // a whole image's rows live in LDS (FuseLayout: 8 (11 + L) + 17 bytes per row, 8 more for the pooled form's weight, 4 more for the
+    // presence form's detector index); the bit-matrix form where its two matrices fit beside them, else the sequential form.  Capacity
+    // at K = 3: 1 192 rows per image ("probEn", "probEn-log"; 1 126 pooled, 1 158 with presence, 1 096 with both), 1 349
+    // ("probEn_binary"), 1 555 ("avg", "max") - a detector contributes at most 100.  The bit-matrix form reaches 576 rows there (556 with pool weights
+    // and presence).
+    const size_t lds_seq = fuse_lds_bytes(R, L, pool, pres, false), lds_bits = fuse_lds_bytes(R, L, pool, pres, true);
+    const bool bits = lds_bits + kFuseLdsStatic <= kFuseLdsLimit;
     const size_t lds = bits ? lds_bits : lds_seq;
-    if (lds + kStatic > 160 * 1024) {
-        // a whole image's rows live in LDS (boxes, 1 / variance, class ids, log-odds, cluster tables: 8 (11 + L) + 17 bytes per row,
-        // 8 more for the pooled form's weight, 4 more for the presence form's detector index);
-        // capacity at K = 3: 1 195 rows per image (probEn), 1 400 (other score modes) - a detector contributes at most 100
+    if (lds + kFuseLdsStatic > kFuseLdsLimit) {
         pe::set_error("%s: %zu bytes of LDS needed (> 160 KiB): max_rows_per_image %d is above the per-image capacity of %zu rows "
-                      "for this score mode / class count", what, lds + kStatic, max_rows_per_image,
-                      (size_t)(160 * 1024 - kStatic - 16) / per_row);
+                      "for this score mode / class count", what, lds + kFuseLdsStatic, max_rows_per_image,
+                      (kFuseLdsLimit - kFuseLdsStatic - fuse_lds_bytes(0, L, pool, pres, false)) / fuse_row_bytes(L, pool, pres));
         return PE_ERR_UNSUPPORTED;
     }
     a.max_rows = R;
-    void (*kernel)(ProbenArgs) =
-        pres   ? (post ? (pool ? (bits ? proben_fuse_kernel<true, true, true, true, true> : proben_fuse_kernel<false, true, true, true, true>)
-                               : (bits ? proben_fuse_kernel<true, true, false, true, true> : proben_fuse_kernel<false, true, false, true, true>))
-                       : (pool ? (bits ? proben_fuse_kernel<true, true, true, false, true> : proben_fuse_kernel<false, true, true, false, true>)
-                               : (bits ? proben_fuse_kernel<true, true, false, false, true> : proben_fuse_kernel<false, true, false, false, true>)))
-        : post ? (pool ? (bits ? proben_fuse_kernel<true, true, true, true, false> : proben_fuse_kernel<false, true, true, true, false>)
-                       : (bits ? proben_fuse_kernel<true, true, false, true, false> : proben_fuse_kernel<false, true, false, true, false>))
-        : pool ? (bits ? proben_fuse_kernel<true, true, true, false, false> : proben_fuse_kernel<false, true, true, false, false>)
-        : logp ? (bits ? proben_fuse_kernel<true, true, false, false, false> : proben_fuse_kernel<false, true, false, false, false>)
-               : (bits ? proben_fuse_kernel<true, false, false, false, false> : proben_fuse_kernel<false, false, false, false, false>);
+    const FuseKernel kernel = kFuseKernels[logp ? 1 + (pool ? 1 : 0) + (post ? 2 : 0) + (pres ? 4 : 0) : 0][bits ? 1 : 0];
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
@@ -605,10 +629,9 @@ extern "C" int pe_proben_fuse_batch(const double* boxes, const double* scores, c
                                     int32_t score_mode, int32_t box_mode, double iou_thresh, double frame_w,
                                     double frame_h, double* out_boxes, float* out_scores, float* out_classes,
                                     int32_t* out_keep, int32_t* out_counts, void* stream) {
-    ProbenArgs a{boxes, scores, probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
-                 score_mode, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    return fuse_impl("pe_proben_fuse_batch", false, false, false, false, a, num_images, num_classes, max_rows_per_image, stream);
+    const ProbenArgs a{boxes, scores, probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
+                       score_mode, box_mode, iou_thresh, frame_w, frame_h, out_boxes, out_scores, out_classes, out_keep, out_counts};
+    return fuse_impl("pe_proben_fuse_batch", false, false, false, false, a, max_rows_per_image, stream);
 }
 
 extern "C" int pe_proben_fuse_batch_logp(const double* boxes, const double* scores, const double* log_probs,
@@ -618,9 +641,9 @@ extern "C" int pe_proben_fuse_batch_logp(const double* boxes, const double* scor
                                          double frame_w, double frame_h, const double* log_prior, double* out_boxes,
                                          float* out_scores, float* out_classes, int32_t* out_keep, int32_t* out_counts, void* stream) {
     ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
-                 PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    return fuse_impl("pe_proben_fuse_batch_logp", true, false, false, false, a, num_images, num_classes, max_rows_per_image, stream);
+                 PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h, out_boxes, out_scores, out_classes, out_keep, out_counts};
+    a.log_prior = log_prior;
+    return fuse_impl("pe_proben_fuse_batch_logp", true, false, false, false, a, max_rows_per_image, stream);
 }
 
 extern "C" int pe_proben_fuse_batch_pooled(const double* boxes, const double* scores, const double* log_probs,
@@ -632,9 +655,9 @@ extern "C" int pe_proben_fuse_batch_pooled(const double* boxes, const double* sc
                                            float* out_classes, int32_t* out_keep, int32_t* out_counts, int32_t* out_cluster,
                                            void* stream) {
     ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
-                 PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, row_source, pool_weights, num_detectors, out_cluster, nullptr, nullptr, nullptr, nullptr, nullptr};
-    return fuse_impl("pe_proben_fuse_batch_pooled", true, true, false, false, a, num_images, num_classes, max_rows_per_image, stream);
+                 PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h, out_boxes, out_scores, out_classes, out_keep, out_counts};
+    a.log_prior = log_prior; a.row_source = row_source; a.pool_weights = pool_weights; a.num_detectors = num_detectors; a.out_cluster = out_cluster;
+    return fuse_impl("pe_proben_fuse_batch_pooled", true, true, false, false, a, max_rows_per_image, stream);
 }
 
 extern "C" int pe_proben_fuse_batch_posterior(const double* boxes, const double* scores, const double* log_probs,
@@ -646,11 +669,10 @@ extern "C" int pe_proben_fuse_batch_posterior(const double* boxes, const double*
                                               float* out_classes, int32_t* out_keep, int32_t* out_counts, int32_t* out_cluster,
                                               double* out_log_posterior, double* out_vars, int32_t* out_members, void* stream) {
     ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
-                 PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, row_source, pool_weights, num_detectors, out_cluster,
-                 out_log_posterior, out_vars, out_members, nullptr, nullptr};
-    return fuse_impl("pe_proben_fuse_batch_posterior", true, row_source != nullptr && pool_weights != nullptr, true, false, a, num_images,
-                     num_classes, max_rows_per_image, stream);
+                 PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h, out_boxes, out_scores, out_classes, out_keep, out_counts};
+    a.log_prior = log_prior; a.row_source = row_source; a.pool_weights = pool_weights; a.num_detectors = num_detectors; a.out_cluster = out_cluster;
+    a.out_log_posterior = out_log_posterior; a.out_vars = out_vars; a.out_members = out_members;
+    return fuse_impl("pe_proben_fuse_batch_posterior", true, row_source != nullptr && pool_weights != nullptr, true, false, a, max_rows_per_image, stream);
 }
 
 extern "C" int pe_proben_fuse_batch_presence(const double* boxes, const double* scores, const double* log_probs,
@@ -663,9 +685,9 @@ extern "C" int pe_proben_fuse_batch_presence(const double* boxes, const double* 
                                              int32_t* out_cluster, double* out_log_posterior, double* out_vars, int32_t* out_members,
                                              int32_t* out_pattern, void* stream) {
     ProbenArgs a{boxes, scores, log_probs, variances, classes, offsets, row_counts, passthrough, num_images, num_classes, 0,
-                 PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h,
-                 out_boxes, out_scores, out_classes, out_keep, out_counts, log_prior, row_source, pool_weights, num_detectors, out_cluster,
-                 out_log_posterior, out_vars, out_members, presence, out_pattern};
-    return fuse_impl("pe_proben_fuse_batch_presence", true, pool_weights != nullptr, out_log_posterior != nullptr, true, a, num_images,
-                     num_classes, max_rows_per_image, stream);
+                 PE_SCORE_PROBEN_LOGP, box_mode, iou_thresh, frame_w, frame_h, out_boxes, out_scores, out_classes, out_keep, out_counts};
+    a.log_prior = log_prior; a.row_source = row_source; a.pool_weights = pool_weights; a.num_detectors = num_detectors; a.out_cluster = out_cluster;
+    a.out_log_posterior = out_log_posterior; a.out_vars = out_vars; a.out_members = out_members;
+    a.presence = presence; a.out_pattern = out_pattern;
+    return fuse_impl("pe_proben_fuse_batch_presence", true, pool_weights != nullptr, out_log_posterior != nullptr, true, a, max_rows_per_image, stream);
 }

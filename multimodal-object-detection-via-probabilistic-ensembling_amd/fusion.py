@@ -123,7 +123,6 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
     if cavg and not (pool or pres or post):     # no entry point that writes "cluster" is selected: the pooled one at w = 1
         pool, weights = True, torch.ones((corr.shape[0],), dtype=torch.float64, device=dev)
     entry = "_presence" if pres else "_posterior" if post else "_pooled" if pool else "_logp" if logp else ""
-    wide = entry in ("_pooled", "_posterior", "_presence")      # the entry points with row_source, pool_weights, num_detectors, out_cluster
     detectors = opts.num_detectors if pres else int(weights.numel()) if pool else 0
 
     def new(shape, dtype, fill):
@@ -146,21 +145,18 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
         out["pattern"] = new((ntot,), torch.int32, -1)
     P = _lib.ptr
     name = "pe_proben_fuse_batch" + entry
-    args = [P(boxes), P(scores), P(probs), P(variances), P(classes)]
-    args += [P(row_source) if pool or pres else None] if wide else []
-    args += [P(offsets), P(row_counts), P(passthrough), B, K, max_rows]
-    args += [] if logp else [SCORE_MODES[opts.score_fusion]]
-    args += [BOX_MODES["v-avg" if cavg else opts.box_fusion], float(iou_thresh), float(frame[0]), float(frame[1])]
-    args += [P(log_prior)] if logp else []
-    args += [P(weights) if pool else None] if wide else []      # NULL with row_source NULL: the unpooled rule
-    args += [P(table)] if entry == "_presence" else []
-    args += [detectors] if wide else []
-    args += [P(out["boxes"]), P(out["scores"]), P(out["classes"]), P(out["keep"]), P(out["counts"])]
-    args += [P(out.get("cluster"))] if wide else []
-    # the three posterior outputs are NULL together on a score-only presence run
-    args += [P(out.get("log_posterior")), P(out.get("vars")), P(out.get("members"))] if entry in ("_posterior", "_presence") else []
-    args += [P(out["pattern"])] if entry == "_presence" else []
-    _lib.check(getattr(_lib.lib(), name)(*args, _lib.stream()), name)
+    # every field of _lib.FUSE_FIELDS; the entry point takes those it has.  row_source / pool_weights NULL: the unpooled rule; the three
+    # posterior outputs are NULL together on a score-only presence run
+    values = {"boxes": P(boxes), "scores": P(scores), "probs": P(probs), "vars": P(variances), "classes": P(classes),
+              "row_source": P(row_source) if pool or pres else None, "offsets": P(offsets), "row_counts": P(row_counts),
+              "passthrough": P(passthrough), "B": B, "K": K, "max_rows": max_rows, "score_mode": SCORE_MODES[opts.score_fusion],
+              "box_mode": BOX_MODES["v-avg" if cavg else opts.box_fusion], "thr": float(iou_thresh), "fw": float(frame[0]), "fh": float(frame[1]),
+              "log_prior": P(log_prior), "pool_weights": P(weights) if pool else None, "presence": P(table), "num_detectors": detectors,
+              "out_boxes": P(out["boxes"]), "out_scores": P(out["scores"]), "out_classes": P(out["classes"]), "out_keep": P(out["keep"]),
+              "out_counts": P(out["counts"]), "out_cluster": P(out.get("cluster")), "out_log_posterior": P(out.get("log_posterior")),
+              "out_vars": P(out.get("vars")), "out_members": P(out.get("members")), "out_pattern": P(out.get("pattern")),
+              "stream": _lib.stream()}
+    _lib.check(getattr(_lib.lib(), name)(*[values[f] for f in _lib.FUSE_ORDER[name]]), name)
     if cavg:
         st = _lib.lib().pe_box_gls_batch(P(boxes), P(variances), P(row_source), P(out["cluster"]), P(offsets), P(row_counts),
                                          P(out["counts"]), B, max_rows, P(corr), int(corr.shape[0]), P(out["boxes"]), P(out.get("vars")),

@@ -77,3 +77,28 @@ def test_argument_checks_answer_before_any_device_work(built_lib):
     sc = (ctypes.c_float * 4)(0.25, 0.125, 0.0625, 0.03125)
     st = L.pe_roi_align_nhwc_sorted(feats, hw, sc, 4, 2, 256, 0, 4096, 1000, None, 7, 7, 0, 1, 4096, None, None, None)
     assert st != 0 and "order workspace" in err()
+
+
+def declared_prototypes():
+    """name -> the ctypes kind of every parameter, read from the prototypes of include/proben_hip.h (a pointer of any type is c_void_p)."""
+    kinds = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "float": ctypes.c_float,
+             "size_t": ctypes.c_size_t}
+    txt = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, "include", "proben_hip.h")).read(), flags=re.S)
+    protos = {}
+    for name, params in re.findall(r"\b(?:int|size_t|const\s+char\s*\*)\s*(pe_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        params = [p.split() for p in params.split(",") if p.strip() and p.strip() != "void"]
+        protos[name] = [ctypes.c_void_p if any("*" in tok for tok in p) else kinds[p[-2]] for p in params]
+    return protos
+
+
+def test_python_signatures_have_the_headers_arity_and_kinds():
+    """Every prototype of the header against _lib.SIGNATURES: the same number of parameters, and pointer -> c_void_p, int32_t -> c_int32,
+    int64_t -> c_int64, double -> c_double, float -> c_float, size_t -> c_size_t in the same places.  The fusion's five signatures are
+    derived from one table (_lib.FUSE_FIELDS); this holds them to the header like the hand-written ones."""
+    import proben_amd
+    protos = declared_prototypes()
+    assert set(protos) == set(declared_symbols()) and len(protos) >= 58, set(declared_symbols()) ^ set(protos)
+    sigs = dict(proben_amd._lib.SIGNATURES, pe_last_error=[])
+    wrong = {n: (len(sigs[n]), len(p)) if len(sigs[n]) != len(p) else [i for i, (a, b) in enumerate(zip(sigs[n], p)) if a is not b]
+             for n, p in protos.items() if list(sigs[n]) != p}
+    assert not wrong, wrong
