@@ -13,6 +13,18 @@
 // accumulated, then divided by the sample count) so results are bit-identical to the CPU kernel.
 // fp16 features (the detector's path): separable, table-driven form below.
 // Output layout: [R, ph, pw, C] (the box head's fc1 weight is permuted to match at load time).
+//
+// Contract (pinned by tests/test_roi_align_edges_gpu.py on the cases of tests/roi_cases.py):
+//  - Block size: the fp16 kernels build their tables with one thread per (axis, bin) slot and no loop, so roi_align_forward gives
+//    every block that builds tables at least pooled_h + pooled_w threads (C = 8, and C = 16 with pooled_h > pooled_w, have fewer
+//    threads per pooled row than slots and are widened to the slot count).
+//  - A box of negative width or height in aligned mode (the reference asserts) has a sampling grid <= 0: the row is zeros, forward,
+//    and receives no gradient, backward.  A zero-area box is zeros too (grid 0); in unaligned mode both are clamped to one pixel.
+//  - The FPN level is floor(4 + log2(sqrt(area) / 224 + eps)) evaluated in FLOAT32, clamped to p2..p5, as the reference's tensors
+//    evaluate it: a side of 224 minus one ulp is p4 (4 + log2 rounds up to 4.0), not the p3 of real arithmetic.  Forward, order and
+//    backward kernels each state the rule; the tests hold all three to the oracle's level at the seams.
+//  - Boxes are finite and of image size: the adaptive grid loops over ceil(size / pooled) samples per bin and axis, so an infinite
+//    box means 2^31 iterations and the conversion of a NaN size to int is undefined.  The stages upstream clip proposals to the image.
 #include <hip/hip_fp16.h>
 
 #include <atomic>
@@ -586,7 +598,13 @@ static int roi_align_forward(const void* const* feats_host, const int32_t* feat_
         // one pooled row per pass when it fits (C = 256: 7 bins x 32 lanes = 224 threads, 7 full passes instead of
         // 6 full + 1 one-eighth-full pass of 256)
         const int row_threads = (C / 8) * pooled_w;
-        const int threads = row_threads <= 256 ? row_threads : 256;
+        // Block-size rule: the table build has ONE thread per (axis, bin) slot and no loop, so a block that builds tables (pooled
+        // <= SEP_MAXB on both axes) has at least pooled_h + pooled_w threads.  C = 8 at any pooled size and C = 16 with
+        // pooled_h > pooled_w have fewer threads per pooled row than slots: the block is widened to the slot count, the surplus
+        // threads only build their slot (the pooling loop strides by blockDim).  From C = 16 with pooled_h <= pooled_w on - C = 256
+        // included - the launch is what it was, and the kernels themselves are untouched.
+        const int slots = (pooled_h <= SEP_MAXB && pooled_w <= SEP_MAXB) ? pooled_h + pooled_w : 0;
+        const int threads = row_threads > 256 ? 256 : (row_threads < slots ? slots : row_threads);
         const int fast = g_roi_fast.load(std::memory_order_relaxed);
         if (C == 256 && pooled_h <= SEP_MAXB && pooled_w <= SEP_MAXB && fast) {
             hipLaunchKernelGGL((roi_align_kernel<_Float16, true, true>), dim3(grid), dim3(threads), 0, (hipStream_t)stream, a);

@@ -101,7 +101,14 @@ def roi_align_nhwc(feats, rois, *, scales, pooled, sampling_ratio=0, aligned=Tru
                    num_rois=None, out=None, want_levels=False, sort=None):
     """feats: list (1 or 4) of NHWC tensors (fp16 or fp32, same dtype/C); rois: [R,5] or boxes [N,per_image,4].
     sort (boxes form only): the workgroups take the ROIs in (level, Morton cell) order, one contiguous stretch per XCD
-    (pe_roi_align_nhwc_sorted) - the same results at the same places, fewer feature bytes fetched."""
+    (pe_roi_align_nhwc_sorted) - the same results at the same places, fewer feature bytes fetched.
+    Contract (tests/test_roi_align_edges_gpu.py): fp32 features give the reference's CPU kernel bit for bit; fp16 features give the
+    same sums in another order (bit for bit wherever the sums are exact).  Any C that is a multiple of the vector width (8 fp16,
+    4 fp32) and any pooled size work: the launch gives a block at least pooled_h + pooled_w threads where it builds tables.  Rows
+    beyond `counts` are zeros with level -1.  In aligned mode a box with x2 < x1 or y2 < y1 - the reference asserts - is zeros.
+    With four levels the level is floor(4 + log2(sqrt(area) / 224 + eps)) in float32, clamped to p2..p5, exactly as the reference's
+    float32 tensors evaluate it (a side one ulp under 224 is still p4).  Boxes must be finite and of image size - NaN, infinite or
+    huge coordinates are out of contract (the adaptive grid loops over ceil(size / pooled) samples); proposals arrive clipped."""
     f0 = feats[0]
     _lib.require_cuda(f0, rois)
     N, C = f0.shape[0], f0.shape[3]

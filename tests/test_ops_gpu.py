@@ -779,6 +779,8 @@ def test_roi_align_fp32_bit_exact_vs_oracle(L, golden_dir):
                                pooled=(7, 7), counts=None, per_image=40, want_levels=True)
     got = out.permute(0, 3, 1, 2).cpu().numpy()
     np.testing.assert_array_equal(got, z["pool_out"])
+    from oracle import detector as OD
+    np.testing.assert_array_equal(lv.cpu().numpy(), OD.assign_levels(boxes.reshape(-1, 4)).numpy())
 
 
 def test_roi_align_module_matches_reference_tables(L):
