@@ -9,9 +9,10 @@ import numpy as np
 import pytest
 import torch
 
+from fuse_inputs import GRID, batch, grid_image, to_dev, weights, write_flir
+from fuse_ref import clusters
 from test_boxcorr_cpu import (C_GLS, LD, U, cluster_correlation, estimate_numpy, pair_stats_numpy, restate, simulate_pairs,
                               detection_with_residual)
-from test_pool_gpu import GRID, _batch, _dev, _image
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +38,7 @@ def _images(rng, k1, D):
              ([12, 12, 11, 9, 8, 6, 2], 4)]
     images = []
     for sizes, single in plans:
-        im = _image(rng, sizes, k1, D, n_single=single)
+        im = grid_image(rng, sizes, k1, D, n_single=single)
         im["vars"] = 10.0 ** rng.uniform(-1.0, 1.0, len(im["scores"]))
         assert 2 <= len(im["scores"]) <= 64
         images.append(im)
@@ -46,8 +47,7 @@ def _images(rng, k1, D):
 
 def _members(im):
     """[(fused row k, the cluster's rows in ascending input-row order)], from the restated greedy clustering."""
-    from test_proben_logp_gpu import _clusters
-    return [(k, sorted(mem)) for k, (_, mem) in enumerate(_clusters(im["boxes"], im["scores"], im["classes"].astype(np.float64)))]
+    return [(k, sorted(mem)) for k, (_, mem) in enumerate(clusters(im["boxes"], im["scores"], im["classes"].astype(np.float64)))]
 
 
 def _check_cluster(ref, m, got_box, got_var, frac):
@@ -79,7 +79,7 @@ def test_fusion_against_the_dense_solve(D, k1):
     from proben_amd import fusion as F
     rng = np.random.default_rng(190 + 10 * D + k1)
     images = _images(rng, k1, D)
-    (b, s, v, c, offs_d, src, lp), offs = _batch(images)
+    (b, s, v, c, offs_d, src, lp), offs = batch(images)
     members = [_members(im) for im in images]
     weights = rng.uniform(0.3, 1.5, D).tolist()
     table = rng.normal(0, 1, (2 ** D, k1))
@@ -88,7 +88,7 @@ def test_fusion_against_the_dense_solve(D, k1):
     live = np.zeros(offs[-1], bool)
     for i in range(len(images)):
         live[offs[i]:offs[i] + len(members[i])] = True
-    live = _dev(live)
+    live = to_dev(live)
     for name, P in _matrices(D).items():
         refs = {}
         for i, im in enumerate(images):
@@ -141,11 +141,11 @@ def test_zero_matrix_is_v_avg():
     D, k1 = 3, 4
     rng = np.random.default_rng(77)
     images = _images(rng, k1, D)
-    (b, s, v, c, offs_d, src, lp), offs = _batch(images)
+    (b, s, v, c, offs_d, src, lp), offs = batch(images)
     passthrough = np.zeros(len(images), np.int32)
     passthrough[1] = 1
-    kw = dict(log_probs=lp, with_posterior=True, row_source=src, pool_weights=[1.0] * D, row_counts=_dev(np.diff(offs).astype(np.int32)),
-              passthrough=_dev(passthrough), max_rows=64)
+    kw = dict(log_probs=lp, with_posterior=True, row_source=src, pool_weights=[1.0] * D, row_counts=to_dev(np.diff(offs).astype(np.int32)),
+              passthrough=to_dev(passthrough), max_rows=64)
     base = F.fuse_batch(b, s, None, v, c, offs_d[:-1], "probEn-log", "v-avg", **kw)
     zero = F.fuse_batch(b, s, None, v, c, offs_d[:-1], "probEn-log", "c-avg", box_correlation=np.zeros((D, D)), **kw)
     other = F.fuse_batch(b, s, None, v, c, offs_d[:-1], "probEn-log", "c-avg", box_correlation=_matrix(D, 0.5, 0.6), **kw)
@@ -214,19 +214,19 @@ def test_edges():
     P = _matrix(D, 0.5, 0.6)
     over = {"boxes": rng.uniform(0, 400, (1101, 4)), "scores": rng.uniform(0, 1, 1101), "lp": np.log(rng.dirichlet(np.ones(k1), 1101)),
             "src": np.zeros(1101, np.int32), "vars": np.ones(1101), "classes": np.zeros(1101, np.int32)}
-    single = _image(rng, [2, 3], k1, D, n_single=2)
+    single = grid_image(rng, [2, 3], k1, D, n_single=2)
     tile = _tile_image(rng, k1, D)
-    empty = _image(rng, [], k1, D)
-    bad = _image(rng, [3, 2, 4], k1, D, n_single=2)
+    empty = grid_image(rng, [], k1, D)
+    bad = grid_image(rng, [3, 2, 4], k1, D, n_single=2)
     images = [over, single, tile, empty, bad]
     bad_members = _members(bad)
     victim = next(mem for _, mem in bad_members if len(mem) == 3)[1]
     bad["src"][victim] = D                                        # outside [0, D)
-    (b, s, v, c, offs_d, src, lp), offs = _batch(images)
+    (b, s, v, c, offs_d, src, lp), offs = batch(images)
     passthrough = np.zeros(len(images), np.int32)
     passthrough[1] = 1
-    kw = dict(max_rows=1100, log_probs=lp, with_posterior=True, row_source=src, row_counts=_dev(np.diff(offs).astype(np.int32)),
-              passthrough=_dev(passthrough))
+    kw = dict(max_rows=1100, log_probs=lp, with_posterior=True, row_source=src, row_counts=to_dev(np.diff(offs).astype(np.int32)),
+              passthrough=to_dev(passthrough))
     # unit pool weights: the entry point that writes "cluster"; a row of an unknown detector then has a NaN score in BOTH runs (POOL)
     base = F.fuse_batch(b, s, None, v, c, offs_d[:-1], "probEn-log", "v-avg", pool_weights=[1.0] * D, **kw)
     got = F.fuse_batch(b, s, None, v, c, offs_d[:-1], "probEn-log", "c-avg", box_correlation=P, pool_weights=[1.0] * D, **kw)
@@ -273,7 +273,7 @@ def test_edges():
     ov = torch.full_like(got["vars"], 54321.0)
     st = _lib.lib().pe_box_gls_batch(_lib.ptr(b), _lib.ptr(v), _lib.ptr(src), _lib.ptr(got["cluster"]), _lib.ptr(offs_d[:-1].contiguous()),
                                      _lib.ptr(kw["row_counts"]), _lib.ptr(got["counts"]), len(images), 1100,
-                                     _lib.ptr(_dev(P)), D, _lib.ptr(ob), _lib.ptr(ov), _lib.stream())
+                                     _lib.ptr(to_dev(P)), D, _lib.ptr(ob), _lib.ptr(ov), _lib.stream())
     assert st == 0
     ob, ov = ob.cpu().numpy(), ov.cpu().numpy()
     written = np.zeros(len(ov), bool)
@@ -287,7 +287,7 @@ def test_edges():
     ob2 = torch.full_like(got["boxes"], 12345.0)
     st = _lib.lib().pe_box_gls_batch(_lib.ptr(b), _lib.ptr(v), _lib.ptr(src), _lib.ptr(got["cluster"]), _lib.ptr(offs_d[:-1].contiguous()),
                                      _lib.ptr(kw["row_counts"]), _lib.ptr(got["counts"]), len(images), 1100,
-                                     _lib.ptr(_dev(P)), D, _lib.ptr(ob2), None, _lib.stream())
+                                     _lib.ptr(to_dev(P)), D, _lib.ptr(ob2), None, _lib.stream())
     assert st == 0 and ob2.cpu().numpy().tobytes() == ob.tobytes()
     print(f"[boxcorr] edges: {crossing} clusters straddle the tile boundary; largest fraction of the bound: boxes {frac['box']:.4f}, "
           f"vars {frac['var']:.4f}")
@@ -345,7 +345,7 @@ def test_pair_stats_against_the_restatement(C):
     rng = np.random.default_rng(C)
     det, var, src, member_rows, cluster_offsets, match, gt = _pair_case(rng, C, D)
     pairs, rows, S, Q, excluded, S_abs, Q_abs, last = pair_stats_numpy(det, var, src, member_rows, cluster_offsets, match, gt, D)
-    args = [_dev(x) for x in (det, var, src, member_rows, cluster_offsets, match, gt)]
+    args = [to_dev(x) for x in (det, var, src, member_rows, cluster_offsets, match, gt)]
     got = cal.box_pair_stats(*args, D)
     again = cal.box_pair_stats(*args, D)
     assert got["pairs"].tolist() == pairs.tolist() and list(got["rows"]) == rows
@@ -391,7 +391,7 @@ def test_fit_box_correlation_end_to_end():
     member_rows = np.arange(2 * n, dtype=np.int32)
     cluster_offsets = np.arange(0, 2 * n + 1, 2, dtype=np.int32)
     match = np.arange(n, dtype=np.int32)
-    fit = cal.fit_box_correlation(*[_dev(x) for x in (det, var, src, member_rows, cluster_offsets, match, gt)], 2)
+    fit = cal.fit_box_correlation(*[to_dev(x) for x in (det, var, src, member_rows, cluster_offsets, match, gt)], 2)
     pairs, rows, S, Q, excluded, _, _, _ = pair_stats_numpy(det, var, src, member_rows, cluster_offsets, match, gt, 2)
     want = estimate_numpy(pairs, rows, S, Q)
     assert fit["pairs"] == [[0, n], [n, 0]] and fit["rows"] == [n, n] and fit["excluded"] == excluded == 0
@@ -408,14 +408,13 @@ def test_drivers(tmp_path, capsys):
     """save_predictions x 2 -> fit_temperature --with-variance --with-box-correlation -> demo_probEn --box_fusion c-avg --calibration (the
     two-stage route and --one-pass write the same fused file, with the c-avg variance) -> calibration_report --fused-posterior (both box
     rules side by side); a file without the key, and a run without the flag, leave everything as it is."""
-    from test_stream_gpu import _weights, _write_flir
     from proben_amd import calibration as Cal
     from proben_amd.cli import calibration_report, demo_probEn, fit_temperature, save_predictions
     from proben_amd.late_fusion import late_fusion, read_j1
     root = tmp_path / "val"
-    _write_flir(root, 6, 96, 120, (150, 180))
+    write_flir(root, 6, 96, 120, (150, 180))
     names = ["thermal_only", "early_fusion"]
-    paths = [_weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
+    paths = [weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
     pdir = tmp_path / "pred"
     for m, p in zip(names, paths):
         save_predictions.main(["--dataset_path", str(root), "--fusion_method", m, "--model_path", p, "--prediction_path", str(pdir), "--batch", "4"])

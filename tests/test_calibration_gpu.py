@@ -7,31 +7,16 @@ import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from fuse_inputs import detector_rows, logit_rows, weights, write_flir
+from fuse_ref import U
 
-U = 2.0 ** -53
+pytestmark = pytest.mark.gpu
 
 
 def _np_softmax(lg32, T):
     z = lg32.astype(np.float64) / T
     e = np.exp(z - z.max(1, keepdims=True))
     return e / e.sum(1, keepdims=True)
-
-
-def _logit_rows(rng, n, K):
-    """[n, K+1] float32 logits on a 2^-12 grid spanning +-60; a fifth of the rows have an exact tie at the top, a tenth are flat."""
-    lg = np.round(rng.uniform(-60.0, 60.0, (n, K + 1)) * 4096.0) / 4096.0
-    narrow = rng.random(n) < 0.5                      # half the rows within a few units of their top, like a head's rows
-    lg[narrow] = lg[narrow, :1] - np.round(rng.uniform(0.0, 6.0, (int(narrow.sum()), K + 1)) * 4096.0) / 4096.0
-    t = rng.integers(0, K, n)
-    top = lg.max(1)
-    lg[np.arange(n), t] = top
-    tie = rng.random(n) < 0.2
-    t2 = (t + 1 + rng.integers(0, max(K - 1, 1), n)) % K
-    lg[tie, t2[tie]] = top[tie]
-    flat = rng.random(n) < 0.1
-    lg[flat] = lg[flat, :1]
-    return lg.astype(np.float32)
 
 
 @pytest.mark.parametrize("K", [3, 80])
@@ -50,7 +35,7 @@ def test_calibrated_probs_against_numpy_float64(K, T):
     float64 exp needs no allowance beyond the 1 ulp the derivation gives it."""
     from proben_amd.calibration import calibrated_probs
     rng = np.random.default_rng(100 * K + int(T * 100))
-    lg = _logit_rows(rng, 100_000, K)
+    lg = logit_rows(rng, 100_000, K)
     p, bg = calibrated_probs(torch.from_numpy(lg).cuda(), T)
     got = np.concatenate([p.cpu().numpy(), bg.cpu().numpy()[:, None]], 1)
     want = _np_softmax(lg, T)
@@ -80,34 +65,6 @@ def test_non_finite_logits_give_nan_rows_like_numpy():
         np.testing.assert_array_equal(np.isnan(got), np.isnan(want))
         assert np.isnan(got[1]).all() and np.isnan(got[2]).all() and np.isnan(got[4]).all() and got[3, 0] == 0.0
         np.testing.assert_allclose(got[[0, 3]], want[[0, 3]], rtol=2 * (K1 + 4) * U * 1.001, atol=0)
-
-
-# ---- detector rows ------------------------------------------------------------------------------------------------------------
-
-_DETS = {}
-
-
-def detector_rows(K):
-    """Two product detectors (R50, synthetic weights, K classes) on 8 synthetic frames: their forward_batch dicts."""
-    if K not in _DETS:
-        import proben_amd
-        from proben_amd.synthetic import synthetic_images
-        frames = synthetic_images(8, height=256, width=320, seed=5)
-        dets = []
-        for seed in (1, 2):
-            cfg = proben_amd.get_cfg()
-            cfg.MODEL.RESNETS.DEPTH = 50
-            cfg.MODEL.ROI_HEADS.NUM_CLASSES = K
-            cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST = 0.5 if K > 1 else 0.05
-            cfg.MODEL.ROI_BOX_HEAD.OUTPUT_LOGITS = True
-            cfg.MODEL.ROI_HEADS.ENABLE_GAUSSIANNLLOSS = True
-            cfg.MODEL.WEIGHTS = f"synthetic://{seed}"
-            m = proben_amd.DefaultPredictor(cfg).model
-            dets.append(m.forward_batch([torch.from_numpy(f).cuda() for f in frames], out_sizes=[(256, 320)] * 8, resize_to=(800, 1000)))
-        torch.cuda.synchronize()
-        assert all(int(d["counts"].sum()) > 0 for d in dets), "the synthetic detectors found nothing"
-        _DETS[K] = dets
-    return _DETS[K]
 
 
 def _f32_softmax_bound(lg):
@@ -343,13 +300,12 @@ def test_fit_reports_a_minimum_on_the_search_range_and_bad_labels():
 # ---- end to end -----------------------------------------------------------------------------------------------------------------
 
 def test_drivers_end_to_end(tmp_path, capsys):
-    from test_stream_gpu import _weights, _write_flir
     from proben_amd import calibration as C
     from proben_amd.cli import demo_probEn, fit_temperature, save_predictions
     root = tmp_path / "val"
-    _write_flir(root, 6, 96, 120, (150, 180))
+    write_flir(root, 6, 96, 120, (150, 180))
     names = ["thermal_only", "early_fusion"]
-    paths = [_weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
+    paths = [weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
     pdir = tmp_path / "pred"
     for m, p in zip(names, paths):
         save_predictions.main(["--dataset_path", str(root), "--fusion_method", m, "--model_path", p, "--prediction_path", str(pdir), "--batch", "4"])

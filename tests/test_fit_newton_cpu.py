@@ -13,7 +13,8 @@ import pytest
 import torch
 
 import frozen_newton
-from test_pool_cpu import cluster_tables, log_softmax64, nll_grad
+from fuse_ref import log_softmax
+from test_pool_cpu import cluster_tables, nll_grad
 from test_presence_cpu import np_bias_nll
 
 
@@ -47,7 +48,7 @@ def pool_case(C, k1, sources, w_true, seed, offset=0.0):
     for t, s in enumerate(sources):
         if s < 0:
             z[:, t] = z[:, 0]
-    lp = log_softmax64(z.reshape(C * m, k1))
+    lp = log_softmax(z.reshape(C * m, k1))
     src = np.tile(np.abs(sources), C).astype(np.int32)
     offs = (np.arange(C + 1) * m).astype(np.int32)
     G, _, _ = cluster_tables(lp, src, np.arange(C * m), offs, D)
@@ -103,8 +104,8 @@ def bias_case(C, k1, seed, shift, absent=None):
     """Fused log-posteriors of C clusters, labels drawn from softmax(base + shift); `absent`: a label that never occurs (its entry of the
     row has its minimum at minus infinity)."""
     rng = np.random.default_rng(seed)
-    base = log_softmax64(rng.normal(0.0, 1.5, (C, k1)))
-    p = np.exp(log_softmax64(base + np.asarray(shift)[None, :]))
+    base = log_softmax(rng.normal(0.0, 1.5, (C, k1)))
+    p = np.exp(log_softmax(base + np.asarray(shift)[None, :]))
     if absent is not None:
         p[:, absent] = 0.0
         p /= p.sum(1, keepdims=True)

@@ -1,41 +1,16 @@
-"""Pooling weights of score_fusion "probEn-log" without a GPU: the NumPy restatement of the pooled rule and of the NLL / gradient (shared
-with tests/test_pool_gpu.py), its own recovery of known weights, weight parsing, the calibration file, and the argument checks of the
-new entry points.  u = 2^-53."""
+"""Pooling weights of score_fusion "probEn-log" without a GPU: the NumPy restatement of the NLL / gradient (shared with
+tests/test_pool_gpu.py; the pooled rule itself is restated in tests/fuse_ref.py), its own recovery of known weights, weight parsing,
+the calibration file, and the argument checks of the new entry points."""
 import ctypes
 import json
 
 import numpy as np
 import pytest
 
-U = 2.0 ** -53
-LD = np.longdouble
+from fuse_ref import log_softmax, restate
 
 
-# ---- the restatement ------------------------------------------------------------------------------------------------------------------
-
-def log_softmax64(z):
-    z = np.asarray(z, np.float64)
-    d = z - z.max(-1, keepdims=True)
-    return d - np.log(np.exp(d).sum(-1, keepdims=True))
-
-
-def pooled_columns(lp, w_rows, log_prior=None, dtype=LD):
-    """a_j = sum_t w_t lp[t][j] - (W - 1) log_prior_j over the rows in the order given (cluster order), W = sum_t w_t."""
-    a = np.zeros(lp.shape[1], dtype)
-    W = dtype(0)
-    for row, w in zip(lp.astype(dtype), w_rows):
-        a = a + dtype(w) * row
-        W = W + dtype(w)
-    if log_prior is not None:
-        a = a - (W - 1) * log_prior.astype(dtype)
-    return a
-
-
-def pooled_posterior(lp, w_rows, log_prior=None, dtype=LD):
-    a = pooled_columns(lp, w_rows, log_prior, dtype)
-    e = np.exp(a - a.max())
-    return e / e.sum(), a
-
+# ---- the restatement of the fit --------------------------------------------------------------------------------------------------------
 
 def cluster_tables(log_probs, row_source, member_rows, cluster_offsets, D, log_prior=None, dtype=np.float64):
     """G [C, D, K+1] = S_dj - n_d lp_j, n [C, D], rows per cluster [C]; every cluster's rows in member order."""
@@ -102,7 +77,7 @@ def recovery_case(seed, C=20000, k1=4, w_true=(0.7, 0.4)):
     size = rng.integers(2, 4, C)
     offs = np.concatenate([[0], np.cumsum(size)]).astype(np.int32)
     N = int(offs[-1])
-    lp = log_softmax64(rng.normal(0.0, 2.0, (N, k1)).astype(np.float32))
+    lp = log_softmax(rng.normal(0.0, 2.0, (N, k1)).astype(np.float32))
     pos = np.arange(N) - np.repeat(offs[:-1], size)
     src = (pos % 2).astype(np.int32)                     # 0, 1, 0
     members = np.arange(N, dtype=np.int32)
@@ -125,9 +100,9 @@ def dependence_case(seed, C=20000, k1=4):
     pos = np.arange(N) - np.repeat(offs[:-1], size)
     z0 = rng.normal(0.0, 2.0, (C, k1))
     z = np.repeat(z0, size, axis=0) + np.where(pos[:, None] > 0, rng.normal(0.0, 1.0, (N, k1)), 0.0)
-    lp = log_softmax64(z.astype(np.float32))
+    lp = log_softmax(z.astype(np.float32))
     src = (pos % 2).astype(np.int32)                     # 0, 1, 0: the third row is a noisy row of detector 0
-    p = np.exp(log_softmax64(z0))
+    p = np.exp(log_softmax(z0))
     labels = (rng.random(C)[:, None] > np.cumsum(p, 1)).sum(1).clip(0, k1 - 1).astype(np.int32)
     return {"log_probs": lp, "row_source": src, "member_rows": np.arange(N, dtype=np.int32), "cluster_offsets": offs, "labels": labels}
 
@@ -179,14 +154,17 @@ def test_restatement_on_dependent_detectors():
 
 
 def test_weights_of_one_are_the_plain_rule():
+    """fuse_ref.restate with a pool weight of 1.0 gives the unpooled columns value for value: sum_t lp_t - (m - 1) log_prior."""
     rng = np.random.default_rng(3)
-    lp = log_softmax64(rng.normal(0, 3, (5, 4)))
+    lp = log_softmax(rng.normal(0, 3, (5, 4)))
     prior = np.log(np.array([0.1, 0.2, 0.3, 0.4]))
-    a = pooled_columns(lp, [1.0] * 5, prior, np.float64)
+    pooled = restate(lp, list(range(5)), src=np.zeros(5, np.int32), weights=[1.0], log_prior=prior)
+    plain = restate(lp, list(range(5)), log_prior=prior)
+    assert (pooled["lq"] == plain["lq"]).all() and pooled["score"] == plain["score"] and pooled["cls"] == plain["cls"]
     acc = np.zeros(4)
     for r in lp:
         acc = acc + r
-    assert (a == acc - 4.0 * prior).all()
+    assert np.abs(plain["lq"].astype(np.float64) - log_softmax(acc - 4.0 * prior)).max() <= 1e-12
 
 
 def test_parse_and_resolve():

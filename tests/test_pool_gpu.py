@@ -1,5 +1,6 @@
 """Pooling weights of score_fusion "probEn-log" on the GPU: pe_proben_fuse_batch_pooled (weights, out_cluster), pe_proben_pack_pooled
-(out_source), pe_pool_nll and calibration.fit_pool_weights, against the NumPy restatement of tests/test_pool_cpu.py.  u = 2^-53."""
+(out_source), pe_pool_nll and calibration.fit_pool_weights, against the np.longdouble restatement of the rule (tests/fuse_ref.py) and
+the NumPy restatement of the fit (tests/test_pool_cpu.py).  u = 2^-53."""
 import json
 import math
 import os
@@ -8,21 +9,12 @@ import numpy as np
 import pytest
 import torch
 
-from test_pool_cpu import LD, U, cluster_tables, dependence_case, log_softmax64, nll_grad, pooled_posterior, recovery_case, standard_errors
+import fuse_inputs
+from fuse_inputs import batch, calibrated_infos, dependent_files, detector_rows, grid_image, image_rows, load_case, log_full, to_dev, write_flir
+from fuse_ref import BOX, LD, U, clusters, log_softmax, restate, ulp32
+from test_pool_cpu import cluster_tables, dependence_case, nll_grad, recovery_case, standard_errors
 
 pytestmark = pytest.mark.gpu
-
-BOX = ["v-avg", "s-avg", "avg", "argmax"]
-
-
-def _dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def _rows(out, offs, i):
-    cnt = int(out["counts"][i])
-    sl = slice(offs[i], offs[i] + max(cnt, 0))
-    return tuple(out[k][sl].cpu().numpy() for k in ("keep", "boxes", "scores", "classes"))
 
 
 # ---- fusion: weights of 1.0 are probEn-log, byte for byte -----------------------------------------------------------------------------
@@ -30,22 +22,21 @@ def _rows(out, offs, i):
 def _flat(infos_per_image, lps):
     from proben_amd import fusion as F
     b, s, p, v, c, offs, src = F.pack_infos(infos_per_image, with_sources=True)
-    lp = _dev(np.concatenate(lps).reshape(-1, lps[0].shape[1]))
+    lp = to_dev(np.concatenate(lps).reshape(-1, lps[0].shape[1]))
     return b, s, v, c, offs, src, lp
 
 
 @pytest.mark.parametrize("rows", ["saturated", "golden"])
 def test_weights_of_one_move_no_bit(golden_dir, rows):
-    from test_proben_logp_gpu import _calibrated_infos, _load_case, _log_full
     from oracle import proben as O
     from proben_amd import fusion as F
     if rows == "saturated":
-        cal = _calibrated_infos()
+        cal = calibrated_infos()
         infos, lps = [i for i, _ in cal], [lp for _, lp in cal]
     else:
         z = np.load(os.path.join(golden_dir, "proben_cases.npz"))
-        infos = [_load_case(z, ci) for ci in range(int(z["num_cases"]))]
-        lps = [_log_full(O.concat_infos(i)[3]) for i in infos]
+        infos = [load_case(z, ci) for ci in range(int(z["num_cases"]))]
+        lps = [log_full(O.concat_infos(i)[3]) for i in infos]
     b, s, v, c, offs, src, lp = _flat(infos, lps)
     k1 = lp.shape[1]
     prior = (np.arange(k1) + 1.0).tolist()
@@ -68,70 +59,12 @@ def test_weights_of_one_move_no_bit(golden_dir, rows):
 
 # ---- fusion: non-trivial weights against the restatement ------------------------------------------------------------------------------
 
-GRID = [(10 + 40 * ix, 10 + 40 * iy) for iy in range(12) for ix in range(15)]      # 180 far-apart 20 x 20 anchors inside 640 x 512
-
-
-def _image(rng, sizes, k1, D, n_single=0, nan_row=False):
-    """One image: a cluster of each size in `sizes` (+ n_single single rows) at distinct anchors, class 0, sources cycling from a random
-    start, log-posteriors of random float32 logits, score = the row's own p[0] - plus, optionally, a low-score row with NaN coordinates."""
-    sizes = list(sizes) + [1] * n_single
-    anchors = rng.permutation(len(GRID))[:len(sizes)]
-    box, src = [], []
-    for a, m in zip(anchors, sizes):
-        x, y = GRID[a]
-        for t in range(m):
-            box.append(np.array([x, y, x + 20, y + 20], np.float64) + rng.integers(-1, 2, 4))
-            src.append((t + a) % D)
-    n = len(box)
-    box = np.asarray(box, np.float64).reshape(-1, 4)
-    lp = log_softmax64(rng.normal(0, 3, (n, k1)).astype(np.float32))
-    score = np.exp(lp[:, 0])
-    if nan_row:
-        box = np.concatenate([box, [[np.nan] * 4]])
-        lp = np.concatenate([lp, log_softmax64(rng.normal(0, 3, (1, k1)))])
-        score = np.append(score, score.min() * 0.5)
-        src.append(0)
-    perm = rng.permutation(len(score))
-    return {"boxes": box[perm], "scores": score[perm], "lp": lp[perm], "src": np.asarray(src, np.int32)[perm],
-            "vars": rng.uniform(0.5, 3.0, len(score)), "classes": np.zeros(len(score), np.int32)}
-
-
-def _batch(images):
-    cat = lambda k: np.concatenate([im[k] for im in images])  # noqa: E731
-    offs = np.concatenate([[0], np.cumsum([len(im["scores"]) for im in images])]).astype(np.int32)
-    return (_dev(cat("boxes").reshape(-1, 4)), _dev(cat("scores")), _dev(cat("vars")), _dev(cat("classes")), _dev(offs), _dev(cat("src")),
-            _dev(cat("lp").reshape(-1, images[0]["lp"].shape[1]))), offs
-
-
-def _ulp32(x):
-    return 2.0 ** (math.floor(math.log2(max(abs(x), 2.0 ** -126))) - 23)
-
-
-def _pooled_bound(lp, w_rows, log_prior, s, a):
-    """First-order bound, in units of u, of the device's float64 score against the longdouble restatement: DESIGN.md section 11's bound
-    extended by the weight products.  Column j: m products w_t lp_tj (each rounds: |w_t lp_tj| u) and m - 1 additions of partial sums
-    <= S_j = sum_t |w_t lp_tj|: m S_j; with a prior, W carries (m - 1) W u, W - 1 rounds (|W - 1| u), the product rounds
-    (|(W - 1) lp_j| u) and the subtraction rounds (|a_j| u): [(m - 1) W + 2 |W - 1|] |lp_j| + |a_j|.  Then as section 11:
-    E_j = A_j + A_best + |a_j - M| + 2, the normaliser's K additions and the division: sum_j s_j E_j + K + 1."""
-    m = len(w_rows)
-    w = np.asarray(w_rows, np.float64)
-    A = m * (np.abs(lp) * w[:, None]).sum(0)
-    if log_prior is not None:
-        W = w.sum()
-        A = A + ((m - 1) * W + 2 * abs(W - 1)) * np.abs(log_prior) + np.abs(a)
-    j = int(np.argmax(s))
-    E = A + A[j] + np.abs(a - a.max()) + 2.0
-    E[j] = 0.0
-    return float((s * E).sum()) + len(a) - 1 + 1
-
-
 @pytest.mark.parametrize("D,k1,weights", [(2, 4, [0.7, 0.4]), (2, 2, [0.0, 1.3]), (3, 4, [0.5, 0.0, 0.25]), (3, 63, [1.5, 0.3, 0.6]), (2, 63, [0.2, 0.9])])
 def test_weights_against_the_restatement(D, k1, weights):
-    from test_proben_logp_gpu import _clusters
     from proben_amd import fusion as F
     rng = np.random.default_rng(100 * D + k1)
-    images = [_image(rng, [1, 2, 3, 9, 2, 5], k1, D, n_single=3) for _ in range(6)]
-    (b, s, v, c, offs_d, src, lp), offs = _batch(images)
+    images = [grid_image(rng, [1, 2, 3, 9, 2, 5], k1, D, n_single=3) for _ in range(6)]
+    (b, s, v, c, offs_d, src, lp), offs = batch(images)
     worst = checked = 0
     for prior in (None, rng.dirichlet(np.ones(k1) * 3)):
         lprior = None if prior is None else np.log(prior / prior.sum())
@@ -144,20 +77,17 @@ def test_weights_against_the_restatement(D, k1, weights):
                                class_prior=None if prior is None else prior.tolist(), pool_weights=weights, row_source=src)
             assert torch.equal(ref["counts"], got["counts"])
             for i, im in enumerate(images):
-                rk, rb, rs, rc = _rows(ref, offs, i)
-                gk, gb, gs, gc = _rows(got, offs, i)
-                cl = _clusters(im["boxes"], im["scores"], im["classes"].astype(np.float64))
+                rk, rb, rs, rc = image_rows(ref, offs, i)
+                gk, gb, gs, gc = image_rows(got, offs, i)
+                cl = clusters(im["boxes"], im["scores"], im["classes"].astype(np.float64))
                 assert gk.tolist() == [p for p, _ in cl] and gk.tobytes() == rk.tobytes() and gb.tobytes() == rb.tobytes()
                 for r, (piv, mem) in enumerate(cl):
                     if len(mem) == 1:
                         assert gs[r] == np.float32(im["scores"][piv]) and gc[r] == 0.0
                         continue
-                    w_rows = [weights[k] for k in im["src"][mem]]
-                    sp, a = pooled_posterior(im["lp"][mem], w_rows, lprior)
-                    j = int(np.argmax(sp))
-                    want = sp[j]
-                    bnd = _pooled_bound(im["lp"][mem], w_rows, lprior, sp.astype(np.float64), a.astype(np.float64))
-                    tol = 0.5 * _ulp32(float(want)) * (1 + 2.0 ** -20) + bnd * U * float(want)
+                    w = restate(im["lp"], mem, src=im["src"], weights=weights, log_prior=lprior)
+                    want, j = w["score"], w["cls"]
+                    tol = 0.5 * ulp32(float(want)) * (1 + 2.0 ** -20) + w["score_bound"] * U * float(want)
                     err = abs(LD(gs[r]) - want)
                     worst = max(worst, float(err / tol))
                     assert err <= tol, (i, r, len(mem), gs[r], float(want), float(err), tol)
@@ -170,27 +100,26 @@ def test_weights_against_the_restatement(D, k1, weights):
 # ---- out_cluster -----------------------------------------------------------------------------------------------------------------------
 
 def test_out_cluster():
-    from test_proben_logp_gpu import _clusters
     from proben_amd import fusion as F
     rng = np.random.default_rng(5)
     k1, D = 4, 2
     images = []
     for n in (0, 1, 2, 63, 64, 65, 129):          # the bit matrices' word boundaries
         pick = [9, 3, 2, 3] if n >= 17 else [2] if n == 2 else []
-        images.append(_image(rng, pick, k1, D, n_single=n - sum(pick)))
+        images.append(grid_image(rng, pick, k1, D, n_single=n - sum(pick)))
         assert len(images[-1]["scores"]) == n
-    images.append(_image(rng, [9, 3, 2, 1], k1, D, n_single=4, nan_row=True))
-    single = _image(rng, [2, 3], k1, D, n_single=2)        # a passthrough image
+    images.append(grid_image(rng, [9, 3, 2, 1], k1, D, n_single=4, nan_row=True))
+    single = grid_image(rng, [2, 3], k1, D, n_single=2)        # a passthrough image
     images.append(single)
-    over = {"boxes": rng.uniform(0, 400, (1101, 4)), "scores": rng.uniform(0, 1, 1101), "lp": log_softmax64(rng.normal(0, 1, (1101, k1))),
+    over = {"boxes": rng.uniform(0, 400, (1101, 4)), "scores": rng.uniform(0, 1, 1101), "lp": log_softmax(rng.normal(0, 1, (1101, k1))),
             "src": np.zeros(1101, np.int32), "vars": np.ones(1101), "classes": np.zeros(1101, np.int32)}
     images.insert(4, over)
-    (b, s, v, c, offs_d, src, lp), offs = _batch(images)
+    (b, s, v, c, offs_d, src, lp), offs = batch(images)
     B = len(images)
-    counts = _dev(np.diff(offs).astype(np.int32))
+    counts = to_dev(np.diff(offs).astype(np.int32))
     passthrough = np.zeros(B, np.int32)
     passthrough[B - 1] = 1
-    call = lambda bound, sl=slice(None), o=offs_d[:-1], cn=counts, pt=_dev(passthrough), args=(b, s, v, c, src, lp): F.fuse_batch(  # noqa: E731
+    call = lambda bound, sl=slice(None), o=offs_d[:-1], cn=counts, pt=to_dev(passthrough), args=(b, s, v, c, src, lp): F.fuse_batch(  # noqa: E731
         args[0], args[1], None, args[2], args[3], o, "probEn-log", "v-avg", max_rows=bound, log_probs=args[5], row_counts=cn, passthrough=pt,
         pool_weights=[0.7, 0.4], row_source=args[4])
     tight, wide = call(129), call(1100)
@@ -209,7 +138,7 @@ def test_out_cluster():
             assert g.tolist() == list(range(n)) and int(tight["counts"][i]) == n
             continue
         want = np.full(n, -1, np.int32)
-        cl = _clusters(im["boxes"], im["scores"], im["classes"].astype(np.float64))
+        cl = clusters(im["boxes"], im["scores"], im["classes"].astype(np.float64))
         for k, (_, mem) in enumerate(cl):
             want[mem] = k
             seen.add(len(mem))
@@ -220,9 +149,9 @@ def test_out_cluster():
         if n == 0:
             continue
         # alone in its launch: the same bytes
-        one = F.fuse_batch(_dev(im["boxes"].reshape(-1, 4)), _dev(im["scores"]), None, _dev(im["vars"]), _dev(im["classes"]),
-                           _dev(np.array([0, n], np.int32)), "probEn-log", "v-avg", max_rows=max(n, 1), log_probs=_dev(im["lp"].reshape(-1, k1)),
-                           pool_weights=[0.7, 0.4], row_source=_dev(im["src"]))
+        one = F.fuse_batch(to_dev(im["boxes"].reshape(-1, 4)), to_dev(im["scores"]), None, to_dev(im["vars"]), to_dev(im["classes"]),
+                           to_dev(np.array([0, n], np.int32)), "probEn-log", "v-avg", max_rows=max(n, 1), log_probs=to_dev(im["lp"].reshape(-1, k1)),
+                           pool_weights=[0.7, 0.4], row_source=to_dev(im["src"]))
         assert one["cluster"].cpu().numpy().tobytes() == g.tobytes(), i
     assert {1, 2, 3, 9} <= seen
 
@@ -243,10 +172,10 @@ def test_out_source(nd):
         cls = rng.integers(0, 5, (B, D)).astype(np.int32)
         cls[:, 62:66] = rng.integers(2, 4, (B, 4))         # drops across the chunk boundary
         cls[:, 0] = 0
-        dets.append({"boxes": _dev(rng.uniform(0, 300, (B, D, 4)).astype(np.float32)), "scores": _dev(rng.uniform(0, 1, (B, D)).astype(np.float32)),
-                     "classes": _dev(cls), "prob_score": _dev(rng.dirichlet(np.ones(K + 1), (B, D))[:, :, :K].astype(np.float32)),
-                     "class_logits": _dev(rng.normal(0, 3, (B, D, K + 1)).astype(np.float32)), "vars": _dev(rng.uniform(0.5, 2, (B, D)).astype(np.float32)),
-                     "counts": _dev(np.array([p[d] for p in pat], np.int32))})
+        dets.append({"boxes": to_dev(rng.uniform(0, 300, (B, D, 4)).astype(np.float32)), "scores": to_dev(rng.uniform(0, 1, (B, D)).astype(np.float32)),
+                     "classes": to_dev(cls), "prob_score": to_dev(rng.dirichlet(np.ones(K + 1), (B, D))[:, :, :K].astype(np.float32)),
+                     "class_logits": to_dev(rng.normal(0, 3, (B, D, K + 1)).astype(np.float32)), "vars": to_dev(rng.uniform(0.5, 2, (B, D)).astype(np.float32)),
+                     "counts": to_dev(np.array([p[d] for p in pat], np.int32))})
     w = [1.0] * nd
     for temps, logp, vs in ((None, False, None), ((1.5, 0.8, 1.1)[:nd], False, (0.5, 2.0, 1.5)[:nd]), ((1.5, 0.8, 1.1)[:nd], True, (0.5, 2.0, 1.5)[:nd])):
         ref = F.pack_rows(dets, 2, temps, log_posteriors=logp, variance_scales=vs or [1.0] * nd)
@@ -256,7 +185,7 @@ def test_out_source(nd):
         assert len(got) == len(ref) + 1
         cnt = ref[6].cpu().numpy()
         S = nd * D
-        live = _dev((np.arange(S)[None] < cnt[:, None]).reshape(-1))
+        live = to_dev((np.arange(S)[None] < cnt[:, None]).reshape(-1))
         for i in (5, 6, 7):
             assert torch.equal(ref[i], got[i])
         for i in [0, 1, 2, 3, 4] + ([8] if logp else []):
@@ -276,7 +205,6 @@ def test_out_source(nd):
 # ---- routes ----------------------------------------------------------------------------------------------------------------------------
 
 def test_fuse_detections_is_pack_plus_fuse_and_equals_the_file_route():
-    from test_calibration_gpu import detector_rows
     from proben_amd import fusion as F
     from proben_amd.late_fusion import late_fusion
     dets = detector_rows(3)
@@ -291,7 +219,7 @@ def test_fuse_detections_is_pack_plus_fuse_and_equals_the_file_route():
     torch.cuda.synchronize()
     cnt = dev["counts"].cpu().numpy()
     assert cnt.sum() > 0 and torch.equal(dev["counts"], two["counts"]) and torch.equal(dev["counts"], plain["counts"])
-    live = _dev((np.arange(S)[None] < cnt[:, None]).reshape(-1))
+    live = to_dev((np.arange(S)[None] < cnt[:, None]).reshape(-1))
     for k in ("boxes", "scores", "classes", "keep"):
         assert dev[k][live].contiguous().cpu().numpy().tobytes() == two[k][live].contiguous().cpu().numpy().tobytes(), k
     assert not torch.equal(dev["scores"][live], plain["scores"][live]), "the weights changed no score"
@@ -339,7 +267,7 @@ def _nll_case(rng, C, D, k1, bad=True):
     if bad and C >= 63:
         src[members[offs[20]]] = D                                # a bad source in cluster 20
         excluded.append(20)
-    lp = log_softmax64(rng.normal(0, 3, (N, k1)).astype(np.float32))
+    lp = log_softmax(rng.normal(0, 3, (N, k1)).astype(np.float32))
     return lp, src, members, offs, labels, sorted(excluded)
 
 
@@ -390,8 +318,8 @@ def test_pool_nll_against_the_restatement(C, D, k1, nc, prior):
     W[0] = 1.0
     if nc > 2:
         W[1, 0] = 0.0
-    args = (_dev(lp), _dev(src), _dev(members), _dev(offs), _dev(labels))
-    lpd = None if lprior is None else _dev(lprior)
+    args = (to_dev(lp), to_dev(src), to_dev(members), to_dev(offs), to_dev(labels))
+    lpd = None if lprior is None else to_dev(lprior)
     nll, grad, bad, last = Cal.pool_nll(*args, W, lpd)
     again = Cal.pool_nll(*args, W, lpd)
     assert nll.tobytes() == again[0].tobytes() and grad.tobytes() == again[1].tobytes()
@@ -419,7 +347,7 @@ def test_pool_nll_gradient_against_central_differences():
     w0 = np.array([0.7, 0.4, 1.1])
     h = 2.0 ** -13
     cand = np.vstack([w0] + [w0 + sgn * h * np.eye(D)[d] for d in range(D) for sgn in (1, -1)])
-    nll, grad, bad, _ = Cal.pool_nll(_dev(lp), _dev(src), _dev(members), _dev(offs), _dev(labels), cand)
+    nll, grad, bad, _ = Cal.pool_nll(to_dev(lp), to_dev(src), to_dev(members), to_dev(offs), to_dev(labels), cand)
     assert bad == 0
     ok = np.ones(C, bool)
     _, _, eps_f, _ = _nll_bounds(lp, src, members, offs, labels, w0, None, ok, C)
@@ -435,7 +363,7 @@ def test_pool_nll_gradient_against_central_differences():
 # ---- the fit ---------------------------------------------------------------------------------------------------------------------------
 
 def _case_dev(case):
-    return tuple(_dev(case[k]) for k in ("log_probs", "row_source", "member_rows", "cluster_offsets", "labels"))
+    return tuple(to_dev(case[k]) for k in ("log_probs", "row_source", "member_rows", "cluster_offsets", "labels"))
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
@@ -457,11 +385,11 @@ def _fused_scores(case, weights):
     lp, offs = case["log_probs"], case["cluster_offsets"]
     N = len(lp)
     boxes = np.tile([[10.0, 10.0, 60.0, 70.0]], (N, 1))
-    out = F.fuse_batch(_dev(boxes), _dev(np.exp(lp.max(1))), None, _dev(np.ones(N)), _dev(np.zeros(N, np.int32)), _dev(offs), "probEn-log", "avg",
-                       max_rows=3, log_probs=_dev(lp), pool_weights=weights, row_source=_dev(case["row_source"]))
+    out = F.fuse_batch(to_dev(boxes), to_dev(np.exp(lp.max(1))), None, to_dev(np.ones(N)), to_dev(np.zeros(N, np.int32)), to_dev(offs), "probEn-log", "avg",
+                       max_rows=3, log_probs=to_dev(lp), pool_weights=weights, row_source=to_dev(case["row_source"]))
     assert int((out["counts"] != 1).sum()) == 0
-    first = _dev(offs[:-1].astype(np.int64))
-    return out["scores"][first].double(), (out["classes"][first].int() == _dev(case["labels"])).int()
+    first = to_dev(offs[:-1].astype(np.int64))
+    return out["scores"][first].double(), (out["classes"][first].int() == to_dev(case["labels"])).int()
 
 
 def test_fit_on_dependent_detectors_lowers_nll_and_ece():
@@ -483,13 +411,12 @@ def test_fit_on_dependent_detectors_lowers_nll_and_ece():
 def test_demo_proben_pool_weights(tmp_path):
     """demo_probEn --score_fusion probEn-log with pool weights from --calibration: the two-stage and the --one-pass route give identical
     AP tables and rows, which differ from the run without weights; --pool_weights 1,1 reproduces the run without weights byte for byte."""
-    from test_stream_gpu import _weights, _write_flir
     from proben_amd import calibration as C
     from proben_amd.cli import demo_probEn, save_predictions
     root = tmp_path / "val"
-    _write_flir(root, 6, 96, 120, (150, 180))
+    write_flir(root, 6, 96, 120, (150, 180))
     names = ["thermal_only", "early_fusion"]
-    paths = [_weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
+    paths = [fuse_inputs.weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
     pdir = tmp_path / "pred"
     for m, p in zip(names, paths):
         save_predictions.main(["--dataset_path", str(root), "--fusion_method", m, "--model_path", p, "--prediction_path", str(pdir), "--batch", "4"])
@@ -529,58 +456,6 @@ def test_demo_proben_pool_weights(tmp_path):
         demo_probEn.main(["--dataset_path", str(root), "--prediction_path", str(pdir), "--detectors", ",".join(names), "--pool_weights", "1,1"])
 
 
-def _dependent_files(tmp_path, n_img=16):
-    """A FLIR val folder of n_img images and two prediction files over it, written by hand: per image 4 objects on a grid of disjoint
-    30 x 35 boxes; detector 0 sees logits z0 ~ N(0, 2^2) per object, detector 1 a noisy copy z0 + N(0, 1) with detector 0's class (rows
-    cluster within a class only), both with boxes within a pixel of the object's; the object's class is drawn from softmax(z0) and an
-    object drawn as background gets no annotation.  Detector 0 adds one detection per image that nothing overlaps: a cluster of one.
-    Returns (root, files, per image: the objects' labels in [0, 3])."""
-    from test_stream_gpu import _write_flir
-    root = tmp_path / "val"
-    _write_flir(root, n_img, 96, 120, (96, 120))
-    val = root / "FLIR_thermal_RGBT_pairs_val.json"
-    ds = json.load(open(val))
-    rng = np.random.default_rng(5)
-    grid = [(5.0, 5.0), (45.0, 5.0), (5.0, 55.0), (45.0, 55.0)]
-    preds = [{k: [] for k in ("image", "boxes", "scores", "classes", "image_id", "class_logits", "probs", "vars")} for _ in range(2)]
-    anns, labels = [], []
-    for im in ds["images"]:
-        z0 = rng.normal(0, 2, (4, 4)).astype(np.float32)
-        p0 = np.exp(log_softmax64(z0))
-        lab = [int(rng.choice(4, p=p / p.sum())) for p in p0]
-        labels.append(lab)
-        for (x, y), l in zip(grid, lab):
-            if l < 3:
-                anns.append({"id": len(anns) + 1, "image_id": im["id"], "category_id": l + 1, "bbox": [x, y, 30.0, 35.0], "area": 1050.0, "iscrowd": 0})
-        cls = z0[:, :3].argmax(1)
-        for d, p in enumerate(preds):
-            z = z0 if d == 0 else (z0 + rng.normal(0, 1, z0.shape)).astype(np.float32)
-            bx = [[x + e[0], y + e[1], x + 30 + e[2], y + 35 + e[3]] for (x, y), e in zip(grid, rng.uniform(-1, 1, (4, 4)))]
-            c = cls.tolist()
-            if d == 0:
-                z = np.concatenate([z, rng.normal(0, 2, (1, 4)).astype(np.float32)])
-                bx.append([85.0, 5.0, 115.0, 40.0])
-                c.append(int(z[4, :3].argmax()))
-            pr = np.exp(log_softmax64(z))
-            p["image"].append(os.path.basename(im["file_name"]))
-            p["image_id"].append(im["id"])
-            p["boxes"].append(bx)
-            p["classes"].append(c)
-            p["class_logits"].append(z.tolist())
-            p["probs"].append(pr[:, :3].tolist())
-            p["scores"].append([float(pr[i, k]) for i, k in enumerate(c)])
-            p["vars"].append([[0.01]] * len(bx))
-    ds["annotations"] = anns
-    json.dump(ds, open(val, "w"))
-    pdir = tmp_path / "pred"
-    pdir.mkdir()
-    files = []
-    for m, p in zip(("thermal_only", "early_fusion"), preds):
-        files.append(str(pdir / f"val_{m}_predictions.json"))
-        json.dump(p, open(files[-1], "w"))
-    return root, files, preds, labels
-
-
 def _own_nll(preds, labels, images, temps, prior, weights):
     """pool_nll per cluster over the 2-row clusters of `images`, from the test's own bookkeeping: object j of an image is rows (j of
     detector 0, j of detector 1) and its label the drawn one.  The clusters are summed in another order than the driver's (object
@@ -597,9 +472,9 @@ def _own_nll(preds, labels, images, temps, prior, weights):
         lab += labels[i]
         n += 9
     C = len(lab)
-    nll, _, bad, _ = Cal.pool_nll(_dev(np.concatenate(lp)), _dev(np.array(src, np.int32)), _dev(np.array(mem, np.int32).reshape(-1)),
-                                  _dev(np.arange(0, 2 * C + 1, 2, dtype=np.int32)), _dev(np.array(lab, np.int32)),
-                                  [[1.0, 1.0], weights], None if prior is None else _dev(np.log(np.asarray(prior, np.float64))))
+    nll, _, bad, _ = Cal.pool_nll(to_dev(np.concatenate(lp)), to_dev(np.array(src, np.int32)), to_dev(np.array(mem, np.int32).reshape(-1)),
+                                  to_dev(np.arange(0, 2 * C + 1, 2, dtype=np.int32)), to_dev(np.array(lab, np.int32)),
+                                  [[1.0, 1.0], weights], None if prior is None else to_dev(np.log(np.asarray(prior, np.float64))))
     assert bad == 0
     return C, nll / C
 
@@ -609,7 +484,7 @@ def test_fit_temperature_and_report_drivers(tmp_path, capsys):
     cluster with and without the weights and fuses its "after" rows with them, and demo_probEn picks the fitted key up."""
     from proben_amd import calibration as Cal
     from proben_amd.cli import calibration_report, demo_probEn, fit_temperature
-    root, files, preds, labels = _dependent_files(tmp_path)
+    root, files, preds, labels = dependent_files(tmp_path)
     names = ["thermal_only", "early_fusion"]
     cal = tmp_path / "cal.json"
     fit_temperature.main(["--predictions", *files, "--dataset_path", str(root), "--holdout", "0.5", "--out", str(cal), "--with-prior",

@@ -1,89 +1,20 @@
 """The fused detection as a full prediction on the GPU: pe_proben_fuse_batch_posterior (log-posterior, box variance, cluster size)
-against the np.longdouble restatement of tests/test_posterior_cpu.py, byte for byte against the entry points it stands for, a cascade
+against the np.longdouble restatement of tests/fuse_ref.py, byte for byte against the entry points it stands for, a cascade
 ((A, B), C) against the direct three-way fusion, and the routes (fuse_detections, late_fusion, demo_probEn --write_fused,
 calibration_report --fused-posterior).  The comparator is never the code under test; clusters come from oracle.proben.order_desc plus
-the greedy rule (tests/test_proben_logp_gpu.py::_clusters).  u = 2^-53."""
+the greedy rule (fuse_ref.clusters).  u = 2^-53."""
 import json
 
 import numpy as np
 import pytest
 import torch
 
-from test_posterior_cpu import BOX, LD, U, restate, var_bound
+from fuse_inputs import anchor_image_set, detector_rows, launch, weights, write_flir
+from fuse_ref import BOX, LD, U, clusters, log_softmax, restate, ulp32, var_bound
 
 pytestmark = pytest.mark.gpu
 
-POOL = np.array([0.6, 0.5])
-
-
-def _ulp32(x):
-    x = np.abs(np.asarray(x, np.float64))
-    return np.exp2(np.maximum(np.floor(np.log2(np.maximum(x, 2.0 ** -126))), -126.0) - 23.0)
-
-
-def _log_softmax(lg):
-    d = lg - lg.max(1, keepdims=True)
-    return d - np.log(np.exp(d).sum(1, keepdims=True))
-
-
-# anchors 70 x 62 apart hold boxes of 60 x 50 jittered by <= 2 px: members of one anchor overlap with IoU > 0.8, anchors never meet
-ANCHORS = [(4 + 70 * ix, 4 + 62 * iy) for iy in range(8) for ix in range(9)]
-
-
-def _image(rng, K1, sizes):
-    """One image's rows (shuffled): an anchor per entry of `sizes`, that many rows of one class on it, from detectors 0 / 1 at random.
-    Log-posteriors are float64 log_softmax of logits with margins from flat to saturated (up to ~40)."""
-    K = K1 - 1
-    n = sum(sizes)
-    boxes, cls = np.empty((n, 4)), np.empty(n, np.int32)
-    r = 0
-    for a, size in zip(rng.permutation(len(ANCHORS))[:len(sizes)], sizes):
-        x, y = ANCHORS[a]
-        boxes[r:r + size] = np.array([x, y, x + 60.0, y + 50.0]) + rng.uniform(-2.0, 2.0, (size, 4))
-        cls[r:r + size] = rng.integers(0, K)
-        r += size
-    lg = rng.normal(0.0, 3.0, (n, K1))
-    lg[np.arange(n), cls] += rng.uniform(2.0, 12.0, n) * rng.choice([1.0, 3.0], n)
-    lp = _log_softmax(lg)
-    perm = rng.permutation(n)
-    boxes, cls, lp = boxes[perm], cls[perm], lp[perm]
-    return {"boxes": boxes, "classes": cls, "lp": lp, "scores": np.exp(lp[np.arange(n), cls]), "vars": rng.uniform(0.5, 4.0, n),
-            "src": rng.integers(0, 2, n).astype(np.int32)}
-
-
-def _sizes(total):
-    out, k = [], 0
-    while sum(out) < total:
-        out.append(min(1 + k % 6, total - sum(out)))          # clusters of 1 .. 6 rows
-        k += 1
-    return out
-
-
-_SETS = {}
-
-
-def image_set(K1):
-    """Images of 1, 2, 64 and 65 rows (65 crosses the 64-row word of the bit matrices), one of 0 rows, one passed through (5 rows) and
-    one of 70 rows for the launches whose bound is 65 (counts == -1).  Computed once per K + 1 and left unchanged."""
-    if K1 not in _SETS:
-        rng = np.random.default_rng(1000 + K1)
-        imgs = [_image(rng, K1, [1]), _image(rng, K1, [2]), _image(rng, K1, _sizes(64)), _image(rng, K1, _sizes(65)), _image(rng, K1, []),
-                _image(rng, K1, [2, 1, 2]), _image(rng, K1, _sizes(70))]
-        _SETS[K1] = (imgs, [0, 0, 0, 0, 0, 1, 0])
-    return _SETS[K1]
-
-
-def _launch(imgs, passthrough, box, max_rows, prior=None, pool=False, with_posterior=True):
-    from proben_amd import fusion as F
-    cat = lambda k, dt: torch.from_numpy(np.ascontiguousarray(np.concatenate([i[k] for i in imgs]).astype(dt))).cuda()  # noqa: E731
-    offs = torch.tensor(np.cumsum([0] + [len(i["scores"]) for i in imgs]), dtype=torch.int32).cuda()
-    out = F.fuse_batch(cat("boxes", np.float64), cat("scores", np.float64), None, cat("vars", np.float64), cat("classes", np.int32), offs,
-                       "probEn-log", box, max_rows=max_rows, log_probs=cat("lp", np.float64), class_prior=prior,
-                       passthrough=None if passthrough is None else torch.tensor(passthrough, dtype=torch.int32).cuda(),
-                       pool_weights=POOL.tolist() if pool else None, row_source=cat("src", np.int32) if pool else None,
-                       with_posterior=with_posterior)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}, offs.cpu().numpy()
+POOL = [0.6, 0.5]
 
 
 # ---- 1. parity with the restatement ---------------------------------------------------------------------------------------------------
@@ -91,20 +22,19 @@ def _launch(imgs, passthrough, box, max_rows, prior=None, pool=False, with_poste
 @pytest.mark.parametrize("box", BOX)
 @pytest.mark.parametrize("K1", [2, 4, 63])
 def test_parity_with_the_restatement(K1, box):
-    """Every fused row of pe_proben_fuse_batch_posterior against test_posterior_cpu.restate on the image's own (reference) clustering,
+    """Every fused row of pe_proben_fuse_batch_posterior against fuse_ref.restate on the image's own (reference) clustering,
     with and without a non-uniform prior, with and without pool weights (0.6, 0.5); bound 65 rows, so the 70-row image gives counts -1.
-      lq:   |lq_j - (a_j - logsumexp(a))| <= (D_j + T + 2 |log tot| + |lq_j|) u, absolute (restate's docstring, DESIGN.md section 17);
-      vars: relative (m + 3) u for v-avg, (3 m + 4) u for s-avg / avg, exact for argmax and single rows (var_bound);
+      lq:   within restate's lq_bound, absolute (fuse_ref's docstring, DESIGN.md section 17);
+      vars: within var_bound, relative; exact for argmax and single rows;
       members: exact.  Rows nothing was written to keep the pre-fill NaN / NaN / 0."""
-    from test_proben_logp_gpu import _clusters
-    imgs, passthrough = image_set(K1)
+    imgs, passthrough = anchor_image_set(K1)
     rng = np.random.default_rng(K1)
     prior = rng.dirichlet(np.full(K1, 2.0)) + 0.01
     prior = prior / prior.sum()
     sizes_seen = set()
     for use_prior in (False, True):
         for pool in (False, True):
-            out, offs = _launch(imgs, passthrough, box, 65, prior.tolist() if use_prior else None, pool)
+            out, offs = launch(imgs, passthrough, box, 65, None, prior.tolist() if use_prior else None, POOL if pool else None)
             lprior = np.log(prior / prior.sum()) if use_prior else None
             worst_lq = worst_var = 0.0
             assert out["counts"].tolist()[4:] == [0, 5, -1]
@@ -114,7 +44,7 @@ def test_parity_with_the_restatement(K1, box):
                 if passthrough[i]:
                     cl = [(r, [r]) for r in range(len(im["scores"]))]
                 else:
-                    cl = _clusters(im["boxes"], im["scores"], im["classes"].astype(np.float64))
+                    cl = clusters(im["boxes"], im["scores"], im["classes"].astype(np.float64))
                 assert out["counts"][i] == len(cl), (i, out["counts"][i], len(cl))
                 np.testing.assert_array_equal(out["keep"][o:o + len(cl)], [p for p, _ in cl])
                 for r, (piv, mem) in enumerate(cl):
@@ -122,7 +52,9 @@ def test_parity_with_the_restatement(K1, box):
                     sizes_seen.add(m)
                     written[o + r] = True
                     assert out["members"][o + r] == m
-                    lq, _, v, bound = restate(im["lp"], im["boxes"], im["scores"], im["vars"], mem, box, lprior, POOL[im["src"]] if pool else None)
+                    w = restate(im["lp"], mem, boxes=im["boxes"], scores=im["scores"], var=im["vars"], box=box, src=im["src"],
+                                weights=POOL if pool else None, log_prior=lprior)
+                    lq, v, bound = w["lq"], w["var"], w["lq_bound"]
                     got_lq, got_v = out["log_posterior"][o + r], out["vars"][o + r]
                     if m == 1:
                         assert got_lq.tobytes() == im["lp"][piv].tobytes() and got_v == im["vars"][piv]
@@ -154,13 +86,13 @@ def test_plain_outputs_are_the_existing_entry_points_bytes(box, pool):
     byte for byte, in both clustering forms (bound = the longest image: bit matrices; 1100: the sequential walk); the posterior outputs
     do not depend on the form either; float32(exp(lq[class])) is within one float32 ulp of the score; the same input twice gives the
     same bytes."""
-    imgs, passthrough = image_set(4)
+    imgs, passthrough = anchor_image_set(4)
     prior = [0.3, 0.2, 0.1, 0.4]
     first = None
     for bound in (None, 1100):
-        new, offs = _launch(imgs, passthrough, box, bound, prior, pool)
-        old, _ = _launch(imgs, passthrough, box, bound, prior, pool, with_posterior=False)
-        again, _ = _launch(imgs, passthrough, box, bound, prior, pool)
+        new, offs = launch(imgs, passthrough, box, bound, None, prior, POOL if pool else None)
+        old, _ = launch(imgs, passthrough, box, bound, None, prior, POOL if pool else None, with_posterior=False)
+        again, _ = launch(imgs, passthrough, box, bound, None, prior, POOL if pool else None)
         assert new["counts"].tobytes() == old["counts"].tobytes() and (new["counts"] >= 0).all() and new["counts"].sum() > 60
         assert set(new) - set(old) == {"log_posterior", "vars", "members"}
         if pool:
@@ -172,7 +104,7 @@ def test_plain_outputs_are_the_existing_entry_points_bytes(box, pool):
             assert new[k][live].tobytes() == again[k][live].tobytes(), k
         cls = new["classes"][live].astype(np.int64)
         back = np.exp(new["log_posterior"][live, cls]).astype(np.float32)
-        assert (np.abs(back.astype(np.float64) - new["scores"][live].astype(np.float64)) <= _ulp32(new["scores"][live])).all()
+        assert (np.abs(back.astype(np.float64) - new["scores"][live].astype(np.float64)) <= ulp32(new["scores"][live])).all()
         if first is None:
             first = new
         else:
@@ -198,7 +130,7 @@ def _cascade_detectors():
             c = cls[b][order]
             lg = rng.uniform(-1.0, 0.0, (6, 4)).astype(np.float32)
             lg[np.arange(6), c] = np.float32(2.0) + rng.uniform(0, 4, 6).astype(np.float32)      # own p >= e^2 / (e^2 + 3) = 0.71
-            p = np.exp(_log_softmax(lg.astype(np.float64)))
+            p = np.exp(log_softmax(lg.astype(np.float64)))
             assert (p[np.arange(6), c] >= 0.6).all()
             d["image"].append(f"c{b}.jpeg")
             d["image_id"].append(b)
@@ -226,7 +158,6 @@ def test_cascade_equals_the_three_way_fusion(with_prior):
     product, m - 1 additions); variance m + 1 = 4 relative.  Cascade: stage two's own bound on its float64 inputs (lq: restate at m = 2;
     box 5 X; variance 3) plus what stage one's error does to it: dlq_j - sum_k s_k dlq_k, so b1_j + sum_k s_k b1_k with b1 stage one's lq
     bound; stage one's box error 5 X lambda_F <= 5 X and its variance error (3 relative) moving the weights, <= 3 X; variance 3 more."""
-    from test_proben_logp_gpu import _clusters
     from proben_amd import fusion as F
     from proben_amd.calibration import calibrated_probs, log_posteriors
     from proben_amd.late_fusion import fused_to_j1, late_fusion
@@ -253,22 +184,24 @@ def test_cascade_equals_the_three_way_fusion(with_prior):
         cat = lambda parts: {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}  # noqa: E731
         abc, ab, fc = cat([ra, rb, rc]), cat([ra, rb]), cat([rf, rc])
         # the precondition, on the reference clustering: the cascade's stage-two clusters are the three-way clusters
-        cl3 = _clusters(abc["boxes"], abc["scores"], abc["classes"].astype(np.float64))
-        cl1 = _clusters(ab["boxes"], ab["scores"], ab["classes"].astype(np.float64))
-        cl2 = _clusters(fc["boxes"], fc["scores"], fc["classes"].astype(np.float64))
+        cl3 = clusters(abc["boxes"], abc["scores"], abc["classes"].astype(np.float64))
+        cl1 = clusters(ab["boxes"], ab["scores"], ab["classes"].astype(np.float64))
+        cl2 = clusters(fc["boxes"], fc["scores"], fc["classes"].astype(np.float64))
         assert len(cl3) == len(cl1) == len(cl2) == 6 and all(len(m) == 3 for _, m in cl3) and all(len(m) == 2 for _, m in cl1 + cl2)
         obj3 = {frozenset(m): k for k, (_, m) in enumerate(cl3)}
         stage1_rows = [m for _, m in cl1]                                  # fused row r of stage one = cluster r of (A, B)
-        out2, _ = _launch([fc], None, "v-avg", None, prior)
+        out2, _ = launch([fc], None, "v-avg", None, None, prior)
         assert out2["counts"][0] == 6
         for r2, (_, mem2) in enumerate(cl2):
             f_row, c_row = [x for x in mem2 if x < 6][0], [x for x in mem2 if x >= 6][0]
             mem3 = frozenset(stage1_rows[f_row]) | {c_row + 6}
             assert mem3 in obj3, "the cascade's stage-two cluster is not a three-way cluster"
             k3 = obj3[mem3]
-            lq3, b3, v3, bd3 = restate(abc["lp"], abc["boxes"], abc["scores"], abc["vars"], cl3[k3][1], "v-avg", lprior)
-            _, _, _, bd1 = restate(ab["lp"], ab["boxes"], ab["scores"], ab["vars"], stage1_rows[f_row], "v-avg", lprior)
-            _, _, _, bd2 = restate(fc["lp"], fc["boxes"], fc["scores"], fc["vars"], mem2, "v-avg", lprior)
+            ref = lambda im, mem: restate(im["lp"], mem, boxes=im["boxes"], scores=im["scores"], var=im["vars"], box="v-avg",  # noqa: E731
+                                          log_prior=lprior)
+            w3 = ref(abc, cl3[k3][1])
+            lq3, b3, v3, bd3 = w3["lq"], w3["box"], w3["var"], w3["lq_bound"]
+            bd1, bd2 = ref(ab, stage1_rows[f_row])["lq_bound"], ref(fc, mem2)["lq_bound"]
             s3 = np.exp(lq3.astype(np.float64))
             casc = bd2 + bd1 + float((s3 * bd1).sum())
             got_d = (direct[b][3][k3], direct[b][0][k3], direct[b][4][k3])
@@ -303,7 +236,6 @@ def test_fuse_detections_is_pack_plus_fuse_and_equals_the_file_route():
     """fuse_detections(with_posterior=True) on two pseudo-head detectors = pack_rows + fuse_batch byte for byte, and the file route
     (late_fusion over prediction dicts holding the same detections) gives the same six arrays; fused_device_to_j1 and fused_to_j1 then
     build the same prediction dict."""
-    from test_calibration_gpu import detector_rows
     from proben_amd import fusion as F
     from proben_amd.late_fusion import fused_device_to_j1, fused_to_j1, late_fusion
     dets = detector_rows(3)
@@ -358,13 +290,12 @@ def test_drivers_write_read_back_and_report(tmp_path, capsys):
     """demo_probEn --write_fused: the two-stage route and --one-pass write equal files on a synthetic dataset of a few pairs; the file read
     back as a detector beside a second file runs and evaluates; calibration_report --fused-posterior prints the new keys and without
     the flag its JSON is the one with the flag minus those keys."""
-    from test_stream_gpu import _weights, _write_flir
     from proben_amd.cli import calibration_report, demo_probEn, fit_temperature, save_predictions
     from proben_amd.late_fusion import read_j1
     root = tmp_path / "val"
-    _write_flir(root, 6, 96, 120, (150, 180))
+    write_flir(root, 6, 96, 120, (150, 180))
     names = ["thermal_only", "early_fusion"]
-    paths = [_weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
+    paths = [weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
     pdir = tmp_path / "pred"
     for m, p in zip(names, paths):
         save_predictions.main(["--dataset_path", str(root), "--fusion_method", m, "--model_path", p, "--prediction_path", str(pdir), "--batch", "4"])
@@ -386,7 +317,7 @@ def test_drivers_write_read_back_and_report(tmp_path, capsys):
     for lg, pr, sc, cl, vr in zip(d2["class_logits"], d2["probs"], d2["scores"], d2["classes"], d2["vars"]):
         for l, p, s, c, v in zip(lg, pr, sc, cl, vr):
             assert len(l) == 4 and len(p) == 3 and c in (0, 1, 2) and len(v) == 1 and v[0] > 0
-            assert abs(np.exp(l).sum() - 1.0) < 1e-12 and abs(np.float32(np.exp(l[c])) - np.float32(s)) <= _ulp32(s)
+            assert abs(np.exp(l).sum() - 1.0) < 1e-12 and abs(np.float32(np.exp(l[c])) - np.float32(s)) <= ulp32(s)
     # without the flag nothing changes: the evaluation is the plain run's
     plain = demo_probEn.main(["--dataset_path", str(root), "--prediction_path", str(pdir), "--detectors", ",".join(names), "--outfolder",
                               str(tmp_path / "o0"), "--dataset_name", "flir_post0"] + log)

@@ -1,120 +1,14 @@
 """Presence evidence for probEn-log (pe_proben_fuse_batch_presence, pe_bias_nll, fuse_batch(presence=...), calibration.fit_presence,
-demo_probEn --presence): what can be checked without a GPU, the np.longdouble restatement of the rule and the NumPy float64 fit that
-the GPU tests (tests/test_presence_gpu.py) compare the kernels against, and the CPU simulation DESIGN.md section 18 quotes.  The
-comparator is never the code under test.  u = 2^-53."""
+demo_probEn --presence): what can be checked without a GPU, the np.longdouble restatement of the fit's terms and the NumPy float64 fit
+that the GPU tests (tests/test_presence_gpu.py) compare the kernels against, and the CPU simulation DESIGN.md section 18 quotes.  The
+comparator is never the code under test; the rule itself is restated in tests/fuse_ref.py.  u = 2^-53."""
 import json
 
 import numpy as np
 import pytest
 import torch
 
-U = 2.0 ** -53
-LD = np.longdouble
-BOX = ["v-avg", "s-avg", "avg", "argmax"]
-
-
-def seq_sum(rows):
-    acc = np.zeros_like(rows[0])
-    for r in rows:
-        acc = acc + r
-    return acc
-
-
-# ---- the rule, restated -----------------------------------------------------------------------------------------------------------
-
-def pattern_of(src, members, D):
-    """(P, every source in range): P = OR of (1 << source) over the members whose source is inside [0, D)."""
-    ok = [0 <= int(src[t]) < D for t in members]
-    return sum({1 << int(src[t]) for t, o in zip(members, ok) if o}), all(ok)
-
-
-def restate(lp, boxes, scores, var, src, members, box, table, log_prior=None, weights=None):
-    """include/proben_hip.h's presence rule for ONE cluster in np.longdouble.  lp f64 [n, K+1], boxes f64 [n, 4], scores / var f64 [n],
-    src i32 [n], members = the cluster's rows in cluster order (matches in sorted order, pivot last), table f64 [2^D, K+1], weights =
-    the pool weight PER DETECTOR or None.  Returns a dict: lq [K+1], score, cls, box [4], var, pattern, lq_bound [K+1] (absolute, in
-    units of u), score_bound (relative, in units of u), nan (a member's source is out of range: score NaN, class 0).
-
-    The bounds, first order in u (DESIGN.md section 18 = section 17's bound and one more addition per column).
-    Column j of a cluster of m >= 2 rows: x_t = w_t lp_tj rounds once per product when pooled (S_j u, S_j = sum_t |x_t|); the sequential sum
-    is m - 1 additions of partial sums <= S_j ((m - 1) S_j u); with a prior the factor c = W - 1 (pooled: W's m - 1 additions, (m - 1) W u,
-    and the subtraction, |c| u; unpooled: exact) times log_prior_j rounds once (|c lprior_j| u) and the subtraction once more (|a'_j| u,
-    a' the column before the presence term); the presence entry is an exact input and its addition rounds once (|a_j| u):
-      A_j = [S_j] + (m - 1) S_j + [((m - 1) W + |c|) |lprior_j|] + [|c lprior_j| + |a'_j|] + |a_j|.
-    A cluster of one row: a_j = lp_j + presence_j, one addition of two exact inputs: A_j = |a_j|.
-    From there as section 17: top is one of the a_j; d_j = a_j - top rounds once: D_j = A_j + A_best + |d_j| absolute.  e_j = exp(d_j)
-    within 1 ulp (<= 2 u relative) of the exp of a d_j that is D_j u off: E_j = D_j + 2 relative (the winning column: exp(0) = 1 exactly).
-    tot adds K roundings of partial sums <= tot to the weighted sum_j s_j E_j: T = sum_j s_j E_j + K relative.
-      score = e_best / tot, one division more:   (sum_{j != best} s_j E_j) + K + 1, relative (section 11);
-      lq_j = d_j - log(tot): T u absolute on log(tot), plus log's own ulp (2 |log tot| u), plus the subtraction (|lq_j| u):
-        |lq_j - exact| <= (D_j + T + 2 |log tot| + |lq_j|) u (section 17)."""
-    m = len(members)
-    D = int(table.shape[0]).bit_length() - 1
-    P, ok = pattern_of(src, members, D)
-    k1 = lp.shape[1]
-    b, v, sc = boxes[members].astype(LD), var[members].astype(LD), scores[members].astype(LD)
-    if m == 1:
-        fbox, fvar = b[0], v[0]
-    elif box == "argmax":
-        t = int(np.argmax(scores[members]))          # first maximum in cluster order
-        fbox, fvar = b[t], v[t]
-    else:
-        lam = {"v-avg": (1 / v) / (1 / v).sum(), "s-avg": sc / sc.sum(), "avg": np.full(m, LD(1) / m)}[box]
-        fvar = 1 / (1 / v).sum() if box == "v-avg" else (lam * lam * v).sum()
-        fbox = (lam[:, None] * b).sum(0)
-    out = {"box": fbox, "var": fvar, "pattern": P, "nan": not ok, "m": m}
-    if not ok:
-        out.update(lq=np.full(k1, np.nan), score=np.nan, cls=0, lq_bound=np.zeros(k1), score_bound=0.0)
-        return out
-    pres = table[P].astype(LD)
-    if m == 1:
-        a = lp[members[0]].astype(LD) + pres
-        A = np.abs(a.astype(np.float64))
-    else:
-        x = lp[members].astype(LD)
-        pooled = weights is not None
-        W = LD(m)
-        if pooled:
-            w = np.asarray(weights, np.float64)[src[members]].astype(LD)
-            x = w[:, None] * x
-            W = seq_sum(list(w))
-        a = seq_sum(list(x))
-        S = np.abs(x.astype(np.float64)).sum(0)
-        A = (m - 1) * S + (S if pooled else 0.0)
-        if log_prior is not None:
-            c = W - LD(1)
-            a = a - c * log_prior.astype(LD)
-            if pooled:
-                A = A + ((m - 1) * float(W) + abs(float(c))) * np.abs(log_prior)
-            A = A + np.abs(float(c) * log_prior) + np.abs(a.astype(np.float64))
-        a = a + pres
-        A = A + np.abs(a.astype(np.float64))
-    top = a.max()
-    jb = int(np.argmax(a))
-    d = a - top
-    e = np.exp(d)
-    tot = seq_sum(list(e))
-    lq = d - np.log(tot)
-    s = (e / tot).astype(np.float64)
-    Dj = A + A[jb] + np.abs(d.astype(np.float64))
-    E = Dj + 2.0
-    T = float((s * E).sum()) + k1 - 1
-    Es = E.copy()
-    Es[jb] = 0.0
-    out.update(lq=lq, score=(e / tot)[jb], cls=jb, lq_bound=Dj + T + 2.0 * abs(float(np.log(tot))) + np.abs(lq.astype(np.float64)),
-               score_bound=float((s * Es).sum()) + k1 - 1 + 1)
-    return out
-
-
-def box_bound(box, m):
-    """Bound on a fused coordinate in units of X u, X = sum_t |c_t lambda_t|: the weights carry at most (m + 1) u (v-avg: a reciprocal,
-    wsum's m - 1 additions, a division; s-avg and avg less), the product one more, the m - 1 additions of partial sums <= X one each:
-    (2 m + 1) X u.  argmax and single rows: a copy."""
-    return 0 if (m == 1 or box == "argmax") else 2 * m + 1
-
-
-def var_bound(box, m):
-    """Relative bound on the fused variance in units of u (tests/test_posterior_cpu.py::var_bound)."""
-    return {"v-avg": m + 3, "s-avg": 3 * m + 4, "avg": 3 * m + 4, "argmax": 0}[box] if m > 1 else 0
+from fuse_ref import LD, seq_sum
 
 
 # ---- the fit, restated ------------------------------------------------------------------------------------------------------------
@@ -268,25 +162,6 @@ def test_simulation_held_out_nll_falls_in_every_pattern():
         assert after.mean() < before.mean()
         for P in (1, 2, 3):
             assert after[pat[held] == P].mean() < before[pat[held] == P].mean(), (seed, P)
-
-
-def test_restatement_on_a_hand_made_cluster():
-    """The rule on numbers small enough to check by hand: a lone row takes lp + presence[1 << source] and may turn into background;
-    a cluster of two takes the product and the 'both' row; a bad source gives NaN and adds no bit."""
-    lp = np.log(np.array([[0.6, 0.4], [0.7, 0.3], [0.5, 0.5]]))
-    boxes, sc, var = np.zeros((3, 4)), np.array([0.6, 0.7, 0.5]), np.ones(3)
-    src = np.array([0, 1, 2], np.int32)
-    table = np.array([[0.0, 0.0], [-1.0, 0.0], [0.5, 0.0], [2.0, 0.0]])
-    lone = restate(lp, boxes, sc, var, src, [0], "v-avg", table)
-    want = np.array([0.6 * np.exp(-1.0), 0.4])
-    assert lone["pattern"] == 1 and lone["cls"] == 1 and abs(float(lone["score"]) - want[1] / want.sum()) < 1e-15
-    pair = restate(lp, boxes, sc, var, src, [0, 1], "v-avg", table)
-    want = np.array([0.6 * 0.7 * np.exp(2.0), 0.4 * 0.3])
-    assert pair["pattern"] == 3 and pair["cls"] == 0 and abs(float(pair["score"]) - want[0] / want.sum()) < 1e-15
-    assert abs(float(np.exp(pair["lq"]).sum()) - 1.0) < 1e-15
-    bad = restate(lp, boxes, sc, var, src, [0, 2], "v-avg", table)
-    assert bad["nan"] and bad["pattern"] == 1 and bad["cls"] == 0 and np.isnan(bad["score"])
-    assert restate(lp, boxes, sc, var, src, [2], "v-avg", table)["pattern"] == 0
 
 
 # ---- argument checks --------------------------------------------------------------------------------------------------------------

@@ -1,90 +1,24 @@
 """Presence evidence for probEn-log on the GPU: pe_proben_fuse_batch_presence against the np.longdouble restatement of
-tests/test_presence_cpu.py, byte for byte against the entry points it extends at a zero table, the file route against the device route,
+tests/fuse_ref.py, byte for byte against the entry points it extends at a zero table, the file route against the device route,
 pe_bias_nll against its restatement and calibration.fit_presence against the NumPy fit.  The comparator is never the code under test;
-clusters come from oracle.proben.order_desc plus the greedy rule (tests/test_proben_logp_gpu.py::_clusters).  u = 2^-53."""
+clusters come from oracle.proben.order_desc plus the greedy rule (fuse_ref.clusters).  u = 2^-53."""
 import json
 
 import numpy as np
 import pytest
 import torch
 
-from test_presence_cpu import BOX, LD, U, bias_terms, box_bound, np_fit_bias, np_bias_nll, restate, simulate, var_bound
+from fuse_inputs import BITS_ROWS, SEQ_ROWS, dependent_files, detector_rows, launch, spec_image_set, weights, write_flir
+from fuse_ref import BOX, LD, U, box_bound, clusters, log_softmax, restate, ulp32, var_bound
+from test_presence_cpu import bias_terms, np_fit_bias, np_bias_nll, simulate
 
 pytestmark = pytest.mark.gpu
 
 POOL = [0.6, 0.5, 0.8, 0.7]
-SEQ_ROWS = {2: 1000, 4: 1000, 63: 250}         # a bound at which the bit matrices no longer fit the LDS: the sequential walk
-BITS_ROWS = 12
-
-
-def _ulp32(x):
-    x = np.abs(np.asarray(x, np.float64))
-    return np.exp2(np.maximum(np.floor(np.log2(np.maximum(x, 2.0 ** -126))), -126.0) - 23.0)
-
-
-def _log_softmax(lg):
-    d = lg - lg.max(1, keepdims=True)
-    return d - np.log(np.exp(d).sum(1, keepdims=True))
-
-
-def _rows(rng, K1, spec):
-    """spec: [(anchor x, anchor y, class, source)]; boxes 60 x 50 jittered by <= 2 px on their anchor (rows of one anchor
-    overlap with IoU > 0.8, anchors 100 px apart never meet).  Scores are the row's own p[class]."""
-    n = len(spec)
-    boxes = np.array([[x, y, x + 60.0, y + 50.0] for x, y, _, _ in spec]) + rng.uniform(-2.0, 2.0, (n, 4))
-    cls = np.array([c for _, _, c, _ in spec], np.int32)
-    lg = rng.normal(0.0, 2.0, (n, K1))
-    lg[np.arange(n), cls] += rng.uniform(1.0, 6.0, n)
-    lp = _log_softmax(lg)
-    return {"boxes": boxes, "classes": cls, "lp": lp, "scores": np.exp(lp[np.arange(n), cls]), "vars": rng.uniform(0.5, 4.0, n),
-            "src": np.array([s for _, _, _, s in spec], np.int32)}
-
-
-_SETS = {}
-
-
-def image_set(K1, D):
-    """The batch of the issue: (0) one row; (1) rows of one detector with the passthrough flag set, two of them overlapping above the gate;
-    (2) rows of every detector: a cluster of three that holds two rows of detector 0, a cluster of two, a lone row of each detector;
-    (3) a row whose NaN coordinate removes it; (4) more rows than any bound used (count -1); (5) a row with source D in a cluster of
-    two, a lone row with source D and a lone row with source -1.  Computed once per (K + 1, D) and left unchanged."""
-    if (K1, D) not in _SETS:
-        rng = np.random.default_rng(100 * K1 + D)
-        K = K1 - 1
-        c = lambda: int(rng.integers(0, K))  # noqa: E731
-        c0, c1 = c(), c()
-        imgs = [_rows(rng, K1, [(10, 10, c(), D - 1)]),
-                _rows(rng, K1, [(10, 10, c0, 1), (10, 10, c0, 1), (210, 10, c(), 1), (410, 10, c(), 1)]),
-                _rows(rng, K1, [(10, 10, c0, 0), (10, 10, c0, 0), (10, 10, c0, 1), (110, 10, c1, D - 1), (110, 10, c1, 0)] +
-                      [(10 + 100 * d, 210, c(), d) for d in range(D)]),
-                _rows(rng, K1, [(10, 10, c0, 0), (10, 10, c0, 1)]),
-                _rows(rng, K1, [(10 + (i % 6) * 100, 10 + (i // 6 % 4) * 100, 0, i % D) for i in range(SEQ_ROWS[K1] + 3)]),
-                _rows(rng, K1, [(10, 10, c0, 0), (10, 10, c0, D), (210, 10, c(), D), (410, 10, c(), -1)])]
-        nan = imgs[3]
-        lo = int(np.argmin(nan["scores"]))
-        nan["boxes"][lo, 0] = np.nan                    # the lower-scored row: its IoU with the pivot is NaN, it leaves without a cluster
-        table = rng.normal(0.0, 1.5, (2 ** D, K1))
-        table[:, K] = 0.0                               # the fit's gauge; row 0 stays random: nothing may read it
-        _SETS[(K1, D)] = (imgs, [0, 1, 0, 0, 0, 0], table)
-    return _SETS[(K1, D)]
-
-
-def _launch(imgs, passthrough, box, max_rows, table, prior=None, pool=None, with_posterior=True, **kw):
-    from proben_amd import fusion as F
-    cat = lambda k, dt: torch.from_numpy(np.ascontiguousarray(np.concatenate([i[k] for i in imgs]).astype(dt))).cuda()  # noqa: E731
-    offs = torch.tensor(np.cumsum([0] + [len(i["scores"]) for i in imgs]), dtype=torch.int32).cuda()
-    out = F.fuse_batch(cat("boxes", np.float64), cat("scores", np.float64), None, cat("vars", np.float64), cat("classes", np.int32), offs,
-                       "probEn-log", box, max_rows=max_rows, log_probs=cat("lp", np.float64), class_prior=prior,
-                       passthrough=None if passthrough is None else torch.tensor(passthrough, dtype=torch.int32).cuda(),
-                       pool_weights=pool, row_source=cat("src", np.int32) if (pool is not None or table is not None or kw.get("src")) else None,
-                       with_posterior=with_posterior, presence=table)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}, offs.cpu().numpy()
 
 
 def _reference(imgs, passthrough, box, table, lprior, pool):
     """Per image: None (over the bound) or [(pivot, members, restate's dict)] on the reference clustering."""
-    from test_proben_logp_gpu import _clusters
     ref = []
     for i, im in enumerate(imgs):
         if i == 4:
@@ -93,8 +27,9 @@ def _reference(imgs, passthrough, box, table, lprior, pool):
         if passthrough[i]:
             cl = [(r, [r]) for r in range(len(im["scores"]))]
         else:
-            cl = _clusters(im["boxes"], im["scores"], im["classes"].astype(np.float64))
-        ref.append([(piv, mem, restate(im["lp"], im["boxes"], im["scores"], im["vars"], im["src"], mem, box, table, lprior, pool))
+            cl = clusters(im["boxes"], im["scores"], im["classes"].astype(np.float64))
+        ref.append([(piv, mem, restate(im["lp"], mem, boxes=im["boxes"], scores=im["scores"], var=im["vars"], box=box, src=im["src"], weights=pool,
+                                        table=table, log_prior=lprior))
                     for piv, mem in cl])
     return ref
 
@@ -105,15 +40,15 @@ def _reference(imgs, passthrough, box, table, lprior, pool):
 @pytest.mark.parametrize("D", [2, 3, 4])
 @pytest.mark.parametrize("K1", [2, 4, 63])
 def test_fusion_against_the_restatement(K1, D, box):
-    """Every fused row of pe_proben_fuse_batch_presence against test_presence_cpu.restate on the image's own (reference) clustering: with
+    """Every fused row of pe_proben_fuse_batch_presence against fuse_ref.restate on the image's own (reference) clustering: with
     and without a non-uniform prior, pool weights and the posterior outputs, in both clustering forms (bound 12: bit matrices; bound
     SEQ_ROWS: the sequential walk; the long image is over both: counts -1).
-      score: float64 relative (sum_{j != best} s_j E_j + K + 1) u plus the float32 exit's half ulp;
-      lq:    |lq_j - exact| <= (D_j + T + 2 |log tot| + |lq_j|) u absolute, A_j carrying the presence addition (restate's docstring);
-      vars:  relative (m + 3) u for v-avg, (3 m + 4) u for s-avg / avg, a copy for argmax and single rows;
-      boxes: (2 m + 1) X u per coordinate, X = sum_t |c_t lambda_t|, a copy for argmax and single rows;
+      score: within restate's score_bound, relative, plus the float32 exit's half ulp;
+      lq:    within restate's lq_bound, absolute, A_j carrying the presence addition (fuse_ref's docstring);
+      vars:  within var_bound, relative; a copy for argmax and single rows;
+      boxes: within box_bound X u per coordinate, X = sum_t |c_t lambda_t|; a copy for argmax and single rows;
       classes, keep, counts, members, pattern, cluster: exact.  Rows nothing writes keep their pre-fill."""
-    imgs, passthrough, table = image_set(K1, D)
+    imgs, passthrough, table = spec_image_set(K1, D)
     rng = np.random.default_rng(K1 + D)
     prior = rng.dirichlet(np.full(K1, 2.0)) + 0.01
     prior = prior / prior.sum()
@@ -125,7 +60,7 @@ def test_fusion_against_the_restatement(K1, D, box):
             ref = _reference(imgs, passthrough, box, table, lprior, pool)
             for post in (False, True):
                 for bound in (BITS_ROWS, SEQ_ROWS[K1]):
-                    out, offs = _launch(imgs, passthrough, box, bound, table, prior.tolist() if use_prior else None, pool, post)
+                    out, offs = launch(imgs, passthrough, box, bound, table, prior.tolist() if use_prior else None, pool, post)
                     assert ("log_posterior" in out) == post and "pattern" in out and "cluster" in out
                     written = np.zeros(offs[-1], bool)
                     for i, (im, cl) in enumerate(zip(imgs, ref)):
@@ -150,7 +85,7 @@ def test_fusion_against_the_restatement(K1, D, box):
                                 assert not post or np.isnan(out["log_posterior"][o + r]).all()
                             else:
                                 want = w["score"]
-                                tol = 0.5 * _ulp32(float(want)) * (1 + 2.0 ** -20) + w["score_bound"] * U * float(want)
+                                tol = 0.5 * ulp32(float(want)) * (1 + 2.0 ** -20) + w["score_bound"] * U * float(want)
                                 err = abs(LD(got_s) - want)
                                 worst["score"] = max(worst["score"], float(err / tol))
                                 assert err <= tol, (i, r, m, got_s, float(want))
@@ -204,16 +139,16 @@ def test_zero_table_equals_the_existing_entry_points(D, box):
     their class is the argmax of the row's K + 1 log-posteriors and their score float32(exp(max_j lp_j)) within one float32 ulp (the
     normalisation of an already normalised row moves the float64 value by a few u)."""
     K1 = 4
-    imgs, passthrough, table = image_set(K1, D)
+    imgs, passthrough, table = spec_image_set(K1, D)
     imgs, passthrough = imgs[:4], passthrough[:4]           # sources in range: the pooled entry point would give NaN otherwise
     zero = np.zeros_like(table)
     prior = [0.3, 0.2, 0.1, 0.4]
     for bound in (BITS_ROWS, SEQ_ROWS[K1]):
         for pool in (None, POOL[:D]):
             for post in (False, True):
-                new, offs = _launch(imgs, passthrough, box, bound, zero, prior, pool, post)
-                old, _ = _launch(imgs, passthrough, box, bound, None, prior, pool, post, src=True)
-                rnd, _ = _launch(imgs, passthrough, box, bound, table, prior, pool, post)
+                new, offs = launch(imgs, passthrough, box, bound, zero, prior, pool, post)
+                old, _ = launch(imgs, passthrough, box, bound, None, prior, pool, post, src=True)
+                rnd, _ = launch(imgs, passthrough, box, bound, table, prior, pool, post)
                 assert np.array_equal(new["counts"], old["counts"]) and np.array_equal(rnd["counts"], old["counts"])
                 live = np.concatenate([np.arange(offs[i], offs[i] + new["counts"][i]) for i in range(len(imgs))])
                 for k in ("keep", "boxes") + (("cluster",) if "cluster" in old else ()):
@@ -223,7 +158,7 @@ def test_zero_table_equals_the_existing_entry_points(D, box):
                     assert np.array_equal(new["members"][live], old["members"][live]) and np.array_equal(new["vars"][live], old["vars"][live])
                     multi = live[old["members"][live] >= 2]
                 else:
-                    m_of, _ = _launch(imgs, passthrough, box, bound, zero, prior, pool, True)
+                    m_of, _ = launch(imgs, passthrough, box, bound, zero, prior, pool, True)
                     multi = live[m_of["members"][live] >= 2]
                 assert len(multi) >= 2
                 for k in set(old) - {"counts"}:
@@ -237,7 +172,7 @@ def test_zero_table_equals_the_existing_entry_points(D, box):
                 own = lp_all[offs[img_of] + new["keep"][single]]                        # keep = the row itself on both kinds of single rows
                 assert np.array_equal(new["classes"][single], own.argmax(1).astype(np.float32))
                 want = np.exp(own.max(1))
-                assert (np.abs(new["scores"][single].astype(np.float64) - want) <= _ulp32(want)).all()
+                assert (np.abs(new["scores"][single].astype(np.float64) - want) <= ulp32(want)).all()
 
 
 # ---- 3. the file route and the device route ---------------------------------------------------------------------------------------------
@@ -246,7 +181,6 @@ def test_late_fusion_and_fuse_detections_agree_byte_for_byte():
     """late_fusion(presence=...) over prediction dicts and fuse_detections(presence=...) over the same detections give the same bytes,
     with and without pool weights, on images where both detectors fired, where only one fired (rescored row by row on both routes)
     and where none fired; without the keyword both routes are what they were."""
-    from test_calibration_gpu import detector_rows
     from proben_amd import fusion as F
     from proben_amd.late_fusion import late_fusion
     src = detector_rows(3)
@@ -318,7 +252,7 @@ def test_bias_nll_against_the_restatement(C, K1, n_c):
     (DESIGN.md sections 16 and 18).  The same input twice gives the same bits."""
     from proben_amd.calibration import bias_nll
     rng = np.random.default_rng(C * 100 + K1 + n_c)
-    base = _log_softmax(rng.normal(0.0, 3.0, (C, K1)))
+    base = log_softmax(rng.normal(0.0, 3.0, (C, K1)))
     labels = rng.integers(0, K1, C).astype(np.int32)
     bad = []
     if C >= 5:
@@ -404,15 +338,14 @@ def test_fit_presence_against_the_numpy_fit():
 # ---- 6. the drivers ---------------------------------------------------------------------------------------------------------------------
 
 def test_fit_temperature_demo_and_report_drivers(tmp_path, capsys):
-    """On the synthetic prediction files of the pool-weights driver test (per image four two-row clusters and one row only thermal_only
+    """On the synthetic prediction files of fuse_inputs.dependent_files (per image four two-row clusters and one row only thermal_only
     made, which nothing in the ground truth overlaps): fit_temperature --with-presence writes the key - the pattern early_fusion alone
     has no cluster and keeps a zero row; the lone thermal_only rows are all background, so their row stops on the search bound and says
     so -, demo_probEn --calibration gives the rows that --presence with the same table typed out gives, and calibration_report prints
     the per-pattern lines and fuses its "after" rows with the table."""
-    from test_pool_gpu import _dependent_files
     from proben_amd import calibration as Cal
     from proben_amd.cli import calibration_report, demo_probEn, fit_temperature
-    root, files, preds, labels = _dependent_files(tmp_path)
+    root, files, preds, labels = dependent_files(tmp_path)
     names = ["thermal_only", "early_fusion"]
     cal = tmp_path / "cal.json"
     fit_temperature.main(["--predictions", *files, "--dataset_path", str(root), "--holdout", "0.5", "--out", str(cal),
@@ -480,12 +413,11 @@ def test_demo_proben_presence_two_stage_and_one_pass(tmp_path):
     """demo_probEn --score_fusion probEn-log --presence: the two-stage route (late_fusion) and --one-pass (FramePairPipeline) give
     identical AP tables and rows, --write_fused files included (the fused log-posterior carries the presence term), and they differ
     from the run without the flag."""
-    from test_stream_gpu import _weights, _write_flir
     from proben_amd.cli import demo_probEn, save_predictions
     root = tmp_path / "val"
-    _write_flir(root, 6, 96, 120, (150, 180))
+    write_flir(root, 6, 96, 120, (150, 180))
     names = ["thermal_only", "early_fusion"]
-    paths = [_weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
+    paths = [weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
     pdir = tmp_path / "pred"
     for m, p in zip(names, paths):
         save_predictions.main(["--dataset_path", str(root), "--fusion_method", m, "--model_path", p, "--prediction_path", str(pdir), "--batch", "4"])

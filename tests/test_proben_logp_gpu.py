@@ -1,7 +1,7 @@
 """Log-posterior ProbEn (score_fusion "probEn-log": pe_proben_pack_log_posteriors, pe_log_softmax, pe_proben_fuse_batch_logp) on the GPU.
 
 The comparator is never the code under test: oracle.proben (pinned to the reference's own outputs) where `probEn` is finite, and an
-in-test NumPy restatement of the header's formulas in np.longdouble elsewhere.  u = 2^-53 throughout."""
+the NumPy restatement of the header's formulas in np.longdouble (tests/fuse_ref.py) elsewhere.  u = 2^-53 throughout."""
 import itertools
 import json
 import os
@@ -10,54 +10,14 @@ import numpy as np
 import pytest
 import torch
 
+from fuse_inputs import (calibrated_infos, detector_rows, fuse_logp, image_rows, load_case, log_full, logit_rows, saturated_images, weights,
+                         write_flir)
+from fuse_ref import BOX, LD, U, clusters, restate, ulp32
+
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -53
-BOX = ["v-avg", "s-avg", "avg", "argmax"]
-LD = np.longdouble
-
-
-def _ulp32(x):
-    x = np.abs(np.asarray(x, np.float64))
-    return np.exp2(np.maximum(np.floor(np.log2(np.maximum(x, 2.0 ** -126))), -126.0) - 23.0)
-
-
-def _seq_sum(cols):
-    acc = np.zeros_like(cols[0])
-    for c in cols:
-        acc = acc + c
-    return acc
-
-
-def _log_full(p):
-    """log([p, 1 - sum p]) in float64, the background formed as oracle.proben.fuse_score forms it (left-to-right sum)."""
-    p = np.asarray(p, np.float64).reshape(len(p), -1)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return np.log(np.concatenate([p, (1.0 - _seq_sum(list(p.T)))[:, None]], 1))
-
-
-def _fuse_logp(infos_per_image, lps_per_image, box, max_rows=None, class_prior=None):
-    """fuse_batch in the new mode over images given as lists of reference-style dicts + one [n, K+1] log-posterior array per image."""
-    from proben_amd import fusion as F
-    b, s, p, v, c, offs = F.pack_infos(infos_per_image)
-    K1 = lps_per_image[0].shape[1]
-    lp = torch.from_numpy(np.concatenate(lps_per_image).reshape(-1, K1)).cuda()
-    out = F.fuse_batch(b, s, None, v, c, offs, "probEn-log", box, max_rows=max_rows, log_probs=lp, class_prior=class_prior)
-    return out, offs.cpu().numpy()
-
-
-def _image_rows(out, offs, i):
-    cnt = int(out["counts"][i])
-    sl = slice(offs[i], offs[i] + cnt)
-    return (out["keep"][sl].cpu().numpy(), out["boxes"][sl].cpu().numpy(), out["scores"][sl].cpu().numpy(), out["classes"][sl].cpu().numpy())
 
 
 # ---- item 2: equals probEn where probEn is sound ----------------------------------------------------------------------------------
-
-def _load_case(z, ci):
-    return [{"img_name": "x", "bbox": z[f"c{ci}_d{di}_bbox"], "score": z[f"c{ci}_d{di}_score"], "class": z[f"c{ci}_d{di}_class"],
-             "prob": z[f"c{ci}_d{di}_prob"], "vars": z[f"c{ci}_d{di}_vars"]} for di in range(int(z[f"c{ci}_ndet"]))]
-
 
 @pytest.mark.parametrize("box", BOX)
 @pytest.mark.parametrize("golden", ["proben_cases.npz", "proben_saturated.npz"])
@@ -69,14 +29,14 @@ def test_equals_proben_where_proben_is_finite(golden_dir, golden, box):
     from oracle import proben as O
     z = np.load(os.path.join(golden_dir, golden))
     n = int(z["num_cases"])
-    cases = [_load_case(z, ci) for ci in range(n)]
-    lps = [_log_full(O.concat_infos(infos)[3]) for infos in cases]
+    cases = [load_case(z, ci) for ci in range(n)]
+    lps = [log_full(O.concat_infos(infos)[3]) for infos in cases]
     finite = worst = 0
     for bound in (None, 1100):
-        out, offs = _fuse_logp(cases, lps, box, max_rows=bound)
+        out, offs = fuse_logp(cases, lps, box, max_rows=bound)
         for ci, infos in enumerate(cases):
             keep, es, eb, ec = O.nms_bayesian(*O.concat_infos(infos), 0.5, "probEn", box)
-            gk, gb, gs, gc = _image_rows(out, offs, ci)
+            gk, gb, gs, gc = image_rows(out, offs, ci)
             assert int(out["counts"][ci]) == len(keep), (golden, ci)
             np.testing.assert_array_equal(gk, keep, err_msg=f"{golden} case {ci}")
             np.testing.assert_array_equal(gb, eb, err_msg=f"{golden} case {ci} boxes")
@@ -84,7 +44,7 @@ def test_equals_proben_where_proben_is_finite(golden_dir, golden, box):
             want = es.astype(np.float32)
             np.testing.assert_array_equal(gc[ok], ec[ok].astype(np.float32), err_msg=f"{golden} case {ci} classes")
             assert np.isfinite(gs[ok]).all()
-            err = np.abs(gs[ok].astype(np.float64) - want[ok].astype(np.float64)) / _ulp32(want[ok])
+            err = np.abs(gs[ok].astype(np.float64) - want[ok].astype(np.float64)) / ulp32(want[ok])
             finite += int(ok.sum())
             worst = max(worst, float(err.max()) if ok.any() else 0.0)
             assert (err <= 1.0).all(), (golden, ci, gs[ok], want[ok])
@@ -113,191 +73,36 @@ def test_binary_vectors_k1(golden_dir):
         info = {"img_name": "x", "bbox": np.tile([[10.0, 10.0, 50.0, 60.0]], (rows, 1)), "score": sc, "class": np.zeros(rows, int),
                 "prob": sc[:, None], "vars": np.ones((rows, 1))}
         empty = dict(info, bbox=np.zeros((0, 4)), score=np.zeros(0), prob=np.zeros((0, 1)), vars=np.zeros((0, 1)), **{"class": np.zeros(0, int)})
-        out, offs = _fuse_logp([[info, empty]], [_log_full(sc[:, None])], "avg")
+        out, offs = fuse_logp([[info, empty]], [log_full(sc[:, None])], "avg")
         assert int(out["counts"][0]) == 1
         got, cls = float(out["scores"][0]), float(out["classes"][0])
         want = np.float32(max(w, 1.0 - w))
         assert cls == (1.0 if 1.0 - w > w else 0.0), (v, cls, w)
-        assert abs(got - float(want)) <= _ulp32(want), (v, got, want)
+        assert abs(got - float(want)) <= ulp32(want), (v, got, want)
         checked += 1
     assert checked >= 5
 
 
 # ---- item 3 / 5 / 6: saturated logits ----------------------------------------------------------------------------------------------
 
-K = 3
-POS = [(60 + 190 * ix, 40 + 160 * iy) for iy in range(3) for ix in range(3)]      # nine far-apart anchors inside 640 x 512
-
-
-def _softmax_f32(logits):
-    """The box head's float32 softmax (max-subtract, exp, left-to-right sum over the K + 1 columns, divide): the recipe of
-    tests/golden/gen_proben_saturated.py restated."""
-    x = (logits - logits.max(1, keepdims=True)).astype(np.float32)
-    e = np.exp(x).astype(np.float32)
-    s = np.zeros(len(x), np.float32)
-    for k in range(x.shape[1]):
-        s = (s + e[:, k]).astype(np.float32)
-    return (e / s[:, None]).astype(np.float32)
-
-
-def _saturated_logits(rng, n):
-    """Foreground margins 8-25, background 14-20 below the top (gen_proben_saturated.saturated_pools' recipe)."""
-    c = rng.integers(0, K, n)
-    m = rng.uniform(8.0, 25.0, n)
-    lg = np.empty((n, K + 1))
-    lg[:, :K] = m[:, None] - rng.uniform(8.0, 25.0, (n, K))
-    lg[:, K] = m - rng.uniform(14.0, 20.0, n)
-    lg[np.arange(n), c] = m
-    return lg.astype(np.float32), c
-
-
-_SAT = {}
-
-
-def saturated_images():
-    """48 images, two and three detectors alternating, each with clusters of 1, 2, 8 and 12 rows of one class at far-apart anchors.
-    Per image: infos with the float32 prob_score route's numbers (prob / score = the float32 softmax, as the JSON carries them), the rows'
-    logits, and the members of every cluster for the checks.  Rows are drawn so that all three float64 sums of the float32
-    probabilities occur: below, exactly and above 1."""
-    if _SAT:
-        return _SAT
-    rng = np.random.default_rng(20261016)
-    # sums of exactly 1 are rare (a few per 2^21 rows): 2^24 rows are searched for them, the first 2^17 serve the two other kinds
-    pool, pcls = [], []
-    for chunk in range(8):
-        lg, c = _saturated_logits(rng, 1 << 21)
-        p = _softmax_f32(lg)[:, :K].astype(np.float64)
-        hit = (p[:, 0] + p[:, 1] + p[:, 2]) == 1.0
-        hit[:1 << 17] |= chunk == 0
-        pool.append(lg[hit])
-        pcls.append(c[hit])
-    pool, pcls = np.concatenate(pool), np.concatenate(pcls)
-    p32 = _softmax_f32(pool)[:, :K].astype(np.float64)
-    s = p32[:, 0] + p32[:, 1] + p32[:, 2]
-    kinds = {"below": np.nonzero(s < 1.0)[0], "exact": np.nonzero(s == 1.0)[0], "over": np.nonzero(s > 1.0)[0]}
-    assert len(kinds["below"]) >= 1000 and len(kinds["over"]) >= 1000 and len(kinds["exact"]) >= 8, {k: len(v) for k, v in kinds.items()}
-    images = []
-    for b in range(48):
-        kdet = 2 + b % 2
-        dets = [{"bbox": [], "rows": []} for _ in range(kdet)]
-        anchors = rng.permutation(len(POS))
-        for a, size in zip(anchors, [1, 2, 8, 12, 2, 1, 9]):
-            kind = ["below", "exact", "over", "mixed"][int(rng.integers(0, 4))]
-            # a cluster has one class; the few exactly-1 rows keep theirs (moving a column would change the float32 sum)
-            cls = int(pcls[kinds["exact"][rng.integers(0, len(kinds["exact"]))]]) if kind in ("exact", "mixed") else int(rng.integers(0, K))
-            x, y = POS[a]
-            for t in range(size):
-                src = kinds[kind if kind != "mixed" else ["below", "exact", "over"][t % 3]]
-                src = src[pcls[src] == cls]
-                r = int(src[rng.integers(0, len(src))])
-                d = dets[(t + a) % kdet]
-                d["bbox"].append([x, y, x + 100, y + 80] + rng.integers(-2, 3, 4))
-                d["rows"].append(r)
-        infos, logits = [], []
-        for d in dets:
-            r = np.asarray(d["rows"], int)
-            pr = _softmax_f32(pool[r])[:, :K].astype(np.float64) if len(r) else np.zeros((0, K))
-            infos.append({"img_name": f"s{b}", "bbox": np.asarray(d["bbox"], np.float64).reshape(-1, 4), "score": pr.max(1) if len(r) else np.zeros(0),
-                          "class": pcls[r].astype(np.int64), "prob": pr, "vars": rng.uniform(0.5, 3.0, (len(r), 1))})
-            logits.append(pool[r].reshape(-1, K + 1))
-        images.append((infos, np.concatenate(logits)))
-    _SAT["images"] = images
-    allp = np.concatenate([np.concatenate([d["prob"] for d in infos]) for infos, _ in images])
-    ss = allp[:, 0] + allp[:, 1] + allp[:, 2]
-    _SAT["sum_kinds"] = (int((ss < 1).sum()), int((ss == 1).sum()), int((ss > 1).sum()))
-    return _SAT
-
-
-def _calibrated_infos(T=(1.0, 1.0, 1.0)):
-    """The images with the rows the new route sees: prob / score = calibrated_probs of the logits (float64, on the device), plus the
-    log-posteriors of calibration.log_posteriors - the inputs of pe_proben_fuse_batch_logp, taken as given by the restatement."""
-    from proben_amd.calibration import calibrated_probs, log_posteriors
-    out = []
-    for infos, logits in saturated_images()["images"]:
-        new, lps, k = [], [], 0
-        for d, t in zip(infos, T):
-            n = len(d["score"])
-            lg = torch.from_numpy(logits[k:k + n]).cuda()
-            k += n
-            if n == 0:
-                new.append(d)
-                continue
-            p, _ = calibrated_probs(lg, t)
-            p = p.cpu().numpy()
-            new.append(dict(d, prob=p, score=p[np.arange(n), d["class"]]))
-            lps.append(log_posteriors(lg, t).cpu().numpy())
-        out.append((new, np.concatenate(lps)))
-    return out
-
-
-def _clusters(boxes, scores, classes, thr=0.5):
-    """Greedy clustering of demo_probEn.py:92-143 restated: [(pivot row, members in cluster order: matches in sorted order, pivot last)]."""
-    from oracle.proben import order_desc
-    x1, y1 = boxes[:, 0] + classes * 640.0, boxes[:, 1] + classes * 512.0
-    x2, y2 = boxes[:, 2] + classes * 640.0, boxes[:, 3] + classes * 512.0
-    area = (x2 - x1 + 1.0) * (y2 - y1 + 1.0)
-    order = order_desc(scores)
-    alive = np.ones(len(scores), bool)
-    out = []
-    for pos, i in enumerate(order):
-        if not alive[i]:
-            continue
-        alive[i] = False
-        rest = order[pos + 1:]
-        rest = rest[alive[rest]]
-        w = np.maximum(0.0, np.minimum(x2[i], x2[rest]) - np.maximum(x1[i], x1[rest]) + 1.0)
-        h = np.maximum(0.0, np.minimum(y2[i], y2[rest]) - np.maximum(y1[i], y1[rest]) + 1.0)
-        inter = w * h
-        ovr = inter / (area[i] + area[rest] - inter)
-        alive[rest[~(ovr <= thr)]] = False
-        out.append((int(i), [int(q) for q in rest[ovr > thr]] + [int(i)]))
-    return out
-
-
-def _restate(lp, members, log_prior=None):
-    """The header's formulas in np.longdouble from the float64 log-posteriors: (score, class, bound in units of u).
-
-    Bound on the device's float64 score against this value, first order in u = 2^-53.  Column j: a_j is a sequential sum of m terms
-    (m - 1 additions, each rounding a partial sum of magnitude <= S_j = sum_t |lp[t][j]|: <= (m - 1) S_j u), with a prior one product
-    (|(m - 1) log_prior_j| u) and one subtraction (|a_j| u): call the total A_j u.  M = max a_j is one of them; a_j - M rounds once
-    (|a_j - M| u) and carries A_j + A_best; exp is within 1 ulp (<= 2 u relative).  So e_j has relative error
-    E_j = A_j + A_best + |a_j - M| + 2 (the winning column: e = exp(0) = 1 exactly, E = 0 + its share through M, counted in the
-    others).  The normaliser adds K roundings of partial sums <= its value (K u) to the weighted sum_j s_j E_j; the division one more.
-    score = e_best / tot: (sum_j s_j E_j) + K + 1, in u."""
-    m = len(members)
-    x = lp[members].astype(LD)
-    a = _seq_sum(list(x))
-    S = np.abs(lp[members]).sum(0)
-    A = (m - 1) * S
-    if log_prior is not None:
-        a = a - LD(m - 1) * log_prior.astype(LD)
-        A = A + np.abs((m - 1) * log_prior) + np.abs(a.astype(np.float64))
-    e = np.exp(a - a.max())
-    s = e / _seq_sum(list(e))
-    j = int(np.argmax(s))
-    E = A + A[j] + np.abs((a - a.max()).astype(np.float64)) + 2.0
-    E[j] = 0.0
-    bound = float((s.astype(np.float64) * E).sum()) + len(a) - 1 + 1
-    return s[j], j, bound
-
-
 def _check_against_restatement(cal, out, offs, log_prior=None):
-    """Every fused row of `out` against _restate on the image's own clustering.  Returns (rows, clusters by size, largest observed error
+    """Every fused row of `out` against fuse_ref.restate on the image's own clustering.  Returns (rows, clusters by size, largest observed error
     in units of its bound).  The float32 exit rounds once more: half an ulp32 of the expected score on top of the float64 bound."""
     rows, worst, sizes = 0, 0.0, {}
     for i, (infos, lp) in enumerate(cal):
         from oracle.proben import concat_infos
         b, s, c, _, _ = concat_infos(infos)
-        cl = _clusters(b, s, c)
-        gk, gb, gs, gc = _image_rows(out, offs, i)
+        cl = clusters(b, s, c)
+        gk, gb, gs, gc = image_rows(out, offs, i)
         np.testing.assert_array_equal(gk, [p for p, _ in cl])
         for r, (piv, mem) in enumerate(cl):
             sizes[len(mem)] = sizes.get(len(mem), 0) + 1
             if len(mem) == 1:           # a cluster of one keeps its row's score and class, prior or not
                 assert gs[r] == np.float32(s[piv]) and gc[r] == c[piv]
                 continue
-            want, j, bound = _restate(lp, mem, log_prior)
-            tol = 0.5 * _ulp32(float(want)) * (1 + 2.0 ** -20) + bound * U * float(want)
+            w = restate(lp, mem, log_prior=log_prior)
+            want, j, bound = w["score"], w["cls"], w["score_bound"]
+            tol = 0.5 * ulp32(float(want)) * (1 + 2.0 ** -20) + bound * U * float(want)
             err = abs(LD(gs[r]) - want)
             worst = max(worst, float(err / tol))
             assert err <= tol, (i, r, len(mem), gs[r], float(want), float(err), tol)
@@ -310,10 +115,9 @@ def test_defined_where_proben_is_not():
     """Condition, not a measurement: on saturated rows every fused score of the new route is finite and in (0, 1], while the `probEn`
     route over the same detections (the float32 prob_score of the same logits, background = 1 - sum p) gives non-finite scores.
 
-    Scores and classes against the longdouble restatement within the bound derived in _restate: for a cluster of m rows and K + 1 = 4
-    columns, [sum_j s_j ((m - 1)(S_j + S_best) + |a_j - M| + 2) + K + 1] u on the float64 score - the losing columns' large sums S_j enter
-    weighted by their own posterior s_j ~ e^-30 - plus the half ulp32 of the float32 exit, which dominates: a float64 error of a few
-    hundred u is 1e-14 relative, the exit's rounding 6e-8.  Measured on an MI355X: see DESIGN.md section 11."""
+    Scores and classes against the longdouble restatement within its score bound (tests/fuse_ref.py) - the losing columns' large sums
+    enter weighted by their own posterior s_j ~ e^-30 - plus the half ulp32 of the float32 exit, which dominates: a float64 error of a
+    few hundred u is 1e-14 relative, the exit's rounding 6e-8.  Measured on an MI355X: see DESIGN.md section 11."""
     from proben_amd import fusion as F
     sat = saturated_images()
     below, exact, over = sat["sum_kinds"]
@@ -322,14 +126,14 @@ def test_defined_where_proben_is_not():
     b, s, p, v, c, offs = F.pack_infos([infos for infos, _ in sat["images"]])
     old = F.fuse_batch(b, s, p, v, c, offs, "probEn", "v-avg")
     oh = offs.cpu().numpy()
-    old_scores = np.concatenate([_image_rows(old, oh, i)[2] for i in range(len(sat["images"]))])
+    old_scores = np.concatenate([image_rows(old, oh, i)[2] for i in range(len(sat["images"]))])
     bad = int((~np.isfinite(old_scores)).sum())
     assert bad > 0, "the inputs are too easy: probEn is finite everywhere"
     # the new route on the same detections' logits
-    cal = _calibrated_infos()
+    cal = calibrated_infos()
     for box in BOX:
-        out, offs2 = _fuse_logp([i for i, _ in cal], [lp for _, lp in cal], box)
-        new_scores = np.concatenate([_image_rows(out, offs2, i)[2] for i in range(len(cal))])
+        out, offs2 = fuse_logp([i for i, _ in cal], [lp for _, lp in cal], box)
+        new_scores = np.concatenate([image_rows(out, offs2, i)[2] for i in range(len(cal))])
         assert len(new_scores) == len(old_scores)
         assert np.isfinite(new_scores).all() and (new_scores > 0).all() and (new_scores <= 1).all(), new_scores[~np.isfinite(new_scores)]
         rows, sizes, worst = _check_against_restatement(cal, out, offs2)
@@ -341,59 +145,59 @@ def test_defined_where_proben_is_not():
 def test_clustering_form_and_batching_move_no_bit():
     """The bit-matrix walk (bound = the longest image) and the sequential walk (max_rows = 1100) give the same bytes in the new mode, and
     an image's result does not depend on which images share its launch."""
-    cal = _calibrated_infos()
+    cal = calibrated_infos()
     infos, lps = [i for i, _ in cal], [lp for _, lp in cal]
     prior = [0.3, 0.2, 0.1, 0.4]
-    tight, offs = _fuse_logp(infos, lps, "s-avg", class_prior=prior)
-    wide, _ = _fuse_logp(infos, lps, "s-avg", max_rows=1100, class_prior=prior)
+    tight, offs = fuse_logp(infos, lps, "s-avg", class_prior=prior)
+    wide, _ = fuse_logp(infos, lps, "s-avg", max_rows=1100, class_prior=prior)
     assert torch.equal(tight["counts"], wide["counts"]) and int(tight["counts"].sum()) > 100
-    rev, offs_r = _fuse_logp(infos[::-1], lps[::-1], "s-avg", class_prior=prior)
+    rev, offs_r = fuse_logp(infos[::-1], lps[::-1], "s-avg", class_prior=prior)
     n = len(infos)
     for i in range(n):
-        a, w = _image_rows(tight, offs, i), _image_rows(wide, offs, i)
-        r = _image_rows(rev, offs_r, n - 1 - i)
+        a, w = image_rows(tight, offs, i), image_rows(wide, offs, i)
+        r = image_rows(rev, offs_r, n - 1 - i)
         for x, y, z in zip(a, w, r):
             assert x.tobytes() == y.tobytes() == z.tobytes(), i
     for i in (0, 7, 47):            # alone in its launch
-        one, o1 = _fuse_logp([infos[i]], [lps[i]], "s-avg", class_prior=prior)
-        for x, y in zip(_image_rows(tight, offs, i), _image_rows(one, o1, 0)):
+        one, o1 = fuse_logp([infos[i]], [lps[i]], "s-avg", class_prior=prior)
+        for x, y in zip(image_rows(tight, offs, i), image_rows(one, o1, 0)):
             assert x.tobytes() == y.tobytes(), i
     from proben_amd import _lib
     with pytest.raises(_lib.HipLibraryError, match="LDS"):
-        _fuse_logp(infos, lps, "s-avg", max_rows=2000)
+        fuse_logp(infos, lps, "s-avg", max_rows=2000)
 
 
 def test_class_prior():
     """A uniform prior subtracts one constant from every column: against None the keep sets, boxes and classes are identical and the
-    scores agree within the bound of _restate (each against the same longdouble value; not necessarily the same bytes).  A non-uniform
+    scores agree within the bound of fuse_ref.restate (each against the same longdouble value; not necessarily the same bytes).  A non-uniform
     prior against the restatement; clusters of one are untouched (checked row by row in _check_against_restatement)."""
-    cal = _calibrated_infos((1.3, 0.8, 2.0))
+    cal = calibrated_infos((1.3, 0.8, 2.0))
     infos, lps = [i for i, _ in cal], [lp for _, lp in cal]
-    none, offs = _fuse_logp(infos, lps, "v-avg")
-    uni, _ = _fuse_logp(infos, lps, "v-avg", class_prior=[1, 1, 1, 1])
+    none, offs = fuse_logp(infos, lps, "v-avg")
+    uni, _ = fuse_logp(infos, lps, "v-avg", class_prior=[1, 1, 1, 1])
     assert torch.equal(none["counts"], uni["counts"])
     for i in range(len(infos)):
-        a, b = _image_rows(none, offs, i), _image_rows(uni, offs, i)
+        a, b = image_rows(none, offs, i), image_rows(uni, offs, i)
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes() and a[3].tobytes() == b[3].tobytes()
     r0, _, w0 = _check_against_restatement(cal, none, offs)
     r1, _, w1 = _check_against_restatement(cal, uni, offs, np.log(np.full(4, 0.25)))
     # the same longdouble value either way (the uniform prior cancels in the softmax): uni is also within None's bound
     r2, _, w2 = _check_against_restatement(cal, uni, offs)
     prior = np.array([0.02, 0.5, 0.08, 0.4])
-    out, _ = _fuse_logp(infos, lps, "v-avg", class_prior=prior.tolist())
+    out, _ = fuse_logp(infos, lps, "v-avg", class_prior=prior.tolist())
     r3, _, w3 = _check_against_restatement(cal, out, offs, np.log(prior / prior.sum()))
-    moved = sum(int((_image_rows(out, offs, i)[2] != _image_rows(none, offs, i)[2]).sum()) for i in range(len(infos)))
+    moved = sum(int((image_rows(out, offs, i)[2] != image_rows(none, offs, i)[2]).sum()) for i in range(len(infos)))
     assert moved > 0, "the non-uniform prior changed no score"
     print(f"prior: {r0} clusters; largest error / bound: none {w0:.3f}, uniform {w1:.3f} (against the prior-free value {w2:.3f}), "
           f"non-uniform {w3:.3f}; {moved} scores moved by the non-uniform prior")
     from proben_amd import fusion as F
     with pytest.raises(ValueError, match=r"lists 3 entries for K \+ 1 = 4"):
-        _fuse_logp(infos, lps, "v-avg", class_prior=[0.2, 0.3, 0.5])
+        fuse_logp(infos, lps, "v-avg", class_prior=[0.2, 0.3, 0.5])
     # fusion() (one image, lists in) takes the same route
     one = [dict(d, class_logits=saturated_images()["images"][0][1][k:k + len(d["score"])].tolist())
            for d, k in zip(infos[0], np.cumsum([0] + [len(d["score"]) for d in infos[0]]))]
     fb, fs, fc = F.fusion(["probEn-log", "v-avg"], *one, temperatures=[1.3, 0.8, 2.0][:len(one)], class_prior=prior.tolist())
-    want = _image_rows(out, offs, 0)
+    want = image_rows(out, offs, 0)
     assert fs.numpy().tobytes() == want[2].tobytes() and fc.numpy().tobytes() == want[3].tobytes()
     assert np.asarray(fb).tobytes() == want[1].tobytes()
 
@@ -407,7 +211,7 @@ def _np_log_softmax(lg32, T):
     return d - np.log(s), d, s
 
 
-def _log_softmax_bound(K, d, s, lp):
+def _log_posterior_bound(K, d, s, lp):
     """|device - NumPy| per element, first order.  d = z - m is the same IEEE operations on both sides: identical.  Either side's sum s
     of the K + 1 exponentials is within (2 + K) u relative (exp within 1 ulp <= 2 u, K additions of partial sums <= s, in any order),
     so log(s) moves by that much ABSOLUTELY, plus its own 1 ulp (<= 2 u |log s|); the subtraction rounds once (u |lp|).  Two sides:
@@ -419,17 +223,16 @@ def _log_softmax_bound(K, d, s, lp):
 @pytest.mark.parametrize("Kc", [3, 1, 80])
 @pytest.mark.parametrize("T", [0.25, 1.0, 1.7])
 def test_log_softmax_against_numpy_float64(Kc, T):
-    """pe_log_softmax on 10^5 rows spanning +-60 with exact ties and flat rows (the rows of tests/test_calibration_gpu.py) against NumPy's
-    float64 log_softmax, within _log_softmax_bound; exp of it is the calibrated probability to the same order; every value finite."""
-    from test_calibration_gpu import _logit_rows
+    """pe_log_softmax on 10^5 rows spanning +-60 with exact ties and flat rows (fuse_inputs.logit_rows) against NumPy's
+    float64 log_softmax, within _log_posterior_bound; exp of it is the calibrated probability to the same order; every value finite."""
     from proben_amd.calibration import calibrated_probs, log_posteriors
     rng = np.random.default_rng(7 * Kc + int(T * 100))
-    lg = _logit_rows(rng, 100_000, Kc)
+    lg = logit_rows(rng, 100_000, Kc)
     dl = torch.from_numpy(np.ascontiguousarray(lg)).cuda()
     got = log_posteriors(dl, T).cpu().numpy()
     want, d, s = _np_log_softmax(lg, T)
     assert got.dtype == np.float64 and got.shape == want.shape and np.isfinite(got).all() and (got <= 0).all()
-    err, bound = np.abs(got - want), _log_softmax_bound(Kc, d, s, want)
+    err, bound = np.abs(got - want), _log_posterior_bound(Kc, d, s, want)
     print(f"K={Kc} T={T}: largest |difference| {err.max() / U:.2f} u, largest error / bound {(err / bound).max():.3f}, most negative {want.min():.1f}")
     assert (err <= bound).all(), (err / bound).max()
     p, bg = calibrated_probs(dl, T)
@@ -445,8 +248,7 @@ def test_log_softmax_against_numpy_float64(Kc, T):
 def test_pack_log_posteriors_parity(Kc, temps):
     """On the synthetic detectors' rows every output pe_proben_pack_log_posteriors shares with pe_proben_pack_logits is byte-identical
     (boxes, scores, probabilities, variances, classes on the live rows; offsets, counts, single-source flags whole); out_log_probs is
-    pe_log_softmax of the same logits byte for byte, and within _log_softmax_bound of NumPy."""
-    from test_calibration_gpu import detector_rows
+    pe_log_softmax of the same logits byte for byte, and within _log_posterior_bound of NumPy."""
     from proben_amd import fusion as F
     from proben_amd.calibration import log_posteriors
     dets = detector_rows(Kc)
@@ -478,7 +280,7 @@ def test_pack_log_posteriors_parity(Kc, temps):
     k, lp_h = 0, lp.cpu().numpy()
     for lg, T in lgs:
         w, d, s = _np_log_softmax(lg, T)
-        assert (np.abs(lp_h[k:k + len(lg)] - w) <= _log_softmax_bound(Kc, d, s, w)).all()
+        assert (np.abs(lp_h[k:k + len(lg)] - w) <= _log_posterior_bound(Kc, d, s, w)).all()
         k += len(lg)
 
 
@@ -487,7 +289,6 @@ def test_pack_log_posteriors_parity(Kc, temps):
 def test_fuse_detections_is_pack_plus_fuse_and_equals_the_file_route():
     """fuse_detections in the new mode = pe_proben_pack_log_posteriors + pe_proben_fuse_batch_logp on the detectors' rows; and the file
     route (late_fusion over prediction dicts holding the same detections as lists, the J1 schema) gives the same rows, bit for bit."""
-    from test_calibration_gpu import detector_rows
     from proben_amd import fusion as F
     from proben_amd.late_fusion import late_fusion
     dets = detector_rows(3)
@@ -526,15 +327,14 @@ def test_fuse_detections_is_pack_plus_fuse_and_equals_the_file_route():
 
 def test_demo_proben_log_two_stage_and_one_pass(tmp_path, capsys):
     """demo_probEn --score_fusion probEn-log: the two-stage route (prediction files) and --one-pass give the same AP table and the same
-    evaluation rows on the synthetic FLIR set of tests/test_stream_gpu.py; --calibration written by fit_temperature --with-prior supplies
+    evaluation rows on the synthetic FLIR set of fuse_inputs.write_flir; --calibration written by fit_temperature --with-prior supplies
     temperatures and the class prior; --class_prior overrides it; the result differs from plain probEn's."""
-    from test_stream_gpu import _weights, _write_flir
     from proben_amd import calibration as C
     from proben_amd.cli import demo_probEn, fit_temperature, save_predictions
     root = tmp_path / "val"
-    _write_flir(root, 6, 96, 120, (150, 180))
+    write_flir(root, 6, 96, 120, (150, 180))
     names = ["thermal_only", "early_fusion"]
-    paths = [_weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
+    paths = [weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
     pdir = tmp_path / "pred"
     for m, p in zip(names, paths):
         save_predictions.main(["--dataset_path", str(root), "--fusion_method", m, "--model_path", p, "--prediction_path", str(pdir), "--batch", "4"])

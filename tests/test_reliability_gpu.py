@@ -9,9 +9,11 @@ import numpy as np
 import pytest
 import torch
 
+from fuse_inputs import weights, write_flir
+from fuse_ref import U
+
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -53
 MAX_BLOCKS, ROWS_PER_BLOCK = 1024, 256          # PE_RELIABILITY_MAX_BLOCKS, the rows per workgroup that size the grid
 
 
@@ -303,14 +305,13 @@ def test_recovery_on_the_device():
 def test_driver_end_to_end(tmp_path, capsys):
     """save_predictions x 2 -> fit_temperature --holdout 0.5 --with-variance --with-prior -> calibration_report, by the recipe of
     tests/test_variance_gpu.py::test_drivers_end_to_end (the annotations are rewritten from the detections so that rows match)."""
-    from test_stream_gpu import _weights, _write_flir
     from proben_amd import calibration as C
     from proben_amd.cli import calibration_report, fit_temperature, save_predictions
     from proben_amd.late_fusion import late_fusion
     root = tmp_path / "val"
-    _write_flir(root, 6, 96, 120, (150, 180))
+    write_flir(root, 6, 96, 120, (150, 180))
     names = ["thermal_only", "early_fusion"]
-    paths = [_weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
+    paths = [weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
     pdir = tmp_path / "pred"
     for m, p in zip(names, paths):
         save_predictions.main(["--dataset_path", str(root), "--fusion_method", m, "--model_path", p, "--prediction_path", str(pdir), "--batch", "4"])

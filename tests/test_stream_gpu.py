@@ -10,36 +10,11 @@ import numpy as np
 import pytest
 import torch
 
+from fuse_inputs import weights, write_flir
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _write_flir(root, n, H, W, rgb_hw):
-    """FLIR val layout (the tests/test_boundary_gpu.py pattern) with RGB frames of their own size."""
-    from PIL import Image
-    from proben_amd.synthetic import synthetic_images
-    (root / "thermal_8_bit").mkdir(parents=True)
-    (root / "RGB").mkdir()
-    th, rgb = synthetic_images(n, H, W, seed=31), synthetic_images(n, rgb_hw[0], rgb_hw[1], seed=32)
-    images, anns = [], []
-    for i in range(n):
-        Image.fromarray(th[i]).save(root / "thermal_8_bit" / f"FLIR_{i:05d}.jpeg", quality=95)
-        Image.fromarray(rgb[i]).save(root / "RGB" / f"FLIR_{i:05d}.jpg", quality=95)
-        images.append({"id": 10 + i, "file_name": f"thermal_8_bit/FLIR_{i:05d}.jpeg", "height": H, "width": W})
-        anns.append({"id": i + 1, "image_id": 10 + i, "category_id": 1 + i % 3, "bbox": [20, 30, 60, 80], "area": 4800, "iscrowd": 0})
-    json.dump({"images": images, "annotations": anns, "categories": [{"id": 1, "name": "person"}, {"id": 2, "name": "bicycle"},
-                                                                      {"id": 3, "name": "car"}]},
-              open(root / "FLIR_thermal_RGBT_pairs_val.json", "w"))
-
-
-def _weights(tmp, method, seed):
-    from proben_amd.synthetic import synthetic_state_dict
-    nin = {"thermal_only": 3, "early_fusion": 4, "middle_fusion": 6}[method]
-    p = tmp / f"r50_{method}.pth"
-    if not p.exists():
-        torch.save(synthetic_state_dict(50, 3, nin, seed=seed), p)
-    return str(p)
 
 
 @pytest.fixture(scope="module")
@@ -50,7 +25,7 @@ def models(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("w")
     out = {}
     for seed, m in enumerate(("early_fusion", "middle_fusion"), 1):
-        out[m] = proben_amd.DefaultPredictor(build_cfg(argparse.Namespace(fusion_method=m, model_path=_weights(tmp, m, seed)))).model
+        out[m] = proben_amd.DefaultPredictor(build_cfg(argparse.Namespace(fusion_method=m, model_path=weights(tmp, m, seed)))).model
     return out
 
 
@@ -101,9 +76,9 @@ def _run_two_stage(root, tmp, names, paths, tag):
 def test_one_pass_equals_two_stages(tmp_path):
     from proben_amd.cli import demo_probEn
     root = tmp_path / "val"
-    _write_flir(root, 6, 96, 120, (150, 180))
+    write_flir(root, 6, 96, 120, (150, 180))
     for tag, names in (("te", ["thermal_only", "early_fusion"]), ("tem", ["thermal_only", "early_fusion", "middle_fusion"])):
-        paths = [_weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
+        paths = [weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
         pdir2, out2, res2 = _run_two_stage(root, tmp_path, names, paths, tag)
         pdir1, out1 = tmp_path / f"one_{tag}", tmp_path / f"out1_{tag}"
         res1 = demo_probEn.main(["--one-pass", "--dataset_path", str(root), "--detectors", ",".join(names), "--model_paths", ",".join(paths),
@@ -129,7 +104,7 @@ def test_one_pass_equals_two_stages(tmp_path):
 def test_one_pass_refuses_rgb_only(tmp_path):
     from proben_amd.cli import demo_probEn
     root = tmp_path / "val"
-    _write_flir(root, 2, 64, 80, (64, 80))
+    write_flir(root, 2, 64, 80, (64, 80))
     with pytest.raises(ValueError, match="two-stage route"):
         demo_probEn.main(["--one-pass", "--dataset_path", str(root), "--detectors", "rgb_only,thermal_only", "--outfolder", str(tmp_path / "o")])
 
@@ -137,9 +112,9 @@ def test_one_pass_refuses_rgb_only(tmp_path):
 def test_one_pass_world_size_2_equals_world_size_1(tmp_path):
     from proben_amd import launch
     root = tmp_path / "val"
-    _write_flir(root, 7, 96, 120, (150, 180))
+    write_flir(root, 7, 96, 120, (150, 180))
     names = ["thermal_only", "early_fusion"]
-    paths = [_weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
+    paths = [weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
     env = launch.launch_env()
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)

@@ -9,9 +9,10 @@ import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from fuse_inputs import weights, write_flir
+from fuse_ref import U
 
-U = 2.0 ** -53
+pytestmark = pytest.mark.gpu
 
 
 # ---- 1. matching -------------------------------------------------------------------------------------------------------------
@@ -436,13 +437,12 @@ def test_drivers_end_to_end(tmp_path, capsys):
     """save_predictions x 2 -> fit_temperature --with-variance -> demo_probEn --calibration (two-stage and --one-pass) and
     --variance_scales.  The dataset's annotations are rewritten after the predictions exist, as displaced copies of each detector's
     first detection per image, so that every detector has matched rows with non-zero residuals whatever the synthetic weights find."""
-    from test_stream_gpu import _weights, _write_flir
     from proben_amd import calibration as C
     from proben_amd.cli import demo_probEn, fit_temperature, save_predictions
     root = tmp_path / "val"
-    _write_flir(root, 6, 96, 120, (150, 180))
+    write_flir(root, 6, 96, 120, (150, 180))
     names = ["thermal_only", "early_fusion"]
-    paths = [_weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
+    paths = [weights(tmp_path, m, s) for s, m in enumerate(names, 1)]
     pdir = tmp_path / "pred"
     for m, p in zip(names, paths):
         save_predictions.main(["--dataset_path", str(root), "--fusion_method", m, "--model_path", p, "--prediction_path", str(pdir), "--batch", "4"])
