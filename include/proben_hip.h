@@ -766,6 +766,48 @@ int pe_cocoeval_bbox(const int32_t* gt_img, const int32_t* gt_cat, const double*
                      int32_t R, const int32_t* max_dets, int32_t M, const double* area_rng, int32_t A,
                      int32_t num_threads, double* precision, double* recall);
 
+/* ---------------------------------------------------------------------------------------------
+ * Paired bootstrap of the COCO statistics over images.  Replaces running COCOeval.accumulate
+ * (detectron2/pycocotools/cocoeval.py:315-421) once per resampled dataset: matching is per image and does not change
+ * under resampling, so it is exported once by the host evaluator and only accumulate runs per replicate, on the GPU.
+ *
+ * pe_cocoeval_bbox_matches (HOST code, every pointer a host pointer): the arguments of pe_cocoeval_bbox up to num_threads,
+ *   with T <= PE_AP_BOOTSTRAP_MAX_T and max_dets[M-1] <= 256 (PE_ERR_UNSUPPORTED otherwise).  Caller-sized outputs:
+ *   list_off [K+1]: category k owns entries [list_off[k], list_off[k+1]) - per image its top max_dets[M-1] detections, images in
+ *     order, stably sorted by descending score (NaN last): what accumulate sorts for maxDet = max_dets[M-1], the same for every area range;
+ *   list_img, list_rank [n_dt]: the entry's dense image index and its rank inside its image (the list of a smaller maxDet is the
+ *     sub-sequence rank < maxDet);
+ *   list_flags [A][n_dt] (row stride n_dt): bit t = matched at iou_thrs[t], bit 16 + t = ignored at iou_thrs[t], for area range a;
+ *   npig [K][A][n_imgs]: the image's non-ignored ground truths.
+ *
+ * pe_ap_bootstrap (device pointers): the lists above (list_stride = the row stride of list_flags, >= list_off[K]); mult u8 [B][I],
+ *   replicate b holds image i mult[b][i] times (0 - 255; the caller checks the range before it narrows to u8); rec_thrs f64 [R]
+ *   ascending; cells i32 [C][3] = (category, area range, maxDet).  Per (replicate, cell, threshold), with w_j = mult[img_j] when
+ *   rank_j < maxDet and 0 otherwise:  NP = sum_i mult_i npig_i,  TP_j / FP_j = running sums of w_j tp_j / w_j fp_j  (tp = matched and not
+ *   ignored, fp = neither),  rc_j = TP_j / NP,  pr_j = TP_j / (FP_j + TP_j + 2^-52) made non-increasing from the right,
+ *   q[r] = pr[first j with rc_j >= rec_thrs[r]] or 0.
+ *   Out: psum f64 [B][C][T] = q[0] + q[1] + ... in that order; recall f64 [B][C][T] = rc_last (0 for an empty list); valid i32 [B][C]
+ *   = 1, or 0 when NP = 0 (psum 0, recall and precision -1, like the reference's untouched cells), or -1 when the cell's triple or its
+ *   list bounds are out of range; precision f64 [B][C][T][R] = q, optional (NULL: not written).
+ *   Counts are int32 (list_stride * 255 must fit) and NP int64: the same bytes whatever B and C are.  One workgroup per
+ *   (replicate, cell), one wavefront per threshold; I <= PE_AP_BOOTSTRAP_MAX_IMAGES, T <= PE_AP_BOOTSTRAP_MAX_T,
+ *   R <= PE_AP_BOOTSTRAP_MAX_R, else PE_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+#define PE_AP_BOOTSTRAP_MAX_T 16
+#define PE_AP_BOOTSTRAP_MAX_R 128
+#define PE_AP_BOOTSTRAP_MAX_IMAGES 32768
+int pe_cocoeval_bbox_matches(const int32_t* gt_img, const int32_t* gt_cat, const double* gt_box, const double* gt_area,
+                             const uint8_t* gt_crowd, const int64_t* gt_id, int64_t n_gt, const int32_t* dt_img,
+                             const int32_t* dt_cat, const double* dt_box, const double* dt_score, int64_t n_dt,
+                             int32_t n_imgs, int32_t n_cats, const double* iou_thrs, int32_t T, const double* rec_thrs,
+                             int32_t R, const int32_t* max_dets, int32_t M, const double* area_rng, int32_t A,
+                             int32_t num_threads, int64_t* list_off, int32_t* list_img, uint8_t* list_rank,
+                             uint32_t* list_flags, int32_t* npig);
+int pe_ap_bootstrap(const int64_t* list_off, const int32_t* list_img, const uint8_t* list_rank, const uint32_t* list_flags,
+                    int64_t list_stride, const int32_t* npig, const uint8_t* mult, int32_t B, int32_t I, int32_t K, int32_t A,
+                    int32_t T, const double* rec_thrs, int32_t R, const int32_t* cells, int32_t C, double* psum,
+                    double* recall, int32_t* valid, double* precision, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

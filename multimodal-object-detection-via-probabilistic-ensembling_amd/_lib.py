@@ -69,6 +69,9 @@ SIGNATURES = {
     "pe_cocoeval_bbox": [c_void_p] * 6 + [ctypes.c_int64] + [c_void_p] * 4 + [ctypes.c_int64, c_int, c_int, c_void_p, c_int,
                          c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "pe_boxhead_finalize": [c_void_p] + [c_int] * 7 + [c_void_p] * 18,
+    "pe_cocoeval_bbox_matches": [c_void_p] * 6 + [ctypes.c_int64] + [c_void_p] * 4 + [ctypes.c_int64, c_int, c_int, c_void_p, c_int,
+                                 c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int] + [c_void_p] * 5,
+    "pe_ap_bootstrap": [c_void_p] * 4 + [ctypes.c_int64] + [c_void_p] * 2 + [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5,
 }
 
 # The fusion's five entry points share one parameter order; each leaves out the fields it does not have.  (field, ctype, the entry

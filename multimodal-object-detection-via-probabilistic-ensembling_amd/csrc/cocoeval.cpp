@@ -222,6 +222,76 @@ void accumulate_cell(const Ctx& c, int k, int a, int m, double* precision, doubl
         }
     }
 }
+// The argument checks and the per-(image, category) matching that both entry points share: `what` names the caller in the message.
+int match_all(Ctx& c, const char* what, const int32_t* gt_img, const int32_t* gt_cat, const double* gt_box, const double* gt_area,
+              const uint8_t* gt_crowd, const int64_t* gt_id, int64_t n_gt, const int32_t* dt_img, const int32_t* dt_cat,
+              const double* dt_box, const double* dt_score, int64_t n_dt, int32_t n_imgs, int32_t n_cats, const double* iou_thrs,
+              int32_t T, const double* rec_thrs, int32_t R, const int32_t* max_dets, int32_t M, const double* area_rng, int32_t A,
+              bool outputs_given, int threads) {
+    if (!(outputs_given && iou_thrs && rec_thrs && max_dets && area_rng) || n_gt < 0 || n_dt < 0 || n_imgs < 0 ||
+        n_cats < 0 || T < 1 || R < 1 || M < 1 || A < 1 ||
+        (n_gt > 0 && !(gt_img && gt_cat && gt_box && gt_area && gt_crowd && gt_id)) ||
+        (n_dt > 0 && !(dt_img && dt_cat && dt_box && dt_score))) {
+        pe::set_error("%s: null pointer or bad sizes", what);
+        return PE_ERR_INVALID_ARG;
+    }
+    for (int64_t r = 0; r < n_gt; ++r)
+        if ((unsigned)gt_img[r] >= (unsigned)n_imgs || (unsigned)gt_cat[r] >= (unsigned)n_cats) {
+            pe::set_error("%s: ground-truth row %lld has image %d / category %d out of range", what, (long long)r, gt_img[r],
+                          gt_cat[r]);
+            return PE_ERR_INVALID_ARG;
+        }
+    for (int64_t r = 0; r < n_dt; ++r)
+        if ((unsigned)dt_img[r] >= (unsigned)n_imgs || (unsigned)dt_cat[r] >= (unsigned)n_cats) {
+            pe::set_error("%s: detection row %lld has image %d / category %d out of range", what, (long long)r, dt_img[r],
+                          dt_cat[r]);
+            return PE_ERR_INVALID_ARG;
+        }
+    c.gt_box = gt_box; c.gt_area = gt_area; c.gt_crowd = gt_crowd; c.gt_id = gt_id;
+    c.dt_box = dt_box; c.dt_score = dt_score;
+    c.iou_thrs = iou_thrs; c.T = T; c.rec_thrs = rec_thrs; c.R = R; c.max_dets = max_dets; c.M = M;
+    c.area_rng = area_rng; c.A = A; c.n_imgs = n_imgs; c.n_cats = n_cats;
+    bucket(gt_img, gt_cat, n_gt, n_imgs, n_cats, c.gt_off, c.gt_idx);
+    bucket(dt_img, dt_cat, n_dt, n_imgs, n_cats, c.dt_off, c.dt_idx);
+    const int64_t cells = (int64_t)n_imgs * n_cats;
+    c.pairs.resize(cells);
+    parallel_for(cells, threads, [&](int64_t cell) { eval_pair(c, cell); });
+    return PE_OK;
+}
+
+int thread_count(int32_t num_threads) {
+    return num_threads > 0 ? num_threads : (int)std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
+}
+
+// The list accumulate_cell sorts for category k at maxDet = maxDets[-1], written out: per image the kept detections in image order,
+// stably sorted by descending score.  It is the same for every area range (only the flags differ), so it is stored once per category.
+void export_category(const Ctx& c, int k, int64_t base, int32_t* list_img, uint8_t* list_rank, uint32_t* list_flags, int64_t stride,
+                     int32_t* npig) {
+    const int T = c.T, A = c.A, I = c.n_imgs;
+    struct Row { double score; int img; int d; };
+    std::vector<Row> rows;
+    for (int i = 0; i < I; ++i) {
+        const PairEval& pe = c.pairs[(int64_t)k * I + i];
+        for (int a = 0; a < A; ++a) npig[((size_t)k * A + a) * I + i] = pe.present ? pe.gt_kept[a] : 0;
+        if (!pe.present) continue;
+        for (int d = 0; d < pe.D; ++d) rows.push_back({pe.scores[d], i, d});
+    }
+    std::stable_sort(rows.begin(), rows.end(), [](const Row& x, const Row& y) { return score_before(x.score, y.score); });
+    for (size_t j = 0; j < rows.size(); ++j) {
+        const PairEval& pe = c.pairs[(int64_t)k * I + rows[j].img];
+        list_img[base + j] = rows[j].img;
+        list_rank[base + j] = (uint8_t)rows[j].d;
+        for (int a = 0; a < A; ++a) {
+            uint32_t matched = 0, ignored = 0;
+            for (int t = 0; t < T; ++t) {
+                const size_t o = ((size_t)a * T + t) * pe.D + rows[j].d;
+                matched |= (uint32_t)(pe.matched[o] != 0) << t;
+                ignored |= (uint32_t)(pe.dt_ignore[o] != 0) << t;
+            }
+            list_flags[(size_t)a * stride + base + j] = matched | ignored << 16;
+        }
+    }
+}
 }  // namespace
 
 extern "C" int pe_cocoeval_bbox(const int32_t* gt_img, const int32_t* gt_cat, const double* gt_box, const double* gt_area,
@@ -231,43 +301,52 @@ extern "C" int pe_cocoeval_bbox(const int32_t* gt_img, const int32_t* gt_cat, co
                                 const double* rec_thrs, int32_t R, const int32_t* max_dets, int32_t M,
                                 const double* area_rng, int32_t A, int32_t num_threads, double* precision,
                                 double* recall) {
-    if (!(precision && recall && iou_thrs && rec_thrs && max_dets && area_rng) || n_gt < 0 || n_dt < 0 || n_imgs < 0 ||
-        n_cats < 0 || T < 1 || R < 1 || M < 1 || A < 1 ||
-        (n_gt > 0 && !(gt_img && gt_cat && gt_box && gt_area && gt_crowd && gt_id)) ||
-        (n_dt > 0 && !(dt_img && dt_cat && dt_box && dt_score))) {
-        pe::set_error("pe_cocoeval_bbox: null pointer or bad sizes");
-        return PE_ERR_INVALID_ARG;
-    }
-    for (int64_t r = 0; r < n_gt; ++r)
-        if ((unsigned)gt_img[r] >= (unsigned)n_imgs || (unsigned)gt_cat[r] >= (unsigned)n_cats) {
-            pe::set_error("pe_cocoeval_bbox: ground-truth row %lld has image %d / category %d out of range", (long long)r,
-                          gt_img[r], gt_cat[r]);
-            return PE_ERR_INVALID_ARG;
-        }
-    for (int64_t r = 0; r < n_dt; ++r)
-        if ((unsigned)dt_img[r] >= (unsigned)n_imgs || (unsigned)dt_cat[r] >= (unsigned)n_cats) {
-            pe::set_error("pe_cocoeval_bbox: detection row %lld has image %d / category %d out of range", (long long)r,
-                          dt_img[r], dt_cat[r]);
-            return PE_ERR_INVALID_ARG;
-        }
     Ctx c;
-    c.gt_box = gt_box; c.gt_area = gt_area; c.gt_crowd = gt_crowd; c.gt_id = gt_id;
-    c.dt_box = dt_box; c.dt_score = dt_score;
-    c.iou_thrs = iou_thrs; c.T = T; c.rec_thrs = rec_thrs; c.R = R; c.max_dets = max_dets; c.M = M;
-    c.area_rng = area_rng; c.A = A; c.n_imgs = n_imgs; c.n_cats = n_cats;
-    bucket(gt_img, gt_cat, n_gt, n_imgs, n_cats, c.gt_off, c.gt_idx);
-    bucket(dt_img, dt_cat, n_dt, n_imgs, n_cats, c.dt_off, c.dt_idx);
-    const int64_t cells = (int64_t)n_imgs * n_cats;
-    c.pairs.resize(cells);
-    int threads = num_threads > 0 ? num_threads : (int)std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
+    const int threads = thread_count(num_threads);
+    if (int st = match_all(c, "pe_cocoeval_bbox", gt_img, gt_cat, gt_box, gt_area, gt_crowd, gt_id, n_gt, dt_img, dt_cat, dt_box,
+                           dt_score, n_dt, n_imgs, n_cats, iou_thrs, T, rec_thrs, R, max_dets, M, area_rng, A, precision && recall,
+                           threads))
+        return st;
     const size_t np = (size_t)T * R * n_cats * A * M, nr = (size_t)T * n_cats * A * M;
     for (size_t i = 0; i < np; ++i) precision[i] = -1.0;
     for (size_t i = 0; i < nr; ++i) recall[i] = -1.0;
-    parallel_for(cells, threads, [&](int64_t cell) { eval_pair(c, cell); });
     const int64_t acc = (int64_t)n_cats * A * M;
     parallel_for(acc, threads, [&](int64_t j) {
         const int m = (int)(j % M), a = (int)((j / M) % A), k = (int)(j / ((int64_t)M * A));
         accumulate_cell(c, k, a, m, precision, recall);
+    });
+    return PE_OK;
+}
+
+extern "C" int pe_cocoeval_bbox_matches(const int32_t* gt_img, const int32_t* gt_cat, const double* gt_box, const double* gt_area,
+                                        const uint8_t* gt_crowd, const int64_t* gt_id, int64_t n_gt, const int32_t* dt_img,
+                                        const int32_t* dt_cat, const double* dt_box, const double* dt_score, int64_t n_dt,
+                                        int32_t n_imgs, int32_t n_cats, const double* iou_thrs, int32_t T, const double* rec_thrs,
+                                        int32_t R, const int32_t* max_dets, int32_t M, const double* area_rng, int32_t A,
+                                        int32_t num_threads, int64_t* list_off, int32_t* list_img, uint8_t* list_rank,
+                                        uint32_t* list_flags, int32_t* npig) {
+    if (T > PE_AP_BOOTSTRAP_MAX_T) {
+        pe::set_error("pe_cocoeval_bbox_matches: %d IoU thresholds, the flag masks hold %d", T, PE_AP_BOOTSTRAP_MAX_T);
+        return PE_ERR_UNSUPPORTED;
+    }
+    if (max_dets && M >= 1 && max_dets[M - 1] > 256) {
+        pe::set_error("pe_cocoeval_bbox_matches: maxDets[-1] = %d, a rank is one byte", max_dets[M - 1]);
+        return PE_ERR_UNSUPPORTED;
+    }
+    Ctx c;
+    const int threads = thread_count(num_threads);
+    const bool outs = list_off && npig && (n_dt == 0 || (list_img && list_rank && list_flags));
+    if (int st = match_all(c, "pe_cocoeval_bbox_matches", gt_img, gt_cat, gt_box, gt_area, gt_crowd, gt_id, n_gt, dt_img, dt_cat,
+                           dt_box, dt_score, n_dt, n_imgs, n_cats, iou_thrs, T, rec_thrs, R, max_dets, M, area_rng, A, outs, threads))
+        return st;
+    list_off[0] = 0;
+    for (int k = 0; k < n_cats; ++k) {
+        int64_t n = 0;
+        for (int i = 0; i < n_imgs; ++i) n += c.pairs[(int64_t)k * n_imgs + i].D;
+        list_off[k + 1] = list_off[k] + n;
+    }
+    parallel_for(n_cats, threads, [&](int64_t k) {
+        export_category(c, (int)k, list_off[k], list_img, list_rank, list_flags, n_dt, npig);
     });
     return PE_OK;
 }

@@ -124,10 +124,9 @@ class COCOevalBBox:
             return
         self._per = {(i, c): self._eval_img(i, c) for c in self.cat_ids for i in self.img_ids}
 
-    def _accumulate_native(self):
-        import ctypes
-        from . import _lib
-        T, R, K, A, M = len(self.iou_thrs), len(self.rec_thrs), len(self.cat_ids), len(self.area_rng), len(self.max_dets)
+    def _native_arrays(self):
+        """The ground-truth, detection and parameter arrays of pe_cocoeval_bbox / pe_cocoeval_bbox_matches, in their argument order
+        (the arrays are returned, not pointers: the caller keeps them alive over the call)."""
         img_ix = {v: i for i, v in enumerate(self.img_ids)}
         cat_ix = {v: i for i, v in enumerate(self.cat_ids)}
         anns = [a for a in self._gt_json.get("annotations", []) if a["category_id"] in cat_ix and a["image_id"] in img_ix]
@@ -142,18 +141,26 @@ class COCOevalBBox:
         dt_cat = np.array([cat_ix[r["category_id"]] for r in res], dtype=np.int32)
         dt_box = np.array([r["bbox"] for r in res], dtype=np.float64).reshape(-1, 4)
         dt_score = np.array([r["score"] for r in res], dtype=np.float64)
-        precision = np.empty((T, R, K, A, M), dtype=np.float64)
-        recall = np.empty((T, K, A, M), dtype=np.float64)
         iou = np.ascontiguousarray(self.iou_thrs, dtype=np.float64)
         rec = np.ascontiguousarray(self.rec_thrs, dtype=np.float64)
         md = np.array(self.max_dets, dtype=np.int32)
         ar = np.array(self.area_rng, dtype=np.float64)
-        p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a.size else None
-        st = _lib.lib().pe_cocoeval_bbox(p(gt_img), p(gt_cat), p(gt_box), p(gt_area), p(gt_crowd), p(gt_id), len(anns),
-                                         p(dt_img), p(dt_cat), p(dt_box), p(dt_score), len(res), len(self.img_ids), K,
-                                         p(iou), T, p(rec), R, p(md), M, p(ar), A, int(self.num_threads), p(precision),
-                                         p(recall))
-        _lib.check(st, "pe_cocoeval_bbox")
+        return [gt_img, gt_cat, gt_box, gt_area, gt_crowd, gt_id, len(anns), dt_img, dt_cat, dt_box, dt_score, len(res),
+                len(self.img_ids), len(self.cat_ids), iou, len(iou), rec, len(rec), md, len(md), ar, len(ar), int(self.num_threads)]
+
+    @staticmethod
+    def _native_call(name, args):
+        """Call the host entry point `name` with NumPy arrays (an empty one travels as NULL) and integers."""
+        import ctypes
+        from . import _lib
+        p = lambda a: (a.ctypes.data_as(ctypes.c_void_p) if a.size else None) if isinstance(a, np.ndarray) else a
+        _lib.check(getattr(_lib.lib(), name)(*[p(a) for a in args]), name)
+
+    def _accumulate_native(self):
+        T, R, K, A, M = len(self.iou_thrs), len(self.rec_thrs), len(self.cat_ids), len(self.area_rng), len(self.max_dets)
+        precision = np.empty((T, R, K, A, M), dtype=np.float64)
+        recall = np.empty((T, K, A, M), dtype=np.float64)
+        self._native_call("pe_cocoeval_bbox", self._native_arrays() + [precision, recall])
         self.eval = {"precision": precision, "recall": recall, "counts": [T, R, K, A, M]}
 
     def accumulate(self):
@@ -247,6 +254,33 @@ def instances_to_coco_json(instances, img_id):
     return out
 
 
+def to_dataset_category_ids(results, id_map):
+    """FLIR_evaluation.py:140-152: contiguous class ids -> the dataset's category ids, in place; `id_map` is the metadata's
+    thing_dataset_id_to_contiguous_id (None or empty: nothing to do)."""
+    if id_map:
+        rev = {v: k for k, v in id_map.items()}
+        for r in results:
+            assert r["category_id"] in rev, "A prediction has category_id={}, which is not available in the dataset.".format(r["category_id"])
+            r["category_id"] = rev[r["category_id"]]
+    return results
+
+
+def prediction_file_results(pred, gt_json):
+    """COCO result rows of a prediction dict (late_fusion.J1_KEYS: a detector's file or demo_probEn --write_fused's) as FLIREvaluator
+    would hand them to COCOevalBBox: float32 XYXY boxes through instances_to_coco_json (class whitelist, XYXY -> XYWH), then the
+    dataset's category ids."""
+    from .structures import Boxes, Instances
+    out = []
+    for i, iid in enumerate(pred["image_id"]):
+        inst = Instances((0, 0))
+        inst.pred_boxes = Boxes(torch.as_tensor(np.asarray(pred["boxes"][i], dtype=np.float64), dtype=torch.float32).reshape(-1, 4))
+        inst.scores = torch.as_tensor(pred["scores"][i], dtype=torch.float32).reshape(-1)
+        inst.pred_classes = torch.as_tensor(pred["classes"][i], dtype=torch.int64).reshape(-1)
+        out += instances_to_coco_json(inst, iid)
+    cats = sorted(c["id"] for c in gt_json.get("categories", []))
+    return to_dataset_category_ids(out, {c: i for i, c in enumerate(cats)})
+
+
 class FLIREvaluator:
     """Same constructor / reset / process / evaluate contract as the reference's FLIREvaluator."""
 
@@ -314,12 +348,7 @@ class FLIREvaluator:
             return {}
         self._results = OrderedDict()
         self._coco_results = list(itertools.chain(*[x["instances"] for x in self._predictions]))
-        rev = getattr(self._metadata, "thing_dataset_id_to_contiguous_id", None)
-        if rev:
-            rev = {v: k for k, v in rev.items()}
-            for r in self._coco_results:
-                assert r["category_id"] in rev, "A prediction has category_id={}, which is not available in the dataset.".format(r["category_id"])
-                r["category_id"] = rev[r["category_id"]]
+        to_dataset_category_ids(self._coco_results, getattr(self._metadata, "thing_dataset_id_to_contiguous_id", None))
         if self._output_dir:
             os.makedirs(self._output_dir, exist_ok=True)
             with open(os.path.join(self._output_dir, "coco_instances_results.json"), "w") as f:
