@@ -808,6 +808,34 @@ int pe_ap_bootstrap(const int64_t* list_off, const int32_t* list_img, const uint
                     int32_t T, const double* rec_thrs, int32_t R, const int32_t* cells, int32_t C, double* psum,
                     double* recall, int32_t* valid, double* precision, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Paired bootstrap of the KAIST log-average miss rate over images.  Replaces running the accumulate of
+ * evalKAIST/evaluation_script.py - the evaluator behind demo/KAIST/demo_LAMR_KAIST.py:85,145 (KAISTPedEval.accumulate) - once per
+ * resampled dataset: the per-image matching is exported once on the host (lamr_bootstrap.export_lamr_matches) and only accumulate runs
+ * per replicate, on the GPU.
+ *
+ * pe_lamr_bootstrap (device pointers): list_img i32 [n_list], the dense image index of every entry of the evaluator's list (all
+ *   images, stably sorted by descending score); list_flags u8 [n_list], bit 0 = matched, bit 1 = ignored; npig i32 [I], the image's
+ *   non-ignored ground truths; mult u8 [B][I], replicate b holds image i mult[b][i] times; fppi_thrs f64 [R]; cells i32 [C][2] =
+ *   (lo, hi), the image-index range [lo, hi) the cell is evaluated over.  Per (replicate, cell), with w_j = mult[img_j] when
+ *   lo <= img_j < hi and entry j is not ignored and 0 otherwise (an image index outside [0, I) weighs 0):
+ *     N = sum_{lo<=i<hi} mult_i,  NP = sum_{lo<=i<hi} mult_i npig_i,  F_j = sum_{j'<j} w_j' [not matched],
+ *     tp_at[r] = sum_j w_j [matched] [(double)F_j / (double)N <= fppi_thrs[r]],
+ *     and tp_at[r] = TP_tot when there is a weighted entry and the first one's first copy (F = 1 for an unmatched entry, 0 for a matched
+ *     one) is not below fppi_thrs[r]: the evaluator's index -1 reads the last operating point.
+ *   Out: tp_at i64 [B][C][R]; totals i64 [B][C][4] = N, NP, TP_tot, FP_tot; valid i32 [B][C] = 1, or 0 when NP = 0 (tp_at 0: the
+ *   evaluator leaves such a cell at -1), or -1 when the cell is not a range inside [0, I] (tp_at and totals 0).
+ *   Counts are int32 inside (n_list * 255 must fit) and int64 outside: the same bytes whatever B and C are.  One workgroup per
+ *   replicate, one wavefront per cell; C <= PE_LAMR_BOOTSTRAP_MAX_CELLS, R <= PE_LAMR_BOOTSTRAP_MAX_R,
+ *   I <= PE_AP_BOOTSTRAP_MAX_IMAGES, n_list <= (2^31 - 1) / 255, B * C < 2^31, else PE_ERR_UNSUPPORTED.  B = 0 or C = 0: PE_OK, nothing
+ *   is done; n_list = 0 with NULL lists is legal.
+ * ------------------------------------------------------------------------------------------- */
+#define PE_LAMR_BOOTSTRAP_MAX_CELLS 16
+#define PE_LAMR_BOOTSTRAP_MAX_R 16
+int pe_lamr_bootstrap(const int32_t* list_img, const uint8_t* list_flags, int64_t n_list, const int32_t* npig, const uint8_t* mult,
+                      int32_t B, int32_t I, const double* fppi_thrs, int32_t R, const int32_t* cells, int32_t C, int64_t* tp_at,
+                      int64_t* totals, int32_t* valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

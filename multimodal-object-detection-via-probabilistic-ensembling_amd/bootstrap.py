@@ -11,6 +11,7 @@ condition: detections of one class that tie in score inside one image must agree
     ap_bootstrap(matches, mult, device)                    psum / recall / valid (and the full precision table on request) per replicate
     statistics(run, matches)                               the 12 summarize() statistics and AP per class, per replicate
     bootstrap_ap(gt_json, results_a, results_b=None, ...)  point estimates, percentile intervals, standard errors, paired differences
+    paired(xa, xb, pa, pb, undefined, confidence)          the paired-difference record (lamr_bootstrap.py, section 28, reports with it too)
 """
 import numpy as np
 import torch
@@ -163,6 +164,16 @@ def _interval(x, point, confidence):
             "replicates": int(x.size)}
 
 
+def paired(xa, xb, pa, pb, undefined, confidence):
+    """The paired-difference record of two files' replicates under the same resamples: b - a with its percentile interval, standard
+    error and the two-sided bootstrap p-value 2 min(P(d* <= 0), P(d* >= 0)), over the replicates both files have defined."""
+    ok = ~(undefined(xa) | undefined(xb))
+    d = (xb - xa)[ok]
+    rec = dict(point=float(pb - pa), **_interval(d, None, confidence))
+    rec["p"] = float(min(1.0, 2.0 * min(np.mean(d <= 0), np.mean(d >= 0)))) if d.size else float("nan")
+    return rec
+
+
 def check_results(gt_json, results, name):
     ids = {im["id"] for im in gt_json["images"]}
     bad = [r["image_id"] for r in results if r["image_id"] not in ids]
@@ -211,13 +222,8 @@ def bootstrap_ap(gt_json, results_a, results_b=None, replicates=2000, seed=0, co
                      "mixed_score_ties": mixed_score_ties(m)}
         out["categories"] = list(ev.cat_ids)
     if results_b is not None:
-        def paired(xa, xb, pa, pb, undefined):
-            ok = ~(undefined(xa) | undefined(xb))
-            d = (xb - xa)[ok]
-            rec = dict(point=float(pb - pa), **_interval(d, None, confidence))
-            rec["p"] = float(min(1.0, 2.0 * min(np.mean(d <= 0), np.mean(d >= 0)))) if d.size else float("nan")
-            return rec
         (sa, ca, pa, pca), (sb, cb, pb, pcb) = reps["a"], reps["b"]
-        out["paired"] = {"stats": {s: paired(sa[1:, i], sb[1:, i], pa[i], pb[i], lambda x: x <= -1) for i, s in enumerate(STAT_NAMES)},
-                         "class_ap": {str(c): paired(ca[1:, k], cb[1:, k], pca[k], pcb[k], np.isnan) for k, c in enumerate(out["categories"])}}
+        out["paired"] = {"stats": {s: paired(sa[1:, i], sb[1:, i], pa[i], pb[i], lambda x: x <= -1, confidence) for i, s in enumerate(STAT_NAMES)},
+                         "class_ap": {str(c): paired(ca[1:, k], cb[1:, k], pca[k], pcb[k], np.isnan, confidence)
+                                      for k, c in enumerate(out["categories"])}}
     return out
