@@ -836,6 +836,58 @@ int pe_lamr_bootstrap(const int32_t* list_img, const uint8_t* list_flags, int64_
                       int32_t B, int32_t I, const double* fppi_thrs, int32_t R, const int32_t* cells, int32_t C, int64_t* tp_at,
                       int64_t* totals, int32_t* valid, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Weighted boxes fusion, batched over images: R. Solovyev, W. Wang, T. Gabruseva, "Weighted boxes fusion: Ensembling
+ * boxes from different object detection models", Image and Vision Computing 107 (2021), section 3.  Not in the reference - its
+ * weighted_box_fusion (demo/FLIR/demo_probEn.py:73-77) is the score-weighted average of a ProbEn cluster's boxes, PE_BOX_SAVG here, and
+ * is not this method.  The late-fusion baseline ProbEn is compared against, on the same rows.
+ *
+ * pe_wbf_fuse_batch: rows of image b are [offsets[b], offsets[b+1]) (or offsets[b] + [0, row_counts[b])) of the flat arrays, in detector
+ *   order; row_source i32 [Ntot] the detector index of each row; det_weights DEVICE f64 [num_detectors] (u: finite, >= 0, not all 0 - a
+ *   device pointer, so the caller's contract; options.FusionOptions validates it).  float64, every operation rounded on its own, in
+ *   this order:
+ *     U = u[0] + u[1] + ...;  s = score * u[source]
+ *     a row is skipped - counted in out_skipped[b], out_cluster = -1 - when source is outside [0, num_detectors), class is outside
+ *     [0, num_classes), a coordinate or s is not finite, !(s > 0), or s < skip_thresh (s == skip_thresh is kept)
+ *     the kept rows are visited by s descending, ties by original index descending; classes are independent; a cluster holds S, X[4], n
+ *     and the fused box F[k] = X[k] / S; a visited row with box b is tested against every cluster of its class, in creation order:
+ *       w = fmax(0, fmin(F.x2, b.x2) - fmax(F.x1, b.x1)), h likewise, inter = w * h
+ *       iou = inter / ((F.x2 - F.x1) * (F.y2 - F.y1) + (b.x2 - b.x1) * (b.y2 - b.y1) - inter)
+ *     the first maximum of iou (a NaN never wins) > iou_thresh (strict): the row joins that cluster, S += s, X[k] += s * b[k], n += 1,
+ *     F[k] = X[k] / S; else it opens a new cluster from zeros by the same update
+ *     conf = ((S / (double)n) * fmin((double)n, U)) / U
+ *   Output rows of image b, at [offsets[b], offsets[b] + out_counts[b]): the clusters by conf descending, ties by class ascending, then
+ *   creation order (a NaN conf first).  out_boxes = F, out_scores = (float)conf, out_classes = (float)class, out_members = n;
+ *   out_cluster[offsets[b] + r] = the output row (image-local) of the cluster input row r ended in.  No passthrough split: an image
+ *   on which one detector fired is fused like any other (a lone row ends at s * min(1, U) / U).  out_counts[b] = -1 and
+ *   out_skipped[b] = 0, nothing else written, if the image has more than max_rows_per_image rows.
+ *   One 1024-thread workgroup per image, a wavefront per class (class mod 16), a lane per cluster; 164 bytes of LDS per row at every
+ *   num_classes: 160 KiB hold PE_WBF_MAX_ROWS rows per image.  max_rows_per_image above it, num_detectors above PE_WBF_MAX_DETECTORS
+ *   and num_images above PE_WBF_MAX_IMAGES (a launch's thread count must stay below 2^32) return PE_ERR_UNSUPPORTED with the capacity
+ *   in the message; num_images = 0 returns PE_OK.  Arguments are checked before any device work.  No floating-point atomics: the
+ *   results of an image depend on its own rows only.
+ * ------------------------------------------------------------------------------------------- */
+#define PE_WBF_MAX_DETECTORS 8
+#define PE_WBF_MAX_ROWS 996
+#define PE_WBF_MAX_IMAGES 4194303
+int pe_wbf_fuse_batch(const double* boxes,        /* [Ntot,4] xyxy */
+                      const double* scores,       /* [Ntot] */
+                      const int32_t* classes,     /* [Ntot] */
+                      const int32_t* row_source,  /* [Ntot] */
+                      const int32_t* offsets,     /* [B+1] (or [B] when row_counts is given) */
+                      const int32_t* row_counts,  /* optional [B] */
+                      int32_t num_images, int32_t num_classes, int32_t max_rows_per_image,
+                      const double* det_weights,  /* DEVICE [num_detectors] */
+                      int32_t num_detectors, double iou_thresh, double skip_thresh,
+                      double* out_boxes,          /* [Ntot,4] */
+                      float* out_scores,          /* [Ntot] */
+                      float* out_classes,         /* [Ntot] */
+                      int32_t* out_counts,        /* [B] */
+                      int32_t* out_cluster,       /* [Ntot] */
+                      int32_t* out_members,       /* [Ntot] */
+                      int32_t* out_skipped,       /* [B] */
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

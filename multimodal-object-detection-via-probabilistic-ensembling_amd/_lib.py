@@ -72,6 +72,7 @@ SIGNATURES = {
     "pe_cocoeval_bbox_matches": [c_void_p] * 6 + [ctypes.c_int64] + [c_void_p] * 4 + [ctypes.c_int64, c_int, c_int, c_void_p, c_int,
                                  c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int] + [c_void_p] * 5,
     "pe_ap_bootstrap": [c_void_p] * 4 + [ctypes.c_int64] + [c_void_p] * 2 + [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5,
+    "pe_wbf_fuse_batch": [c_void_p] * 6 + [c_int] * 3 + [c_void_p, c_int, c_double, c_double] + [c_void_p] * 8,
     "pe_lamr_bootstrap": [c_void_p] * 2 + [ctypes.c_int64] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 4,
 }
 

@@ -124,6 +124,7 @@ _TEMPERATURES = ("temperature", lambda vals, names, source: [check_temperature(v
 _VARIANCE_SCALES = ("variance scale",
                     lambda vals, names, source: [check_variance_scale(v, f"variance scale of {n}") for v, n in zip(vals, names)])
 _POOL_WEIGHTS = ("pool weight", lambda vals, names, source: check_pool_weights(vals, len(names), source))
+_WBF_WEIGHTS = ("wbf weight", lambda vals, names, source: check_wbf_weights(vals, len(names), source))
 
 
 def calibrated_probs(logits, T):
@@ -682,6 +683,38 @@ def check_pool_weights(weights, num_detectors, who):
     if not any(w > 0 for w in out):
         raise ValueError(f"{who}: pool weights {out} are all 0")
     return out
+
+
+WBF_MAX_DETECTORS = 8        # PE_WBF_MAX_DETECTORS
+
+
+def check_wbf_weights(weights, num_detectors, who):
+    """wbf_weights argument of the fusion entry points -> [u per detector] or None: the detector weights of weighted boxes fusion
+    (score_fusion / box_fusion "wbf"), s = score * u.  Every u finite and >= 0, not all of them 0, one per detector, at most
+    WBF_MAX_DETECTORS."""
+    if weights is None:
+        return None
+    if isinstance(weights, torch.Tensor):
+        weights = weights.detach().cpu().reshape(-1).tolist()
+    weights = list(weights)
+    if len(weights) != num_detectors:
+        raise ValueError(f"{who}: {len(weights)} wbf weights for {num_detectors} detectors")
+    if not 1 <= num_detectors <= WBF_MAX_DETECTORS:
+        raise ValueError(f"{who}: wbf weights for {num_detectors} detectors (1 to {WBF_MAX_DETECTORS})")
+    out = [check_pool_weight(w, f"{who}: wbf weight of detector {k + 1}") for k, w in enumerate(weights)]
+    if not any(w > 0 for w in out):
+        raise ValueError(f"{who}: wbf weights {out} are all 0")
+    return out
+
+
+def check_wbf_skip(skip, who):
+    """wbf_skip -> the score floor of weighted boxes fusion as a float: finite and >= 0 (rows with score * u below it are skipped)."""
+    return check_pool_weight(skip, f"{who}: wbf_skip")
+
+
+def parse_wbf_weights(text, names):
+    """--wbf_weights value -> [u per name].  'a,b[,c]' is matched by position, 'name=a,name=b' by name; not both."""
+    return _parse(_WBF_WEIGHTS, "--wbf_weights", str(text), names)
 
 
 def _check_pool_table(table, what):

@@ -47,6 +47,14 @@ detectors' files have (late_fusion.fused_to_j1): class_logits = the fused log-po
 vars = the variance of the fused box under its box rule.  Fused rows whose class is the background column are not detections and are
 not written; the run prints how many.  The file is a detector's file: name it val_<name>_predictions.json and list <name> in
 --detectors to fuse it with a further detector, or hand it to fit_temperature / calibration_report.
+
+--score_fusion wbf --box_fusion wbf (either route): weighted boxes fusion (Solovyev, Wang, Gabruseva 2021; pe_wbf_fuse_batch), the
+baseline ProbEn is compared against - every row is matched against the running fused box of each cluster of its class, and a cluster
+fewer detectors than the weights' sum agree on is scored down.  --wbf_weights 1,0.7 (by position) or thermal_only=1,early_fusion=0.7 (by
+name), --wbf_iou (default 0.55), --wbf_skip (default 0).  There is no case split: an image on which one detector fired is fused too.
+--temperatures / --calibration still rebuild the scores; every other calibration option is refused.  --write_fused FILE writes the
+fused rows with class_logits [], probs [], vars [1.0] (late_fusion.wbf_to_j1) and prints how many rows were skipped:
+`bootstrap_ap val_thermal_only_predictions.json FILE` then compares the two.
 """
 import json
 import os
@@ -95,13 +103,17 @@ def main(cmd=None):
                        out_eval_path=os.path.join(args.outfolder, "FLIR_probEn_eval.json"))
     _warn_fitted(opts, [i for d in dets for i in d["image_id"]])
     fused = [] if args.write_fused else None
+    stats = {"skipped": 0}
     res = apply_late_fusion_and_evaluate(cfg, ev, dets[0], dets[1], [args.score_fusion, args.box_fusion],
                                          det_3=dets[2] if len(dets) > 2 else "", image_hw=hw, device=str(dev), names=files,
-                                         fused_out=fused, options=opts)
+                                         fused_out=fused, options=opts, iou_thresh=args.wbf_iou if opts.wbf else None, stats=stats)
     res.update(opts.named(names))
+    if opts.wbf:
+        res["wbf_iou"] = args.wbf_iou
     if fused is not None:
-        from ..late_fusion import fused_to_j1
-        _write_fused(args.write_fused, [fused_to_j1(dets, fused)], main_rank)
+        from ..late_fusion import fused_to_j1, wbf_to_j1
+        part = (wbf_to_j1(dets, fused), stats["skipped"]) if opts.wbf else fused_to_j1(dets, fused)
+        _write_fused(args.write_fused, [part], main_rank, "rows skipped" if opts.wbf else "background rows dropped")
     if main_rank:
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
@@ -109,9 +121,9 @@ def main(cmd=None):
     return res
 
 
-def _write_fused(path, parts, main_rank):
+def _write_fused(path, parts, main_rank, left_out="background rows dropped"):
     """--write_fused: this rank's (prediction dict, dropped rows) parts, in image order, gathered to rank 0 (rank order == dataset
-    order) and written as one prediction file."""
+    order) and written as one prediction file.  left_out words the count: "wbf" drops no background rows, it skips input rows."""
     from ..late_fusion import J1_KEYS, write_j1
     gathered = comm.gather(parts, dst=0)
     if not main_rank:
@@ -123,7 +135,7 @@ def _write_fused(path, parts, main_rank):
         os.makedirs(folder, exist_ok=True)
     write_j1(path, pred)
     print(f"fused detections: {path}: {sum(len(r) for r in pred['scores'])} rows on {len(pred['image'])} images written, "
-          f"{sum(d for _, d in parts)} background rows dropped")
+          f"{sum(d for _, d in parts)} {left_out}")
 
 
 def _warn_fitted(opts, image_ids):
@@ -153,7 +165,7 @@ def one_pass(args, names, world, dev, opts):
     import time
     import torch
     from ..data import PairFrames, resize_shortest_edge_shape
-    from ..late_fusion import fused_device_to_j1, fused_rows_device, predictions_to_j1, write_j1
+    from ..late_fusion import fused_device_to_j1, fused_rows_device, predictions_to_j1, wbf_device_to_j1, write_j1
     from ..pipeline import FramePairPipeline, HostFeeder
     from ..predictor import DefaultPredictor
     from ..stream import FlirPairLoader, check_workers
@@ -178,7 +190,7 @@ def one_pass(args, names, world, dev, opts):
     need_rgb = any(p.input_format in ("BGRT", "BGRTTT") for p in preds)
     loader = FlirPairLoader(args.dataset_path, args.batch, need_rgb=need_rgb, workers=workers)
     _warn_fitted(opts, [loader.items[i]["id"] for i in loader.mine])
-    pipe = FramePairPipeline([p.model for p in preds], options=opts)
+    pipe = FramePairPipeline([p.model for p in preds], options=opts, iou_thresh=args.wbf_iou if opts.wbf else None)
     fused_parts = []
     j1 = [([], [], []) for _ in names]       # per detector: names, ids, instances
     rows = []
@@ -190,7 +202,7 @@ def one_pass(args, names, world, dev, opts):
         dets, fused, batch = p
         rows.append(fused_rows_device(fused, batch.ids))        # the batch's one host synchronisation
         if args.write_fused:
-            fused_parts.append(fused_device_to_j1(fused, batch.names, batch.ids))
+            fused_parts.append((wbf_device_to_j1 if opts.wbf else fused_device_to_j1)(fused, batch.names, batch.ids))
         if args.write_predictions:
             for d, det, (nm, ids, insts) in zip(preds, dets, j1):
                 nm += batch.names
@@ -238,7 +250,7 @@ def one_pass(args, names, world, dev, opts):
                 os.makedirs(pdir, exist_ok=True)
                 write_j1(os.path.join(pdir, f"val_{m}_predictions.json"), {k: sum((g[k] for g in gathered), []) for k in pred})
     if args.write_fused:
-        _write_fused(args.write_fused, fused_parts, main_rank)
+        _write_fused(args.write_fused, fused_parts, main_rank, "rows skipped" if opts.wbf else "background rows dropped")
     res = {}
     if main_rank:
         print(f"one-pass: {stats['timed_pairs']} pairs timed, {stats['pairs_per_s']:.1f} pairs/s, GPU side waited on decode "
@@ -249,6 +261,8 @@ def one_pass(args, names, world, dev, opts):
         res = ev.evaluate()
         res["one_pass"] = stats
         res.update(opts.named(names))
+        if opts.wbf:
+            res["wbf_iou"] = args.wbf_iou
         print(json.dumps(res, indent=1))
     if comm.is_distributed():
         launch.shutdown()

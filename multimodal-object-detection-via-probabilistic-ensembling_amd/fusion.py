@@ -21,6 +21,10 @@ box_fusion "c-avg" ("probEn-log" only, with `box_correlation`, one correlation o
 generalised-least-squares mean of a cluster's boxes under that correlation and the variance the mean really has: the fusion runs at
 "v-avg" and a second launch (pe_box_gls_batch, csrc/boxcorr.hip) overwrites the boxes - and the variances, with_posterior - of the fused
 rows whose cluster has two or more rows.  Scores, classes, clusters and rows of one never read the matrix; a zero matrix is "v-avg".
+score_fusion "wbf" with box_fusion "wbf" (not in the reference, whose weighted_box_fusion is "s-avg") is weighted boxes fusion
+(Solovyev, Wang, Gabruseva 2021), the baseline ProbEn is compared against: every row is matched against the running fused box of each
+cluster of its class, a cluster's score is its mean weighted score times min(n, U) / U, and there is no passthrough case split.  A
+kernel of its own (pe_wbf_fuse_batch, csrc/wbf.hip), with `wbf_weights` (one per detector) and `wbf_skip`; DESIGN.md section 29.
 """
 import numpy as np
 import torch
@@ -33,11 +37,32 @@ SCORE_MODES = {"probEn": 0, "avg": 1, "max": 2, "probEn_binary": 3, "probEn-log"
 LOGP = "probEn-log"
 BOX_MODES = {"v-avg": 0, "s-avg": 1, "avg": 2, "argmax": 3}
 CAVG = "c-avg"      # not a mode of the fusion kernel: "v-avg" there, then pe_box_gls_batch
+WBF = "wbf"         # not a mode of the fusion kernel either: score_fusion and box_fusion together, pe_wbf_fuse_batch (csrc/wbf.hip)
+WBF_IOU = 0.55      # the method's published IoU threshold
 FRAME_W, FRAME_H = 640.0, 512.0  # class-band shift hard-coded by the reference (demo_probEn.py:100-103)
 
 
 def _check_mode(score_fusion, class_prior, who, pool_weights=None, with_posterior=False, presence=None, box_fusion=None,
-                box_correlation=None):
+                box_correlation=None, variance_scales=None, wbf_weights=None, wbf_skip=None):
+    if WBF in (score_fusion, box_fusion):
+        if score_fusion != WBF:
+            raise ValueError(f"{who}: box_fusion '{WBF}' belongs to score_fusion '{WBF}' (got {score_fusion!r}): weighted boxes fusion is "
+                             "one method, its clusters and its scores come from one walk")
+        if box_fusion != WBF:
+            raise ValueError(f"{who}: score_fusion '{WBF}' belongs to box_fusion '{WBF}' (got {box_fusion!r}): weighted boxes fusion is "
+                             "one method, its clusters and its scores come from one walk")
+        owner = f"score_fusion '{LOGP}'"
+        refused = [("class_prior belongs", class_prior, owner), ("pool_weights belong", pool_weights, owner),
+                   ("presence belongs", presence, owner), ("with_posterior belongs", with_posterior or None, owner),
+                   ("box_correlation belongs", box_correlation, f"box_fusion '{CAVG}'"),
+                   ("variance_scales belong", variance_scales, f"box_fusion 'v-avg' and '{CAVG}'")]
+        for what, value, owner in refused:
+            if value is not None:
+                raise ValueError(f"{who}: {what} to {owner} (got '{WBF}'): weighted boxes fusion reads no variance, probability or logit")
+        return
+    if wbf_weights is not None or wbf_skip is not None:
+        raise ValueError(f"{who}: {'wbf_weights belong' if wbf_weights is not None else 'wbf_skip belongs'} to score_fusion '{WBF}' with "
+                         f"box_fusion '{WBF}' (got {score_fusion!r}, {box_fusion!r})")
     if score_fusion not in SCORE_MODES:
         raise ValueError(f"{who}: unknown score_fusion {score_fusion!r} (one of {', '.join(SCORE_MODES)})")
     if box_fusion == CAVG and score_fusion != LOGP:
@@ -62,9 +87,9 @@ def _check_mode(score_fusion, class_prior, who, pool_weights=None, with_posterio
 
 
 def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="probEn", box_fusion="v-avg",
-               max_rows=None, iou_thresh=0.5, frame=(FRAME_W, FRAME_H), row_counts=None, passthrough=None, log_probs=None,
+               max_rows=None, iou_thresh=None, frame=(FRAME_W, FRAME_H), row_counts=None, passthrough=None, log_probs=None,
                class_prior=None, pool_weights=None, row_source=None, with_posterior=False, presence=None, box_correlation=None,
-               options=None):
+               options=None, wbf_weights=None, wbf_skip=None, num_classes=None):
     """Fuse B images in one launch.
 
     boxes f64 [Ntot,4], scores f64 [Ntot], probs f64 [Ntot,K], variances f64 [Ntot],
@@ -85,9 +110,23 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
       pe_proben_fuse_batch_posterior   with_posterior                        given, or NULL / NULL / 0     c-avg    yes        -
       pe_proben_fuse_batch_presence    presence                              row_source, weights or NULL   yes      or NULL    yes
     (first match from the bottom).  "c-avg" runs the chosen entry point at "v-avg" - the pooled one at weights of 1.0, which is
-    "probEn-log" bit for bit, when nothing else selects one that writes "cluster" - and then pe_box_gls_batch."""
+    "probEn-log" bit for bit, when nothing else selects one that writes "cluster" - and then pe_box_gls_batch.
+
+    iou_thresh: None (the signature default) is 0.5, and 0.55 - the method's published threshold - for "wbf".
+
+    score_fusion "wbf" with box_fusion "wbf" (weighted boxes fusion; wbf_weights one per detector - required here unless `options`
+    knows the detector count -, wbf_skip): pe_wbf_fuse_batch.  It needs row_source and reads boxes, scores and classes only: probs
+    (or num_classes, where probs is None) gives K, variances, log_probs and passthrough are ignored - an image on which one detector
+    fired is fused like any other.  Returns boxes f64 [Ntot,4], scores f32, classes f32, counts i32 [B], cluster i32 [Ntot] (the
+    image-local output row of the cluster each input row ended in; -1: the row was skipped; -2 where nothing was written), members i32
+    [Ntot] (rows in the cluster, indexed like "scores") and skipped i32 [B] (rows skipped: a bad source or class, a non-finite
+    coordinate, a score * weight that is not finite, not > 0 or below wbf_skip); no "keep"."""
     opts = O.FusionOptions.of(options, "fuse_batch", None, score_fusion, box_fusion, class_prior=class_prior, pool_weights=pool_weights,
-                              with_posterior=with_posterior, presence=presence, box_correlation=box_correlation)
+                              with_posterior=with_posterior, presence=presence, box_correlation=box_correlation, wbf_weights=wbf_weights,
+                              wbf_skip=wbf_skip)
+    if opts.wbf:
+        return _wbf_batch(opts, boxes, scores, probs, classes, offsets, max_rows, iou_thresh, row_counts, row_source, num_classes)
+    iou_thresh = 0.5 if iou_thresh is None else iou_thresh
     logp, cavg, post = opts.logp, opts.cavg, opts.with_posterior
     pool, pres = opts.pool_weights is not None, opts.presence is not None
     ntot = boxes.shape[0]
@@ -165,6 +204,49 @@ def fuse_batch(boxes, scores, probs, variances, classes, offsets, score_fusion="
     return out
 
 
+def _wbf_batch(opts, boxes, scores, probs, classes, offsets, max_rows, iou_thresh, row_counts, row_source, num_classes):
+    """fuse_batch for score_fusion / box_fusion "wbf": one pe_wbf_fuse_batch launch, no host synchronisation when max_rows is given."""
+    ntot = boxes.shape[0]
+    if row_source is None or row_source.dim() != 1 or row_source.shape[0] != ntot:
+        raise ValueError(f"fuse_batch: '{WBF}' needs row_source [Ntot] for the {ntot} rows, got "
+                         f"{None if row_source is None else tuple(row_source.shape)}")
+    if opts.wbf_weights is None:
+        raise ValueError(f"fuse_batch: '{WBF}' needs wbf_weights, one per detector (1.0 each is the unweighted method)")
+    if num_classes is None:
+        if probs is None or probs.dim() != 2:
+            raise ValueError(f"fuse_batch: '{WBF}' needs probs [Ntot, K] or num_classes for the class count")
+        num_classes = probs.shape[1]
+    _lib.require_cuda(boxes, scores, classes, offsets, row_source, row_counts)
+    dev = boxes.device
+    B = offsets.numel() - (0 if row_counts is not None else 1)
+    boxes = boxes.contiguous().double()
+    scores = scores.contiguous().double()
+    classes = classes.contiguous().to(torch.int32)
+    offsets = offsets.contiguous().to(torch.int32)
+    row_source = row_source.contiguous().to(torch.int32)
+    if max_rows is None:
+        assert row_counts is None, "max_rows must be given with row_counts (avoids a host sync)"
+        max_rows = int((offsets[1:] - offsets[:-1]).max().item()) if B > 0 else 1
+    max_rows = max(int(max_rows), 1)
+    weights = opts.wbf_on(dev)
+    out = {
+        "boxes": torch.empty((ntot, 4), dtype=torch.float64, device=dev),
+        "scores": torch.empty((ntot,), dtype=torch.float32, device=dev),
+        "classes": torch.empty((ntot,), dtype=torch.float32, device=dev),
+        "counts": torch.zeros((max(B, 1),), dtype=torch.int32, device=dev)[:B],
+        "cluster": torch.full((ntot,), -2, dtype=torch.int32, device=dev),
+        "members": torch.zeros((ntot,), dtype=torch.int32, device=dev),
+        "skipped": torch.zeros((max(B, 1),), dtype=torch.int32, device=dev)[:B],
+    }
+    P = _lib.ptr
+    st = _lib.lib().pe_wbf_fuse_batch(P(boxes), P(scores), P(classes), P(row_source), P(offsets), P(row_counts), B, int(num_classes),
+                                      max_rows, P(weights), int(weights.numel()), float(WBF_IOU if iou_thresh is None else iou_thresh),
+                                      float(opts.wbf_skip), P(out["boxes"]), P(out["scores"]), P(out["classes"]), P(out["counts"]),
+                                      P(out["cluster"]), P(out["members"]), P(out["skipped"]), _lib.stream())
+    _lib.check(st, "pe_wbf_fuse_batch")
+    return out
+
+
 def pack_infos(per_image_infos, device="cuda", with_log_probs=False, with_sources=False):
     """per_image_infos: list (images) of lists (detectors) of reference-style dicts
     {bbox, score, class, prob, vars}.  Returns the flat device tensors + offsets (with_log_probs: + the rows' "log_prob"
@@ -215,7 +297,8 @@ def fusion(method, info_1, info_2, info_3="", temperatures=None, class_prior=Non
     CPU tensors - the reference's return types.
     The option keywords, or `options` (options.FusionOptions, which documents them; not both), one value per info: the rows' prob /
     score are rebuilt from their class_logits as softmax(logits / T) (calibration.calibrate_rows; an info without logits is refused),
-    their vars multiplied by s in float64, and a row's detector is its info's position."""
+    their vars multiplied by s in float64, and a row's detector is its info's position.
+    method ("wbf", "wbf"): weighted boxes fusion at weights of 1.0 and the IoU threshold 0.55 (other weights: `options`)."""
     infos = [info_1, info_2] + ([info_3] if info_3 else [])
     opts = O.FusionOptions.of(options, "fusion", len(infos), method[0], method[1], temperatures=temperatures, class_prior=class_prior,
                               variance_scales=variance_scales, pool_weights=pool_weights, box_correlation=box_correlation)
@@ -319,7 +402,7 @@ def pack_rows(dets, max_class=2, temperatures=None, log_posteriors=False, varian
     return (ob, os_, op, ov, oc, ooff, ocnt, osingle) + ((olp,) if log_posteriors else ()) + ((osrc,) if osrc is not None else ())
 
 
-def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=0.5, temperatures=None,
+def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2, iou_thresh=None, temperatures=None,
                     class_prior=None, variance_scales=None, pool_weights=None, with_posterior=False, presence=None,
                     box_correlation=None, options=None):
     """Device-to-device stage fusion: `dets` = the result dicts of 2 or 3 detectors run on the SAME batch
@@ -331,6 +414,8 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     on "probEn-log") instead of the float32 prob_score / scores, with variance_scales through pe_proben_pack_calibrated; where the
     fusion needs each row's detector (pool_weights, presence, box_fusion "c-avg") pe_proben_pack_pooled writes it and the result
     also holds it as "row_source".  With presence, images on which one detector fired are rescored row by row, not copied.
+    iou_thresh: None is 0.5, and 0.55 for "wbf" (fuse_batch).  "wbf" has no case split: an image on which one detector fired is fused
+    like any other (the single-source flag is not read), and the result holds "cluster", "members" and "skipped" instead of "keep".
     No host synchronisation.  Returns a dict: boxes f64 [B*S,4], scores f32, classes f32, counts i32 [B],
     offsets i32 [B], stride S = len(dets) * D."""
     opts = O.FusionOptions.of(options, "fuse_detections", len(dets), score_fusion, box_fusion, temperatures=temperatures,
@@ -347,7 +432,7 @@ def fuse_detections(dets, score_fusion="probEn", box_fusion="v-avg", max_class=2
     if opts.score_fusion == "max" and opts.box_fusion == "argmax":
         from .layers import nms_batched_raw
         b32 = ob.float().view(B, S, 4)
-        keep, kcnt = nms_batched_raw(b32, os_.float().view(B, S), oc.view(B, S), ocnt, None, iou_thresh, 0, S)
+        keep, kcnt = nms_batched_raw(b32, os_.float().view(B, S), oc.view(B, S), ocnt, None, 0.5 if iou_thresh is None else iou_thresh, 0, S)
         # images where only ONE detector fired are passed through untouched by the reference (demo_probEn.py:239-254)
         single = osingle.bool()
         keep = torch.where(single[:, None], torch.arange(S, dtype=torch.int32, device=dev).expand(B, S), keep)

@@ -84,7 +84,8 @@ def _calibrated(dets, opts, names, device):
 
 
 def late_fusion(dets, method, device="cuda", temperatures=None, names=None, class_prior=None, variance_scales=None,
-                pool_weights=None, with_posterior=False, presence=None, box_correlation=None, options=None):
+                pool_weights=None, with_posterior=False, presence=None, box_correlation=None, options=None, iou_thresh=None,
+                stats=None):
     """dets: 2 or 3 J1 dicts over the same images (order = detector order).  Returns per-image
     (boxes float64 [m,4] | None, scores f32, classes f32); None = skipped image (no detector fired).
     Case split of demo_probEn.py:237-267: 0 detectors -> skip, 1 -> passthrough, >= 2 -> fusion of the
@@ -97,7 +98,10 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
     the device route's passthrough copies.
     presence: images on which one detector fired are no longer answered on the host: they go into the batched launch with their
     passthrough flag set and come back rescored row by row (never clustered), which is what the device route does with the pack
-    kernel's single-source flag - the two routes stay byte-identical."""
+    kernel's single-source flag - the two routes stay byte-identical.
+    method ("wbf", "wbf") (weighted boxes fusion, pe_wbf_fuse_batch): there is no case split at all, an image on which one detector
+    fired goes into the batched launch like any other and comes back fused (a lone box at score * min(1, U) / U).  iou_thresh: None is
+    fuse_batch's default (0.5; 0.55 for "wbf").  stats: a dict that receives "skipped", the rows "wbf" skipped over all images."""
     opts = O.FusionOptions.of(options, "late_fusion", len(dets), method[0], method[1], temperatures=temperatures, class_prior=class_prior,
                               variance_scales=variance_scales, pool_weights=pool_weights, with_posterior=with_posterior,
                               presence=presence, box_correlation=box_correlation)
@@ -111,7 +115,7 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
         live = [x for x in infos if len(x["bbox"]) > 0]
         if len(live) == 0:
             continue
-        if len(live) == 1 and presence is None:
+        if len(live) == 1 and presence is None and not opts.wbf:
             x = live[0]
             results[i] = (np.array(x["bbox"], dtype=np.float64), torch.tensor(x["score"], dtype=torch.float32),
                           torch.tensor(x["class"], dtype=torch.float32))
@@ -131,7 +135,7 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
         else:
             b, s, p, v, c, offs, *rest = F.pack_infos(batch, device, with_log_probs=logp, with_sources=opts.needs_row_source)
             out = F.fuse_batch(b, s, p, v, c, offs, log_probs=rest[0] if logp else None,
-                               row_source=rest[-1] if opts.needs_row_source else None, options=opts,
+                               row_source=rest[-1] if opts.needs_row_source else None, options=opts, iou_thresh=iou_thresh,
                                passthrough=torch.tensor(single, dtype=torch.int32, device=b.device) if presence is not None else None)
             cnt = out["counts"].cpu().numpy()
             ob, os_, oc = out["boxes"].cpu().numpy(), out["scores"].cpu(), out["classes"].cpu()
@@ -140,6 +144,8 @@ def late_fusion(dets, method, device="cuda", temperatures=None, names=None, clas
             for j, i in enumerate(where):
                 sl = slice(oh[j], oh[j] + cnt[j])
                 results[i] = (ob[sl], os_[sl], oc[sl]) + tuple(x[sl] for x in post)
+            if stats is not None and opts.wbf:
+                stats["skipped"] = stats.get("skipped", 0) + int(out["skipped"].sum().item())
     return results
 
 
@@ -184,6 +190,54 @@ def fused_to_j1(dets, fused):
         dropped += _fused_j1_rows(out, r[0], r[1].numpy() if isinstance(r[1], torch.Tensor) else r[1],
                                   r[2].numpy() if isinstance(r[2], torch.Tensor) else r[2], r[3], r[4])
     return out, dropped
+
+
+def _plain_j1_rows(out, boxes, scores, classes):
+    """One image's fused rows appended to the J1 lists of `out` as predictions_to_j1 writes a detector without logit, probability and
+    variance heads: class_logits [], probs [], vars [1.0]."""
+    m = len(scores)
+    out["boxes"].append(np.asarray(boxes, dtype=np.float64).reshape(-1, 4).tolist())
+    out["scores"].append([float(x) for x in np.asarray(scores, dtype=np.float32)])
+    out["classes"].append(np.asarray(classes).astype(np.int64).tolist())
+    out["class_logits"].append([[] for _ in range(m)])
+    out["probs"].append([[] for _ in range(m)])
+    out["vars"].append([[1.0] for _ in range(m)])
+
+
+def wbf_to_j1(dets, fused):
+    """The fused detections of late_fusion(dets, ("wbf", "wbf")) as a prediction dict (J1 schema) over the same images: boxes, scores and
+    classes as fused, and what predictions_to_j1 writes for a detector without those heads - class_logits [], probs [], vars [1.0] -,
+    since weighted boxes fusion forms no posterior and no variance.  Enough for bootstrap_ap and the evaluators; not an input of
+    "probEn".  image / image_id are dets[1]'s, as the driver pairs them; an image no detector fired on gets empty lists."""
+    ref = dets[1] if len(dets) > 1 else dets[0]
+    out = {k: [] for k in J1_KEYS}
+    for i, r in enumerate(fused):
+        out["image"].append(ref["image"][i])
+        out["image_id"].append(ref["image_id"][i])
+        if r is None:
+            r = (np.zeros((0, 4)), np.zeros((0,), dtype=np.float32), np.zeros((0,), dtype=np.float32))
+        _plain_j1_rows(out, r[0], r[1].numpy() if isinstance(r[1], torch.Tensor) else r[1],
+                       r[2].numpy() if isinstance(r[2], torch.Tensor) else r[2])
+    return out
+
+
+def wbf_device_to_j1(fused, file_names, image_ids):
+    """wbf_to_j1 for the device route: `fused` = the result of fusion.fuse_detections(..., "wbf", "wbf") on one batch.  Synchronises (the
+    rows leave for the host).  Returns (the dict, the rows the fusion skipped on this batch)."""
+    if "skipped" not in fused:
+        raise ValueError("wbf_device_to_j1: the fused rows are not those of score_fusion 'wbf'")
+    S = fused["stride"]
+    cnt = fused["counts"].cpu().numpy()
+    host = {k: fused[k].cpu().numpy() for k in ("boxes", "scores", "classes")}
+    out = {k: [] for k in J1_KEYS}
+    for b, (name, iid) in enumerate(zip(file_names, image_ids)):
+        out["image"].append(name)
+        out["image_id"].append(iid)
+        if cnt[b] < 0:
+            raise RuntimeError(f"wbf_device_to_j1: image {name} has more rows than the fusion's bound")
+        sl = slice(b * S, b * S + int(cnt[b]))
+        _plain_j1_rows(out, *(host[k][sl] for k in ("boxes", "scores", "classes")))
+    return out, int(fused["skipped"].sum().item())
 
 
 def fused_device_to_j1(fused, file_names, image_ids):
@@ -290,26 +344,28 @@ def presence_rows(dets, box_fusion="v-avg", device="cuda", temperatures=None, na
 def apply_late_fusion_and_evaluate(cfg, evaluator, det_1, det_2, method, det_3="", image_hw=None, device="cuda",
                                    img_folder="../../../Datasets/FLIR/val/thermal_8_bit/", temperatures=None, names=None,
                                    class_prior=None, variance_scales=None, pool_weights=None, fused_out=None, presence=None,
-                                   box_correlation=None, options=None):
+                                   box_correlation=None, options=None, iou_thresh=None, stats=None):
     """Same call as the reference (demo_probEn.py:198).  `image_hw`: {image_id: (H, W)} from the dataset
     json (the reference re-reads every thermal JPEG just for its shape); default 512 x 640 (FLIR).
     `img_folder`: the prefix the reference hard-codes into the `file_name` it hands to the evaluator (:200,271).
     `fused_out`: a list; when given ("probEn-log" only) the fusion keeps its posterior and the per-image 6-tuples of late_fusion are
     appended to it, for fused_to_j1 - the evaluator receives what it receives without it.
     The option keywords, or `options` (options.FusionOptions; not both), are late_fusion's; with `options`, fused_out needs one
-    built with_posterior.
+    built with_posterior - or, for ("wbf", "wbf"), nothing: the per-image 3-tuples are appended, for wbf_to_j1.  iou_thresh and stats
+    are late_fusion's.
     What the evaluator receives per image is pinned by tests/golden/p5_cases.json (the reference's function run with a recording
     evaluator): tests/test_pipeline_gpu.py::test_late_fusion_driver_reproduces_the_references_records."""
     dets = [det_1, det_2] + ([det_3] if det_3 else [])
     opts = O.FusionOptions.of(options, "late_fusion", len(dets), method[0], method[1], temperatures=temperatures, class_prior=class_prior,
                               variance_scales=variance_scales, pool_weights=pool_weights,
-                              with_posterior=fused_out is not None and options is None, presence=presence, box_correlation=box_correlation)
-    if fused_out is not None and not opts.with_posterior:
+                              with_posterior=fused_out is not None and options is None and F.WBF not in method, presence=presence,
+                              box_correlation=box_correlation)
+    if fused_out is not None and not (opts.with_posterior or opts.wbf):
         raise ValueError("apply_late_fusion_and_evaluate: fused_out needs options built with_posterior")
     evaluator.reset()
     print("Method: ", method)
     start = time.time()
-    fused = late_fusion(dets, method, device, names=names, options=opts)
+    fused = late_fusion(dets, method, device, names=names, options=opts, iou_thresh=iou_thresh, stats=stats)
     if fused_out is not None:
         fused_out.extend(fused)
     for i, r in enumerate(fused):

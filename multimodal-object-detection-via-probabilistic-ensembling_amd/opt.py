@@ -12,12 +12,14 @@ def config_parser(cmd=None):
     p.add_argument("--fusion_method", type=str, default="middle_fusion",
                    choices=["rgb_only", "thermal_only", "early_fusion", "middle_fusion"], help="Which fusion method to use?")
     p.add_argument("--model_path", type=str, default=None, help="path to trained model")
-    p.add_argument("--score_fusion", type=str, default="probEn", choices=["avg", "max", "probEn", "probEn-log"],
+    p.add_argument("--score_fusion", type=str, default="probEn", choices=["avg", "max", "probEn", "probEn-log", "wbf"],
                    help="Which fusion method to use?  probEn-log (not in the reference): ProbEn on log_softmax(class_logits / T) with the "
-                        "background column kept - needs prediction files with class_logits")
-    p.add_argument("--box_fusion", type=str, default="v-avg", choices=["avg", "s-avg", "v-avg", "argmax", "c-avg"],
+                        "background column kept - needs prediction files with class_logits.  wbf (not in the reference; with "
+                        "--box_fusion wbf): weighted boxes fusion, Solovyev et al. 2021")
+    p.add_argument("--box_fusion", type=str, default="v-avg", choices=["avg", "s-avg", "v-avg", "argmax", "c-avg", "wbf"],
                    help="Which fusion method to use?  c-avg (not in the reference; --score_fusion probEn-log with --box_correlation or a "
-                        "--calibration file that carries one): the generalised-least-squares mean under correlated box errors")
+                        "--calibration file that carries one): the generalised-least-squares mean under correlated box errors.  wbf "
+                        "(with --score_fusion wbf): weighted boxes fusion - not the reference's weighted_box_fusion, which is s-avg")
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--batch", type=int, default=16)
     p.add_argument("--world-size", type=int, default=1,
@@ -59,13 +61,31 @@ def config_parser(cmd=None):
                         "normalised box errors, 'thermal_only:early_fusion=0.6,thermal_only:thermal_only=0.2' (one entry per detector "
                         "pair, the same name twice = two rows of one detector; pairs not listed get 0), or a bare number for the one "
                         "pair of two detectors; default: the calibration file's box_correlation (fit_temperature --with-box-correlation)")
+    p.add_argument("--wbf_weights", type=str, default=None,
+                   help="demo_probEn --score_fusion wbf --box_fusion wbf (either route): one detector weight per --detectors entry, "
+                        "'a,b[,c]' by position or 'name=a,name=b' by name (a row counts with score * weight); default 1 each")
+    p.add_argument("--wbf_iou", type=float, default=0.55,
+                   help="demo_probEn --score_fusion wbf --box_fusion wbf: the IoU above which a row joins a cluster's fused box "
+                        "(the method's published default)")
+    p.add_argument("--wbf_skip", type=float, default=0.0,
+                   help="demo_probEn --score_fusion wbf --box_fusion wbf: rows with score * weight below this are skipped")
     p.add_argument("--write_fused", type=str, default=None, metavar="FILE",
                    help="demo_probEn --score_fusion probEn-log (either route): write the fused detections as a prediction file (the "
                         "schema of val_<method>_predictions.json: class_logits = the fused log-posterior, vars = the fused box's "
-                        "variance), a detector's file for a later fusion, fit_temperature or calibration_report")
+                        "variance), a detector's file for a later fusion, fit_temperature or calibration_report.  With --score_fusion "
+                        "wbf: boxes, scores and classes with class_logits [], probs [], vars [1.0] - a file for bootstrap_ap")
     args = p.parse_args(cmd) if cmd is not None else p.parse_args()
-    if args.write_fused is not None and args.score_fusion != "probEn-log":
-        p.error(f"--write_fused belongs to --score_fusion probEn-log (got {args.score_fusion}): the other score fusions form no posterior")
+    wbf = args.score_fusion == "wbf"
+    if wbf != (args.box_fusion == "wbf"):
+        p.error(f"--score_fusion wbf and --box_fusion wbf go together (got {args.score_fusion}, {args.box_fusion}): weighted boxes "
+                "fusion is one method")
+    if args.wbf_weights is not None and not wbf:
+        p.error(f"--wbf_weights belongs to --score_fusion wbf --box_fusion wbf (got {args.score_fusion}, {args.box_fusion})")
+    if wbf and args.variance_scales is not None:
+        p.error("--variance_scales belongs to the ProbEn box rules (got wbf): weighted boxes fusion reads no variance")
+    if args.write_fused is not None and args.score_fusion not in ("probEn-log", "wbf"):
+        p.error(f"--write_fused belongs to --score_fusion probEn-log or wbf (got {args.score_fusion}): the other score fusions form no "
+                "posterior")
     if args.box_fusion == "c-avg" and args.score_fusion != "probEn-log":
         p.error(f"--box_fusion c-avg belongs to --score_fusion probEn-log (got {args.score_fusion})")
     if args.box_correlation is not None and args.box_fusion != "c-avg":

@@ -68,6 +68,8 @@ def checked(name, value, num_detectors, who):
         return calibration.check_pool_weights(value, len(value) if D is None else D, who)
     if name == "presence":
         return calibration.check_presence(value, D, None, f"{who}: presence")
+    if name == "wbf_weights":
+        return calibration.check_wbf_weights(value, len(value) if D is None else D, who)
     assert name == "box_correlation", name
     return calibration.check_box_correlation(value, D, f"{who}: box_correlation")
 
@@ -97,6 +99,12 @@ class FusionOptions:
                      with_posterior - of the fused rows whose cluster has two or more rows with the generalised-least-squares mean and
                      the variance it really has.  A row whose source is outside [0, D) makes its cluster's box and variance NaN; a zero
                      matrix is "v-avg".  The result then also holds "cluster".
+    wbf_weights      (score_fusion "wbf" with box_fusion "wbf": weighted boxes fusion, one method, so either half alone is refused) one
+                     detector weight u_d >= 0, not all 0; None = 1.0 per detector.  A row counts with s = score * u_d(row), a row's
+                     detector comes from row_source.  The method reads no variance, probability or logit: class_prior, pool_weights,
+                     presence, with_posterior, box_correlation and variance_scales are refused beside it; temperatures stay legal (they
+                     rebuild the score ahead of any fusion).  The result holds "cluster", "members" and "skipped" and no "keep".
+    wbf_skip         ("wbf" only) the score floor: rows with s < wbf_skip are skipped (s == wbf_skip is kept); None = 0.
 
     pool_weights, presence and box_correlation are also taken as the CUDA tensors on() returns (fusion.pool_weight_tensor,
     calibration.presence_table, calibration.box_correlation_tensor).  num_detectors: D where the caller knows it (every per-detector
@@ -104,10 +112,12 @@ class FusionOptions:
     What needs K + 1 (the prior's length, the table's width) is checked when on() is first given it."""
 
     def __init__(self, score_fusion="probEn", box_fusion="v-avg", temperatures=None, class_prior=None, variance_scales=None,
-                 pool_weights=None, with_posterior=False, presence=None, box_correlation=None, num_detectors=None, who="FusionOptions"):
-        F._check_mode(score_fusion, class_prior, who, pool_weights, with_posterior, presence, box_fusion, box_correlation)
+                 pool_weights=None, with_posterior=False, presence=None, box_correlation=None, num_detectors=None, who="FusionOptions",
+                 wbf_weights=None, wbf_skip=None):
+        F._check_mode(score_fusion, class_prior, who, pool_weights, with_posterior, presence, box_fusion, box_correlation,
+                      variance_scales, wbf_weights, wbf_skip)
         self.score_fusion, self.box_fusion, self.with_posterior, self.who = score_fusion, box_fusion, bool(with_posterior), who
-        self.logp, self.cavg = score_fusion == F.LOGP, box_fusion == F.CAVG
+        self.logp, self.cavg, self.wbf = score_fusion == F.LOGP, box_fusion == F.CAVG, score_fusion == F.WBF
         D = num_detectors
         self.temperatures = checked("temperatures", temperatures, D, who)
         self.box_correlation = checked("box_correlation", box_correlation, D, who)
@@ -117,6 +127,8 @@ class FusionOptions:
         self._prior = class_prior
         self.class_prior = class_prior if class_prior is None or _uploaded(class_prior) else calibration.check_class_prior(class_prior)
         self.variance_scales = checked("variance_scales", variance_scales, D, who)
+        self.wbf_weights = checked("wbf_weights", wbf_weights, D, who)
+        self.wbf_skip = calibration.check_wbf_skip(0.0 if wbf_skip is None else wbf_skip, who) if self.wbf else None
         n_w = None if self.pool_weights is None else len(self.pool_weights)
         n_c = None if self.box_correlation is None else int(self.box_correlation.shape[0])
         n_p = None if self.presence is None else calibration.presence_detectors(self.presence)
@@ -126,10 +138,13 @@ class FusionOptions:
             raise ValueError(f"{who}: {n_w} pool weights beside a presence table over {n_p} detectors")
         if None not in (n_c, n_p) and n_c != n_p:
             raise ValueError(f"{who}: a box correlation over {n_c} detectors beside a presence table over {n_p}")
-        self.num_detectors = next((n for n in (D, n_w, n_c, n_p) if n is not None), None)
+        n_u = None if self.wbf_weights is None else len(self.wbf_weights)
+        self.num_detectors = next((n for n in (D, n_w, n_c, n_p, n_u) if n is not None), None)
+        if self.wbf and self.wbf_weights is None and self.num_detectors is not None:
+            self.wbf_weights = checked("wbf_weights", [1.0] * self.num_detectors, self.num_detectors, who)
         if self.logp and self.temperatures is None and self.num_detectors is not None:
             self.temperatures = [1.0] * self.num_detectors
-        self.needs_row_source = self.pool_weights is not None or self.presence is not None or self.cavg
+        self.needs_row_source = self.pool_weights is not None or self.presence is not None or self.cavg or self.wbf
         self.needs_cluster = self.needs_row_source
         self.fitted = set()         # from_args: the image ids the calibration file's temperatures were fitted on
         self._on = {}
@@ -152,7 +167,8 @@ class FusionOptions:
         """A new object with some of the constructor's arguments changed; everything is validated again."""
         now = dict(score_fusion=self.score_fusion, box_fusion=self.box_fusion, temperatures=self.temperatures, class_prior=self._prior,
                    variance_scales=self.variance_scales, pool_weights=self.pool_weights, with_posterior=self.with_posterior,
-                   presence=self.presence, box_correlation=self.box_correlation, num_detectors=self.num_detectors, who=self.who)
+                   presence=self.presence, box_correlation=self.box_correlation, num_detectors=self.num_detectors, who=self.who,
+                   wbf_weights=self.wbf_weights, wbf_skip=self.wbf_skip)
         now.update(changes)
         return FusionOptions(**now)
 
@@ -170,6 +186,13 @@ class FusionOptions:
                 calibration.box_correlation_tensor(self.box_correlation, D, device))
         return self._on[key]
 
+    def wbf_on(self, device):
+        """The detector weights of "wbf" on the device, f64 [D]; uploaded at the first call for a device and kept."""
+        key = (torch.device(device), "wbf")
+        if key not in self._on:
+            self._on[key] = torch.tensor(self.wbf_weights, dtype=torch.float64).to(device)
+        return self._on[key]
+
     def named(self, names):
         """The result keys that name the calibration a run was made with; a run without any carries none of them."""
         res = {}
@@ -185,6 +208,9 @@ class FusionOptions:
             res["presence"] = {"detectors": list(names), "table": self.presence.tolist()}
         if self.box_correlation is not None:
             res["box_correlation"] = {"detectors": list(names), "matrix": self.box_correlation.tolist()}
+        if self.wbf:
+            res["wbf_weights"] = dict(zip(names, self.wbf_weights))
+            res["wbf_skip"] = self.wbf_skip
         return res
 
     @classmethod
@@ -192,10 +218,10 @@ class FusionOptions:
         """The options of a command line (opt.config_parser) for the detectors `names`: each from its flag, else from the --calibration
         file's entry, else none.  The file is loaded once.  Options that do not belong to the chosen fusion (class prior, pool weights and
         presence without "probEn-log"; box correlation without "c-avg") are not read at all, so a file that carries them serves every
-        fusion.  What the file supplies beyond temperatures and prior is said through `say` (None: silent)."""
+        fusion ("wbf" reads the file's temperatures and nothing else).  What the file supplies beyond temperatures and prior is said through `say` (None: silent)."""
         path = getattr(args, "calibration", None)
         rec = calibration.load(path) if path is not None else {}
-        logp, cavg = args.score_fusion == F.LOGP, args.box_fusion == F.CAVG
+        logp, cavg, wbf = args.score_fusion == F.LOGP, args.box_fusion == F.CAVG, F.WBF in (args.score_fusion, args.box_fusion)
 
         def pick(key, parse, table, resolve, show):
             text = getattr(args, key, None)
@@ -216,7 +242,8 @@ class FusionOptions:
         if logp:
             prior = calibration.parse_class_prior(args.class_prior).tolist() if getattr(args, "class_prior", None) is not None \
                 else rec.get("class_prior")
-        scales = pick("variance_scales", calibration.parse_variance_scales, calibration.load_variance(path) if path is not None else None,
+        scales = pick("variance_scales", calibration.parse_variance_scales,
+                      calibration.load_variance(path) if path is not None and not wbf else None,
                       calibration.resolve_variance_scales, lambda v: f"variance scales of {path}: {per_name(v)}")
         pool = pick("pool_weights", calibration.parse_pool_weights, rec.get("pool_weights"), calibration.resolve_pool_weights,
                     lambda v: f"pool weights of {path}: {per_name(v)}") if logp else None
@@ -230,7 +257,9 @@ class FusionOptions:
             if corr is None:
                 raise ValueError("--box_fusion c-avg needs --box_correlation or a --calibration file that carries \"box_correlation\" "
                                  "(fit_temperature --with-box-correlation)")
-        opts = cls(args.score_fusion, args.box_fusion, temps, prior, scales, pool, bool(getattr(args, "write_fused", None)), presence, corr,
-                   num_detectors=len(names), who=who)
+        weights = calibration.parse_wbf_weights(args.wbf_weights, names) if getattr(args, "wbf_weights", None) is not None else None
+        opts = cls(args.score_fusion, args.box_fusion, temps, prior, scales, pool, bool(getattr(args, "write_fused", None)) and not wbf,
+                   presence, corr, num_detectors=len(names), who=who, wbf_weights=weights,
+                   wbf_skip=getattr(args, "wbf_skip", None) if wbf else None)
         opts.fitted = set(rec.get("fitted_image_ids", []))
         return opts

@@ -24,8 +24,9 @@ class FramePairPipeline:
 
     def __init__(self, models, score_fusion="probEn", box_fusion="v-avg", max_class=2, concurrent=True,
                  staggered=False, stagger_stage=4, fuse=True, temperatures=None, class_prior=None, variance_scales=None,
-                 pool_weights=None, with_posterior=False, presence=None, box_correlation=None, options=None):
+                 pool_weights=None, with_posterior=False, presence=None, box_correlation=None, options=None, iou_thresh=None):
         self.models = list(models)
+        self.iou_thresh = iou_thresh        # None: fuse_detections' default (0.5; 0.55 for "wbf")
         self.fuse = fuse and len(self.models) > 1   # a single detector has nothing to fuse (configs[1])
         self.max_class = max_class
         # the fusion and its calibration (the keywords, or an options.FusionOptions, which documents them): validated here, uploaded at
@@ -121,7 +122,7 @@ class FramePairPipeline:
         return dets, fused
 
     def _fuse(self, dets):
-        return F.fuse_detections(dets, max_class=self.max_class, options=self.options)
+        return F.fuse_detections(dets, max_class=self.max_class, iou_thresh=self.iou_thresh, options=self.options)
 
     temperatures = property(lambda self: self.options.temperatures)
     class_prior = property(lambda self: self.options.class_prior)
