@@ -888,6 +888,52 @@ int pe_wbf_fuse_batch(const double* boxes,        /* [Ntot,4] xyxy */
                       int32_t* out_skipped,       /* [B] */
                       void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Probability-based Detection Quality: D. Hall et al., "Probabilistic object detection: definition and evaluation",
+ * WACV 2020, for box ground truth and one scalar box variance per detection.  Not in the reference, and restated from the paper: the
+ * rule below is the specification, tests/pdq_ref.py restates it in NumPy.
+ *
+ * pe_pdq_pair_quality: detections of image b are rows [det_offsets[b], det_offsets[b+1]) of det_boxes f64 [M,4] XYXY, det_vars f64 [M]
+ *   (box-delta units, already scaled) and det_log_probs f64 [M, K+1]; its ground truths are [gt_offsets[b], gt_offsets[b+1]) of gt_boxes
+ *   f64 [G,4], gt_classes i32 [G], gt_crowd i32 [G]; image_hw i32 [B,2] = (H, W); pair_offsets i64 [B+1], pair_offsets[b+1] -
+ *   pair_offsets[b] = G_b * M_b; pair (g, d) of image b is at pair_offsets[b] + g_local * M_b + d_local.  float64, built without fused
+ *   multiply-adds.  With (wx, wy, ww, wh) = bbox_reg_weights_host (null: 10, 10, 5, 5, as pe_variance_stats), eps = 1e-14,
+ *   Phi(z) = 0.5 erfc(-z / sqrt 2), Phic(z) = 0.5 erfc(z / sqrt 2):
+ *     sx = sqrt(var) * (x2 - x1) * sqrt(1 / wx^2 + 1 / (4 ww^2)), sy likewise with y, wy, wh
+ *     column u: a = (u + 0.5 - x1) / sx, b = (x2 - u - 0.5) / sx, px[u] = Phi(a) Phi(b), qx[u] = Phic(a) + Phi(a) Phic(b);
+ *       sx == 0: px[u] = 1 where x1 <= u + 0.5 <= x2 else 0, qx = 1 - px; rows v the same: py, qy
+ *     P(v, u) = px[u] py[v], Q(v, u) = qx[u] + px[u] qy[v]
+ *     a ground truth's pixels S_g: x1g <= u + 0.5 < x2g, y1g <= v + 0.5 < y2g inside the image, n_g of them
+ *     FG = (1 / n_g) sum over S_g of log max(P, eps);  BG = (1 / n_g) sum over {P > tau} \ S_g (inside the image) of log max(Q, eps)
+ *     (log max(P, eps) is evaluated as log1p(-Q) where P > 0.5 and log max(Q, eps) as log1p(-P) where Q > 0.5)
+ *     Q_S = exp(FG + BG), Q_L = exp(det_log_probs[d][class_g]), q = sqrt(Q_S * Q_L)
+ *   out_q, out_fg = exp(FG), out_bg = exp(BG), out_label = Q_L: f64 [num_pairs].
+ *   A ground truth is ignored - out_gt_live i32 [G] = 0, counted in out_flags[2], out_flags[3] = 1 + the index of one of them - when
+ *   gt_crowd is set, n_g == 0, a coordinate is not finite or its class is outside [0, K); a detection is excluded - counted in
+ *   out_flags[0], out_flags[1] = 1 + the index of one - when a coordinate is not finite, its width or height is not > 0, or its variance is
+ *   negative or not finite.  The four outputs are 0 for every pair of an ignored ground truth or an excluded detection.
+ *   max_width_plus_height sizes the tables in LDS (16 bytes per column and per row): above PE_PDQ_MAX_TABLE it is refused; an image with
+ *   H < 1, W < 1 or W + H above it has its detections excluded and its ground truths ignored.  Offsets are device memory: an image whose
+ *   offsets would leave the arrays is left unwritten.  One 256-thread workgroup per detection (the four tables once, then the sum over
+ *   {P > tau}, then per ground truth the sums over its own rectangle) and ceil(G / 256) more for out_gt_live.  No floating-point
+ *   atomics: the same input gives the same bits.  Arguments are checked before any device work.
+ *
+ * pe_pdq_assign (HOST pointers, no device work): per image the one-to-one assignment of the ground truths with gt_live != 0 to the
+ *   detections with det_take != 0 (null: all) that maximises the sum of q, by the O(n^3) Hungarian algorithm on the block in either
+ *   orientation; a q that is not > 0 counts as 0.  out_match i32 [G] = the detection's row index, or -1 (not live, unassigned, or
+ *   assigned at q = 0).  The offsets must start at 0, rise, and end at the counts; pair_offsets must span G_b * M_b per image.
+ * ------------------------------------------------------------------------------------------- */
+#define PE_PDQ_MAX_TABLE 4096
+int pe_pdq_pair_quality(const double* det_boxes, const double* det_vars, const double* det_log_probs, const int32_t* det_offsets,
+                        const double* gt_boxes, const int32_t* gt_classes, const int32_t* gt_crowd, const int32_t* gt_offsets,
+                        const int32_t* image_hw, const int64_t* pair_offsets, int32_t num_images, int32_t num_classes, int32_t num_dets,
+                        int32_t num_gt, int64_t num_pairs, int32_t max_width_plus_height, const float* bbox_reg_weights_host, double tau,
+                        double* out_q, double* out_fg, double* out_bg, double* out_label, int32_t* out_gt_live, int32_t* out_flags,
+                        void* stream);
+int pe_pdq_assign(const double* q_host, const int32_t* gt_live_host, const int32_t* det_take_host, const int32_t* det_offsets_host,
+                  const int32_t* gt_offsets_host, const int64_t* pair_offsets_host, int32_t num_images, int32_t num_dets, int32_t num_gt,
+                  int64_t num_pairs, int32_t* out_match_host);
+
 #ifdef __cplusplus
 }
 #endif

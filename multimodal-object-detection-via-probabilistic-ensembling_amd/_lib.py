@@ -74,6 +74,8 @@ SIGNATURES = {
     "pe_ap_bootstrap": [c_void_p] * 4 + [ctypes.c_int64] + [c_void_p] * 2 + [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5,
     "pe_wbf_fuse_batch": [c_void_p] * 6 + [c_int] * 3 + [c_void_p, c_int, c_double, c_double] + [c_void_p] * 8,
     "pe_lamr_bootstrap": [c_void_p] * 2 + [ctypes.c_int64] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 4,
+    "pe_pdq_pair_quality": [c_void_p] * 10 + [c_int] * 4 + [ctypes.c_int64, c_int, c_void_p, c_double] + [c_void_p] * 7,
+    "pe_pdq_assign": [c_void_p] * 6 + [c_int] * 3 + [ctypes.c_int64, c_void_p],
 }
 
 # The fusion's five entry points share one parameter order; each leaves out the fields it does not have.  (field, ctype, the entry
@@ -95,7 +97,8 @@ _RESTYPE = {"pe_last_error": ctypes.c_char_p, "pe_nms_scratch_bytes": ctypes.c_s
 
 
 # exported for tests/ and scripts/ only (csrc/test_hooks.h) - not in include/proben_hip.h
-TEST_HOOKS = {"pe_test_set_conv_policy": [c_int, c_int], "pe_test_get_conv_policy": [], "pe_test_conv_variant": [c_int] * 10 + [ctypes.c_int64], "pe_test_set_wd9_mode": [c_int], "pe_test_wd9_takes": [c_int] * 5, "pe_test_wd9_head_takes": [c_int] * 3, "pe_test_set_wd9_wgs": [c_int, c_int], "pe_test_set_ring_wgs": [c_int], "pe_test_set_roi_fast": [c_int], "pe_test_set_nms_presorted": [c_int]}
+TEST_HOOKS = {"pe_test_set_conv_policy": [c_int, c_int], "pe_test_get_conv_policy": [], "pe_test_conv_variant": [c_int] * 10 + [ctypes.c_int64], "pe_test_set_wd9_mode": [c_int], "pe_test_wd9_takes": [c_int] * 5, "pe_test_wd9_head_takes": [c_int] * 3, "pe_test_set_wd9_wgs": [c_int, c_int], "pe_test_set_ring_wgs": [c_int], "pe_test_set_roi_fast": [c_int], "pe_test_set_nms_presorted": [c_int],
+              "pe_test_pdq_terms": [c_void_p] * 4 + [ctypes.c_int64] + [c_void_p] * 3}
 
 
 class HipLibraryError(RuntimeError):

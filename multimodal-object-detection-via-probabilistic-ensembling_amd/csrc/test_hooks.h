@@ -44,6 +44,11 @@ int pe_test_set_ring_ablation(int bits);
 int pe_test_set_nms_presorted(int on);
 /* ROIAlign (fp16, C == 256): 1 (default) = the wave-uniform form, 0 = the per-lane form for every launch (same bits; A/B and the identity test) */
 int pe_test_set_roi_fast(int on);
+/* PDQ (csrc/pdq.hip): the foreground and background terms log max(P, eps), log max(Q, eps) of n pixels from their four arguments - column
+ * (ax, bx) and row (ay, by), the a and b of the rule - through the device functions the pair-quality kernel calls.  Device pointers, f64 [n].
+ * tests/test_pdq_gpu.py measures the per-term error against 50-digit arithmetic with it. */
+int pe_test_pdq_terms(const double* ax, const double* bx, const double* ay, const double* by, long long n, double* out_fg, double* out_bg,
+                      void* stream);
 #ifdef __cplusplus
 }
 #endif
