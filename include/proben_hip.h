@@ -747,6 +747,29 @@ int pe_boxhead_finalize(const float* head, int32_t head_stride, int32_t N, int32
                         float* det_probs, float* det_vars, int32_t* det_rows, int32_t* det_counts,
                         void* stream);
 
+/* Variance voting (He, Zhu, Wang, Savvides, Zhang: "Bounding Box Regression with Uncertainty for Accurate Object Detection",
+ * CVPR 2019, section 3.3), opt-in, one launch between pe_nms_batched and pe_boxhead_finalize.  In the reference's flow this is the
+ * point of fast_rcnn_inference_single_image (modeling/roi_heads/fast_rcnn.py:43-147) right after batched_nms, where boxes[keep] is
+ * gathered; the reference itself does not vote.  DESIGN.md section 31 states the rule:
+ *   var_i = exp(head[n*per_image + orow_i, 5K+1]) (float32 as pe_boxhead_finalize computes it, then float64; always the candidate's
+ *   OWN proposal row - quirk Q3 / fix_vars only choose the variance finalize REPORTS).  For a kept candidate b the voters are the
+ *   candidates i of the image with class_i == class_b, IoU(b, i) > 0 (finetune.pairwise_iou's float64 expression) and var_i finite
+ *   and > 0;  p_i = exp(-(1 - IoU(b, i))^2 / sigma_t),  w_i = p_i / var_i,  b'[c] = sum_i w_i box_i[c] / sum_i w_i, rounded once
+ *   to float32.  A kept box that is no voter of itself (variance NaN, 0 or inf, or a box without area) keeps its bits.
+ * out_boxes [N, cand_max, 4] (must not alias cand_boxes): rows [0, cand_counts[n]) of every image are written completely - a
+ * candidate that is not kept gets its input row, a kept one its voted box - and nothing else is touched; pe_boxhead_finalize then
+ * takes out_boxes in place of cand_boxes.  keep [N, max_det] / keep_counts [N] as pe_nms_batched leaves them; a keep id outside
+ * [0, cand_counts[n]) is skipped.  Scores, classes, row ids, counts and the variances finalize reports are not changed by voting.
+ * One workgroup per image, candidates staged in LDS in tiles of PE_VAR_VOTE_TILE, a wavefront per kept box, float64 sums in a
+ * fixed order without atomics: image n's rows do not depend on N, on the other images or on the run.
+ * Checked before any device work: null pointers, num_classes in [1, 80], head_stride >= 5K + 2, cand_max in [1, 16384],
+ * max_det >= 1, sigma_t finite and > 0, out_boxes != cand_boxes; N == 0 returns PE_OK. */
+#define PE_VAR_VOTE_TILE 4096
+int pe_boxhead_var_vote(const float* head, int32_t head_stride, int32_t N, int32_t per_image, int32_t num_classes,
+                        int32_t cand_max, int32_t max_det, const float* cand_boxes, const int32_t* cand_class,
+                        const int32_t* cand_rows, const int32_t* cand_counts, const int32_t* keep,
+                        const int32_t* keep_counts, float sigma_t, float* out_boxes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Native COCO bbox evaluator (HOST code, multithreaded; no GPU involved).  Replaces COCOeval.evaluate /
  * computeIoU / evaluateImg / accumulate of the reference's vendored pycocotools

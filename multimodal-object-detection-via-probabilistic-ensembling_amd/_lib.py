@@ -69,6 +69,7 @@ SIGNATURES = {
     "pe_cocoeval_bbox": [c_void_p] * 6 + [ctypes.c_int64] + [c_void_p] * 4 + [ctypes.c_int64, c_int, c_int, c_void_p, c_int,
                          c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "pe_boxhead_finalize": [c_void_p] + [c_int] * 7 + [c_void_p] * 18,
+    "pe_boxhead_var_vote": [c_void_p] + [c_int] * 6 + [c_void_p] * 6 + [c_float] + [c_void_p] * 2,
     "pe_cocoeval_bbox_matches": [c_void_p] * 6 + [ctypes.c_int64] + [c_void_p] * 4 + [ctypes.c_int64, c_int, c_int, c_void_p, c_int,
                                  c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int] + [c_void_p] * 5,
     "pe_ap_bootstrap": [c_void_p] * 4 + [ctypes.c_int64] + [c_void_p] * 2 + [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5,

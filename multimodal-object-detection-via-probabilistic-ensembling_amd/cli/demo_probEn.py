@@ -55,6 +55,10 @@ name), --wbf_iou (default 0.55), --wbf_skip (default 0).  There is no case split
 --temperatures / --calibration still rebuild the scores; every other calibration option is refused.  --write_fused FILE writes the
 fused rows with class_logits [], probs [], vars [1.0] (late_fusion.wbf_to_j1) and prints how many rows were skipped:
 `bootstrap_ap val_thermal_only_predictions.json FILE` then compares the two.
+
+--var_voting [SIGMA_T], with --one-pass (the route that runs detectors; it changes nothing without it): every detector votes its kept
+boxes after its box-head NMS (PROBEN.VAR_VOTING / VAR_VOTING_SIGMA_T; SIGMA_T defaults to 0.025).  ProbEn then
+fuses ordinary detections.  On the two-stage route give the flag to save_predictions.
 """
 import json
 import os
@@ -158,10 +162,22 @@ def _register(args):
     return cfg
 
 
+def detector_cfgs(args, names, paths, device_type="cuda"):
+    """--one-pass: one cfg per --detectors entry, as save_predictions.build_cfg builds it for that fusion method and weights file; the
+    run's --var_voting [SIGMA_T] goes to every detector."""
+    import argparse
+    from .save_predictions import build_cfg
+    cfgs = []
+    for m, p in zip(names, paths):
+        c = build_cfg(argparse.Namespace(fusion_method=m, model_path=p, var_voting=getattr(args, "var_voting", None)))
+        c.MODEL.DEVICE = device_type
+        cfgs.append(c)
+    return cfgs
+
+
 def one_pass(args, names, world, dev, opts):
     """`opts`: the run's FusionOptions (FusionOptions.from_args).  loader -> FramePairPipeline (one DefaultPredictor model per --detectors entry, cfg as save_predictions.build_cfg) ->
     ProbEn -> evaluation rows on the device (late_fusion.fused_rows_device) -> one all-gather -> FLIREvaluator on rank 0."""
-    import argparse
     import time
     import torch
     from ..data import PairFrames, resize_shortest_edge_shape
@@ -169,7 +185,6 @@ def one_pass(args, names, world, dev, opts):
     from ..pipeline import FramePairPipeline, HostFeeder
     from ..predictor import DefaultPredictor
     from ..stream import FlirPairLoader, check_workers
-    from .save_predictions import build_cfg
     if "rgb_only" in names:
         raise ValueError("--one-pass does not run rgb_only: that detector sees the RGB frame at its own size while the frame-pair "
                          "pipeline shares one output size over its detectors.  Use the two-stage route: save_predictions per "
@@ -182,11 +197,7 @@ def one_pass(args, names, world, dev, opts):
     if main_rank:
         os.makedirs(args.outfolder, exist_ok=True)
     cfg = _register(args)
-    preds = []
-    for m, p in zip(names, paths):
-        c = build_cfg(argparse.Namespace(fusion_method=m, model_path=p))
-        c.MODEL.DEVICE = dev.type
-        preds.append(DefaultPredictor(c))
+    preds = [DefaultPredictor(c) for c in detector_cfgs(args, names, paths, dev.type)]
     need_rgb = any(p.input_format in ("BGRT", "BGRTTT") for p in preds)
     loader = FlirPairLoader(args.dataset_path, args.batch, need_rgb=need_rgb, workers=workers)
     _warn_fitted(opts, [loader.items[i]["id"] for i in loader.mine])

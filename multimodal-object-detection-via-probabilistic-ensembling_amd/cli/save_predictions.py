@@ -2,9 +2,10 @@
 on the GPU, images sharded over ranks) and write val_<method>_predictions.json in the reference's schema.
 
     python -m proben_amd.cli.save_predictions --dataset_path DATA/FLIR/val --fusion_method thermal_only \
-        --model_path model.pth --prediction_path out/ [--batch 16]
+        --model_path model.pth --prediction_path out/ [--batch 16] [--var_voting [SIGMA_T]]
 Input building per method follows :98-121 (early: B,G,R,T(ch 0); middle: B,G,R,T,T,T; RGB resized to the
-thermal size with OpenCV's 2x2-tap bilinear rule, data.cv2_linear_resize_u8)."""
+thermal size with OpenCV's 2x2-tap bilinear rule, data.cv2_linear_resize_u8).  --var_voting [SIGMA_T] (default 0.025) turns on variance
+voting after the box-head NMS (PROBEN.VAR_VOTING); the file has the same schema, its boxes are the voted ones."""
 import json
 import os
 
@@ -45,6 +46,9 @@ def build_cfg(args, config_dir=None):
         cfg.INPUT.FORMAT, cfg.INPUT.NUM_IN_CHANNELS = "BGRTTT", 6
         cfg.MODEL.PIXEL_MEAN = [103.53, 116.28, 123.675, THERMAL_MEAN, THERMAL_MEAN, THERMAL_MEAN]
         cfg.MODEL.PIXEL_STD = [1.0] * 6
+    if getattr(args, "var_voting", None) is not None:      # --var_voting [SIGMA_T]
+        cfg.PROBEN.VAR_VOTING = True
+        cfg.PROBEN.VAR_VOTING_SIGMA_T = float(args.var_voting)
     return cfg
 
 

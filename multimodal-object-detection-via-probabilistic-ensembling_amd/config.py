@@ -108,7 +108,7 @@ _DEFAULTS = {
     "INPUT": {"MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "FORMAT": "BGR", "NUM_IN_CHANNELS": 3},
     "DATASETS": {"TRAIN": (), "TEST": ()},
     "TEST": {"DETECTIONS_PER_IMAGE": 100, "KEYPOINT_OKS_SIGMAS": []},
-    "PROBEN": {"FIX_VARS": False},
+    "PROBEN": {"FIX_VARS": False, "VAR_VOTING": False, "VAR_VOTING_SIGMA_T": 0.025},
 }
 
 

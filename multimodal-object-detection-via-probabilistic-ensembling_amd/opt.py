@@ -74,7 +74,13 @@ def config_parser(cmd=None):
                         "schema of val_<method>_predictions.json: class_logits = the fused log-posterior, vars = the fused box's "
                         "variance), a detector's file for a later fusion, fit_temperature or calibration_report.  With --score_fusion "
                         "wbf: boxes, scores and classes with class_logits [], probs [], vars [1.0] - a file for bootstrap_ap")
+    p.add_argument("--var_voting", type=float, nargs="?", const=0.025, default=None, metavar="SIGMA_T",
+                   help="save_predictions, demo_probEn --one-pass: variance voting inside every detector after its box-head NMS "
+                        "(PROBEN.VAR_VOTING, DESIGN.md section 31): a kept box becomes the mean of its overlapping same-class candidates, "
+                        "weighted by exp(-(1 - IoU)^2 / SIGMA_T) / variance; SIGMA_T defaults to 0.025")
     args = p.parse_args(cmd) if cmd is not None else p.parse_args()
+    if args.var_voting is not None and not (0.0 < args.var_voting < float("inf")):
+        p.error(f"--var_voting takes a finite SIGMA_T > 0 (got {args.var_voting})")
     wbf = args.score_fusion == "wbf"
     if wbf != (args.box_fusion == "wbf"):
         p.error(f"--score_fusion wbf and --box_fusion wbf go together (got {args.score_fusion}, {args.box_fusion}): weighted boxes "

@@ -25,7 +25,8 @@ def detector_config_from_cfg(cfg):
         nms_thresh=cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST, detections_per_image=cfg.TEST.DETECTIONS_PER_IMAGE,
         min_size_test=mn[0] if isinstance(mn, (list, tuple)) else mn, max_size_test=cfg.INPUT.MAX_SIZE_TEST,
         output_logits=bool(cfg.MODEL.ROI_BOX_HEAD.OUTPUT_LOGITS), enable_gaussian_nll=bool(cfg.MODEL.ROI_HEADS.ENABLE_GAUSSIANNLLOSS),
-        fix_vars=bool(cfg.get("PROBEN", {}).get("FIX_VARS", False)))
+        fix_vars=bool(cfg.get("PROBEN", {}).get("FIX_VARS", False)), var_voting=bool(cfg.get("PROBEN", {}).get("VAR_VOTING", False)),
+        var_voting_sigma_t=float(cfg.get("PROBEN", {}).get("VAR_VOTING_SIGMA_T", 0.025)))
 
 
 def load_weights(cfg):

@@ -46,6 +46,8 @@ class DetectorConfig:
     output_logits: bool = True
     enable_gaussian_nll: bool = True
     fix_vars: bool = False
+    var_voting: bool = False            # variance voting after the box-head NMS; needs the variance head
+    var_voting_sigma_t: float = 0.025   # a starting value in the range He et al. sweep - a setting, not a parity claim
     size_divisibility: int = 32
 
     @property
@@ -67,6 +69,11 @@ def cell_anchor_table(sizes, ratios):
 
 class GeneralizedRCNN:
     def __init__(self, cfg: DetectorConfig, state_dict, device="cuda"):
+        if cfg.var_voting and not cfg.enable_gaussian_nll:
+            raise ValueError("var_voting (PROBEN.VAR_VOTING) weights every candidate box by the variance its own proposal row predicts: "
+                             "it needs the variance head (MODEL.ROI_HEADS.ENABLE_GAUSSIANNLLOSS)")
+        if cfg.var_voting and not (math.isfinite(cfg.var_voting_sigma_t) and cfg.var_voting_sigma_t > 0):
+            raise ValueError(f"var_voting_sigma_t (PROBEN.VAR_VOTING_SIGMA_T) must be finite and > 0, got {cfg.var_voting_sigma_t}")
         if not torch.cuda.is_available():
             raise _lib.HipLibraryError("GeneralizedRCNN (MODEL.DEVICE=cuda) needs an MI355X; there is no CPU fallback "
                                        "in proben_amd (the CPU restatement lives in oracle/ for testing only).")
@@ -339,6 +346,13 @@ class GeneralizedRCNN:
         D = cfg.detections_per_image
         mode = 1 if cmax * 4 > 20000 else 0
         keep, kcnt = L.nms_batched_raw(cb, cs, cc, ccnt, None, cfg.nms_thresh, mode, D)
+        fb = cb                      # the boxes finalize gathers: the candidates', or their variance-voted copy
+        if cfg.var_voting:
+            fb = torch.empty_like(cb)
+            st = lib.pe_boxhead_var_vote(_lib.ptr(head), w.head_stride, N, P, K, cmax, D, _lib.ptr(cb), _lib.ptr(cc), _lib.ptr(cr),
+                                         _lib.ptr(ccnt), _lib.ptr(keep), _lib.ptr(kcnt), cfg.var_voting_sigma_t, _lib.ptr(fb),
+                                         _lib.stream())
+            _lib.check(st, "pe_boxhead_var_vote")
         det = {
             "boxes": torch.empty((N, D, 4), dtype=torch.float32, device=dev),
             "scores": torch.empty((N, D), dtype=torch.float32, device=dev),
@@ -350,7 +364,7 @@ class GeneralizedRCNN:
             "counts": torch.empty((N,), dtype=torch.int32, device=dev),
         }
         st = lib.pe_boxhead_finalize(_lib.ptr(head), w.head_stride, N, P, K, cmax, D, int(cfg.fix_vars), _lib.ptr(probs),
-                                     _lib.ptr(cb), _lib.ptr(cs), _lib.ptr(cc), _lib.ptr(cr), _lib.ptr(keep), _lib.ptr(kcnt),
+                                     _lib.ptr(fb), _lib.ptr(cs), _lib.ptr(cc), _lib.ptr(cr), _lib.ptr(keep), _lib.ptr(kcnt),
                                      _lib.ptr(sizes_dev), _lib.ptr(out_dev), _lib.ptr(det["boxes"]), _lib.ptr(det["scores"]),
                                      _lib.ptr(det["classes"]), _lib.ptr(det["class_logits"]), _lib.ptr(det["prob_score"]),
                                      _lib.ptr(det["vars"]), _lib.ptr(det["rows"]), _lib.ptr(det["counts"]), _lib.stream())
