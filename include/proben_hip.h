@@ -957,6 +957,53 @@ int pe_pdq_assign(const double* q_host, const int32_t* gt_live_host, const int32
                   const int32_t* gt_offsets_host, const int64_t* pair_offsets_host, int32_t num_images, int32_t num_dets, int32_t num_gt,
                   int64_t num_pairs, int32_t* out_match_host);
 
+/* ---------------------------------------------------------------------------------------------
+ * TIDE error typing: D. Bolya, S. Foley, J. Hays, J. Hoffman, "TIDE: A General Toolbox for Identifying Object Detection
+ * Errors", ECCV 2020, for this project's evaluator.  Not in the reference, and restated from the paper: the rule below is the
+ * specification, tests/tide_ref.py restates it in NumPy.
+ *
+ * pe_tide_classify: the detections of image b are rows [det_offsets[b], det_offsets[b+1]) of det_boxes f64 [M,4] XYWH and det_cats
+ *   i32 [M] (device), in the caller's total order (descending score, NaN last, ties by category, then by the evaluator's rank); its
+ *   ground truths are rows [gt_offsets[b], gt_offsets[b+1]) of gt_boxes f64 [G,4] XYWH, gt_cats i32 [G], gt_crowd u8 [G] (device), in
+ *   annotation order.  det_offsets_host / gt_offsets_host i32 [num_images + 1] are HOST arrays: they are checked (start at 0, rise,
+ *   end at num_dets / num_gt, the limits below) before any device work, then copied into offsets_ws, DEVICE i32 [2 (num_images + 1)],
+ *   on the stream.  0 <= t_b < t_f <= 1.  float64, every operation rounded on its own.
+ *   A. base matching = cocoeval.py:236-313 at one threshold with every non-crowd ground truth counted (area range "all"), category
+ *      by category, detections in order: among the unmatched non-crowd ground truths of the detection's category with
+ *      inter / (a_d + a_g - inter) >= min(t_f, 1 - 1e-10) the largest, the LATER one on a tie; if there is none, the same among its
+ *      crowd ground truths with inter / a_d (a crowd box may be matched repeatedly).  The quotient is used unguarded; the evaluator's
+ *      comparison lets a NaN through and then every later candidate, which is kept: with a NaN among a group's candidates the group's
+ *      last candidate is taken.
+ *   B. every unmatched detection is typed on iou = inter > 0 ? inter / (a_d + a_g - inter) : 0 against the image's non-crowd ground
+ *      truths: own / other = the largest iou (>= 0) over those of its category / of the other categories, the LOWEST index on a tie,
+ *      0 with partner -1 if there is none.  First hit: Loc t_b <= own < t_f (partner own's); Cls other >= t_f (other's); Dupe
+ *      own >= t_f (own's); Bkg other < t_b; Both otherwise.
+ *   C. a non-crowd ground truth is missed when A left it unmatched and it is the partner of no Loc and of no Cls error.
+ *   D. two independent walks in the total order, over the Loc errors and over the Cls errors: an error claims its partner if A left
+ *      the partner unmatched and no earlier error of the same walk claimed it.
+ *   Out, i32: out_match [M] the image-local ground-truth index of A or -1; out_type [M] PE_TIDE_TP (matched), PE_TIDE_IGNORED (matched
+ *   to a crowd box) or the error type; out_partner [M] image-local, -1 for matched, Bkg and Both; out_claim [M] 0 / 1;
+ *   out_gt [G] bits: 1 matched in A, 2 partner of a Loc error, 4 partner of a Cls error, 8 missed.
+ *   One 256-thread workgroup per image, ground truths in LDS (47 KiB): an image with more than PE_TIDE_MAX_GT ground truths or
+ *   PE_TIDE_MAX_DETS detections (100 per category at PE_TIDE_MAX_CLASSES categories), or num_classes above PE_TIDE_MAX_CLASSES,
+ *   returns PE_ERR_UNSUPPORTED before anything is launched; num_images = 0 returns PE_OK.  Nothing is shared between workgroups and
+ *   there are no floating-point atomics: an image's output does not depend on the rest of the launch.
+ * ------------------------------------------------------------------------------------------- */
+#define PE_TIDE_MAX_DETS 8000
+#define PE_TIDE_MAX_GT 1024
+#define PE_TIDE_MAX_CLASSES 80
+#define PE_TIDE_TP 0
+#define PE_TIDE_CLS 1
+#define PE_TIDE_LOC 2
+#define PE_TIDE_BOTH 3
+#define PE_TIDE_DUPE 4
+#define PE_TIDE_BKG 5
+#define PE_TIDE_IGNORED 6
+int pe_tide_classify(const double* det_boxes, const int32_t* det_cats, const int32_t* det_offsets_host, const double* gt_boxes,
+                     const int32_t* gt_cats, const uint8_t* gt_crowd, const int32_t* gt_offsets_host, int32_t num_images,
+                     int32_t num_classes, int32_t num_dets, int32_t num_gt, double t_f, double t_b, int32_t* offsets_ws,
+                     int32_t* out_match, int32_t* out_type, int32_t* out_partner, int32_t* out_claim, int32_t* out_gt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,7 @@ SIGNATURES = {
     "pe_lamr_bootstrap": [c_void_p] * 2 + [ctypes.c_int64] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 4,
     "pe_pdq_pair_quality": [c_void_p] * 10 + [c_int] * 4 + [ctypes.c_int64, c_int, c_void_p, c_double] + [c_void_p] * 7,
     "pe_pdq_assign": [c_void_p] * 6 + [c_int] * 3 + [ctypes.c_int64, c_void_p],
+    "pe_tide_classify": [c_void_p] * 7 + [c_int] * 4 + [c_double] * 2 + [c_void_p] * 7,
 }
 
 # The fusion's five entry points share one parameter order; each leaves out the fields it does not have.  (field, ctype, the entry

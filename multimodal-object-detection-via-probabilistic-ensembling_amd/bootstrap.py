@@ -103,18 +103,18 @@ def _narrow(mult, n_images):
     return np.ascontiguousarray(mult, dtype=np.uint8)
 
 
-def ap_bootstrap(matches, mult, device="cuda", cells=None, full_table=False):
-    """One launch of pe_ap_bootstrap over mult [B, I].  Returns host arrays: psum [B, C, T] (the sum of the R interpolated precisions),
-    recall [B, C, T], valid [B, C] and, with full_table, precision [B, C, T, R]; "cells" [C, 3] is what was evaluated."""
-    ev = matches["evaluator"]
-    I, K, A, T, R = len(ev.img_ids), len(ev.cat_ids), len(ev.area_rng), len(ev.iou_thrs), len(ev.rec_thrs)
+def launch_ap_bootstrap(lists, mult, sizes, rec_thrs, cells, device="cuda", full_table=False):
+    """One launch of pe_ap_bootstrap over host lists ("list_off", "list_img", "list_rank", "list_flags" [A, n], "npig" [K, A, I]) with
+    sizes = (I, K, A, T): ap_bootstrap's launch, which tide.price shares with its own planes on the area-range axis."""
+    I, K, A, T = sizes
+    R = len(rec_thrs)
     m8 = _narrow(mult, I)
-    cells = summary_cells(matches) if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+    cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
     B, C = m8.shape[0], cells.shape[0]
     dev = torch.device(device)
     up = lambda a: torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(dev)      # noqa: E731
-    d = {k: up(matches[k]) for k in ("list_off", "list_img", "list_rank", "list_flags", "npig")}
-    d_mult, d_cells, d_thr = up(m8), up(cells), up(np.ascontiguousarray(ev.rec_thrs, dtype=np.float64))
+    d = {k: up(lists[k]) for k in ("list_off", "list_img", "list_rank", "list_flags", "npig")}
+    d_mult, d_cells, d_thr = up(m8), up(cells), up(np.ascontiguousarray(rec_thrs, dtype=np.float64))
     _lib.require_cuda(d_mult)
     psum = torch.empty((B, C, T), dtype=torch.float64, device=dev)
     recall = torch.empty((B, C, T), dtype=torch.float64, device=dev)
@@ -123,7 +123,7 @@ def ap_bootstrap(matches, mult, device="cuda", cells=None, full_table=False):
     ptr = lambda t: _lib.ptr(t) if t is not None and t.numel() else None      # noqa: E731
     with torch.cuda.device(dev):
         st = _lib.lib().pe_ap_bootstrap(ptr(d["list_off"]), ptr(d["list_img"]), ptr(d["list_rank"]), ptr(d["list_flags"]),
-                                        int(matches["list_img"].shape[0]), ptr(d["npig"]), ptr(d_mult), B, I, K, A, T, ptr(d_thr), R,
+                                        int(lists["list_img"].shape[0]), ptr(d["npig"]), ptr(d_mult), B, I, K, A, T, ptr(d_thr), R,
                                         ptr(d_cells), C, ptr(psum), ptr(recall), ptr(valid), ptr(prec), _lib.stream())
     _lib.check(st, "pe_ap_bootstrap")
     out = {"psum": psum.cpu().numpy(), "recall": recall.cpu().numpy(), "valid": valid.cpu().numpy(), "cells": cells}
@@ -132,6 +132,14 @@ def ap_bootstrap(matches, mult, device="cuda", cells=None, full_table=False):
     if full_table:
         out["precision"] = prec.cpu().numpy()
     return out
+
+
+def ap_bootstrap(matches, mult, device="cuda", cells=None, full_table=False):
+    """One launch of pe_ap_bootstrap over mult [B, I].  Returns host arrays: psum [B, C, T] (the sum of the R interpolated precisions),
+    recall [B, C, T], valid [B, C] and, with full_table, precision [B, C, T, R]; "cells" [C, 3] is what was evaluated."""
+    ev = matches["evaluator"]
+    sizes = (len(ev.img_ids), len(ev.cat_ids), len(ev.area_rng), len(ev.iou_thrs))
+    return launch_ap_bootstrap(matches, mult, sizes, ev.rec_thrs, summary_cells(matches) if cells is None else cells, device, full_table)
 
 
 def statistics(run, matches):
